@@ -52,6 +52,31 @@ def tile_bytes(tile, block_size, pool):
 
 CPU_BASELINE_TILES = 4  # the cpu_baseline sample: ONE reference-written archive of this many corpus tiles
 
+DUMP_SEED = 20261015           # --dump-outputs: the byte sample's windows are drawn by this seed
+DUMP_WINDOW = 4096             # bytes per sampled window
+DUMP_SAMPLE_BYTES = 8 << 20    # at most this many output bytes per array (32 MiB as float32)
+
+
+def dump_outputs(dump_dir, arrays):
+    """--dump-outputs: {name: 1-D uint8 / int32 device tensor} -> dump_dir/<name>.npy. Statuses and sizes go out whole as float64;
+    byte streams whole as float32 up to DUMP_SAMPLE_BYTES, above that a fixed, seeded sample of DUMP_WINDOW-byte windows (their
+    offsets in <name>_offsets.npy). The same arguments give the same inputs, so two builds compare array for array."""
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t.dtype != torch.uint8:
+            np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+            continue
+        n = int(t.numel())
+        if n <= DUMP_SAMPLE_BYTES:
+            np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+            continue
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        starts = np.sort(rng.choice(n // DUMP_WINDOW, size=DUMP_SAMPLE_BYTES // DUMP_WINDOW, replace=False)).astype(np.int64) * DUMP_WINDOW
+        idx = torch.from_numpy(starts).to(t.device)[:, None] + torch.arange(DUMP_WINDOW, device=t.device)[None, :]
+        np.save(os.path.join(dump_dir, name + ".npy"), t[idx.reshape(-1)].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(dump_dir, name + "_offsets.npy"), starts.astype(np.float64))
+
 
 def _ref_compress_cached(ref, key, data, level, block_size, seekable, checksum):
     """ref.compress, kept on disk when ZXC_BENCH_CACHE names a directory (tools/profile.sh: its five rocprofv3 passes run the same
@@ -72,11 +97,44 @@ def _ref_compress_cached(ref, key, data, level, block_size, seekable, checksum):
     return comp
 
 
+REF_PIECE_BYTES = 16 << 20  # the reference encodes of the input preparation run as pieces of whole blocks of about this size
+
+
+def _ref_submit(tp, ref, key, data, level, block_size, checksum):
+    """The reference's seekable archive of `data`, submitted to the thread pool tp as pieces of whole blocks -> [future of a
+    piece's archive]. Seekable blocks are independent: the pieces' blocks, header and EOF block are byte for byte those of ONE
+    archive of `data` (one call would keep one core busy for minutes at level 7)."""
+    step = max(1, REF_PIECE_BYTES // block_size) * block_size
+    return [tp.submit(_ref_compress_cached, ref, f"{key}@{o}", data[o:o + step], level, block_size, True, checksum)
+            for o in range(0, len(data), step)]
+
+
+def _ref_join(futs, block_size):
+    """[future of a piece's archive] -> (blocks region, comp_sizes, header16, eof8) of the whole archive"""
+    parts = [archive_parts(f.result(), block_size) for f in futs]
+    return b"".join(bytes(p[0]) for p in parts), np.concatenate([p[1] for p in parts]), parts[0][2], parts[0][3]
+
+
+def _ref_archive(ref, futs, block_size, total):
+    """The whole seekable archive (without checksums) from its pieces: header, blocks, EOF block, SEK block written by the
+    reference's zxc_write_seek_table, footer (decoded size, 4 zero bytes) — the bytes zxc_compress writes in one call."""
+    region, sizes, hdr, eof = _ref_join(futs, block_size)
+    L = ref.lib
+    L.zxc_seek_table_size.restype = C.c_size_t
+    L.zxc_seek_table_size.argtypes = [C.c_uint32]
+    L.zxc_write_seek_table.restype = C.c_int64
+    L.zxc_write_seek_table.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
+    cs = np.ascontiguousarray(sizes, dtype=np.uint32)
+    sek = C.create_string_buffer(int(L.zxc_seek_table_size(cs.size)))
+    assert L.zxc_write_seek_table(sek, len(sek), cs.ctypes.data, cs.size) == len(sek)
+    return hdr + region + eof + sek.raw + int(total).to_bytes(8, "little") + (0).to_bytes(4, "little")
+
+
 def build_rank_corpus(first, last, level, block_size, pool, dev, checksum=False, baseline_tiles=0):
     """Blocks [first, last) of the global corpus, encoded by the unmodified reference (the metric is defined on
     archives written by the reference encoder: "silesia.tar at -3"; untimed input preparation). Only the tiles
-    this range touches are generated; compressed blocks and plaintext go straight to HBM, tile by tile, so the
-    host never holds more than a few tiles. -> (d_comp, comp_sizes of the range, d_want, header16, eof8, info)"""
+    this range touches are generated; compressed blocks and plaintext go straight to HBM, tile by tile.
+    -> (d_comp, comp_sizes of the range, d_want, header16, eof8, info, the CPU baseline's archive or None)"""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from zxc_amd import corpus
@@ -90,37 +148,34 @@ def build_rank_corpus(first, last, level, block_size, pool, dev, checksum=False,
     t0 = time.time()
     regions, sizes_all, wants = [], [], []
     hdr = eof = None
-    first_tile_comp = None
     src = ""
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    base_fut, base_data = None, []
-    with ThreadPoolExecutor(max_workers=max(1, min(16, len(tiles) + 1, (os.cpu_count() or 1) // world // 2))) as tp:
+    base_futs, base_data, base_arc = None, [], None
+    with ThreadPoolExecutor(max_workers=max(1, min(64, (os.cpu_count() or 1) // world // 2))) as tp:
         futs = []
         for t in tiles:
             data, src = tile_bytes(t, block_size, pool)
             if len(base_data) < baseline_tiles:  # the CPU baseline's archive: the first tiles as ONE seekable archive
                 base_data.append(data)
                 if len(base_data) == min(baseline_tiles, len(tiles)):
-                    base_fut = tp.submit(_ref_compress_cached, ref, f"base{tiles[0]}x{len(base_data)}_{src}", b"".join(base_data), level, block_size, True, False)
+                    joined = b"".join(base_data)
+                    base_futs = (_ref_submit(tp, ref, f"base{tiles[0]}x{len(base_data)}_{src}", joined, level, block_size, False), len(joined))
+                    del joined
             lo, hi = max(first, t * tb) - t * tb, min(last, (t + 1) * tb) - t * tb
             wants.append(torch.frombuffer(bytearray(data[lo * block_size: hi * block_size]), dtype=torch.uint8).to(dev))
-            futs.append((lo, hi, tp.submit(_ref_compress_cached, ref, f"tile{t}_{src}", data, level, block_size, True, checksum)))
+            futs.append((lo, hi, _ref_submit(tp, ref, f"tile{t}_{src}", data, level, block_size, checksum)))
             del data
-        for lo, hi, f in futs:
-            comp = f.result()
-            if first_tile_comp is None:
-                first_tile_comp = comp
-            region, sizes, hdr, eof = archive_parts(comp, block_size)
+        for lo, hi, fs in futs:
+            region, sizes, hdr, eof = _ref_join(fs, block_size)
             off = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
             regions.append(torch.frombuffer(bytearray(region[off[lo]: off[hi]]), dtype=torch.uint8).to(dev))
             sizes_all.append(sizes[lo:hi])
+        if base_futs is not None:
+            base_arc = _ref_archive(ref, base_futs[0], block_size, base_futs[1])
     d_comp = torch.cat(regions + [torch.zeros(256, dtype=torch.uint8, device=dev)])  # (+ slack for 16-byte reads)
     d_want = torch.cat(wants)
     info = dict(prep_s=round(time.time() - t0, 1), tiles=len(tiles), encoder="reference _ref", source=src)
-    if base_fut is not None:
-        first_tile_comp = base_fut.result()
-        info["prep_s"] = round(time.time() - t0, 1)
-    return d_comp, np.concatenate(sizes_all), d_want, hdr, eof, info, first_tile_comp
+    return d_comp, np.concatenate(sizes_all), d_want, hdr, eof, info, base_arc
 
 
 def open_global_table(all_sizes, block_size, hdr, eof, total_decoded):
@@ -184,11 +239,12 @@ def cpu_baseline(comp, total, budget_s=12.0, what="corpus tile 0"):
             "sample": f"oracle C restatement, first {n >> 20} MiB, 1 thread"}
 
 
-def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True, block_size=None, extras=True):
+def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True, block_size=None, extras=True, dump_dir=None):
     """configs[2]: per-block LZ77 hash-chain match finding + GLO serialisation on the device over enc_mib MiB of unique
     enwik-like text per GPU, source resident in HBM, compressed blocks left in HBM. value = source GB/s. The
     compressed stream of the LAST timed launch is round-tripped: every block decoded on the device and compared
     with the source (all of it), and a 64 MiB sample decoded by the unmodified reference decoder on the host.
+    dump_dir: rank 0 writes that launch's block sizes and compacted blocks there (dump_outputs).
     -> the result line (a dict) on rank 0, None elsewhere."""
     import multiprocessing as mp
     import torch
@@ -247,6 +303,9 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
     rc = L.zxc_mi355x_gather_blocks_device(C.c_void_p(d_slots.data_ptr()), bs, C.c_void_p(d_sizes.data_ptr()),
                                            C.c_void_p(d_offs.data_ptr()), C.c_void_p(d_comp.data_ptr()), nb, C.c_void_p(stream))
     assert rc == 0
+    if dump_dir and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(dump_dir, {"encode_block_sizes": d_sizes, "encode_blocks": d_comp[:csize]})
     jobs = np.zeros(nb, dtype=zxc_amd.api.JOB_DTYPE)
     jobs["comp_off"] = offs.cpu().numpy().astype(np.uint64)
     jobs["comp_size"] = sizes.cpu().numpy().astype(np.uint32)
@@ -297,7 +356,7 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
     # every block must come out RAW (stored: 8-byte header + the bytes) and decode back
     try:
         rn = 256 << 20
-        d_rnd = torch.randint(0, 256, (rn + 256,), dtype=torch.uint8, device=dev)
+        d_rnd = torch.randint(0, 256, (rn + 256,), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
         rnb = rn // bs
         def rstep():
             assert L.zxc_mi355x_encode_blocks_device(C.c_void_p(d_rnd.data_ptr()), rn, bs, level, 0, C.c_void_p(d_slots.data_ptr()),
@@ -353,7 +412,7 @@ def calibration_launch(dev, bs, n=16384):
     import zxc_amd
     hdr = bytearray(8)  # type 0 = RAW, comp_size = bs; the header check byte is the frame walker's business, not the kernel's
     hdr[3:7] = bs.to_bytes(4, "little")
-    t = torch.randint(0, 256, (n, bs + 8), dtype=torch.uint8, device=dev)
+    t = torch.randint(0, 256, (n, bs + 8), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(2))
     t[:, :8] = torch.tensor(list(hdr), dtype=torch.uint8, device=dev)
     jobs = np.zeros(n, dtype=zxc_amd.api.JOB_DTYPE)
     jobs["comp_off"] = np.arange(n, dtype=np.uint64) * (bs + 8)
@@ -414,9 +473,10 @@ def prep_estimate_s(n_tiles, level, world):
 
 
 def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_launch=False, with_cpu_baseline=True,
-               cpu_budget_s=12.0, block_size=None):
+               cpu_budget_s=12.0, block_size=None, dump_dir=None):
     """One decode measurement: this rank's block range of ONE corpus of world x tiles tiles, `steps` timed launches
-    bracketed by barrier + synchronize, every byte and status checked before and after. -> the result line on rank 0."""
+    bracketed by barrier + synchronize, every byte and status checked before and after. dump_dir: rank 0 writes what the
+    last timed launch left (block statuses, decoded bytes) there (dump_outputs). -> the result line on rank 0."""
     import multiprocessing as mp
     import torch
     import zxc_amd
@@ -492,6 +552,8 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
         dist.barrier()
     wall = time.perf_counter() - t0
     kern_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"decode_status": d_status, "decode_out": d_out[:out_bytes]})
     d_out.zero_()
     d_status.fill_(-999)
     step()
@@ -902,9 +964,14 @@ def main():
     ap.add_argument("--total-tiles", type=int, default=0,
                     help="--scaling strong: tiles of the one corpus (default 8 x --tiles = 328 tiles = 64.7 GiB decoded; N = 1 holds "
                          "all of it: 69 GB out + 69 GB reference copy + 35 GB compressed of the 288 GB)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline line computed to DIR/<name>.npy "
+                         "(float32 / float64, a fixed seeded sample of large outputs, < 64 MB in all; rank 0)")
     ap.add_argument("--max-prep-s", type=float, default=float(os.environ.get("ZXC_BENCH_MAX_PREP_S", "1500")),
                     help="refuse a run whose (untimed) input preparation is estimated above this many seconds per rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.rehearse:
         os.environ.setdefault("ZXC_BENCH_BACKEND", "gloo")
     # --gpus N is the contract: N ranks, one per GPU. Under a launcher WORLD_SIZE must agree with it; without one this
@@ -926,12 +993,13 @@ def main():
         torch.cuda.set_device(local)
         zxc_amd.lib().zxc_mi355x_set_device(local)
         if args.mode == "encode":
-            line = encode_run(args, args.level, args.enc_mib, args.steps, args.warmup, comm, not args.no_cpu_baseline)
+            line = encode_run(args, args.level, args.enc_mib, args.steps, args.warmup, comm, not args.no_cpu_baseline,
+                              dump_dir=args.dump_outputs)
         else:
             # (the headline line of the default run measures its HBM traffic itself: two short rocprofv3 passes in a child process)
             args.live_traffic = world == 1 and args.level == 3 and not args.checksum and not args.calib and not args.no_secondary and args.block_size == 65536
             line = decode_run(args, args.level, args.tiles, args.steps, args.warmup, comm, args.checksum, args.calib,
-                              not args.no_cpu_baseline)
+                              not args.no_cpu_baseline, dump_dir=args.dump_outputs)
             args.live_traffic = False
             # The default single-GPU run also measures the other two single-GPU configurations of BASELINE.json, each with its
             # own roofline / cpu_baseline objects and its own bit-exactness check (next #2).

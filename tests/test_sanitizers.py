@@ -38,7 +38,7 @@ def test_four_thread_stress(san, kind):
 def test_reference_unit_cases(san, kind):
     exe = os.path.join(BIN, "unit_" + kind)
     if not os.path.exists(exe):
-        pytest.skip("needs /root/reference at build time")
+        pytest.skip("oracle/_ref/tests not built (needs the reference's sources at build time)")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=1500, env=san)
     _clean(r, "unit_" + kind)
     assert "SUMMARY ran 94 failed 0" in r.stdout, r.stdout[-500:]
@@ -50,7 +50,7 @@ def test_reference_fuzz_harnesses_under_asan(san, name):
     valid archives): the host's parsers — frame walk, seek table, push-stream state machines, .zxd — must stay in bounds"""
     exe = os.path.join(BIN, "fuzz_asan_" + name)
     if not os.path.exists(exe):
-        pytest.skip("needs /root/reference at build time")
+        pytest.skip("oracle/_ref/tests not built (needs the reference's sources at build time)")
     r = subprocess.run([exe, "1500", "3"], capture_output=True, text=True, timeout=900, env=dict(san, ZXC_MI355X_FRAME_BATCH_MIB=""))
     _clean(r, "fuzz_asan_" + name)
     assert "FUZZ OK 1500 inputs" in r.stdout

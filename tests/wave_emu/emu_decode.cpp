@@ -32,9 +32,12 @@ extern "C" __attribute__((visibility("default")))
 int emu_decode_blocks(const uint8_t* comp, size_t comp_bytes, const zxc_dev_job_t* jobs, uint32_t n_jobs, uint8_t* out,
                       size_t out_bytes, int32_t* status, uint32_t block_size, int verify_trailer, const uint8_t* dict,
                       uint32_t dict_size, const uint8_t* dict_huf) {
-    // padded private copies: the kernels read (never use) a few bytes past the ends, as they may in device buffers
+    // padded private copies: the kernels read (never use) a few bytes past the ends, as they may in device buffers. The output
+    // starts as the caller's buffer between two 4 KiB pads of 0xDD; the return value tells whether a pad changed (bit 0: the one
+    // in front, bit 1: the one behind), so a caller's own guard bytes and these pads together catch every stray store.
     std::vector<uint8_t> c(comp_bytes + 8192, 0xEE), o(out_bytes + 8192, 0xDD);
     memcpy(c.data() + 4096, comp, comp_bytes);
+    memcpy(o.data() + 4096, out, out_bytes);
     const uint32_t stride = ZXC_DEV_SLOT_STRIDE(block_size);
     const uint32_t n_slots = 4;
     std::vector<uint8_t> scratch((size_t)n_slots * stride + 4096, 0xCC);
@@ -117,5 +120,10 @@ int emu_decode_blocks(const uint8_t* comp, size_t comp_bytes, const zxc_dev_job_
         }
     }
     memcpy(out, o.data() + 4096, out_bytes);
-    return 0;
+    int pads = 0;
+    for (size_t i = 0; i < 4096; i++) {
+        if (o[i] != 0xDD) pads |= 1;
+        if (o[4096 + out_bytes + i] != 0xDD) pads |= 2;
+    }
+    return pads;
 }

@@ -26,16 +26,22 @@ class Emu:
                                         C.c_void_p, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32, C.c_char_p]
 
     def decode_jobs(self, comp: bytes, jobs: np.ndarray, out_bytes: int, block_size: int, verify_trailer=False,
-                    dict_=None, dict_huf=None, cap_override=0, ck_apart=True):
+                    dict_=None, dict_huf=None, cap_override=0, ck_apart=True, init=None):
         """Runs every job through one emulated wavefront. -> (status int32[n], output bytes).
-        cap_override: the strict per-block capacity of zxc_decompress_block_safe (0: block_size + 2112)."""
+        cap_override: the strict per-block capacity of zxc_decompress_block_safe (0: block_size + 2112).
+        init: the output buffer's contents before the launch (default: 0xDD everywhere). Afterwards self.last_pads tells
+        whether a store landed in the 4 KiB in front of the buffer (bit 0) or behind it (bit 1)."""
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
         self.lib.emu_set_cap_override(int(cap_override))
         self.lib.emu_set_ck_apart(int(ck_apart))  # (checksums by zxc_block_checksum_kernel beside the decode, or inside the decode kernels)
-        out = C.create_string_buffer(max(out_bytes, 1))
+        if init is None:
+            out = C.create_string_buffer(b"\xDD" * out_bytes, max(out_bytes, 1))
+        else:
+            assert len(init) == out_bytes
+            out = C.create_string_buffer(bytes(init), max(out_bytes, 1))
         status = np.full(jobs.size, -999, dtype=np.int32)
-        self.lib.emu_decode_blocks(comp, len(comp), jobs.ctypes.data, jobs.size, out, out_bytes, status.ctypes.data,
-                                   block_size, int(verify_trailer), dict_, len(dict_) if dict_ else 0, dict_huf)
+        self.last_pads = self.lib.emu_decode_blocks(comp, len(comp), jobs.ctypes.data, jobs.size, out, out_bytes, status.ctypes.data,
+                                                    block_size, int(verify_trailer), dict_, len(dict_) if dict_ else 0, dict_huf)
         self.lib.emu_set_cap_override(0)
         return status, out.raw[:out_bytes]
 

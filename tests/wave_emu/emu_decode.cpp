@@ -19,14 +19,17 @@ static size_t emu_rscratch_bytes = (size_t)4 << 20;  // scratch for the expanded
 extern "C" __attribute__((visibility("default"))) void emu_set_rscratch_bytes(size_t n) { emu_rscratch_bytes = n; }
 extern "C" __attribute__((visibility("default"))) uint32_t emu_last_section_count(int size_class) { return emu_last_secs[size_class]; }
 
-// per-block checksums: 1 = hashed by zxc_block_checksum_kernel beside the decode and merged into the statuses (the product's plan without
-// PRE blocks), 0 = inside the decode kernels (its plan with PRE blocks, dictionaries, the strict capacity)
+// per-block checksums: 1 = by zxc_block_checksum_kernel beside the decode, merged into the statuses; 0 = inside the decode kernels
 static int emu_ck_apart = 1;
 extern "C" __attribute__((visibility("default"))) void emu_set_ck_apart(int on) { emu_ck_apart = on; }
 
 // the strict per-block capacity of zxc_decompress_block_safe (the kernels' cap_override argument; 0 = block_size + 2112)
 static uint32_t emu_cap_override = 0;
 extern "C" __attribute__((visibility("default"))) void emu_set_cap_override(uint32_t cap) { emu_cap_override = cap; }
+
+// the product's plan table and launch-order buffer layout (zxc_dev.h), for tests/test_wave_emu_plans.py
+extern "C" __attribute__((visibility("default"))) void emu_decode_plan_choose(const zxc_dev_plan_in_t* in, zxc_dev_plan_t* out) { *out = zxc_dev_plan_choose(in); }
+extern "C" __attribute__((visibility("default"))) void emu_ord_layout(uint32_t n_jobs, zxc_dev_ord_layout_t* out) { *out = zxc_dev_ord_layout(n_jobs); }
 
 extern "C" __attribute__((visibility("default")))
 int emu_decode_blocks(const uint8_t* comp, size_t comp_bytes, const zxc_dev_job_t* jobs, uint32_t n_jobs, uint8_t* out,
@@ -45,78 +48,70 @@ int emu_decode_blocks(const uint8_t* comp, size_t comp_bytes, const zxc_dev_job_
     std::vector<uint8_t> dct;
     const uint8_t* dptr = nullptr;
     if (dict && dict_size) { dct.assign(dict_size + 8192, 0xBB); memcpy(dct.data() + 4096, dict, dict_size); dptr = dct.data() + 4096; }
-    if (emu_cap_override && !(dptr || dict_huf)) {  // strict capacity: the full kernel alone, one block per workgroup (zxc_hip_shim.hip)
-        for (uint32_t b = 0; b < n_jobs; b++) {
-            memset(__start_emu_lds, 0xA5, (size_t)(__stop_emu_lds - __start_emu_lds));
-            emu::run_wave([&] {
-                zxc_decode_blocks_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, verify_trailer ? 4u : 0u, scratch.data(),
-                                         stride, 0u, busy.data(), n_slots, nullptr, emu_cap_override, nullptr);
-            }, b, n_jobs, 64);
-        }
-    } else if (dptr || dict_huf) {
-        for (uint32_t b = 0; b < n_jobs; b++) {
+    // The plan from the knobs, through the product's chooser as for a first launch (the knobs' scratch sizes); emu_set_ck_apart(1)
+    // also puts the checksums apart beside PRE blocks, which the product's chooser never picks.
+    zxc_dev_plan_in_t in = {(uint32_t)(dptr || dict_huf), emu_cap_override, n_jobs, ~0u, 0u, (uint32_t)(verify_trailer != 0), block_size, 1u, 1u};
+    in.ck_inline = !emu_ck_apart, in.pscratch_failed = !emu_pscratch_bytes;
+    zxc_dev_plan_t p = zxc_dev_plan_choose(&in);
+    if (p.kind >= ZXC_DEV_PLAN_TWO_PASS && verify_trailer && emu_ck_apart) p.ck_apart = 1u, p.trailer_bytes = 4u | ZXC_DEV_TRAILER_ELSEWHERE;
+    const uint32_t tb = p.trailer_bytes, g256 = (n_jobs + 255u) / 256u;
+    auto launch = [&](unsigned grid, int threads, const std::function<void()>& k) {
+        for (unsigned g = 0; g < grid; g++) {
             memset(__start_emu_lds, 0xA5, (size_t)(__stop_emu_lds - __start_emu_lds));  // LDS is not zero at launch
-            emu::run_wave([&] {
-                zxc_decode_blocks_dict_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size,
-                                              verify_trailer ? 4u : 0u, scratch.data(), stride, 0u, busy.data(), n_slots,
-                                              nullptr, emu_cap_override, dptr, dict_size, dict_huf);
-            }, b, n_jobs, 64);
+            emu::run_wave(k, g, grid, threads);
         }
+    };
+    if (p.kind < ZXC_DEV_PLAN_TWO_PASS) {  // dictionary kernel, or the full kernel alone under the strict capacity (zxc_hip_shim.hip)
+        launch(n_jobs, 64, [&] {
+            if (p.kind == ZXC_DEV_PLAN_DICT)
+                zxc_decode_blocks_dict_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, tb, scratch.data(), stride,
+                                              0u, busy.data(), n_slots, nullptr, emu_cap_override, dptr, dict_size, dict_huf);
+            else
+                zxc_decode_blocks_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, tb, scratch.data(), stride, 0u,
+                                         busy.data(), n_slots, nullptr, emu_cap_override, nullptr);
+        });
     } else {
-        // the two-pass launch of zxc_hip_shim.hip, kernel by kernel: launch-order pass (histogram + scatter: order[], classes, work
-        // lists), the section kernels of the three size classes, the lean kernel over every block, its second entry over the PRE
-        // blocks, the full kernel over its list
-        const uint32_t tb0 = verify_trailer ? 4u : 0u, g256 = (n_jobs + 255u) / 256u;
-        const bool ck_apart = tb0 && emu_ck_apart;
-        const uint32_t tb = ck_apart ? tb0 | ZXC_DEV_TRAILER_ELSEWHERE : tb0;
-        std::vector<uint8_t> ck_bad(n_jobs + 16u, 0xEE);
-        std::vector<uint32_t> hist(128, 0u), order(n_jobs), list(n_jobs + 2u, 0u), ctl(ZXC_DEV_CTL_WORDS, 0u), pre_entries(n_jobs);
-        std::vector<zxc_dev_pre_t> pre(n_jobs);
-        std::vector<zxc_dev_sec_t> secs(6u * (size_t)n_jobs);
+        // the two-pass launch of zxc_hip_shim.hip, kernel by kernel, over one launch-order buffer carved as on the device and
+        // poisoned except where the shim zeroes it: launch-order pass, section kernels, lean kernel, its second entry, full kernel
+        const zxc_dev_ord_layout_t at = zxc_dev_ord_layout(n_jobs);
+        std::vector<uint32_t> buf(at.words, 0xA3A3A3A3u);
+        memset(buf.data(), 0, 130u * 4u);
+        memset(buf.data() + at.ctl, 0, ZXC_DEV_CTL_WORDS * 4u);
+        uint32_t *order = buf.data() + at.order, *list = buf.data() + at.list, *ctl = buf.data() + at.ctl, *pre_entries = buf.data() + at.pre_ent;
+        zxc_dev_sec_t* secs = (zxc_dev_sec_t*)(buf.data() + at.secs);
+        zxc_dev_pre_t* pre = (zxc_dev_pre_t*)(buf.data() + at.pre);
+        uint8_t* ck_bad = (uint8_t*)(buf.data() + at.ck_bad);
         std::vector<uint8_t> pscratch(emu_pscratch_bytes + 4096, 0xC3);
         std::vector<uint8_t> rscratch(emu_rscratch_bytes + 4096, 0xC7);  // expanded literals of the LEAN_RLE blocks
-        auto launch = [&](unsigned grid, int threads, const std::function<void()>& k) {
-            for (unsigned g = 0; g < grid; g++) {
-                memset(__start_emu_lds, 0xA5, (size_t)(__stop_emu_lds - __start_emu_lds));  // LDS is not zero at launch
-                emu::run_wave(k, g, grid, threads);
-            }
-        };
-        launch(g256, 256, [&] { zxc_order_hist_kernel(c.data() + 4096, jobs, n_jobs, block_size, hist.data()); });
+        launch(g256, 256, [&] { zxc_order_hist_kernel(c.data() + 4096, jobs, n_jobs, block_size, buf.data()); });
         launch(g256, 256, [&] {
-            zxc_order_scatter_kernel(c.data() + 4096, jobs, n_jobs, block_size, hist.data(), order.data(), list.data(), tb0, pre.data(), ctl.data(),
-                                     pre_entries.data(), secs.data(), (uint32_t)(emu_pscratch_bytes >> 4), emu_cap_override ? emu_cap_override : block_size + 2112u,
+            zxc_order_scatter_kernel(c.data() + 4096, jobs, n_jobs, block_size, buf.data(), order, list, tb & ~ZXC_DEV_TRAILER_ELSEWHERE, pre, ctl,
+                                     pre_entries, secs, (uint32_t)(emu_pscratch_bytes >> 4), emu_cap_override ? emu_cap_override : block_size + 2112u,
                                      (uint32_t)(emu_rscratch_bytes >> 4));
         });
         emu_last_pre = ctl[ZXC_DEV_CTL_PRE];
-        uint32_t* sec_hdr = ctl.data() + ZXC_DEV_CTL_SEC;
+        uint32_t* sec_hdr = ctl + ZXC_DEV_CTL_SEC;
         for (int k = 0; k < 3; k++) emu_last_secs[k] = sec_hdr[2 * k];
-        if (sec_hdr[0]) launch(2, 128, [&] { zxc_pivco_sections_small_kernel(c.data() + 4096, secs.data(), sec_hdr, pre.data(), pscratch.data()); });
-        if (sec_hdr[2]) launch(2, 256, [&] { zxc_pivco_sections_medium_kernel(c.data() + 4096, secs.data() + 2u * (size_t)n_jobs, sec_hdr + 2, pre.data(), pscratch.data()); });
-        if (sec_hdr[4]) launch(2, 512, [&] { zxc_pivco_sections_large_kernel(c.data() + 4096, secs.data() + 4u * (size_t)n_jobs, sec_hdr + 4, pre.data(), pscratch.data()); });
-        if (ctl[ZXC_DEV_CTL_RLE_LIST]) {
-            launch(3u, 64, [&] {
-                zxc_rle_expand_kernel(c.data() + 4096, jobs, pre.data(), rscratch.data(), ctl.data() + ZXC_DEV_CTL_RLE_LIST, pre_entries.data() + n_jobs - 1u);
-            });
-        }
+        if (sec_hdr[0]) launch(2, 128, [&] { zxc_pivco_sections_small_kernel(c.data() + 4096, secs, sec_hdr, pre, pscratch.data()); });
+        if (sec_hdr[2]) launch(2, 256, [&] { zxc_pivco_sections_medium_kernel(c.data() + 4096, secs + 2u * (size_t)n_jobs, sec_hdr + 2, pre, pscratch.data()); });
+        if (sec_hdr[4]) launch(2, 512, [&] { zxc_pivco_sections_large_kernel(c.data() + 4096, secs + 4u * (size_t)n_jobs, sec_hdr + 4, pre, pscratch.data()); });
+        if (ctl[ZXC_DEV_CTL_RLE_LIST])
+            launch(3u, 64, [&] { zxc_rle_expand_kernel(c.data() + 4096, jobs, pre, rscratch.data(), ctl + ZXC_DEV_CTL_RLE_LIST, pre_entries + n_jobs - 1u); });
         launch(n_jobs, 64, [&] {
-            zxc_decode_blocks_lean_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, order.data(), emu_cap_override, tb, pre.data(), rscratch.data());
+            zxc_decode_blocks_lean_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, order, emu_cap_override, tb, pre, rscratch.data());
         });
         if (ctl[ZXC_DEV_CTL_PRE]) launch(n_jobs, 64, [&] {
-            zxc_decode_blocks_lean_pre_kernel(c.data() + 4096, jobs, o.data() + 4096, status, block_size, emu_cap_override, tb, pre.data(), pscratch.data(),
-                                              ctl.data() + ZXC_DEV_CTL_PRE, pre_entries.data());
+            zxc_decode_blocks_lean_pre_kernel(c.data() + 4096, jobs, o.data() + 4096, status, block_size, emu_cap_override, tb, pre, pscratch.data(),
+                                              ctl + ZXC_DEV_CTL_PRE, pre_entries);
         });
         emu_last_deferred = list[0];
-        const uint32_t grid = n_jobs < 3u ? n_jobs : 3u;
-        for (uint32_t b = 0; b < grid; b++) {
-            memset(__start_emu_lds, 0xA5, (size_t)(__stop_emu_lds - __start_emu_lds));
-            emu::run_wave([&] {
-                zxc_decode_blocks_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, tb, scratch.data(),
-                                         stride, 0u, busy.data(), n_slots, order.data(), emu_cap_override, list.data());
-            }, b, grid, 64);
-        }
-        if (ck_apart) {
-            launch((n_jobs + 8u) / 9u, 64, [&] { zxc_block_checksum_kernel(c.data() + 4096, jobs, n_jobs, order.data(), ck_bad.data()); });
-            launch(g256, 256, [&] { zxc_checksum_merge_kernel(ck_bad.data(), status, n_jobs); });
+        launch(n_jobs < 3u ? n_jobs : 3u, 64, [&] {
+            zxc_decode_blocks_kernel(c.data() + 4096, jobs, n_jobs, o.data() + 4096, status, block_size, tb, scratch.data(), stride, 0u,
+                                     busy.data(), n_slots, order, emu_cap_override, list);
+        });
+        if (p.ck_apart) {
+            launch((n_jobs + 8u) / 9u, 64, [&] { zxc_block_checksum_kernel(c.data() + 4096, jobs, n_jobs, order, ck_bad); });
+            launch(g256, 256, [&] { zxc_checksum_merge_kernel(ck_bad, status, n_jobs); });
         }
     }
     memcpy(out, o.data() + 4096, out_bytes);

@@ -52,4 +52,58 @@ typedef struct {          /* one coded section on a size class's work list */
  * (level 7); R = block_size + 64 bytes of slack. */
 #define ZXC_DEV_SLOT_REGION(bs) ((bs) + 64u)
 #define ZXC_DEV_SLOT_STRIDE(bs) ((2u * ZXC_DEV_SLOT_REGION(bs) + (bs) / 5u + 16u + 64u + 255u) & ~255u)
+
+/* Host only, plain C (the shim, the CPU emulator, tests). A stream's launch-order buffer, u32 words: [128 histogram + cursors |
+ * list: count, next, n entries | order[n] | ctl | PRE job indices[n] | section records, 3 size classes x 2 n x 8 words, 32-byte
+ * aligned | pre[n] x 4 words | ck_bad: one byte per block, checksum mismatch]; the shim zeroes [0, 130) and ctl per launch. */
+typedef struct { size_t list, order, ctl, pre_ent, secs, pre, ck_bad, words; } zxc_dev_ord_layout_t;
+static inline zxc_dev_ord_layout_t zxc_dev_ord_layout(uint32_t n_jobs) {
+    const size_t n = n_jobs, ctl = 130u + 2u * n, pre_ent = ctl + ZXC_DEV_CTL_WORDS, secs = (pre_ent + n + 7u) & ~(size_t)7u;
+    const zxc_dev_ord_layout_t l = {128u, 130u + n, ctl, pre_ent, secs, secs + 48u * n, secs + 52u * n, secs + 52u * n + (n + 3u) / 4u};
+    return l;
+}
+
+/* Decode launch plans. TWO_PASS (no dictionary, no strict capacity): the lean kernel over every block beside the full kernel over
+ * the blocks only it decodes, on helper streams; TWO_PASS_PRE: also the section kernels and the lean kernel's second entry. With
+ * the checksums apart (ck_apart), a block whose checksum fails is still decoded into its own output slot: those bytes are
+ * undefined, its status is ZXC_ERROR_BAD_CHECKSUM, and nothing is written outside the slot. */
+enum { ZXC_DEV_PLAN_FULL, ZXC_DEV_PLAN_DICT, ZXC_DEV_PLAN_TWO_PASS, ZXC_DEV_PLAN_TWO_PASS_PRE };
+#define ZXC_DEV_DBG_NO_TWO_PASS 0x40000000u /* debug flags of experiment builds */
+#define ZXC_DEV_DBG_NO_ORDER 0x80000000u
+typedef struct {
+    uint32_t kind, ordered, ck_apart, trailer_bytes; /* ZXC_DEV_PLAN_*; the launch-order pass runs; checksums by their own kernel
+                                                      * beside the decode; the decode kernels' argument */
+    uint64_t pscratch_bytes, rscratch_bytes; /* section / RLE scratch wanted (0: none) */
+} zxc_dev_plan_t;
+typedef struct { /* all u32, flags 0 / 1 */
+    uint32_t dict, cap_override, n_jobs, max_slots, debug, verify_trailer, block_size;
+    uint32_t slot, helpers, hint, hint0, hint1; /* the stream's launch-order slot, its helper streams, its hint page and words */
+    uint32_t ck_inline, no_rle_scratch, rle_lean_max_jobs, no_pre; /* ZXC_MI355X_CK_INLINE / _NO_RLE_SCRATCH set; ZXC_RLE_LEAN_MAX_JOBS; EXP_NO_PRE */
+    uint32_t order_failed, pscratch_failed, rscratch_failed; /* what provisioning the chosen plan could not grant */
+} zxc_dev_plan_in_t;
+
+/* Every downgrade is a rule here (what the stream has, what provisioning could not grant). The two-pass plan follows the last
+ * launch on the stream (hint0: its PRE-qualified blocks, 0xFFFFFFFF before the first): if none (levels 1-5), no section kernels,
+ * whose idle LDS cost the lean kernel 5-30 % beside it, 2 % in front (profiles/r3z_*). Any plan decodes any input. */
+static inline zxc_dev_plan_t zxc_dev_plan_choose(const zxc_dev_plan_in_t* in) {
+    const uint64_t gib = (uint64_t)1 << 30, n = in->n_jobs, bs = in->block_size;
+    const int two_pass = !in->dict && !in->cap_override && !(in->debug & ZXC_DEV_DBG_NO_TWO_PASS);
+    const int wants_order = two_pass || (in->n_jobs > in->max_slots && !(in->debug & ZXC_DEV_DBG_NO_ORDER));
+    zxc_dev_plan_t p = {in->dict ? ZXC_DEV_PLAN_DICT : ZXC_DEV_PLAN_FULL, wants_order && in->slot && !in->order_failed, 0u,
+                        in->verify_trailer ? 4u : 0u, 0u, 0u};
+    if (!two_pass || !p.ordered || !in->helpers) return p;
+    /* section scratch: what this launch can need at most, capped at 1 GiB (blocks beyond it go to the full kernel) */
+    p.kind = (!in->hint || in->hint0 != 0u) && !in->no_pre && !in->pscratch_failed ? ZXC_DEV_PLAN_TWO_PASS_PRE : ZXC_DEV_PLAN_TWO_PASS;
+    if (p.kind == ZXC_DEV_PLAN_TWO_PASS_PRE) p.pscratch_bytes = n * (bs + bs / 5u + 256u) < gib ? n * (bs + bs / 5u + 256u) : gib;
+    /* RLE scratch: a quarter more than the last launch's LEAN_RLE blocks wanted (hint1, 16-byte units; none: full kernel). Only in
+     * launches of < rle_lean_max_jobs blocks: in a short launch the one-wave full kernel ends it with these heaviest blocks (9 702
+     * blocks: 1.25 -> 0.90 ms with RLE scratch), in a long one it is faster beside the lean kernel (profiles/r4b_rle_variants.log). */
+    if (in->hint && n < in->rle_lean_max_jobs && in->hint1 && !in->no_rle_scratch && !in->rscratch_failed) {
+        const uint64_t need = ((uint64_t)in->hint1 * 16u * 5u / 4u + 65536u) & ~(uint64_t)4095u, most = n * (bs + 96u) < gib ? n * (bs + 96u) : gib;
+        p.rscratch_bytes = need < most ? need : most;
+    }
+    p.ck_apart = p.kind == ZXC_DEV_PLAN_TWO_PASS && in->verify_trailer && !in->ck_inline;
+    if (p.ck_apart) p.trailer_bytes |= ZXC_DEV_TRAILER_ELSEWHERE;
+    return p;
+}
 #endif

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Kernel experiment harness (development tool, GPU box only): times
-zxc_decode_blocks_kernel on single data classes / levels with optional ablation flags.
+the decode launch on single data classes / levels, optionally under forced plans.
 Usage: python tools/kbench.py [class ...]   classes: text exe source records chem image16 mixed zeros
-Env: KB_MIB (per-class MiB, default 16), KB_REPL (replicas, default 16), KB_LEVELS ("3"), KB_DBG ("0,1,2,...")"""
+Env: KB_MIB (per-class MiB, default 16), KB_REPL (replicas, default 16), KB_LEVELS ("3"),
+KB_DBG ("0,0x40000000,..."): ORs of the ZXC_DEV_DBG_* plan bits (zxc_dev.h); any non-zero value needs a
+-DZXC_EXPERIMENT build (tools/build_variant.sh, ZXC_LIB_VARIANT). Every flag set decodes correctly: each is checked."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,25 +35,24 @@ def run(name, data, level, dbgs, R, bs=65536):
     for dbg in dbgs:
         zxc_amd.api.set_debug(L, dbg)
         def step(): zxc_amd.decode_blocks_device(d_comp.data_ptr(), d_jobs.data_ptr(), jobs.size, d_out.data_ptr(), d_st.data_ptr(), bs, False, stream)
-        step(); torch.cuda.synchronize()
-        if dbg == 0:
-            st = d_st.cpu().numpy()
-            ok = (st == jobs["out_len"].astype(np.int32)).all() and bytes(d_out[:total].cpu().numpy()) == data
+        d_out.zero_(); step(); torch.cuda.synchronize()
+        st = d_st.cpu().numpy()
+        ok = (st == jobs["out_len"].astype(np.int32)).all() and bytes(d_out[:total].cpu().numpy()) == data
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(3): step()
         e1.record(); torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / 3
-        res.append((dbg, ms, R * total / ms / 1e6))
+        res.append((dbg, ms, R * total / ms / 1e6, ok))
     zxc_amd.api.set_debug(L, 0)
-    print(f"{name:8s} L{level} ratio {total/len(comp):5.2f} blocks {jobs.size:6d} ok={ok} | " +
-          " | ".join(f"dbg{d}: {ms:7.2f} ms {g:7.1f} GB/s" for d, ms, g in res), flush=True)
+    print(f"{name:8s} L{level} ratio {total/len(comp):5.2f} blocks {jobs.size:6d} | " +
+          " | ".join(f"dbg{d:#x}: {ms:7.2f} ms {g:7.1f} GB/s ok={ok}" for d, ms, g, ok in res), flush=True)
 
 if __name__ == "__main__":
     classes = sys.argv[1:] or ["text", "source", "exe", "mixed"]
     mib = int(os.environ.get("KB_MIB", "16")); R = int(os.environ.get("KB_REPL", "16"))
     levels = [int(x) for x in os.environ.get("KB_LEVELS", "3").split(",")]
-    dbgs = [int(x) for x in os.environ.get("KB_DBG", "0").split(",")]
+    dbgs = [int(x, 0) for x in os.environ.get("KB_DBG", "0").split(",")]
     for c in classes:
         if c == "mixed": data = corpus.synth_silesia(mib << 20, seed=0)
         elif c == "zeros": data = bytes(mib << 20)

@@ -418,8 +418,8 @@ def pstream_decompress(comp: bytes, in_chunk, out_chunk, checksum=False, library
 
 
 def set_debug(lib_handle, flags: int) -> None:
-    """tools/ only: the kernel debug switches exist in libraries built with -DZXC_EXPERIMENT (tools/build_variant.sh <name>
-    -DZXC_EXPERIMENT, selected with ZXC_LIB_VARIANT); the release library does not export the setter."""
+    """tools/ only: the plan-forcing bits ZXC_DEV_DBG_* (zxc_dev.h) exist in libraries built with -DZXC_EXPERIMENT
+    (tools/build_variant.sh <name>, selected with ZXC_LIB_VARIANT); the release library does not export the setter."""
     if not hasattr(lib_handle, "zxc_mi355x__set_debug"):
         if flags:
             raise RuntimeError("this library was built without -DZXC_EXPERIMENT: set ZXC_LIB_VARIANT to an experiment build")

@@ -42,42 +42,17 @@ typedef v4u __attribute__((aligned(1))) v4u_unaligned;
 
 #include "zxc_lds.h"
 
-#ifndef RING_BYTES
 #define RING_BYTES 4096u   // sliding window kept in LDS; older history is read back through L2
-#endif
 #define RING_MASK (RING_BYTES - 1u)
 #define RING_WORDS (RING_BYTES / 4u)
-#ifndef REDIRECT_PASSES
 #define REDIRECT_PASSES 2   // chained containment levels resolved before round 0 (A/B: 0: -6 %, 1: -2 %, 2: best, 3: -1 %)
-#endif
-#ifndef SPARSE_MAX
 #define SPARSE_MAX 8   // at most this many unfinished sequences after a round: finish them one by one (A/B: 2: -0.3 %, 4: 0, 8: +1 %, 12 / 16: 0)
-#endif
-#ifndef TILE_MAX
 // A batch never spans more output than this: the ring must hold the batch, the not yet flushed tail of the
 // previous one (< 16 B) and the round-up of the zeroed region to 16 B.
 #define TILE_MAX 3584u
-#endif
-#ifndef LIT_MED
 #define LIT_MED 128u     // literal runs up to this long are put lane-per-sequence (16-byte grid steps), longer ones by the whole wave
                          // (A/B on the bench corpus: 32: -9 %, 48: 0, 96: +8 %, 128 / 160 / 224: +10 %)
-#endif
-#ifndef MATCH_MED
 #define MATCH_MED 128u   // matches up to this long are copied lane-per-sequence (16-byte grid steps)
-#endif
-#ifndef LIT_LOOP2
-#define LIT_LOOP2 1      // literal groups beyond the third: two per step, requested unconditionally (0: one conditional load per step)
-#endif
-#ifndef LIT_PRELOAD
-#define LIT_PRELOAD 3    // literal groups of a run requested before the dependency analysis (2: the third joins the loop; register diet A/B)
-#endif
-#ifndef FAR_PRELOAD
-#define FAR_PRELOAD 2    // far-source groups of a match requested before the literal puts (1: the second is fetched in its step)
-#endif
-#ifndef FAR_EARLY
-#define FAR_EARLY 0      // far-source groups: 0 requested after the literal wait; 1 by every lane, unconditionally, before it (A/B: -6.5 %);
-                         // 2 by the lanes that need them, before the dependency analysis (A/B: -4.5 %)
-#endif
 #define BYTEWISE_MAX 32u // short-period overlapping matches up to this long: lane-local byte loop
 
 // zxc_error_t values (reference include/zxc_error.h:38-74)
@@ -90,11 +65,6 @@ typedef v4u __attribute__((aligned(1))) v4u_unaligned;
 #define E_OVERFLOW (-10)
 #define E_BAD_BLOCK_TYPE (-13)
 #define E_DICT_REQUIRED (-15)
-
-// timing-ablation switches of the PivCo decoder (experiment builds only; see ZXC_EXPERIMENT below)
-#define DBG_NO_SEQ 512u      // stop after the literal / token sections are expanded (timing only)
-#define DBG_PIV_NO_P2 1024u  // PivCo: skip the bottom-up merges (timing only)
-#define DBG_PIV_NO_P1 2048u  // PivCo: skip everything after the tree set-up (timing only)
 
 #ifdef EXP_PHASES  // experiment only: per-phase shader-clock totals of each block, written over the block's first 32 output bytes
 #define PH(i) do { const uint64_t t_ = __builtin_readcyclecounter(); ph[i] += (uint32_t)(t_ - ph_last); ph_last = t_; } while (0)
@@ -151,11 +121,8 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 // LDS traffic between lanes of the one wave. One wave's DS instructions execute in program order, so a read issued
 // after another lane's write sees it: only the COMPILER must keep the order (wavefront-scope fence: no instruction,
 // where a workgroup-scope one drains the LDS queue with s_waitcnt lgkmcnt(0), ~10 times per batch).
-#ifndef LDS_FENCE_SCOPE
-#define LDS_FENCE_SCOPE "wavefront"
-#endif
 __device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, LDS_FENCE_SCOPE);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -234,11 +201,7 @@ __device__ __forceinline__ void flush_to(RingLds& L, Out& O, uint32_t upto, int 
     for (uint32_t c = O.flushed + 16u * (uint32_t)lane; c < end; c += 1024u) {
         const v4u v = ring_rd128_aligned(L, c);
         if (c + 16u <= O.out_len) {
-#ifdef FLUSH_NT
-            __builtin_nontemporal_store(v, (v4u*)(O.dst + c));
-#else
             *(v4u*)(O.dst + c) = v;  // one coalesced 16 B store per lane
-#endif
         } else if (c < O.out_len) {
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
             for (uint32_t k = 0; c + k < O.out_len; k++) O.dst[c + k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
@@ -411,12 +374,8 @@ __device__ __forceinline__ uint32_t parse_varints(const uint8_t* ext, uint32_t e
 
 // (Two other section decoders were built and measured this round — a top-down wavelet-tree walk and an LDS-tiled
 // bottom-up merge, tools/experiments/zxc_pivco_*.inc — both slower on the GPU than this one: DESIGN.md §3.)
-#ifdef PIV_VARIANT_FILE
-#include PIV_VARIANT_FILE
-#else
 #include "zxc_pivco.inc"
 #include "zxc_pivco_dir.inc"
-#endif
 #include "zxc_rapidhash.inc"
 
 // ------------------------------------------------------------------ block decode
@@ -657,11 +616,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const bool mine = (uint32_t)lane < k;
             const uint32_t tile_end = (uint32_t)__builtin_amdgcn_readlane((int)E, (int)(k - 1u));
             const uint32_t z_new = (tile_end + 15u) & ~15u;
-#ifdef EXP_NO_FAR  // experiment only (wrong output): every source is taken from the ring — the launch time with no read-back traffic at all
-            const uint32_t ring_lo = 0u;
-#else
             const uint32_t ring_lo = z_new > RING_BYTES ? z_new - RING_BYTES : 0u;
-#endif
             if (z_new > z_end) {
                 ring_zero(L, z_end, z_new, lane);
                 z_end = z_new;
@@ -676,16 +631,11 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const uint32_t le = la + ll;              // end of the run on its grid (bytes from the grid origin)
             const bool lshort = mine && ll != 0u && ll <= LIT_MED;
             const uint8_t* lsrc = S.lit + (int32_t)(lst - la);
-            v4u lv0 = {0, 0, 0, 0}, lv1 = {0, 0, 0, 0};
-#if LIT_PRELOAD >= 3
-            v4u lv2 = {0, 0, 0, 0};
-#endif
+            v4u lv0 = {0, 0, 0, 0}, lv1 = {0, 0, 0, 0}, lv2 = {0, 0, 0, 0};
             if (lshort) {
                 lv0 = ld128(lsrc);
                 if (le > 16u) lv1 = ld128(lsrc + 16u);
-#if LIT_PRELOAD >= 3
                 if (le > 32u) lv2 = ld128(lsrc + 32u);
-#endif
             }
 
             // ---- matches. Sequence i may only copy once every earlier match of this batch
@@ -704,20 +654,6 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const uint32_t me = ma + ml;
             const uint32_t mg = M - ma;          // grid origin (4-aligned output position)
             const bool overlap = off < ml;
-#if FAR_EARLY == 2
-            // Sources older than the ring come back from the block's own output through L2 (~2 K clocks under load).
-            // Such a source ends at least 350 bytes before the batch (ring_lo <= p - 497, ml <= MATCH_MED): the lane
-            // depends on nothing in this batch and is not redirected, and its bytes were flushed by an earlier batch
-            // (one wave's stores and loads reach L2 in program order). Its first two groups are requested HERE, behind
-            // the literal loads, so the round trip runs under the whole dependency analysis below.
-            const bool pf = pending && !fromdict && ml <= MATCH_MED && (!overlap || off >= 16u) && qa < ring_lo && qa >= 4u &&
-                            (qa - ma) + 32u <= O.out_pad;
-            v4u fr0 = {0, 0, 0, 0}, fr1 = {0, 0, 0, 0};
-            if (pf) {
-                fr0 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + (qa - ma)));
-                if (me > 16u) fr1 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + (qa - ma) + 16u));
-            }
-#endif
             {
                 // all lanes run the same bpermute sequence; only lanes reaching into the batch use it
                 const uint32_t ja = lanes_le(Es, fromdict ? 0u : qa);     // first lane with E > qa
@@ -749,42 +685,20 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const bool stepable = !fromdict && ml <= MATCH_MED && (!overlap || off >= 16u) && !(farsrc && qsrc < 4u);
             const bool bytewise = !fromdict && overlap && off < 16u && ml <= BYTEWISE_MAX && !farsrc;
             const bool is_long = !stepable && !bytewise;
-            bool far_waited = false;
             // Sources older than the ring come back from the block's own output through L2 (~700 clk). Such a
             // lane depends on nothing in this batch, so its first two groups are requested here: the literal
             // loads above are older (VMEM returns in order), so waiting for them below does not wait for
             // these, and the literal puts run under the round trip.
-#if FAR_EARLY != 2
             const bool pf = pending && need == 0ull && stepable && farsrc && sg + 32u <= O.out_pad;
             v4u fr0 = {0, 0, 0, 0}, fr1 = {0, 0, 0, 0};
-#endif
-#if FAR_EARLY == 2
-            __builtin_amdgcn_s_waitcnt(0);  // literal data and the far groups (also: every flush store has landed)
-            far_waited = true;
-#elif FAR_EARLY
-            // Both groups are requested by EVERY lane (lanes without a far source read the block's first 32
-            // bytes: one cache line, no divergence), right behind the literal loads and without waiting for
-            // anything: a wave's own stores and loads reach L2 in program order, so the flush stores that wrote
-            // those bytes are ahead of these loads, and with a fixed number of younger loads the compiler waits
-            // for the literal data with vmcnt(2) — the far round trip runs under the literal puts.
-            {
-                const uint8_t* fa = O.dst + (pf ? sg : 0u);
-                fr0 = __builtin_nontemporal_load((const v4u_unaligned*)fa);
-                fr1 = __builtin_nontemporal_load((const v4u_unaligned*)(fa + 16u));
-            }
-#else
             // (unconditional wait: the literal data is needed next anyway, and with every older access known to
             // be complete on both paths the compiler does not force these loads to finish before the literal puts)
             PH(13);
-            __builtin_amdgcn_s_waitcnt(0);  // also: the flush stores that wrote those bytes have landed
-            far_waited = true;
+            __builtin_amdgcn_s_waitcnt(0);  // also: the flush stores of earlier batches have landed (every far read below relies on it)
             if (pf) {
                 fr0 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + sg));
-#if FAR_PRELOAD >= 2
                 if (me > 16u) fr1 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + sg + 16u));
-#endif
             }
-#endif
             PH(2);
             // ---- literals, part 2: one masked ds_or group per 16 bytes of grid
             {
@@ -799,15 +713,12 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     const uint32_t t = (lshort && le > 16u) ? (le - 16u < 16u ? le - 16u : 16u) : 0u;
                     ring_or_group(L, lg + 16u, group_keep_first(L, lv1, t));
                 }
-#if LIT_PRELOAD >= 3
                 if (__ballot(lshort && le > 32u)) {
                     const uint32_t t = (lshort && le > 32u) ? (le - 32u < 16u ? le - 32u : 16u) : 0u;
                     ring_or_group(L, lg + 32u, group_keep_first(L, lv2, t));
                 }
-#endif
-#if LIT_LOOP2
 #pragma unroll 1
-                for (uint32_t go = LIT_PRELOAD >= 3 ? 48u : 32u; go < LIT_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
+                for (uint32_t go = 48u; go < LIT_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
                     const bool actA = lshort && le > go, actB = lshort && le > go + 16u;
                     if (__ballot(actA) == 0ull) break;
                     // (a load under a condition is waited for on the spot: idle lanes re-read the start of the literal stream)
@@ -818,17 +729,6 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     ring_or_group(L, lg + go, group_keep_first(L, lvA, tA));
                     ring_or_group(L, lg + go + 16u, group_keep_first(L, lvB, tB));
                 }
-#else
-#pragma unroll 1
-                for (uint32_t go = 48u; go < LIT_MED + 4u; go += 16u) {
-                    const bool act = lshort && le > go;
-                    if (__ballot(act) == 0ull) break;
-                    v4u lv = {0, 0, 0, 0};
-                    if (act) lv = ld128(lsrc + go);
-                    const uint32_t t = act ? (le - go < 16u ? le - go : 16u) : 0u;
-                    ring_or_group(L, lg + go, group_keep_first(L, lv, t));
-                }
-#endif
                 PH(7);  // (experiment builds: slot 7 = literal groups, slot 1 = long literals)
                 uint64_t lm = __ballot(mine && ll > LIT_MED);
                 while (lm) {
@@ -853,12 +753,11 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                         const bool act = sa && me > go;
                         if (__ballot(act) == 0ull) break;
                         const uint32_t q = sg + go;                       // source of this group
-                        const bool usepf = act && pf && go < 16u * FAR_PRELOAD;  // requested before the literal puts
+                        const bool usepf = act && pf && go < 32u;  // requested before the literal puts
                         const bool isfar = act && !usepf && farsrc && q < ring_lo;  // (farsrc lanes have qsrc >= 4: q does not wrap)
                         v4u d = {0, 0, 0, 0};
                         if (usepf) d = go == 0u ? fr0 : fr1;
                         if (__ballot(isfar)) {
-                            if (!far_waited) { __builtin_amdgcn_s_waitcnt(0); far_waited = true; }
                             if (isfar) d = far_rd128(O, q);
                         }
                         if (act && !isfar && !usepf) d = ring_rd128(L, q);
@@ -891,7 +790,6 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     const int j = __ffsll((unsigned long long)lm) - 1;
                     lm &= lm - 1ull;
                     const uint32_t jM = __shfl(M, j), jml = __shfl(ml, j), joff = __shfl(off, j);
-                    if (jM - joff < ring_lo && !far_waited) { __builtin_amdgcn_s_waitcnt(0); far_waited = true; }
                     coop_match<DICT>(L, O, jM, jml, joff, ring_lo, false, lane);
                 }
                 if (can) pending = false;
@@ -913,7 +811,6 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                                        joff = (uint32_t)__builtin_amdgcn_readlane((int)off, j);
                         const uint32_t jq = jM - joff;
                         if (((longm >> j) & 1ull) || jq < ring_lo) {
-                            if (jq < ring_lo && !far_waited) { __builtin_amdgcn_s_waitcnt(0); far_waited = true; }
                             coop_match<DICT>(L, O, jM, jml, joff, ring_lo, false, lane);
                             continue;
                         }
@@ -933,9 +830,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                         wave_lds_fence();
                     }
                     pending = false;
-#ifdef EXP_PHASES
                     PH(4);
-#endif
                     break;
                 }
             }
@@ -950,17 +845,6 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             PH(5);
         }
 
-#ifdef EXP_EXTRA_VALU  // experiment only: EXP_EXTRA_VALU independent VALU instructions per batch (is the kernel VALU-bound?)
-        {
-            uint32_t dummy = (uint32_t)lane;
-#pragma unroll
-            for (int i = 0; i < EXP_EXTRA_VALU; i++) asm volatile("v_add_u32 %0, %0, 1" : "+v"(dummy));
-            asm volatile("" ::"v"(dummy));
-        }
-#endif
-#ifdef EXP_EXTRA_SLEEP  // experiment only: the wave sleeps 64 x EXP_EXTRA_SLEEP clocks per batch (is it latency-bound?)
-        __builtin_amdgcn_s_sleep(EXP_EXTRA_SLEEP);
-#endif
         if (!strict && ((seq_base + k) & 3u) != 0u) {
             const uint32_t g = (seq_base + k) & ~3u;  // the group the next batch starts inside
             if (g >= seq_base) {
@@ -998,9 +882,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
 // The sequence executor of round 3 (8-waves-per-SIMD capable, far sources requested early, aligned loads, whole-KiB
 // flushes). Both kernels run it: the lean kernel on raw sections, the full kernel on the sections it has expanded into its
 // scratch slot; run_sequences() above remains for archives with a dictionary.
-#ifndef LEAN_WAVES_PER_SIMD
 #define LEAN_WAVES_PER_SIMD 6
-#endif
 #include "zxc_seq_lean.inc"
 
 // Scratch (expanded literals / PivCo ping-pong / decoded tokens) is only needed by blocks with
@@ -1126,7 +1008,7 @@ __device__ int rle_expand(const uint8_t* __restrict__ r_, uint32_t rsize, uint8_
 template <bool DICT>
 __device__ __forceinline__ int decode_lz_block(const uint8_t* data, uint32_t comp_sz, bool ghi, uint8_t* dst, uint32_t out_len,
                                uint32_t cap, uint32_t block_size, ScratchPool& pool, WaveLds& L, int lane,
-                               uint32_t dbg, const uint8_t* dict, uint32_t dict_size, const uint8_t* dict_huf, const bool strict) {
+                               const uint8_t* dict, uint32_t dict_size, const uint8_t* dict_huf, const bool strict) {
     if (comp_sz < 12u) return E_BAD_HEADER;
     LzStreams S;
     S.dict = dict;
@@ -1169,7 +1051,7 @@ __device__ __forceinline__ int decode_lz_block(const uint8_t* data, uint32_t com
             if (S.n_lit > block_size) return E_CORRUPT;
             uint8_t* scratch = scratch_acquire(pool, lane) + 16;  // (the executor reads up to 3 bytes below a literal run)
             const int rc = pivco_decode(pdata, lit_comp, scratch, S.n_lit, scratch + ZXC_DEV_SLOT_REGION(block_size) - 16u,
-                                  reinterpret_cast<PivLds&>(L), lane, enc_lit == 3u ? dict_huf : nullptr, dbg);
+                                  reinterpret_cast<PivLds&>(L), lane, enc_lit == 3u ? dict_huf : nullptr, 0u);
             if (rc != 0) return rc;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // literals are read back with L1-cached loads
@@ -1198,7 +1080,7 @@ __device__ __forceinline__ int decode_lz_block(const uint8_t* data, uint32_t com
         uint8_t* scratch = scratch_acquire(pool, lane);
         uint8_t* tokbuf = scratch + 2u * ZXC_DEV_SLOT_REGION(block_size);
         const int rc = pivco_decode(S.tok, tok_comp, tokbuf, S.n_seq, scratch + ZXC_DEV_SLOT_REGION(block_size),
-                                    reinterpret_cast<PivLds&>(L), lane, nullptr, dbg);
+                                    reinterpret_cast<PivLds&>(L), lane, nullptr, 0u);
         if (rc != 0) return rc;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -1211,38 +1093,25 @@ __device__ __forceinline__ int decode_lz_block(const uint8_t* data, uint32_t com
     S.off8 = enc_off;
     S.ext = S.offs + sz_off;
     S.ext_size = avail - (uint32_t)consumed;
-#ifdef ZXC_EXPERIMENT
-    if (dbg & DBG_NO_SEQ) return (int)out_len;
-#endif
     if (!DICT) return run_sequences_lean<false>(S, dst, out_len, cap, reinterpret_cast<LeanLds&>(L), lane, strict);
     return run_sequences<DICT, false>(S, dst, out_len, cap, L, lane, strict);
 }
 
-#ifndef WAVES_PER_SIMD
 #define WAVES_PER_SIMD 5   // 20 workgroups per CU fit the LDS (7.5 KiB each): keep everyone, callees included, within 96 VGPRs
-#endif
 template <bool DICT>
 __device__ __forceinline__ void decode_one_block(const uint8_t* __restrict__ comp, const zxc_dev_job_t* __restrict__ jobs,
                                                  uint32_t n_jobs, uint8_t* __restrict__ out, int32_t* __restrict__ status,
                                                  uint32_t block_size, uint32_t trailer_bytes, uint8_t* __restrict__ scratch,
-                                                 uint32_t scratch_stride, uint32_t dbg, uint32_t* __restrict__ slot_busy,
+                                                 uint32_t scratch_stride, uint32_t* __restrict__ slot_busy,
                                                  uint32_t n_slots, const uint32_t* __restrict__ order, uint32_t cap_override,
                                                  const uint8_t* __restrict__ dict, uint32_t dict_size,
                                                  const uint8_t* __restrict__ dict_huf, uint32_t slot) {
     // One workgroup (= one wavefront) per block: the hardware dispatcher hands out blocks as
     // wave slots free up, which is all the dynamic scheduling RAW-vs-dense blocks need.
-#if defined(EXP_NO_PIV_LDS) || defined(ZXC_LEAN_KERNEL)  // (experiment: occupancy without the PivCo tables; lean variant: never decodes a section)
-#ifdef LEAN_OWNER
-    __shared__ union { WaveLds w; LeanLds l; } lds;
-#else
+#ifdef ZXC_LEAN_KERNEL  // (lean variant: never decodes a section)
     __shared__ union { WaveLds w; } lds;
-#endif
-#else
-#ifdef LEAN_OWNER
-    __shared__ union { WaveLds w; PivLds p; LeanLds l; } lds;  // (the owner executor's queue and window make its LDS the larger one)
 #else
     __shared__ union { WaveLds w; PivLds p; } lds;  // the PivCo tables reuse the ring's LDS (never live together)
-#endif
 #endif
     WaveLds& L = lds.w;
     const int lane = threadIdx.x;
@@ -1277,7 +1146,7 @@ __device__ __forceinline__ void decode_one_block(const uint8_t* __restrict__ com
         } else if (trailer_bytes && ck_here && wave_checksum32(src + 8, comp_sz, lane) != uni(ld32(src + 8 + comp_sz))) {
             rc = E_BAD_CHECKSUM;  // per-block checksum of the compressed payload (zxc_decompress.c:1662-1666)
         } else if (type == 1u || type == 2u) {
-            rc = decode_lz_block<DICT>(src + 8, comp_sz, type == 2u, dst, out_len, cap, block_size, pool, L, lane, dbg, dict,
+            rc = decode_lz_block<DICT>(src + 8, comp_sz, type == 2u, dst, out_len, cap, block_size, pool, L, lane, dict,
                                  dict_size, dict_huf, cap_override != 0u);
             scratch_release(pool, lane);
         } else if (type == 0u) {  // RAW: stored bytes
@@ -1327,11 +1196,12 @@ zxc_decode_blocks_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* 
                          uint32_t trailer_bytes, uint8_t* __restrict__ scratch, uint32_t scratch_stride, uint32_t dbg,
                          uint32_t* __restrict__ slot_busy, uint32_t n_slots, const uint32_t* __restrict__ order,
                          uint32_t cap_override, uint32_t* __restrict__ list) {
+    // (dbg: no kernel-side bits any more; kept only because removing it changes the kernarg layout)
     // (one call site for both modes. Plain launch: one block per workgroup, grid = n_jobs, the hardware dispatcher is the
     // dynamic scheduler. List mode: a fixed grid of workgroups PULLS list entries through a counter — list[0] = number of
     // entries, list[1] = next entry to hand out, entries from list[2] — so a slow block delays only its own workgroup.)
     if (!list) {
-        decode_one_block<false>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride, dbg,
+        decode_one_block<false>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride,
                                 slot_busy, n_slots, order, cap_override, nullptr, 0u, nullptr, blockIdx.x);
         return;
     }
@@ -1341,7 +1211,7 @@ zxc_decode_blocks_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* 
         if (threadIdx.x == 0) i = atomicAdd(list + 1, 1u);
         i = uni(i);
         if (i >= n) break;
-        decode_one_block<false>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride, dbg,
+        decode_one_block<false>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride,
                                 slot_busy, n_slots, order, cap_override, nullptr, 0u, nullptr, uni(list[2u + i]));
         wave_lds_fence();
     }
@@ -1354,7 +1224,8 @@ zxc_decode_blocks_dict_kernel(const uint8_t* __restrict__ comp, const zxc_dev_jo
                               uint32_t* __restrict__ slot_busy, uint32_t n_slots, const uint32_t* __restrict__ order,
                               uint32_t cap_override, const uint8_t* __restrict__ dict, uint32_t dict_size,
                               const uint8_t* __restrict__ dict_huf) {
-    decode_one_block<true>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride, dbg,
+    // (dbg: no kernel-side bits any more; kept only because removing it changes the kernarg layout)
+    decode_one_block<true>(comp, jobs, n_jobs, out, status, block_size, trailer_bytes, scratch, scratch_stride,
                            slot_busy, n_slots, order, cap_override, dict, dict_size, dict_huf, blockIdx.x);
 }
 
@@ -1393,14 +1264,12 @@ __device__ __forceinline__ BlockClass classify_block(const uint8_t* __restrict__
                                                      uint32_t block_size, uint32_t cap) {
     BlockClass r = {ZXC_DEV_CLS_LEAN, 0, 0, 3, 3, 0, 0, 0, 0, 0, 0};
     if (!block_needs_full_kernel(src, src_sz, trailer_bytes)) return r;
-#ifndef EXP_RLE_FULL  // (A/B: RLE blocks to the full kernel, as in round 3)
     if (rle_block_for_lean(src + 8, ld32(src + 3), block_size, cap)) {
         r.cls = ZXC_DEV_CLS_LEAN_RLE;
         r.n_lit = ld32(src + 12);
         r.lit16 = r.n_lit ? (16u + r.n_lit + 64u + 15u) >> 4 : 0u;  // 16 bytes in front (the executor reads up to 3 bytes below a literal run), 64 behind
         return r;
     }
-#endif
     r.cls = ZXC_DEV_CLS_FULL;
     const uint8_t* data = src + 8;
     const uint32_t comp_sz = ld32(src + 3);

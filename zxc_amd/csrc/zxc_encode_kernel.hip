@@ -54,22 +54,6 @@ __device__ __forceinline__ uint32_t e_ld8(const uint8_t* p) { return *p; }
 __device__ __forceinline__ uint32_t e_ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ uint64_t e_ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 __device__ __forceinline__ v4u e_ld128(const uint8_t* p) { v4u v; __builtin_memcpy(&v, p, 16); return v; }
-// 16 bytes at any byte address, fetched DWORD-ALIGNED (four dwords + a fifth, moved into place with v_alignbyte): an unaligned
-// 16-byte gather costs the CU's address / data-return pipeline 4 clocks per lane, an aligned one 1.3
-// (profiles/r3_vmem_test.log), and the encoder's walk is bound by exactly that pipeline (profiles/r3enc_kprof.txt: TD 75 %
-// busy, every ALU under 30 %). `ok` = the 3 bytes in front of p are readable (not the very first bytes of the buffer).
-__device__ __forceinline__ v4u e_ld128_al(const uint8_t* p, bool ok) {
-    const uint32_t sh = ok ? ((uint32_t)(uintptr_t)p & 3u) : 0u;
-    const uint8_t* b = p - sh;
-    const v4u a = e_ld128(b);
-    const uint32_t e = e_ld32(b + 16);
-    v4u r;
-    r.x = __builtin_amdgcn_alignbyte(a.y, a.x, sh);
-    r.y = __builtin_amdgcn_alignbyte(a.z, a.y, sh);
-    r.z = __builtin_amdgcn_alignbyte(a.w, a.z, sh);
-    r.w = __builtin_amdgcn_alignbyte(e, a.w, sh);
-    return r;
-}
 __device__ __forceinline__ uint32_t e_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // LDS traffic between the lanes of the ONE wave of a workgroup: order it (lgkmcnt only). __syncthreads() would also wait
@@ -213,13 +197,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
 
     // Level 6 (the level table's ZXC_ENC_PARSE_OPTIMAL): the match finder only RECORDS the longest match of every position (mp[], in the block's PivCo scratch, which is
     // idle until the sections are coded); the price-based optimal parse (zxc_optparse.inc) then picks the sequences.
-#ifdef EXP_NO_OPTPARSE  // (A/B: level 6 with the lazy parse of round 3)
-    const bool OPT = false;
-#elif defined(EXP_OPTPARSE_L7)  // (A/B: level 7 with the optimal parse too)
-    const bool OPT = DEEP && !GHI && huf != 0u && block_size <= OPT_MAX_BLOCK;
-#else
     const bool OPT = DEEP && !GHI && huf != 0u && lazy == ZXC_ENC_PARSE_OPTIMAL && block_size <= OPT_MAX_BLOCK;
-#endif
     uint32_t* const mp = OPT ? (uint32_t*)(huf_scratch + (uint64_t)b * 4u * ((uint64_t)block_size + 64u)) : nullptr;
     uint32_t skip_until = 0;  // OPT: positions below it lie strictly inside a match of >= OPT_LONG_SKIP bytes and are not searched
     // Skip acceleration (round 5; reference: step = step_base + (distance from the anchor >> step_shift), src/lib/zxc_compress.c:1176, :1860 —
@@ -271,7 +249,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
         publish(i, ins, h, d0);
     }
 
-    // The main loop takes ENC_U chunks of 64 positions per iteration (round 3 experiment, kept as a template parameter). A
+    // The main loop takes U chunks of 64 positions per iteration (round 3 experiment, kept as a template parameter; every entry passes 1). A
     // chunk's work is a chain of dependent steps — head lookup, publish, chain links, candidate bytes from memory, parse,
     // emission — and a workgroup owns 20-48 KiB of tables, so only 3-8 waves share a CU and every unit is under half busy
     // (profiles/r3enc_kprof.txt: ~850 instructions, 500 of them scalar, per chunk at ~12 clocks each). With U chunks in flight
@@ -279,9 +257,6 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     // wave issues in order and its own dependent ALU / LDS / scalar chains are the time, not the memory round trips.
     // Semantics per chunk are unchanged: its head lookups see every earlier chunk (those of the same iteration included:
     // lookup and publish alternate chunk by chunk), never its own positions.
-#ifdef ENC_ALIGNED_CANDIDATES
-    const bool lowok = b != 0u || D != 0u || ((uint32_t)(uintptr_t)src & 3u) == 0u;  // (3 readable bytes in front of `in`)
-#endif
     uint32_t c0 = D & ~63u;
     v4u v_next[U];  // 16 bytes at every position of the next U chunks
 #pragma unroll
@@ -334,17 +309,10 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
 #pragma unroll
         // (positions in front of the parse position lie inside the match carried into the chunk: they are in the tables, but the
         //  parse never asks for their matches — no candidates are fetched for them)
-#ifdef EXP_ENC_WALK_ALL
-        for (uint32_t u = 0; u < U; u++) { lenA[u] = 0; distA[u] = 0; triedA[u] = 0; dA[u] = d0A[u]; }
-#else
         for (uint32_t u = 0; u < U; u++) {
             const bool skip = !OPT && dry >= ENC_DRY_CHUNKS && (((c0 >> 6) + u) & 3u) != 0u;  // (wave-uniform)
             lenA[u] = 0; distA[u] = 0; triedA[u] = 0; dA[u] = ((OPT || iA[u] >= pos) && !skip) ? d0A[u] : 0u;
         }
-#endif
-#ifdef EXP_ENC_NOWALK  // (experiment, wrong output: no candidate is fetched or compared — lookup, publish, parse and emission only)
-        for (uint32_t u = 0; u < U; u++) dA[u] = 0;
-#endif
         for (;;) {
             bool actA[U];
             uint64_t anyact = 0;
@@ -375,11 +343,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
                 dkA[u][0] = actA[u] ? dA[u] : 0u;
 #pragma unroll
                 for (uint32_t k = 0; k < NC; k++) {
-#ifdef ENC_ALIGNED_CANDIDATES  // experiment (profiles/r3q_encal.log: +1 % at level 3, -11 % at levels 5-7)
-                    c1A[u][k] = e_ld128_al(pme - dkA[u][k], lowok || iA[u] - dkA[u][k] >= 4u);
-#else
                     c1A[u][k] = e_ld128(pme - dkA[u][k]);
-#endif
                     dkA[u][k + 1] = next(u, dkA[u][k], triedA[u] + k + 1u < depth);
                 }
             }
@@ -491,9 +455,6 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
                 pos = cu + 64u;
                 continue;
             }
-#ifdef EXP_ENC_NOPARSE  // (experiment, wrong output: the match finder alone — nothing is parsed or emitted)
-            pos = cu + 64u; continue;
-#endif
             const uint32_t i = iA[u], len = lenA[u], dist = distA[u], bk = bkA[u];
             const uint64_t v = vA[u];
             ENC_T(5);  // (round bookkeeping, backward extension)
@@ -551,7 +512,6 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             const uint32_t etot = (uint32_t)__builtin_amdgcn_readlane((int)eincl, 63);
             const uint32_t nsel = __popcll(sel);
             if (seq_count + nsel > max_seq || ext_count + etot > ext_cap) { overflow = true; break; }
-    #ifndef EXP_ENC_NOSTORE  // (experiment, wrong output: the main loop without its emission stores)
             if (issel) {
                 const uint32_t sidx = seq_count + __popcll(below);
                 if (GHI) {  // 32-bit word LL(8) | ML-5(8) | offset-1(16), src/lib/zxc_compress.c:1907-1913
@@ -566,7 +526,6 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
                 if (ll >= esc) { put_varint(e, ll - esc); e += varint_len(ll - esc); }
                 if (mlm >= esc) put_varint(e, mlm - esc);
             }
-    #endif
             // only the 8-bit / 16-bit offset decision needs the maximum: one ballot instead of a wave reduction
             if (__ballot(issel && dist > 256u)) max_off = 65535u;
             else if (sel && max_off == 0u) max_off = 1u;
@@ -587,9 +546,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             const uint64_t litmask = __ballot(islit);
             // (the byte is already here: low byte of the 16 fetched for this position. No load in the emission: a load whose result a
             // store needs makes the wave wait for every store in front of it, i.e. for this chunk's own sequence stores)
-    #ifndef EXP_ENC_NOSTORE
             if (islit) lit_out[lit_count + __popcll(litmask & lt_mask)] = (uint8_t)v;
-    #endif
             lit_count += __popcll(litmask);
             seq_count += nsel;
             dry = nsel ? 0u : dry + 1u;  // (also counts the chunks inside a long match: behind one, up to three chunks go unsearched until the next sequence — rare, and three scalar instructions here instead of nine)
@@ -601,22 +558,6 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             pos = next_pos;
             ENC_T(7);  // emission
         }
-#ifdef EXP_ENC_EXTRA_SALU  // experiment only: EXP_ENC_EXTRA_SALU scalar instructions per chunk (is the encoder scalar-issue-bound?)
-        {
-            uint32_t sd = c0;
-#pragma unroll
-            for (int q = 0; q < EXP_ENC_EXTRA_SALU; q++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sd) : : "scc");
-            asm volatile("" ::"s"(sd));
-        }
-#endif
-#ifdef EXP_ENC_EXTRA_VALU  // experiment only: EXP_ENC_EXTRA_VALU vector instructions per chunk
-        {
-            uint32_t vd = (uint32_t)lane;
-#pragma unroll
-            for (int q = 0; q < EXP_ENC_EXTRA_VALU; q++) asm volatile("v_add_u32 %0, %0, 1" : "+v"(vd));
-            asm volatile("" ::"v"(vd));
-        }
-#endif
         // a match reaching past these chunks: skip the chunks it covers entirely
         c0 += 64u * U;
         if (pos > c0) c0 = pos & ~63u;
@@ -862,16 +803,14 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
 //     5     2^13     2^14        18          6                   256        lazy 2    GLO
 //     6     2^13     2^15        33          6                   256        optimal   GLO + PivCo literals (zxc_optparse.inc)
 //     7     2^13     2^15        66          6                   256        lazy 2    GLO + PivCo literals and tokens
-#ifndef ENC_U
-#define ENC_U 1u   // chunks of 64 positions in flight per loop iteration (A/B, profiles/r3p_encu.log: 1 / 2 / 3 / 4 all within 2 % at
-                   // level 3 — a wave issues in order, only the memory round trips overlap — and 1 keeps the archives of round 2 byte for byte)
-#endif
+// Every entry runs ONE chunk of 64 positions per loop iteration (U = 1; A/B, profiles/r3p_encu.log: 1 / 2 / 3 / 4 all within 2 % at
+// level 3 — a wave issues in order, only the memory round trips overlap — and 1 keeps the archives of round 2 byte for byte).
 #define ZXC_ENCODE_ENTRY(name, hb, cwb, ghi, waves, nc)                                                                    \
     extern "C" __global__ void __launch_bounds__(64, waves) name(                                                      \
         const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size, uint8_t* __restrict__ slots,          \
         uint32_t slot_stride, uint32_t* __restrict__ sizes, uint32_t n_blocks, uint32_t with_checksum, uint32_t depth, \
         uint32_t sufficient, uint32_t lazy, uint32_t dict_size, uint8_t* __restrict__ huf_scratch, uint32_t huf) {     \
-        encode_one_block<hb, cwb, ghi, nc, ENC_U>(src, src_size, block_size, slots, slot_stride, sizes, n_blocks, with_checksum,  \
+        encode_one_block<hb, cwb, ghi, nc, 1u>(src, src_size, block_size, slots, slot_stride, sizes, n_blocks, with_checksum,  \
                                        depth, sufficient, lazy, dict_size, huf_scratch, huf);                          \
     }
 ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l1, 4096u, 0u, true, 5, 3u)    // level 1 (A/B: one candidate per round instead of three: -3 %)
@@ -879,34 +818,19 @@ ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l2, 4096u, 11u, true, 3, 3u)   // leve
 // Level 3 (round 4): head 2^13 + ring 2^11 = 20 KiB -> EIGHT workgroups per CU = two waves on every SIMD instead of six (two SIMDs
 // with one wave and nothing to hide its round trips behind): +40 % at the same search effort, for 1.25 % of ratio (the ring's far
 // hops); four candidates in ONE round and two lazy probes buy 0.8 % back for 9 % of the time (profiles/r4f_encoder_ablations.log).
-#ifndef ENC_L3_HB  // (A/B: tools/build_enc_variant.sh)
-#define ENC_L3_HB 13u
-#define ENC_L3_CWB 11u
-#define ENC_L3_NC 4u
-#endif
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l3, (1u << ENC_L3_HB), ENC_L3_CWB, false, 2, ENC_L3_NC) // level 3
-#ifndef ENC_L4_HB  // (A/B: tools/build_enc_variant.sh)
-#define ENC_L4_HB 13u
-#define ENC_L4_CWB 12u   // 24 KiB -> six per CU: level 4's size bound (1.05 x the reference, today 1.047 x) has nothing to spend on a smaller ring
-#define ENC_L4_NC 6u    // (all six candidates in one round: +3 % over two rounds of three, sizes -0.08 %)
-#endif
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l4, (1u << ENC_L4_HB), ENC_L4_CWB, false, 2, ENC_L4_NC) // level 4
-#ifndef ENC_L57_HB  // (A/B: tools/build_enc_variant.sh)
-#define ENC_L57_HB 13u   // (A/B at level 5 on text, head / ring: 2^14 / 2^14 3.70 GB/s ratio 2.301; 2^13 / 2^14 4.76, 2.287;
-#define ENC_L57_CWB 14u  //  2^14 / 2^13 4.99, 2.275; 2^13 / 2^13 6.30, 2.249: the head table is the cheaper one to halve)
-#endif
-#ifndef ENC_L57_NC
-#define ENC_L57_NC 6u   // candidates per round of the deep levels (18 / 33 / 66 per position: half the round trips of 3)
-#endif
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l57, (1u << ENC_L57_HB), ENC_L57_CWB, false, 1, ENC_L57_NC) // level 5
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l3, 8192u, 11u, false, 2, 4u) // level 3
+// Level 4: a ring of 2^12 = 24 KiB -> six per CU: level 4's size bound (1.05 x the reference, today 1.047 x) has nothing to spend on a
+// smaller ring; all six candidates in one round: +3 % over two rounds of three, sizes -0.08 %.
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l4, 8192u, 12u, false, 2, 6u) // level 4
+// Level 5 (A/B on text, head / ring: 2^14 / 2^14 3.70 GB/s ratio 2.301; 2^13 / 2^14 4.76, 2.287; 2^14 / 2^13 4.99, 2.275; 2^13 / 2^13
+// 6.30, 2.249: the head table is the cheaper one to halve). Six candidates per round of the deep levels (18 / 33 / 66 per position:
+// half the round trips of 3).
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l57, 8192u, 14u, false, 1, 6u) // level 5
 // Levels 6-7 (round 5): a chain ring of 2^15 entries. The reference's chain reaches 65 536 positions back (ZXC_LZ_WINDOW_SIZE,
 // src/lib/zxc_common.c:199); with 2^14 the ultra levels came out 2.2-2.5 % larger than the reference's on text, with 2^15 0.8-0.9 %
 // (2^16: 0.3 %, but 144 KiB of tables = one workgroup per CU): 80 KiB of tables = two workgroups per CU instead of three —
 // the ultra tiers buy ratio with speed (tests/test_wave_emu.py, profiles/r5f_*).
-#ifndef ENC_L67_CWB
-#define ENC_L67_CWB 15u
-#endif
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l67, (1u << ENC_L57_HB), ENC_L67_CWB, false, 1, ENC_L57_NC) // levels 6-7
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l67, 8192u, 15u, false, 1, 6u) // levels 6-7
 
 // [dict | block b] images for the dictionary path: work + b * (block_size + dict_size)
 extern "C" __global__ void __launch_bounds__(64)

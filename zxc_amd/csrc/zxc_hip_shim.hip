@@ -77,9 +77,7 @@ extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32
 // Per-device scratch for expanded literal / token sections: one slot per resident
 // workgroup. Grown on demand, never shrunk; freed at process exit by the driver.
 #define ZXC_MAX_DEVICES 16
-#ifndef ZXC_RLE_LEAN_MAX_JOBS
 #define ZXC_RLE_LEAN_MAX_JOBS 16384u
-#endif
 #define ZXC_ORDER_STREAMS 16
 #define ZXC_POOLS 10 /* block_size_log2 12..21 */
 /* One scratch pool per block size: slot stride and count depend on block_size only, so concurrent launches on different streams
@@ -98,7 +96,7 @@ static struct {
 } g_dev[ZXC_MAX_DEVICES];
 static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER;
 
-#ifdef ZXC_EXPERIMENT  // timing ablations exist only in experiment builds (tools/build_variant.sh); release passes dbg = 0
+#ifdef ZXC_EXPERIMENT  // the plan-forcing bits ZXC_DEV_DBG_* (zxc_dev.h) exist only in experiment builds (tools/build_variant.sh)
 static uint32_t g_debug_flags = 0;
 #else
 #define g_debug_flags 0u
@@ -113,7 +111,7 @@ static int current_device(void) {
 extern "C" {
 
 #ifdef ZXC_EXPERIMENT
-/* experiment builds only (not in include/): kernel timing ablations for tools/kbench.py */
+/* experiment builds only (not in include/): forces decode plans (ZXC_DEV_DBG_NO_ORDER / _NO_TWO_PASS) for tools/kbench.py */
 __attribute__((visibility("default"))) void zxc_mi355x__set_debug(uint32_t flags) { g_debug_flags = flags; }
 #endif
 
@@ -339,11 +337,6 @@ static void launch_rle(const Launch& L, hipStream_t st) {
                        L.rscratch, L.ctl + ZXC_DEV_CTL_RLE_LIST, L.pre_entries + L.n - 1u);
 }
 
-#ifdef EXP_SKIP_FULL  // (experiment: the lean kernel's own time; the full kernel's blocks stay undecoded, nothing is forked)
-static const bool skip_full = true;
-#else
-static const bool skip_full = false;
-#endif
 // The two-pass plans' streams, s0 = the caller's, aux / aux2 = its slot's helpers:
 //   TWO_PASS:      s0: [RLE literals,] lean kernel over every block, [checksum merge] | aux: full kernel over its list
 //                  | aux2: [checksum kernel]
@@ -368,8 +361,8 @@ static int join(Ord& o, hipStream_t s0, bool aux, bool aux2) {
 
 static int enqueue_two_pass(const Launch& L) {
     Ord& o = *L.o; const hipStream_t s0 = L.s0;
-    const bool aux = !skip_full && hipEventRecord(o.fork, s0) == hipSuccess && fork_to(o, o.aux);
-    if (!skip_full) launch_full(L, aux ? o.aux : s0, L.n < L.max_slots ? L.n : L.max_slots);
+    const bool aux = hipEventRecord(o.fork, s0) == hipSuccess && fork_to(o, o.aux);
+    launch_full(L, aux ? o.aux : s0, L.n < L.max_slots ? L.n : L.max_slots);
     const bool aux2 = L.plan.ck_apart && aux && fork_to(o, o.aux2);
     if (L.plan.ck_apart)
         hipLaunchKernelGGL(zxc_block_checksum_kernel, dim3((L.n + 8u) / 9u), dim3(64), 0, aux2 ? o.aux2 : s0, L.comp, L.jobs, L.n, L.order, L.ck_bad);
@@ -384,7 +377,7 @@ static int enqueue_two_pass(const Launch& L) {
 
 static int enqueue_two_pass_pre(const Launch& L) {
     Ord& o = *L.o;
-    const bool forked = !skip_full && hipEventRecord(o.fork, L.s0) == hipSuccess && fork_to(o, o.aux) && fork_to(o, o.aux2);
+    const bool forked = hipEventRecord(o.fork, L.s0) == hipSuccess && fork_to(o, o.aux) && fork_to(o, o.aux2);
     const hipStream_t s0 = L.s0, s1 = forked ? o.aux : s0, s2 = forked ? o.aux2 : s0;
     uint32_t* sec_hdr = L.ctl + ZXC_DEV_CTL_SEC;
     auto grid = [&](uint32_t per_cu) { const uint32_t g = per_cu * L.cus; return dim3(2u * L.n < g ? 2u * L.n : g); };
@@ -394,7 +387,7 @@ static int enqueue_two_pass_pre(const Launch& L) {
     // (the small class runs beside the medium / large ones, on its own stream: +1 % level 7, +4 % level 6)
     hipLaunchKernelGGL(zxc_pivco_sections_small_kernel, grid(10), dim3(128), 0, s2, L.comp, L.secs, sec_hdr, L.pre, L.pscratch);
     if (forked && hipEventRecord(o.small_done, s2) != hipSuccess) return fail(o);
-    if (!skip_full) launch_full(L, s2, L.n < L.max_slots ? L.n : L.max_slots);
+    launch_full(L, s2, L.n < L.max_slots ? L.n : L.max_slots);
     hipLaunchKernelGGL(zxc_pivco_sections_medium_kernel, grid(3), dim3(256), 0, s0, L.comp, L.secs + 2u * (size_t)L.n, sec_hdr + 2, L.pre, L.pscratch);
     hipLaunchKernelGGL(zxc_pivco_sections_large_kernel, grid(2), dim3(512), 0, s0, L.comp, L.secs + 4u * (size_t)L.n, sec_hdr + 4, L.pre, L.pscratch);
     if (forked && hipStreamWaitEvent(s0, o.small_done, 0) != hipSuccess) return fail(o);
@@ -505,9 +498,6 @@ static int encode_launch(const void* d_src, uint64_t src_size, uint32_t block_si
         in = (const uint8_t*)d_work;
     }
     zxc_enc_level_t lp = zxc_enc_level_bs(level, block_size);
-#ifdef EXP_ENC_ENV  // (A/B builds only: search effort from the environment, "depth,sufficient,lazy")
-    if (const char* e = getenv("ZXC_EXP_ENC")) { unsigned a, b2, c; if (sscanf(e, "%u,%u,%u", &a, &b2, &c) == 3) { lp.depth = a; lp.sufficient = b2; lp.lazy = c; } }
-#endif
     uint8_t* huf_scratch = NULL;
     if (lp.huf) {
         // levels 6-7: level buffers + coded sections of the PivCo encoder, 4 x (block_size + 64) per block. Stream-ordered

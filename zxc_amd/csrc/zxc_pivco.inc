@@ -22,12 +22,8 @@
 #define PIV_MAXLEN 11
 #define PIV_INT 256      // internal nodes of a 256-symbol code: <= 255
 #define PIV_SMAP 3584u   // slots of the slot -> node map of one group of 64 small nodes (above it: binary search)
-#ifndef PIV_INFLIGHT
 #define PIV_INFLIGHT 8   // 64-symbol words of a merge whose child runs are requested together (A/B: 12 and 16 are slower: fewer whole rounds)
-#endif
-#ifndef PIV_FLAT_INFLIGHT
 #define PIV_FLAT_INFLIGHT 8  // 64-symbol steps of a flat node's code run requested together
-#endif
 
 #ifdef EXP_PIV_PROF  // experiment only: shader-clock split of the section decoder, per block (tools/abbench.py AB_PIVPROF=1)
 __shared__ uint32_t g_piv_prof[16];
@@ -76,7 +72,7 @@ __device__ __forceinline__ void g_st32(uint8_t* p, uint32_t v) { *(gptr32_t)(uin
 
 // One depth of pass 2.
 __device__ __forceinline__ void piv_level(PivLds& P, int d, const uint8_t* __restrict__ body, uint32_t bsize,
-                                          uint8_t* __restrict__ buf_d, const uint8_t* __restrict__ buf_c, int lane, uint32_t dbg) {
+                                          uint8_t* __restrict__ buf_d, const uint8_t* __restrict__ buf_c, int lane) {
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     auto rd_child = [&](uint32_t idx) -> uint32_t { return g_nt_ld8(buf_c + idx); };
     auto wr = [&](uint32_t idx, uint32_t v) { g_st8(buf_d + idx, v); };
@@ -153,9 +149,6 @@ __device__ __forceinline__ void piv_level(PivLds& P, int d, const uint8_t* __res
             for (uint32_t q = 0; q < ncs; q++) P.smap[nincl - ncs + q] = (uint8_t)lane;
             wave_lds_fence();
         }
-#ifdef ZXC_EXPERIMENT
-        if (!(dbg & 4096u))  // DBG_PIV_NO_SMALL (timing only)
-#endif
         for (uint32_t s0 = 0; s0 < ntotal; s0 += 64u) {
             const uint32_t sidx = s0 + (uint32_t)lane;
             const bool valid = sidx < ntotal;
@@ -204,9 +197,6 @@ __device__ __forceinline__ void piv_level(PivLds& P, int d, const uint8_t* __res
         }
         PIVP(0);
         uint64_t bigm = __ballot(nc > 64u);
-#ifdef ZXC_EXPERIMENT
-        if (dbg & 8192u) bigm = 0;  // DBG_PIV_NO_BIG (timing only)
-#endif
         // up to 4096 bits of a big node's run, one 64-bit word per lane, requested by EVERY lane (lanes beyond the run
         // re-read its last word and drop it): an unconditional load can stay in flight across the work on another node
         auto run_words = [&](const uint8_t* runp, uint32_t bits) -> uint64_t {
@@ -369,11 +359,7 @@ __device__ __forceinline__ void piv_level(PivLds& P, int d, const uint8_t* __res
 #pragma unroll
                                 for (int u = 0; u < PIV_INFLIGHT; u++) {
                                     const uint32_t v = word_value(cur[u], mcur[u], leaf0, leaf1, sym0, sym1);
-#ifdef EXP_PIV_NOSTORE  // experiment only (wrong output): what the merge loop costs without its stores
-                                    asm volatile("" ::"v"(v));
-#else
                                     g_st8(buf_d + so + kb + 64u * (r * PIV_INFLIGHT + (uint32_t)u) + lane, v);
-#endif
                                 }
                                 rb0 = tb0; rb1 = tb1;
                                 nb0 = xb0; nb1 = xb1;
@@ -518,7 +504,7 @@ __device__ __forceinline__ int piv_tree(const uint8_t* __restrict__ lens128, PL&
 struct PivPrep { const uint8_t* body; uint32_t bsize, maxlen, single; };
 template <typename PL>
 __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, uint32_t psize, uint32_t n, PL& P, int lane,
-                                           const uint8_t* __restrict__ shared_lens, uint32_t dbg, PivPrep& R) {
+                                           const uint8_t* __restrict__ shared_lens, PivPrep& R) {
     R.single = 256u;
     R.maxlen = 0;
     const uint32_t hdr = shared_lens ? 0u : 128u;
@@ -547,9 +533,6 @@ __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, 
         return 0;
     }
 
-#ifdef ZXC_EXPERIMENT
-    if (dbg & 2048u) return 0;  // DBG_PIV_NO_P1
-#endif
     PIVP(13);
     // ---- C. pass 1: counts and run pointers, one depth at a time
     if (lane == 0) P.cnt[0] = n;
@@ -657,10 +640,11 @@ __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, 
 
 // Decodes one section: payload[0..psize) -> out[0..n) (tmp: scratch of >= n bytes; shared_lens: the dictionary's 128-byte
 // code-length table for enc_lit = 3, zxc_huffman.c:2467-2473, the payload then has no inline header). Returns 0 or a zxc error.
+// (The unnamed last parameter is unused: it keeps the function's symbol, and so the code object, as it was; it goes with the
+// decode kernels' dbg.)
 __device__ int pivco_decode(const uint8_t* __restrict__ payload_, uint32_t psize, uint8_t* __restrict__ out_, uint32_t n,
                             uint8_t* __restrict__ tmp_, PivLds& P, int lane, const uint8_t* __restrict__ shared_lens_,
-                            uint32_t dbg) {
-    dbg = uni(dbg);
+                            uint32_t) {
     const uint8_t* __restrict__ payload = uni_ptr(payload_);
     uint8_t* __restrict__ out = uni_ptr(out_);
     uint8_t* __restrict__ tmp = uni_ptr(tmp_);
@@ -668,7 +652,7 @@ __device__ int pivco_decode(const uint8_t* __restrict__ payload_, uint32_t psize
     psize = uni(psize);
     n = uni(n);
     PivPrep R;
-    const int prc = piv_prepare(payload, psize, n, P, lane, shared_lens, dbg, R);
+    const int prc = piv_prepare(payload, psize, n, P, lane, shared_lens, R);
     if (prc != 0) return prc;
     if (R.single < 256u) {
         for (uint32_t i = lane; i < n; i += 64u) out[i] = (uint8_t)R.single;
@@ -676,15 +660,12 @@ __device__ int pivco_decode(const uint8_t* __restrict__ payload_, uint32_t psize
     }
     const uint8_t* body = R.body;
     const uint32_t bsize = R.bsize, maxlen = R.maxlen;
-#ifdef ZXC_EXPERIMENT
-    if (dbg & (1024u | 2048u)) return 0;  // DBG_PIV_NO_P2 / DBG_PIV_NO_P1
-#endif
     PIVP(6);
     // ---- D. pass 2: rebuild sequences bottom-up
     for (int d = (int)maxlen - 1; d >= 0; d--) {
         uint8_t* const buf_d = (d & 1) ? tmp : out;
         const uint8_t* const buf_c = (d & 1) ? out : tmp;  // children live one depth down
-        piv_level(P, d, body, bsize, buf_d, buf_c, lane, dbg);
+        piv_level(P, d, body, bsize, buf_d, buf_c, lane);
         __builtin_amdgcn_s_waitcnt(0);  // this depth's stores are out before the next depth gathers them (nt loads: L2)
         wave_lds_fence();
         PIVP(7);

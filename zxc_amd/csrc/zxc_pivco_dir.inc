@@ -253,9 +253,6 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
     __syncthreads();
     int rc = (int)uni((uint32_t)P.rc_tree);
     const uint32_t maxlen = uni(P.maxlen), single = uni(P.single);
-#ifdef EXP_PDIR_STOP1  // (experiment, wrong output: stop after the staging)
-    rc = 1;
-#endif
     // ---- 2. run offsets, child counts (wave 0) | flat tables (waves 1..)
     if (rc == 0) {
         if (wave == 0u) {
@@ -273,9 +270,6 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
         __syncthreads();
         rc = (int)uni((uint32_t)P.rc_pass1);
     }
-#ifdef EXP_PDIR_STOP2  // (experiment, wrong output: stop in front of the node records and the walk)
-    rc = 1;
-#endif
     if (rc == 0 && !single) {
         pdir_records(P, tid, (uint32_t)THREADS, maxlen);
         __syncthreads();
@@ -351,10 +345,7 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const bool on = (act >> u) & 1u, fin = on && done[u];
-                    uint32_t sv = flat[u] ? fsym[u] : child[u];
-#ifdef EXP_PDIR_BADOUT  // (experiment: garbage sections, the lean kernel must name an error)
-                    sv ^= 0x5Au;
-#endif
+                    const uint32_t sv = flat[u] ? fsym[u] : child[u];
                     const uint32_t a1 = acc[u] | (sv << (8u * (pos[u] & 3u)));
                     const bool full = (pos[u] & 3u) == 3u;
                     const uint32_t npos = pos[u] + (full ? kStride - 3u : 1u);  // next byte of my dword, or my next dword
@@ -370,9 +361,6 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
         }
     }
     __syncthreads();  // the next section reuses the tables
-#ifdef EXP_PDIR_STOP3  // (experiment, wrong output: the whole decoder runs, the lean kernel then skips the block)
-    rc = 1;
-#endif
     return rc;
 }
 

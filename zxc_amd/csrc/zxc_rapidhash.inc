@@ -91,10 +91,8 @@ __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len,
 
 // ------------------------------------------------------------------ nine blocks per wavefront (round 6)
 typedef uint32_t rh_v4u __attribute__((ext_vector_type(4)));
-#ifndef RH_GROUP_DEPTH
 #define RH_GROUP_DEPTH 8   // stripes of loads in flight per lane. (Round 6 also tried to fit the kernel BESIDE six lean waves per SIMD — 32 VGPRs: depth 1
                            // still needs 34-36, one granule too many — so its waves take the place of decode waves while they run.)
-#endif
 // The bulk loop has seven accumulators per block and no more: hashed inside the decode kernels, 57 of a wave's 64 lanes idle through
 // ~290 stripes of two 64-bit multiplies each (the checksummed decode cost 10.5 % of the launch in rounds 4-5). Here lanes 7 g .. 7 g + 6
 // hash block g of nine (lane 63 idles), every lane of a group carrying one accumulator of ITS block; the <= 112-byte tail and the

@@ -16,9 +16,6 @@
 //     hands every lane the (up to two) varints it needs.
 //   * dependency analysis: one 6-step binary search over packed (end | start << 16) positions relative to the batch,
 //     three probes behind it instead of a second search; the redirect passes test readiness on a ballot.
-#ifdef LEAN_OWNER  // (A/B, round 6: the output-owner executor takes the place of the one below; decode_lz_block_lean at the end is shared)
-#include "zxc_seq_own.inc"
-#else
 struct __attribute__((aligned(16))) LeanLds : RingLds {
     uint32_t vval[64];   // general varint path: values / positions of at most LEAN_VARINTS varints per batch
     uint32_t vpos[66];
@@ -28,33 +25,6 @@ struct __attribute__((aligned(16))) LeanLds : RingLds {
 // this kernel ~2 % of its time whatever it moves), so up to 1 KiB + a partial 16-byte chunk of the previous batches stays
 // unflushed in the ring beside the batch: a tile spans at most RING_BYTES - 1024 - 32 bytes.
 #define LEAN_TILE_MAX (RING_BYTES - 1056u)
-#ifndef LIT_PREFETCH_AHEAD
-#define LIT_PREFETCH_AHEAD 256u
-#endif
-
-// Experiment switches of the loads (A/B builds only, tools/build_variant.sh; the product Makefile defines none of them):
-// EXP_NT_FAR / EXP_NT_LIT / EXP_NT_TOK = nontemporal (L1-bypassing) loads for the far sources / literal runs / token streams;
-// EXP_PRIO = s_setprio around the request phase (1) or from the batch's top to the end of its requests (2).
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-#ifdef EXP_NT_FAR
-#define FLD128(p) __builtin_nontemporal_load((const v4u_unaligned*)(p))
-#define FLD32(p) __builtin_nontemporal_load((const u32_unaligned*)(p))
-#else
-#define FLD128(p) ld128(p)
-#define FLD32(p) ld32(p)
-#endif
-#ifdef EXP_NT_LIT
-#define LLD128(p) __builtin_nontemporal_load((const v4u_unaligned*)(p))
-#define LLD32(p) __builtin_nontemporal_load((const u32_unaligned*)(p))
-#else
-#define LLD128(p) ld128(p)
-#define LLD32(p) ld32(p)
-#endif
-#if defined(EXP_PRIO) && EXP_PRIO
-#define LEAN_PRIO(when, v) do { if (EXP_PRIO == (when) || (when) == 0) __builtin_amdgcn_s_setprio(v); } while (0)
-#else
-#define LEAN_PRIO(when, v) do { } while (0)
-#endif
 
 #ifdef ASM_MARKERS  // (design builds: tools/isacount.py counts the instructions between these comments)
 #define PHM(i) asm volatile("; PHMARK " #i)
@@ -111,7 +81,6 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
 
     while (seq_base < n_total) {
         PHM(0);
-        LEAN_PRIO(2, 2);
         const uint32_t s = seq_base + (uint32_t)lane;
         const bool real = s < S.n_seq;
         bool valid = s < n_total;
@@ -242,16 +211,6 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
         }
         const int32_t xi0 = (int32_t)(cur + (uint32_t)lane);
         const uint32_t nxw = ld8(S.ext + (xi0 < ext_last ? xi0 : ext_last));
-#ifdef LIT_PREFETCH
-        // The literal loads of a batch can only be requested once its cursors are known, and are needed a few hundred clocks
-        // later: the lines they want are touched a batch or two ahead (one dword per 64-byte sector of the LIT_PREFETCH bytes
-        // behind this batch's literals; the value is kept alive to the end of the batch and never used).
-        uint32_t lpf;
-        {
-            const uint32_t o = lst + LIT_PREFETCH_AHEAD + 64u * ((uint32_t)lane & (LIT_PREFETCH / 64u - 1u));
-            lpf = ld32(S.lit + (o + 4u <= n_lit ? (o & ~3u) : 0u));
-        }
-#endif
 
         PHM(4);
         if (k == 0u) {
@@ -279,19 +238,13 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const bool mine = (uint32_t)lane < k;
             const uint32_t tile_end = (uint32_t)__builtin_amdgcn_readlane((int)E, (int)(k - 1u));
             const uint32_t z_new = (tile_end + 15u) & ~15u;
-#ifdef ABL_ALL_NEAR  // (timing only, wrong output: every match source is taken from the ring and nothing is read back from memory —
-                     // what a window of the WHOLE block on chip would cost at this kernel's occupancy: DESIGN.md §3)
-            const uint32_t ring_lo = 0u;
-#else
             const uint32_t ring_lo = z_new > RING_BYTES ? z_new - RING_BYTES : 0u;
-#endif
             if (z_new > z_end) {
                 ring_zero(L, z_end, z_new, lane);
                 z_end = z_new;
             }
 
             PHM(5);
-            LEAN_PRIO(1, 2);
             // ---- requests. Literal run: group g = the 16 bytes at output position (est & ~3) + 16 g, from literal offset
             // lst - (est & 3) + 16 g (loads take any alignment: the bytes arrive on the destination's dword grid).
             const uint32_t la = est & 3u;
@@ -303,10 +256,10 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             // for the lanes whose last bytes sit there; v_alignbyte moves them onto the destination grid.
             const uint32_t lob = lo + 4u + lit_ph;           // offset from lit_al = (S.lit - 8) rounded down to a dword
             const uint32_t ldl = lob & 3u;
-            const v4u lv0 = LLD128(lit_al + (lshort ? (lob & ~3u) : 8u));
-            const uint32_t lv0e = LLD32(lit_al + ((lshort && ldl != 0u && le > 12u) ? (lob & ~3u) + 16u : 8u));
-            const v4u lv1 = LLD128(litm4 + (lshort && le > 16u ? lo + 16u : 4u - lit_ph));
-            const v4u lv2 = LLD128(litm4 + (lshort && le > 32u ? lo + 32u : 4u - lit_ph));
+            const v4u lv0 = ld128(lit_al + (lshort ? (lob & ~3u) : 8u));
+            const uint32_t lv0e = ld32(lit_al + ((lshort && ldl != 0u && le > 12u) ? (lob & ~3u) + 16u : 8u));
+            const v4u lv1 = ld128(litm4 + (lshort && le > 16u ? lo + 16u : 4u - lit_ph));
+            const v4u lv2 = ld128(litm4 + (lshort && le > 32u ? lo + 32u : 4u - lit_ph));
 
             // Match: group g = 16 bytes at (M & ~3) + 16 g, from source position qsrc - (M & 3) + 16 g.
             const uint32_t ma = M & 3u;
@@ -321,40 +274,25 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             // block's own output in memory, the first two are requested here.
             // (round 5: output leaves the ring in whole KiB — see the flush at the batch's end — so the source must also END inside what
             //  has been flushed; a source that straddles the flushed mark, ~3 % of them, takes the near path's whole-wave copy)
-#ifndef LEAN_FLUSH_CHUNKS
             const bool far_ok = far_en && pending && qa < ring_lo && ml <= MATCH_MED && qa >= 4u && qa + ml <= O.flushed &&
                                 (qa - ma) + ((me + 15u) & ~15u) + 4u <= O.out_pad;
-#else  // (A/B: round 4's flush of every finished 16-byte chunk)
-            const bool far_ok = far_en && pending && qa < ring_lo && ml <= MATCH_MED && qa >= 4u &&
-                                (qa - ma) + ((me + 15u) & ~15u) + 4u <= O.out_pad;
-#endif
             const uint32_t sgf = qa - ma;
             const uint32_t fdl = sgf & 3u;  // (the block's slot is 16-byte aligned: the source's phase against the destination grid)
             v4u fr0 = {0, 0, 0, 0}, fr1 = {0, 0, 0, 0};
             uint32_t fr0e = 0;
-#ifndef ABL_ALL_NEAR
-            if (far_en)  // wave-uniform. Group 0 dword-aligned like the literals'; group 1 is wanted by few lanes.
-#else
-            if (false)
-#endif
-            {
-                fr0 = FLD128(dst + (far_ok ? (sgf & ~3u) : 0u));
-                fr0e = FLD32(dst + ((far_ok && fdl != 0u && me > 12u) ? (sgf & ~3u) + 16u : 0u));
-                fr1 = FLD128(dst + (far_ok && me > 16u ? sgf + 16u : 0u));
+            if (far_en) {  // wave-uniform. Group 0 dword-aligned like the literals'; group 1 is wanted by few lanes.
+                fr0 = ld128(dst + (far_ok ? (sgf & ~3u) : 0u));
+                fr0e = ld32(dst + ((far_ok && fdl != 0u && me > 12u) ? (sgf & ~3u) + 16u : 0u));
+                fr1 = ld128(dst + (far_ok && me > 16u ? sgf + 16u : 0u));
             }
 
-            LEAN_PRIO(0, 0);
             // ---- dependencies. Sequence i may only copy once every earlier match of this batch that overlaps its
             // source [qa, qb) is finished: lanes ja .. jb-1.
             const uint32_t qb = (qa + ml < M) ? qa + ml : M;
             uint64_t need = 0;
             uint32_t qsrc = qa;
             const bool inb = pending && !far_ok && qb > p;  // the source reaches into this batch
-#ifdef ABL_NO_DEPS
-            if (false) {
-#else
             if (__ballot(inb)) {
-#endif
                 // positions relative to the batch: 12 bits each (a tile spans at most TILE_MAX < 4096 bytes)
                 const uint32_t key = mine ? ((E - p) | ((M - p) << 16)) : 0xFFFFFFFFu;
                 const uint32_t xa = qa > p ? qa - p : 0u;
@@ -402,7 +340,6 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
 
             PHM(8);
             // ---- literals: one masked ds_or group per 16 bytes of grid (the far groups stay in flight)
-#ifndef ABL_NO_LIT
             {
                 const uint32_t lg = est - la;
                 {
@@ -424,19 +361,17 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     const uint32_t t = (lshort && le > 32u) ? (le - 32u < 16u ? le - 32u : 16u) : 0u;
                     ring_or_group(L, lg + 32u, group_keep_first(L, lv2, t));
                 }
-#ifndef ABL_NO_LITTAIL
 #pragma unroll 1
                 for (uint32_t go = 48u; go < LIT_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
                     const bool actA = lshort && le > go, actB = lshort && le > go + 16u;
                     if (__ballot(actA) == 0ull) break;
-                    const v4u lvA = LLD128(litm4 + (actA ? lo + go : 4u - lit_ph));
-                    const v4u lvB = LLD128(litm4 + (actB ? lo + go + 16u : 4u - lit_ph));
+                    const v4u lvA = ld128(litm4 + (actA ? lo + go : 4u - lit_ph));
+                    const v4u lvB = ld128(litm4 + (actB ? lo + go + 16u : 4u - lit_ph));
                     const uint32_t tA = actA ? (le - go < 16u ? le - go : 16u) : 0u;
                     const uint32_t tB = actB ? (le - go - 16u < 16u ? le - go - 16u : 16u) : 0u;
                     ring_or_group(L, lg + go, group_keep_first(L, lvA, tA));
                     ring_or_group(L, lg + go + 16u, group_keep_first(L, lvB, tB));
                 }
-#endif
                 uint64_t lm = __ballot(mine && ll > LIT_MED);
                 while (lm) {
                     const int j = __ffsll((unsigned long long)lm) - 1;
@@ -446,16 +381,10 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     coop_copy<false>(L, O, je, 0, S.lit + js, jl, 0, lane);
                 }
             }
-#endif
 
             PHM(9);
             // ---- far matches: their own pass (nothing in this batch can be their source)
-#ifdef ABL_NO_FARPUT
-            if (far_ok) pending = false;
-            if (false) {
-#else
             if (__ballot(far_ok)) {
-#endif
                 {
                     const uint32_t t = far_ok ? (me < 16u ? me : 16u) : 0u;
                     v4u d;
@@ -471,28 +400,23 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     const uint32_t t = (far_ok && me > 16u) ? (me - 16u < 16u ? me - 16u : 16u) : 0u;
                     ring_or_group(L, mg + 16u, group_keep_first(L, fr1, t));
                 }
-#ifndef ABL_NO_FARTAIL
 #pragma unroll 1
                 for (uint32_t go = 32u; go < MATCH_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
                     const bool actA = far_ok && me > go, actB = far_ok && me > go + 16u;
                     if (__ballot(actA) == 0ull) break;
-                    const v4u fA = FLD128(dst + (actA ? sgf + go : 0u));
-                    const v4u fB = FLD128(dst + (actB ? sgf + go + 16u : 0u));
+                    const v4u fA = ld128(dst + (actA ? sgf + go : 0u));
+                    const v4u fB = ld128(dst + (actB ? sgf + go + 16u : 0u));
                     const uint32_t tA = actA ? (me - go < 16u ? me - go : 16u) : 0u;
                     const uint32_t tB = actB ? (me - go - 16u < 16u ? me - go - 16u : 16u) : 0u;
                     ring_or_group(L, mg + go, group_keep_first(L, fA, tA));
                     ring_or_group(L, mg + go + 16u, group_keep_first(L, fB, tB));
                 }
-#endif
                 if (far_ok) pending = false;
             }
             wave_lds_fence();
 
             PHM(10);
             // ---- near matches: rounds over the dependency masks
-#ifdef ABL_NO_NEAR
-            pending = false;
-#endif
             for (uint32_t round = 0;; round++) {
                 const uint64_t dm = __ballot(!pending);
                 if (dm == ~0ull) break;
@@ -579,51 +503,12 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             p = tile_end;
             lp = (uint32_t)__builtin_amdgcn_readlane((int)(lst + ll), (int)(k - 1u));
             __builtin_amdgcn_s_waitcnt(0);  // (only the flush stores stay outstanding across the loop edge)
-#ifdef EXP_EXTRA_VMEM  // experiment only: EXP_EXTRA_VMEM more 16-byte loads per batch, every lane the block's first bytes (L1 hits: the price of the instruction itself)
-            {
-#pragma unroll
-                for (int i = 0; i < EXP_EXTRA_VMEM; i++) {
-                    v4u t;
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(t) : "v"(dst + 16 * i) : "memory");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    asm volatile("" ::"v"(t));
-                }
-            }
-#endif
-#ifndef ABL_NO_FLUSH
             // Whole KiB only: one full 64-lane store instruction per KiB (round 4 flushed every finished 16-byte chunk: 87 store
             // instructions per 64 KiB block instead of 64, and a vector-memory instruction is what a batch pays for: +1-2 %,
             // profiles/r5e_*). Up to 1 KiB + 15 bytes of earlier batches stay in the ring: LEAN_TILE_MAX leaves room for them.
-#ifndef LEAN_FLUSH_CHUNKS
             flush_to(L, O, p & ~1023u, lane);
-#else
-            flush_to(L, O, p, lane);
-#endif
-#endif
         }
         PHM(14);
-#ifdef EXP_EXTRA_VALU  // experiment only: EXP_EXTRA_VALU independent VALU instructions per batch (is the kernel VALU-issue-bound?)
-        {
-            uint32_t dummy = (uint32_t)lane;
-#pragma unroll
-            for (int i = 0; i < EXP_EXTRA_VALU; i++) asm volatile("v_add_u32 %0, %0, 1" : "+v"(dummy));
-            asm volatile("" ::"v"(dummy));
-        }
-#endif
-#ifdef EXP_EXTRA_SALU  // experiment only: EXP_EXTRA_SALU scalar instructions per batch
-        {
-            uint32_t sd = seq_base;
-#pragma unroll
-            for (int i = 0; i < EXP_EXTRA_SALU; i++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sd) : : "scc");
-            asm volatile("" ::"s"(sd));
-        }
-#endif
-#ifdef EXP_EXTRA_SLEEP  // experiment only: the wave sleeps 64 x EXP_EXTRA_SLEEP clocks per batch (is it latency-bound?)
-        __builtin_amdgcn_s_sleep(EXP_EXTRA_SLEEP);
-#endif
-#ifdef LIT_PREFETCH
-        asm volatile("" ::"v"(lpf));
-#endif
         if (!strict && ((seq_base + k) & 3u) != 0u) {  // (only behind a cut batch: full batches keep seq_base a multiple of 4)
             const uint32_t g = (seq_base + k) & ~3u;   // the group the next batch starts inside
             if (g >= seq_base) {
@@ -646,8 +531,6 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
     }
     return (int)p;
 }
-
-#endif  // LEAN_OWNER
 
 // Block body of the lean kernel. Returns the decoded size / a negative zxc_error_t, or ZXC_DEV_DEFER for a block that
 // needs the full kernel (a coded literal / token section).

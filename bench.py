@@ -26,6 +26,19 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 
 
+def usable_cpus():
+    """CPUs this process may keep busy: its affinity mask, capped by a cgroup v2 CPU quota (cpu.max) where one is set —
+    os.cpu_count() counts the whole host, and pools sized by it only oversubscribe a quota."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, -(-int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return max(1, n)
+
+
 def archive_parts(comp, block_size):
     """A seekable archive written by the reference -> (its blocks region, comp_sizes[] of its seek table,
     its 16-byte file header, its 8-byte EOF block). Layout: docs/FORMAT.md §3-§9 (header 16 B, blocks, EOF
@@ -115,6 +128,30 @@ def _ref_join(futs, block_size):
     return b"".join(bytes(p[0]) for p in parts), np.concatenate([p[1] for p in parts]), parts[0][2], parts[0][3]
 
 
+class _InlineExecutor:
+    """_ref_submit's executor inside a worker that already has a core of its own: every piece runs at submit."""
+
+    def submit(self, fn, *args):
+        from concurrent.futures import Future
+        f = Future()
+        f.set_result(fn(*args))
+        return f
+
+
+def _prep_tile(task):
+    """One corpus tile of build_rank_corpus, start to end in one worker process: its plaintext, the reference's seekable
+    archive of it, and that archive's blocks [lo, hi). -> (blocks region as a bytearray, comp_sizes[lo:hi], header16, eof8,
+    source name, the plaintext or None)"""
+    t, lo, hi, level, block_size, checksum, keep_plain = task
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle_py
+    data, src = tile_bytes(t, block_size, None)
+    futs = _ref_submit(_InlineExecutor(), oracle_py.Ref(), f"tile{t}_{src}", data, level, block_size, checksum)
+    region, sizes, hdr, eof = _ref_join(futs, block_size)
+    off = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
+    return bytearray(region[off[lo]: off[hi]]), sizes[lo:hi], hdr, eof, src, (data if keep_plain else None)
+
+
 def _ref_archive(ref, futs, block_size, total):
     """The whole seekable archive (without checksums) from its pieces: header, blocks, EOF block, SEK block written by the
     reference's zxc_write_seek_table, footer (decoded size, 4 zero bytes) — the bytes zxc_compress writes in one call."""
@@ -130,11 +167,12 @@ def _ref_archive(ref, futs, block_size, total):
     return hdr + region + eof + sek.raw + int(total).to_bytes(8, "little") + (0).to_bytes(4, "little")
 
 
-def build_rank_corpus(first, last, level, block_size, pool, dev, checksum=False, baseline_tiles=0):
+def build_rank_corpus(first, last, level, block_size, pool, dev, checksum=False, baseline_tiles=0, want=True):
     """Blocks [first, last) of the global corpus, encoded by the unmodified reference (the metric is defined on
     archives written by the reference encoder: "silesia.tar at -3"; untimed input preparation). Only the tiles
-    this range touches are generated; compressed blocks and plaintext go straight to HBM, tile by tile.
-    -> (d_comp, comp_sizes of the range, d_want, header16, eof8, info, the CPU baseline's archive or None)"""
+    this range touches are generated, one tile per task of the process pool `pool` (None: in this process); compressed
+    blocks, and the plaintext if `want`, go straight to HBM, tile by tile as they come back.
+    -> (d_comp, comp_sizes of the range, d_want or None, header16, eof8, info, the CPU baseline's archive or None)"""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from zxc_amd import corpus
@@ -151,29 +189,25 @@ def build_rank_corpus(first, last, level, block_size, pool, dev, checksum=False,
     src = ""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     base_futs, base_data, base_arc = None, [], None
-    with ThreadPoolExecutor(max_workers=max(1, min(64, (os.cpu_count() or 1) // world // 2))) as tp:
-        futs = []
-        for t in tiles:
-            data, src = tile_bytes(t, block_size, pool)
+    tasks = [(t, max(first, t * tb) - t * tb, min(last, (t + 1) * tb) - t * tb, level, block_size, checksum, want or i < baseline_tiles)
+             for i, t in enumerate(tiles)]
+    with ThreadPoolExecutor(max_workers=max(1, usable_cpus() // world)) as tp:
+        for (t, lo, hi, *_), (region, sizes, hdr, eof, src, data) in zip(tasks, pool.imap(_prep_tile, tasks) if pool else map(_prep_tile, tasks)):
             if len(base_data) < baseline_tiles:  # the CPU baseline's archive: the first tiles as ONE seekable archive
                 base_data.append(data)
                 if len(base_data) == min(baseline_tiles, len(tiles)):
                     joined = b"".join(base_data)
                     base_futs = (_ref_submit(tp, ref, f"base{tiles[0]}x{len(base_data)}_{src}", joined, level, block_size, False), len(joined))
                     del joined
-            lo, hi = max(first, t * tb) - t * tb, min(last, (t + 1) * tb) - t * tb
-            wants.append(torch.frombuffer(bytearray(data[lo * block_size: hi * block_size]), dtype=torch.uint8).to(dev))
-            futs.append((lo, hi, _ref_submit(tp, ref, f"tile{t}_{src}", data, level, block_size, checksum)))
-            del data
-        for lo, hi, fs in futs:
-            region, sizes, hdr, eof = _ref_join(fs, block_size)
-            off = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
-            regions.append(torch.frombuffer(bytearray(region[off[lo]: off[hi]]), dtype=torch.uint8).to(dev))
-            sizes_all.append(sizes[lo:hi])
+            if want:
+                wants.append(torch.frombuffer(bytearray(data[lo * block_size: hi * block_size]), dtype=torch.uint8).to(dev))
+            regions.append(torch.frombuffer(region, dtype=torch.uint8).to(dev))
+            sizes_all.append(sizes)
+            del data, region
         if base_futs is not None:
             base_arc = _ref_archive(ref, base_futs[0], block_size, base_futs[1])
     d_comp = torch.cat(regions + [torch.zeros(256, dtype=torch.uint8, device=dev)])  # (+ slack for 16-byte reads)
-    d_want = torch.cat(wants)
+    d_want = torch.cat(wants) if want else None
     info = dict(prep_s=round(time.time() - t0, 1), tiles=len(tiles), encoder="reference _ref", source=src)
     return d_comp, np.concatenate(sizes_all), d_want, hdr, eof, info, base_arc
 
@@ -239,9 +273,10 @@ def cpu_baseline(comp, total, budget_s=12.0, what="corpus tile 0"):
             "sample": f"oracle C restatement, first {n >> 20} MiB, 1 thread"}
 
 
-def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True, block_size=None, extras=True, dump_dir=None):
+def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True, block_size=None, extras=True, dump_dir=None,
+               full=True):
     """configs[2]: per-block LZ77 hash-chain match finding + GLO serialisation on the device over enc_mib MiB of unique
-    enwik-like text per GPU, source resident in HBM, compressed blocks left in HBM. value = source GB/s. The
+    enwik-like text per GPU, source resident in HBM, compressed blocks left in HBM. value = source GB/s. full: the
     compressed stream of the LAST timed launch is round-tripped: every block decoded on the device and compared
     with the source (all of it), and a 64 MiB sample decoded by the unmodified reference decoder on the host.
     dump_dir: rank 0 writes that launch's block sizes and compacted blocks there (dump_outputs).
@@ -251,7 +286,7 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
     import zxc_amd
     from zxc_amd import corpus
     rank, world, local, backend, dist = comm
-    pool = mp.get_context("spawn").Pool(max(1, min(32, (os.cpu_count() or 1) // world)))
+    pool = mp.get_context("spawn").Pool(max(1, min(32, usable_cpus() // world)))
     L = zxc_amd.lib()
     L.zxc_mi355x_gather_blocks_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     dev = torch.device("cuda", local)
@@ -293,8 +328,8 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
-    # ---- round trip of what was timed: compact the slots (seek-table entries = d_sizes), decode every block on
-    # the device, compare with the source
+    # ---- what was timed: compact the slots (seek-table entries = d_sizes); full: round trip, every block decoded on the
+    # device and compared with the source
     sizes = d_sizes.to(torch.int64)
     offs = torch.cumsum(sizes, 0) - sizes
     csize = int(sizes.sum().item())
@@ -306,26 +341,27 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
     if dump_dir and rank == 0:
         torch.cuda.synchronize()
         dump_outputs(dump_dir, {"encode_block_sizes": d_sizes, "encode_blocks": d_comp[:csize]})
-    jobs = np.zeros(nb, dtype=zxc_amd.api.JOB_DTYPE)
-    jobs["comp_off"] = offs.cpu().numpy().astype(np.uint64)
-    jobs["comp_size"] = sizes.cpu().numpy().astype(np.uint32)
-    jobs["out_off"] = np.arange(nb, dtype=np.uint64) * bs
-    jobs["out_len"] = np.minimum(bs, n - np.arange(nb, dtype=np.int64) * bs).astype(np.uint32)
-    d_jobs = torch.frombuffer(bytearray(jobs.tobytes()), dtype=torch.uint8).to(dev)
-    d_out = torch.zeros(n + 256, dtype=torch.uint8, device=dev)
-    d_st = torch.zeros(nb, dtype=torch.int32, device=dev)
-    zxc_amd.decode_blocks_device(d_comp.data_ptr(), d_jobs.data_ptr(), nb, d_out.data_ptr(), d_st.data_ptr(), bs, False, stream)
-    torch.cuda.synchronize()
-    assert torch.equal(d_st, torch.from_numpy(jobs["out_len"].astype(np.int32)).to(dev)), "a block written by the encoder does not decode"
-    assert torch.equal(d_out[:n], d_src[:n]), "encoder output does not decode to the source"
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle_py
     ref_ok = None
-    if oracle_py.Ref.available():  # the unmodified reference decoder accepts the stream (host API: same kernels + framing)
-        comp = zxc_amd.compress(sample, level, bs, True)
-        rc, out = oracle_py.Ref().decompress(comp, len(sample))
-        assert rc == len(sample) and out == sample, "reference decoder rejects the encoder's archive"
-        ref_ok = f"{len(sample) >> 20} MiB archive decoded bit-exact by the unmodified reference decoder"
+    if full:
+        jobs = np.zeros(nb, dtype=zxc_amd.api.JOB_DTYPE)
+        jobs["comp_off"] = offs.cpu().numpy().astype(np.uint64)
+        jobs["comp_size"] = sizes.cpu().numpy().astype(np.uint32)
+        jobs["out_off"] = np.arange(nb, dtype=np.uint64) * bs
+        jobs["out_len"] = np.minimum(bs, n - np.arange(nb, dtype=np.int64) * bs).astype(np.uint32)
+        d_jobs = torch.frombuffer(bytearray(jobs.tobytes()), dtype=torch.uint8).to(dev)
+        d_out = torch.zeros(n + 256, dtype=torch.uint8, device=dev)
+        d_st = torch.zeros(nb, dtype=torch.int32, device=dev)
+        zxc_amd.decode_blocks_device(d_comp.data_ptr(), d_jobs.data_ptr(), nb, d_out.data_ptr(), d_st.data_ptr(), bs, False, stream)
+        torch.cuda.synchronize()
+        assert torch.equal(d_st, torch.from_numpy(jobs["out_len"].astype(np.int32)).to(dev)), "a block written by the encoder does not decode"
+        assert torch.equal(d_out[:n], d_src[:n]), "encoder output does not decode to the source"
+        if oracle_py.Ref.available():  # the unmodified reference decoder accepts the stream (host API: same kernels + framing)
+            comp = zxc_amd.compress(sample, level, bs, True)
+            rc, out = oracle_py.Ref().decompress(comp, len(sample))
+            assert rc == len(sample) and out == sample, "reference decoder rejects the encoder's archive"
+            ref_ok = f"{len(sample) >> 20} MiB archive decoded bit-exact by the unmodified reference decoder"
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -348,8 +384,10 @@ def encode_run(args, level, enc_mib, steps, warmup, comm, with_cpu_baseline=True
         "roofline": {"bound": "hbm", "achieved": round(algo / kern_s / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(algo / kern_s / 1e9 / HBM_PEAK_GBS, 4), "traffic": profiled_traffic("encode_l%d" % level, enc_mib=enc_mib, block_size=bs),
                      "kernel": f"zxc_encode_blocks_kernel_{entry}", "avg_launch_ms": round(kern_s * 1e3, 4),
-                     "algorithmic_bytes_per_launch": algo},
-        "round_trip": {"device": f"all {nb} blocks decoded on the device == source", "reference": ref_ok}}
+                     "algorithmic_bytes_per_launch": algo}}
+    if not full:
+        return line
+    line["round_trip"] = {"device": f"all {nb} blocks decoded on the device == source", "reference": ref_ok}
     if not extras:
         return line
     # incompressible input (where the reference's match finder accelerates its steps, src/lib/zxc_compress.c:1176): 256 MiB of random bytes,
@@ -473,16 +511,15 @@ def prep_estimate_s(n_tiles, level, world):
 
 
 def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_launch=False, with_cpu_baseline=True,
-               cpu_budget_s=12.0, block_size=None, dump_dir=None):
+               cpu_budget_s=12.0, block_size=None, dump_dir=None, full=True):
     """One decode measurement: this rank's block range of ONE corpus of world x tiles tiles, `steps` timed launches
-    bracketed by barrier + synchronize, every byte and status checked before and after. dump_dir: rank 0 writes what the
-    last timed launch left (block statuses, decoded bytes) there (dump_outputs). -> the result line on rank 0."""
+    bracketed by barrier + synchronize, every block status checked before them. full: every byte checked as well, before
+    and after (a launch of its own). dump_dir: rank 0 writes what the last timed launch left (block statuses, decoded
+    bytes) there (dump_outputs). -> the result line on rank 0."""
     import multiprocessing as mp
     import torch
     import zxc_amd
     rank, world, local, backend, dist = comm
-    # generator processes (numpy only; spawn keeps them free of torch state)
-    pool = mp.get_context("spawn").Pool(max(1, min(48, (os.cpu_count() or 1) // world)))
     dev = torch.device("cuda", local)
     bs = block_size or args.block_size
     strong = getattr(args, "scaling", "weak") == "strong"
@@ -500,8 +537,10 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
         raise SystemExit(f"bench.py: preparing {my_tiles} tiles per rank at level {level} would take ~{est:.0f} s (> --max-prep-s "
                          f"{args.max_prep_s}): lower --tiles / --total-tiles or raise --max-prep-s")
     base_tiles = min(CPU_BASELINE_TILES, tiles) if (with_cpu_baseline and world == 1) else 0
-    d_comp, my_sizes, d_want, hdr, eof, prep, tile0_comp = build_rank_corpus(first, last, level, bs, pool, dev, checksum, base_tiles)
-    pool.close()
+    # tile workers (numpy + the reference library; spawn keeps them free of torch state)
+    with mp.get_context("spawn").Pool(max(1, min(my_tiles, usable_cpus() // world))) as pool:
+        d_comp, my_sizes, d_want, hdr, eof, prep, tile0_comp = build_rank_corpus(first, last, level, bs, pool, dev, checksum, base_tiles,
+                                                                                 want=full)
     if world > 1:  # control plane only: every rank learns the whole seek table (4 B per block)
         gathered = [None] * world
         dist.all_gather_object(gathered, my_sizes.tobytes())
@@ -528,7 +567,8 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
 
     def check(when):
         assert torch.equal(d_status, want_status), f"{when}: block status mismatch on rank {rank}"
-        assert torch.equal(d_out[:out_bytes], d_want), f"{when}: decoded bytes differ from the corpus on rank {rank}"
+        if full:
+            assert torch.equal(d_out[:out_bytes], d_want), f"{when}: decoded bytes differ from the corpus on rank {rank}"
 
     calib = None
     if calib_launch:
@@ -536,7 +576,7 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
     for _ in range(max(warmup, 1)):
         step()
     torch.cuda.synchronize()
-    check("before timing")  # bit-exactness of what is being timed: every block's status and every byte
+    check("before timing")  # what is being timed decodes: every block's status (full: and every byte)
 
     if world > 1:
         dist.barrier()
@@ -554,11 +594,12 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
     kern_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
     if dump_dir and rank == 0:
         dump_outputs(dump_dir, {"decode_status": d_status, "decode_out": d_out[:out_bytes]})
-    d_out.zero_()
-    d_status.fill_(-999)
-    step()
-    torch.cuda.synchronize()
-    check("after timing")
+    if full:
+        d_out.zero_()
+        d_status.fill_(-999)
+        step()
+        torch.cuda.synchronize()
+        check("after timing")
     # every rank's own numbers (an imbalance must be visible): control plane only, after the timed region
     # (world_seen / backend / device: what THIS rank's process group and device really were — the driver's N-GPU line can be checked
     #  for "N ranks, N distinct devices" from the line alone)
@@ -618,7 +659,8 @@ def decode_run(args, level, tiles, steps, warmup, comm, checksum=False, calib_la
                                if level <= 5 else "zxc_pivco_sections_{small,medium,large}_kernel (coded sections -> scratch), then "
                                                   "zxc_decode_blocks_lean_pre_kernel; zxc_decode_blocks_kernel beside them for the rest",
                      "avg_launch_ms": round(avg_kernel_s * 1e3, 4), "algorithmic_bytes_per_launch": algo_bytes},
-        "bit_exact": "every byte and block status checked before and after the timed loop",
+        "bit_exact": "every byte and block status checked before and after the timed loop" if full else
+                     "every block status checked before the timed loop (bytes: --full)",
     }
     if calib:
         line["calibration"] = calib
@@ -694,7 +736,7 @@ def measure_traffic_live(level, bs, n_blocks, algo_bytes):
             for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
                 env.pop(k, None)
             cmd = ["rocprofv3", "--pmc", ctr, "-d", d, "-o", "t", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--tiles", str(child_tiles), "--steps", str(steps), "--warmup", "2", "--no-secondary", "--no-cpu-baseline", "--calib",
+                   "--tiles", str(child_tiles), "--steps", str(steps), "--warmup", "2", "--full", "--no-secondary", "--no-cpu-baseline", "--calib",
                    "--level", str(level), "--block-size", str(bs)]
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=300)
             line = next((json.loads(x) for x in r.stdout.splitlines() if x.startswith("{") and '"metric"' in x), None)
@@ -943,12 +985,17 @@ def main():
                     help="corpus tiles per GPU, 211 943 424 B of unique silesia-mix plaintext each (41 = 8.7 GB decoded / "
                          "4.4 GB compressed per GPU = configs[3]'s 64 GiB over 8 GPUs)")
     ap.add_argument("--enc-mib", type=int, default=1024, help="MiB of unique enwik-like text per GPU for the encoder workload (configs[2]: 1 GiB)")
-    ap.add_argument("--l7-tiles", type=int, default=10, help="corpus tiles of the level-7 line of the default run (configs[4])")
+    ap.add_argument("--l7-tiles", type=int, default=10, help="corpus tiles of the level-7 line of the default --full run (configs[4])")
     ap.add_argument("--level", type=int, default=3)
     ap.add_argument("--block-size", type=int, default=65536)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: every output byte checked before and after timing, the CPU "
+                         "baseline, and for the default single-GPU level-3 decode the HBM traffic measured in the run and the "
+                         "secondary lines. Without it a run prepares its inputs, warms up, times the steps, writes --dump-outputs "
+                         "and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default run only: skip the level-7 decode (configs[4]) and level-3 encode (configs[2]) lines")
+                    help="--full, default run only: skip the level-7 decode (configs[4]) and level-3 encode (configs[2]) lines")
     ap.add_argument("--checksum", action="store_true",
                     help="archives carry per-block rapidhash trailers and every launch verifies them on the device")
     ap.add_argument("--calib", action="store_true",
@@ -992,18 +1039,19 @@ def main():
         rank, world, local, backend, dist = comm
         torch.cuda.set_device(local)
         zxc_amd.lib().zxc_mi355x_set_device(local)
+        full = args.full
         if args.mode == "encode":
-            line = encode_run(args, args.level, args.enc_mib, args.steps, args.warmup, comm, not args.no_cpu_baseline,
-                              dump_dir=args.dump_outputs)
+            line = encode_run(args, args.level, args.enc_mib, args.steps, args.warmup, comm, full and not args.no_cpu_baseline,
+                              dump_dir=args.dump_outputs, full=full)
         else:
-            # (the headline line of the default run measures its HBM traffic itself: two short rocprofv3 passes in a child process)
-            args.live_traffic = world == 1 and args.level == 3 and not args.checksum and not args.calib and not args.no_secondary and args.block_size == 65536
+            # (the headline line of the default --full run measures its HBM traffic itself: two short rocprofv3 passes in a child process)
+            args.live_traffic = full and world == 1 and args.level == 3 and not args.checksum and not args.calib and not args.no_secondary and args.block_size == 65536
             line = decode_run(args, args.level, args.tiles, args.steps, args.warmup, comm, args.checksum, args.calib,
-                              not args.no_cpu_baseline, dump_dir=args.dump_outputs)
+                              full and not args.no_cpu_baseline, dump_dir=args.dump_outputs, full=full)
             args.live_traffic = False
-            # The default single-GPU run also measures the other two single-GPU configurations of BASELINE.json, each with its
+            # The default single-GPU --full run also measures the other two single-GPU configurations of BASELINE.json, each with its
             # own roofline / cpu_baseline objects and its own bit-exactness check (next #2).
-            if world == 1 and args.level == 3 and not args.checksum and not args.calib and not args.no_secondary:
+            if full and world == 1 and args.level == 3 and not args.checksum and not args.calib and not args.no_secondary:
                 sec = {}
                 sec["level7"] = decode_run(args, 7, args.l7_tiles, max(5, args.steps // 2), 2, comm,
                                            with_cpu_baseline=not args.no_cpu_baseline, cpu_budget_s=6.0)

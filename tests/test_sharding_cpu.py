@@ -196,3 +196,20 @@ def test_bench_strong_scaling_is_one_fixed_corpus(ref):
     assert rc1 == 0 and lines1[0]["blocks_total"] == 20 and lines1[0]["blocks_rank0"] == [0, 20], err1[-2000:]
     assert lines1[0]["decoded_bytes_all_ranks"] == lines[0]["decoded_bytes_all_ranks"] == 20 * 65536
     assert bench.prep_estimate_s(41, 3, 8) < bench.prep_estimate_s(328, 3, 1) < bench.prep_estimate_s(328, 7, 1)
+
+
+def test_bench_prep_without_the_plaintext_is_the_same_archive(ref, monkeypatch):
+    """A plain bench run prepares its corpus without the plaintext (want=False): the compressed blocks, the seek-table
+    entries, header and EOF block must be those of the --full preparation, which keeps the plaintext; a range that starts
+    and ends inside tiles, and the CPU baseline's archive of the first tiles, included."""
+    import bench
+    from zxc_amd import corpus
+    monkeypatch.setattr(corpus, "TILE_BYTES", 5 * 65536)
+    monkeypatch.setattr(corpus, "CHUNK_BYTES", 2 * 65536)
+    cpu = torch.device("cpu")
+    full = bench.build_rank_corpus(3, 12, 3, 65536, None, cpu, baseline_tiles=2)
+    lean = bench.build_rank_corpus(3, 12, 3, 65536, None, cpu, want=False)
+    assert torch.equal(full[0], lean[0]) and (full[1] == lean[1]).all() and full[3:5] == lean[3:5]
+    assert full[2].numel() == 9 * 65536 and lean[2] is None and lean[6] is None
+    assert full[6][:16] == full[3] and int.from_bytes(full[6][-12:-4], "little") == 10 * 65536
+    assert 1 <= bench.usable_cpus() <= (os.cpu_count() or 1)

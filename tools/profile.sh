@@ -2,7 +2,8 @@
 # tools/profile.sh <tag> [bench args...] : rocprofv3 passes of a bench command (kernel trace + stats, then the HBM traffic
 # counters and the instruction counts, each in its own --pmc run) -> gpurun_out/<tag>_{kt,fetch,write,sq}/ ; condense with
 # python tools/profile_summary.py <tag> [what]
-# Default command: the headline decode (python bench.py --no-secondary --calib). Examples:
+# Default command: the headline decode (python bench.py --full --no-secondary --calib: the re-check launch after the timed ones
+# is part of the dispatch sequence tools/profile_summary.py expects). Examples:
 #   tools/profile.sh r3              headline (configs[1])
 #   tools/profile.sh r3l7 --level 7 --tiles 10          level-7 decode (configs[4])
 #   tools/profile.sh r3enc --mode encode --enc-mib 1024 encoder (configs[2])
@@ -11,7 +12,7 @@ export ZXC_BENCH_CACHE=/tmp/zxc_bench_cache   # (the passes share the reference-
 R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=$1; shift
 extra="$*"
-case "$extra" in *--mode\ encode*) base="--steps 5 --warmup 1 --no-cpu-baseline";; *) base="--steps 5 --warmup 2 --no-cpu-baseline --no-secondary --calib";; esac
+case "$extra" in *--mode\ encode*) base="--steps 5 --warmup 1 --full --no-cpu-baseline";; *) base="--steps 5 --warmup 2 --full --no-cpu-baseline --no-secondary --calib";; esac
 CMD="python $R/bench.py $base $extra"
 T=${PROFILE_TIMEOUT:-400}
 P=${PROFILE_PASSES:-kt fetch write sq tcp}   # (subset of the passes, e.g. PROFILE_PASSES="kt fetch write")

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=$1; lv=${2:-3}
-CMD="python $R/bench.py --mode encode --level $lv --steps 5 --warmup 1 --no-cpu-baseline"
+CMD="python $R/bench.py --mode encode --level $lv --steps 5 --warmup 1 --full --no-cpu-baseline"  # (--full: the verification decode and the incompressible leg)
 timeout -k 5 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${tag}_kt -o kt --output-format csv -- $CMD > $R/gpurun_out/${tag}_kt.log 2>&1
 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE -d $R/gpurun_out/${tag}_fetch -o f --output-format csv -- $CMD > $R/gpurun_out/${tag}_fetch.log 2>&1
 timeout -k 5 300 rocprofv3 --pmc WRITE_SIZE -d $R/gpurun_out/${tag}_write -o w --output-format csv -- $CMD > $R/gpurun_out/${tag}_write.log 2>&1

@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "zxc_export.h"
+#include "zxc_opts.h"
 #include "zxc_seekable.h"
 #ifdef __cplusplus
 extern "C" {
@@ -105,6 +106,33 @@ ZXC_EXPORT int zxc_mi355x_encode_blocks_dict_device(const void* d_src, uint64_t 
 ZXC_EXPORT int zxc_mi355x_gather_blocks_device(const void* d_slots, uint32_t block_size,
                                                const uint32_t* d_sizes, const uint64_t* d_offsets,
                                                void* d_out, uint32_t n_blocks, void* stream);
+
+/* ---- whole archive, device to device (zxc_amd/csrc/zxc_frame_device.hip) ----
+ * zxc_compress for a source that already lives in device memory: the blocks are encoded, the container (file header, EOF
+ * block, seek table, footer, global hash) is written and the blocks are compacted, all on the device. The archive is byte for
+ * byte the one zxc_compress writes for the same source, level, block_size, checksum_enabled and seekable.
+ * Options are read like zxc_compress reads them (opts may be NULL); n_threads, progress_cb and user_data are ignored, and
+ * opts->dict != NULL gives ZXC_ERROR_GPU_UNSUPPORTED.
+ * Reads exactly d_src[0, src_size) (the encoder's over-read is served from a staged copy of the last block or two), writes
+ * nothing at or past d_dst + dst_capacity; d_dst may have any alignment. d_work is scratch of at least
+ * zxc_mi355x_compress_device_work_size() bytes, any alignment, owned by the call until *d_result is written. */
+
+/* Bytes of device scratch zxc_mi355x_compress_device needs for src_size bytes under opts (0 when opts are invalid). */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_device_work_size(uint64_t src_size, const zxc_compress_opts_t* opts);
+
+/* Compress d_src[0..src_size) into a complete v8 archive at d_dst[0..dst_capacity), asynchronously on `stream`.
+ * Returns ZXC_OK once everything is enqueued, or a negative zxc_error_t for arguments / launch failures (synchronous):
+ * NULL d_dst / d_work / d_result (or d_src with src_size > 0) -> ZXC_ERROR_NULL_INPUT, bad options as above,
+ * work_size too small -> ZXC_ERROR_MEMORY, dst_capacity below the part of the archive known before encoding (header,
+ * 8 (+4 with checksums) bytes per block, EOF block, seek table, footer) -> ZXC_ERROR_DST_TOO_SMALL; then, without a
+ * device, ZXC_ERROR_GPU_UNAVAILABLE. No device allocation (beyond the encoder's stream-ordered scratch at levels 6-7)
+ * and no host synchronisation. Calls on different streams with different work areas may run concurrently.
+ * *d_result (device memory) receives the archive size or a negative zxc_error_t, written once, after the archive:
+ * ZXC_ERROR_DST_TOO_SMALL when the encoded archive does not fit (nothing is compacted then), ZXC_ERROR_CORRUPT_DATA when
+ * the encoder reported a block size outside [8 (+4), block_size + 64]. After an error the bytes of d_dst are undefined. */
+ZXC_EXPORT int zxc_mi355x_compress_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity,
+                                          const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size,
+                                          int64_t* d_result, void* stream);
 
 #ifdef __cplusplus
 }

@@ -231,6 +231,36 @@ def decode_blocks_device(d_comp, d_jobs, n_jobs, d_out, d_status, block_size, ve
         raise ZxcError(rc, "zxc_mi355x_decode_blocks_device")
 
 
+def _compress_device_opts(level, block_size, seekable, checksum):
+    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
+
+
+def compress_device_work_size(src_size, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_device_work_size(): bytes of device scratch compress_device needs (0 for invalid options)."""
+    L = lib()
+    L.zxc_mi355x_compress_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts)]
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(L.zxc_mi355x_compress_device_work_size(src_size, C.byref(o)))
+
+
+def compress_device(d_src, src_size, d_dst, dst_capacity, d_work, work_size, d_result, level=3, block_size=0,
+                    seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_device(): raw device pointers (ints, e.g. tensor.data_ptr()), asynchronous on `stream`
+    (e.g. torch.cuda.current_stream().cuda_stream). The archive size or a negative zxc_error_t lands in the int64 at
+    d_result; a synchronous failure raises ZxcError."""
+    L = lib()
+    L.zxc_mi355x_compress_device.restype = C.c_int
+    L.zxc_mi355x_compress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts),
+                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = L.zxc_mi355x_compress_device(C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity,
+                                      C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None),
+                                      C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_device")
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

@@ -134,6 +134,58 @@ ZXC_EXPORT int zxc_mi355x_compress_device(const void* d_src, uint64_t src_size, 
                                           const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size,
                                           int64_t* d_result, void* stream);
 
+/* ---- and back (zxc_amd/csrc/zxc_unframe_device.hip, container rules in zxc_amd/csrc/zxc_container.h) ----
+ * zxc_decompress for an archive that already lives in device memory: the container (file header, block headers, seek table, EOF
+ * block, footer size, global hash) is parsed, validated and judged on the device, the blocks are decoded by the launch behind
+ * zxc_mi355x_decode_blocks_device, and one 8-byte word says what zxc_decompress would have returned.
+ * block_size is the archive's block size: the host sizes the grids and the work area with it and never reads the archive. The
+ * writer of the archive knows it; anyone else asks zxc_mi355x_frame_info_device. The call launches
+ * n_max + 1 jobs, n_max = ceil(dst_capacity / block_size): an archive with more blocks cannot fit, and the extra job lets a
+ * failing block behind a full destination keep its precedence over ZXC_ERROR_DST_TOO_SMALL. */
+
+/* Bytes of device scratch the call below needs (0 for arguments it would refuse: src_size < 28, block_size not a power of two in
+ * [4 KiB, 2 MiB], more than 2^31 - 2 blocks of capacity). Does not depend on opts. */
+ZXC_EXPORT uint64_t zxc_mi355x_decompress_device_work_size(uint64_t src_size, uint64_t dst_capacity, uint32_t block_size);
+
+/* Decode the complete v8 archive d_src[0, src_size) into d_dst[0, dst_capacity), asynchronously on `stream`.
+ * Returns ZXC_OK once everything is enqueued, or synchronously, in this order and before any device is touched: NULL d_src /
+ * d_work / d_result, or NULL d_dst with dst_capacity > 0 -> ZXC_ERROR_NULL_INPUT; src_size < 28 -> ZXC_ERROR_SRC_TOO_SMALL;
+ * block_size as above -> ZXC_ERROR_BAD_BLOCK_SIZE; opts->dict != NULL -> ZXC_ERROR_GPU_UNSUPPORTED; d_dst not 16-byte aligned
+ * -> ZXC_ERROR_GPU_UNSUPPORTED; work_size too small -> ZXC_ERROR_MEMORY; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE.
+ * opts may be NULL; only checksum_enabled and dict are read.
+ * No host synchronisation and no device allocation of its own (the decode launch keeps its per-stream buffers as it does for
+ * zxc_mi355x_decode_blocks_device), capturable like that call; calls on different streams with different work areas may overlap.
+ * Writes nothing at or past d_dst + dst_capacity: the decoders store 16 bytes at a time, so the blocks whose slot
+ * [i * block_size, (i + 1) * block_size + 32) does not lie inside the capacity (at most three jobs) are decoded into the work
+ * area and copied out, min(decoded size, capacity left) bytes each. d_src must be READABLE up to src_size + 64 (as d_comp of
+ * zxc_mi355x_decode_blocks_device; the bytes are never used) and is never written. d_work is scratch of at least
+ * zxc_mi355x_decompress_device_work_size() bytes, any alignment, owned by the call until *d_result is written.
+ * opts->checksum_enabled with an archive that carries checksums: every block's trailer is verified by the decode launch and the
+ * footer's global hash on the device; otherwise nothing is hashed. (The host cannot know whether the archive carries them, and
+ * the decode launch takes that by value: such a call enqueues the decode launch over two job tables, of which the device fills
+ * one; the jobs of the other are empty and cost a wavefront that exits at once.)
+ * *d_result (device memory) receives, once, after the last byte of d_dst: the decoded size, or the negative zxc_error_t that
+ * zxc_decompress returns for the same bytes, capacity and options, with the same precedence: file header (BAD_MAGIC, BAD_VERSION,
+ * BAD_HEADER, BAD_BLOCK_SIZE; a dictionary id -> DICT_REQUIRED), no block decoded then; the first failing block in archive order;
+ * a bad block header found at block k only if blocks 0..k-1 decode; DST_TOO_SMALL when block i's decoded size passes the capacity
+ * left; footer size -> CORRUPT_DATA; global hash -> BAD_CHECKSUM. dst_capacity == 0 is the empty-frame probe: 0 for an empty
+ * archive, else DST_TOO_SMALL. Two departures: a header block size other than the argument is ZXC_ERROR_BAD_BLOCK_SIZE; an
+ * irregular frame (a block that is not the last decodes to something other than block_size: legal, written neither by the
+ * reference encoder nor by this library) is ZXC_ERROR_GPU_UNSUPPORTED, because its blocks do not sit back to back in d_dst and
+ * there is no host to fall back to. A seek table is used only when it provably describes the chain a header walk follows;
+ * otherwise one workgroup walks the headers, a serial chain of loads: write archives for this call with seekable = 1.
+ * After an error the bytes of d_dst[0, dst_capacity) are undefined. */
+ZXC_EXPORT int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity,
+                                            uint32_t block_size, const zxc_decompress_opts_t* opts, void* d_work,
+                                            uint64_t work_size, int64_t* d_result, void* stream);
+
+/* The one call here that synchronises: copies the 16-byte file header and the 12-byte footer to the host, waits for `stream`, and
+ * reports what a caller who did not write the archive needs to size the call above (any of the three outputs may be NULL).
+ * decompressed_size is what zxc_get_decompressed_size gives for the archive (0 when the footer's size is implausible).
+ * -> ZXC_OK, ZXC_ERROR_NULL_INPUT, ZXC_ERROR_SRC_TOO_SMALL, ZXC_ERROR_GPU_UNAVAILABLE, or the file header's error. */
+ZXC_EXPORT int zxc_mi355x_frame_info_device(const void* d_src, uint64_t src_size, uint32_t* block_size,
+                                            uint64_t* decompressed_size, int* has_checksum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

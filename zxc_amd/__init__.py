@@ -6,5 +6,6 @@ ctypes view of its C-ABI used by tests and bench.py. There is no Python or CPU
 decoder behind it: if the library or a GPU is missing, calls raise.
 """
 from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_size, decode_blocks_device,  # noqa: F401
-                  compress_device, compress_device_work_size, lib, lib_path, JOB_DTYPE, error_name)
+                  compress_device, compress_device_work_size, decompress_device, decompress_device_work_size,
+                  frame_info_device, lib, lib_path, JOB_DTYPE, error_name)
 from . import api  # noqa: F401  (stream_* helpers live there)

@@ -261,6 +261,46 @@ def compress_device(d_src, src_size, d_dst, dst_capacity, d_work, work_size, d_r
         raise ZxcError(rc, "zxc_mi355x_compress_device")
 
 
+def _bind_decompress_device(L):
+    L.zxc_mi355x_decompress_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_decompress_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+    L.zxc_mi355x_decompress_device.restype = C.c_int
+    L.zxc_mi355x_decompress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                               C.POINTER(_DecompressOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_frame_info_device.restype = C.c_int
+    L.zxc_mi355x_frame_info_device.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_int), C.c_void_p]
+    return L
+
+
+def decompress_device_work_size(src_size, dst_capacity, block_size):
+    """zxc_mi355x_decompress_device_work_size(): bytes of device scratch decompress_device needs (0 for refused arguments)."""
+    return int(_bind_decompress_device(lib()).zxc_mi355x_decompress_device_work_size(src_size, dst_capacity, block_size))
+
+
+def decompress_device(d_src, src_size, d_dst, dst_capacity, block_size, d_work, work_size, d_result, checksum=False, stream=0):
+    """zxc_mi355x_decompress_device(): raw device pointers (ints, e.g. tensor.data_ptr()), asynchronous on `stream`. The
+    decoded size or the negative zxc_error_t zxc_decompress would return lands in the int64 at d_result; a synchronous
+    failure raises ZxcError."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    rc = _bind_decompress_device(lib()).zxc_mi355x_decompress_device(
+        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, block_size, C.byref(o),
+        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_device")
+
+
+def frame_info_device(d_src, src_size, stream=0):
+    """zxc_mi355x_frame_info_device(): -> (block_size, decompressed_size, has_checksum) of an archive in device memory.
+    Synchronises `stream`."""
+    bs, n, ck = C.c_uint32(0), C.c_uint64(0), C.c_int(0)
+    rc = _bind_decompress_device(lib()).zxc_mi355x_frame_info_device(C.c_void_p(d_src or None), src_size, C.byref(bs), C.byref(n),
+                                                                     C.byref(ck), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_frame_info_device")
+    return int(bs.value), int(n.value), bool(ck.value)
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

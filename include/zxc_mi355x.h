@@ -186,6 +186,76 @@ ZXC_EXPORT int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size
 ZXC_EXPORT int zxc_mi355x_frame_info_device(const void* d_src, uint64_t src_size, uint32_t* block_size,
                                             uint64_t* decompressed_size, int* has_checksum, void* stream);
 
+/* ---- random access, device to device (zxc_amd/csrc/zxc_ranges_device.hip, rules in zxc_amd/csrc/zxc_ranges.h) ----
+ * zxc_seekable_open and zxc_seekable_decompress_range for a seekable archive that already lives in device memory: the seek table
+ * is read and judged on the device once (open), and then any number of calls fetch many ranges each, the ranges themselves lying
+ * in device memory. Both calls return ZXC_OK once everything is enqueued, are asynchronous on `stream`, do not synchronise with
+ * the host, allocate no device memory of their own (the decode launch keeps its per-stream buffers as it does for
+ * zxc_mi355x_decode_blocks_device) and never write d_src. No dictionary support: an archive written with one gives every range
+ * ZXC_ERROR_DICT_REQUIRED. Block checksum trailers are skipped, not verified, as in zxc_seekable_decompress_range. */
+
+/* One range to fetch (24 bytes, device-visible layout). */
+typedef struct zxc_dev_range {
+    uint64_t offset;  /* first decoded byte wanted */
+    uint64_t len;     /* bytes wanted */
+    uint64_t dst_off; /* where they go: d_dst + dst_off */
+} zxc_dev_range_t;
+
+/* Bytes of the index of an archive of at most max_blocks blocks: a 64-byte header (status, block count, decoded size, checksum
+ * flag, dictionary id) and one uint64_t archive offset per block plus one behind the last. */
+ZXC_EXPORT uint64_t zxc_mi355x_seekable_index_size(uint32_t max_blocks);
+
+/* zxc_seekable_open on the device, once per archive: d_index (16-byte aligned, caller-owned, read-only afterwards) receives the
+ * index. max_blocks = ceil(decompressed_size / block_size), which the writer knows and zxc_mi355x_frame_info_device tells.
+ * Synchronous errors, in this order, before any device is touched: NULL d_src / d_index -> ZXC_ERROR_NULL_INPUT; src_size < 44
+ * -> ZXC_ERROR_SRC_TOO_SMALL; block_size not a power of two in [4 KiB, 2 MiB] -> ZXC_ERROR_BAD_BLOCK_SIZE; d_index not 16-byte
+ * aligned -> ZXC_ERROR_GPU_UNSUPPORTED; index_size < zxc_mi355x_seekable_index_size(max_blocks) -> ZXC_ERROR_MEMORY; then, without
+ * a device, ZXC_ERROR_GPU_UNAVAILABLE.
+ * The index's status word is ZXC_OK under exactly the conditions of zxc_seekable_open (file header, non-zero footer size, a SEK
+ * block header with a valid check byte and length 4 nb where the footer says it is, every entry >= 8, the entries summing from
+ * offset 16 to a valid EOF block header right in front of the SEK block), plus: the header's block size is the argument (else
+ * ZXC_ERROR_BAD_BLOCK_SIZE), nb <= max_blocks (else ZXC_ERROR_MEMORY) and, a departure, no entry above 4 MiB (no legal block is
+ * that large). A failed open stores the file header's own error where that is what failed, else ZXC_ERROR_CORRUPT_DATA, and every
+ * non-empty range read through that index gets that status. Like the host's open it does not look at the block headers; the
+ * decoder does when a block is used. */
+ZXC_EXPORT int zxc_mi355x_seekable_open_device(const void* d_src, uint64_t src_size, uint32_t block_size, uint32_t max_blocks,
+                                               void* d_index, uint64_t index_size, void* stream);
+
+/* Bytes of device scratch the call below needs; 0 for arguments it would refuse (block_size, n_ranges x J > 2^31 - 2). The host
+ * never sees the ranges, only the promise that none is longer than max_len: a range of that length touches at most
+ * J = (max_len - 1) / block_size + 2 blocks, the call launches n_ranges x J jobs, and every job has a slot of its own. The size is
+ * at most n_ranges x J x (block_size + 64) + 44 x n_ranges x J + 1536. That is the price of not knowing the ranges on the host;
+ * keep it down with a tight max_len, and keep the slots unused with dst_off = offset (mod 16), which lets every block that lies
+ * inside a range decode straight into d_dst. */
+ZXC_EXPORT uint64_t zxc_mi355x_decompress_ranges_device_work_size(uint32_t n_ranges, uint64_t max_len, uint32_t block_size);
+
+/* For r in [0, n_ranges): decoded bytes [offset_r, offset_r + len_r) of the archive d_src[0, src_size), opened into d_index with
+ * the same block_size, go to d_dst + dst_off_r; d_results[r] (device memory) receives, once, after that range's last byte, what
+ * zxc_seekable_decompress_range returns for the same archive, offset, len and a destination of dst_capacity - dst_off_r bytes:
+ * len == 0 -> 0 (whatever else is wrong); a failed index -> its status; len > max_len, or dst_off + len > dst_capacity ->
+ * ZXC_ERROR_DST_TOO_SMALL; offset > total or len > total - offset -> ZXC_ERROR_SRC_TOO_SMALL; a dictionary id in the file header ->
+ * ZXC_ERROR_DICT_REQUIRED; then the first failing covered block's status in block order, a covered block that decoded to fewer
+ * bytes than the range needs of it being ZXC_ERROR_CORRUPT_DATA; else len. (An index opened with another block_size gives
+ * ZXC_ERROR_BAD_BLOCK_SIZE, a src_size below the archive that was opened ZXC_ERROR_SRC_TOO_SMALL.)
+ * d_ranges lies in device memory and is read on the stream: a kernel enqueued before the call may write it, a replayed graph may
+ * see other ranges each time.
+ * Synchronous errors, in this order: NULL d_src / d_index / d_work / d_results, NULL d_ranges with n_ranges > 0, NULL d_dst with
+ * dst_capacity > 0 -> ZXC_ERROR_NULL_INPUT; block_size -> ZXC_ERROR_BAD_BLOCK_SIZE; d_dst not 16-byte aligned ->
+ * ZXC_ERROR_GPU_UNSUPPORTED; n_ranges x J above 2^31 - 2, or work_size too small -> ZXC_ERROR_MEMORY; n_ranges == 0 is ZXC_OK
+ * here and enqueues nothing; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE.
+ * Guarantees: nothing is written outside the destinations [dst_off_r, dst_off_r + len_r) of the valid ranges and d_work (a block
+ * is decoded straight into d_dst only when all of it is wanted, its place is 16-byte aligned and its slot plus the 32 bytes the
+ * decoders may store behind it end inside that range's destination; every other block goes through a slot of d_work and a copy).
+ * A range that fails leaves its own destination bytes undefined and every other range untouched. Ranges may overlap in the
+ * archive (a shared block is decoded once per range). Ranges whose destinations overlap are the caller's error: undefined bytes,
+ * no fault. d_src must be READABLE up to src_size + 64 (as d_comp of zxc_mi355x_decode_blocks_device). d_work: any alignment, owned
+ * by the call until the last result is written. Calls on different streams with different work areas may overlap and may share
+ * one index. */
+ZXC_EXPORT int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, const void* d_index,
+                                                   const zxc_dev_range_t* d_ranges, uint32_t n_ranges, uint64_t max_len,
+                                                   void* d_dst, uint64_t dst_capacity, uint32_t block_size, void* d_work,
+                                                   uint64_t work_size, int64_t* d_results, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

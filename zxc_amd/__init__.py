@@ -7,5 +7,6 @@ decoder behind it: if the library or a GPU is missing, calls raise.
 """
 from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_size, decode_blocks_device,  # noqa: F401
                   compress_device, compress_device_work_size, decompress_device, decompress_device_work_size,
-                  frame_info_device, lib, lib_path, JOB_DTYPE, error_name)
+                  frame_info_device, seekable_index_size, seekable_open_device, decompress_ranges_device_work_size,
+                  decompress_ranges_device, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, error_name)
 from . import api  # noqa: F401  (stream_* helpers live there)

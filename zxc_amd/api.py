@@ -11,6 +11,8 @@ _LIB = None
 
 # zxc_dev_job_t (include/zxc_mi355x.h)
 JOB_DTYPE = np.dtype([("comp_off", "<u8"), ("out_off", "<u8"), ("comp_size", "<u4"), ("out_len", "<u4")])
+# zxc_dev_range_t (include/zxc_mi355x.h)
+RANGE_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("dst_off", "<u8")])
 
 
 class ZxcError(RuntimeError):
@@ -299,6 +301,51 @@ def frame_info_device(d_src, src_size, stream=0):
     if rc < 0:
         raise ZxcError(rc, "zxc_mi355x_frame_info_device")
     return int(bs.value), int(n.value), bool(ck.value)
+
+
+def _bind_ranges_device(L):
+    L.zxc_mi355x_seekable_index_size.restype = C.c_uint64
+    L.zxc_mi355x_seekable_index_size.argtypes = [C.c_uint32]
+    L.zxc_mi355x_seekable_open_device.restype = C.c_int
+    L.zxc_mi355x_seekable_open_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_decompress_ranges_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_decompress_ranges_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
+    L.zxc_mi355x_decompress_ranges_device.restype = C.c_int
+    L.zxc_mi355x_decompress_ranges_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                      C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                      C.c_void_p]
+    return L
+
+
+def seekable_index_size(max_blocks):
+    """zxc_mi355x_seekable_index_size(): bytes of the device index of an archive of at most max_blocks blocks."""
+    return int(_bind_ranges_device(lib()).zxc_mi355x_seekable_index_size(max_blocks))
+
+
+def seekable_open_device(d_src, src_size, block_size, max_blocks, d_index, index_size, stream=0):
+    """zxc_mi355x_seekable_open_device(): raw device pointers (ints), asynchronous on `stream`. Whether the archive's seek table
+    was accepted lands in the index's first int32; a synchronous failure raises ZxcError."""
+    rc = _bind_ranges_device(lib()).zxc_mi355x_seekable_open_device(C.c_void_p(d_src or None), src_size, block_size, max_blocks,
+                                                                    C.c_void_p(d_index or None), index_size, C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_seekable_open_device")
+
+
+def decompress_ranges_device_work_size(n_ranges, max_len, block_size):
+    """zxc_mi355x_decompress_ranges_device_work_size(): bytes of device scratch the call needs (0 for refused arguments)."""
+    return int(_bind_ranges_device(lib()).zxc_mi355x_decompress_ranges_device_work_size(n_ranges, max_len, block_size))
+
+
+def decompress_ranges_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, d_work, work_size,
+                             d_results, stream=0):
+    """zxc_mi355x_decompress_ranges_device(): raw device pointers (ints); d_ranges is n_ranges x RANGE_DTYPE in device memory,
+    d_results n_ranges x int64. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    rc = _bind_ranges_device(lib()).zxc_mi355x_decompress_ranges_device(
+        C.c_void_p(d_src or None), src_size, C.c_void_p(d_index or None), C.c_void_p(d_ranges or None), n_ranges, max_len,
+        C.c_void_p(d_dst or None), dst_capacity, block_size, C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
+        C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_ranges_device")
 
 
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.

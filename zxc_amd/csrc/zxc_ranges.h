@@ -1,0 +1,192 @@
+/* zxc_ranges.h — the rules of zxc_mi355x_seekable_open_device and zxc_mi355x_decompress_ranges_device on top of
+ * zxc_container.h: the index a seek table becomes, when it is accepted, what a range may ask for, which block job (r, j) is,
+ * whether that block is decoded straight into the destination or into a staged slot, what is copied out of a slot, the
+ * per-range result, and the call's shape. Plain inline C that hipcc and a host C compiler both take, so that the kernels of
+ * zxc_ranges_device.hip and the CPU tests run the same lines. Every function states what zxc_seekable_open /
+ * zxc_seekable_decompress_range (zxc_host.c) do for the same bytes; where the device call departs from them, it says so. */
+#ifndef ZXC_RANGES_H
+#define ZXC_RANGES_H
+#include "zxc_container.h"
+
+#define ZR_OPEN_MIN (ZC_FILE_HDR + 2u * ZC_BLK_HDR + ZC_FOOTER) /* 44: file header, EOF block, SEK header, footer */
+#define ZR_INDEX_HDR 64u   /* bytes of zr_index_t in front of comp_offsets[] */
+#define ZR_SLOT_PAD 64u    /* behind every staged slot: the decoders store up to 32 bytes past out_len, and slots stay 16-aligned */
+#define ZR_COPY_CHUNK 8192u /* destination bytes one wavefront of the copy-out moves */
+#define ZR_JOB_BYTES 44u   /* work area per job besides its slot: zxc_dev_job_t + status + zr_copy_t */
+#define ZR_WORK_FIXED 1536u /* work area besides the jobs: alignment of the four parts and of the caller's pointer */
+
+/* The index: this header, then comp_offsets[0 .. nb] (uint64_t archive offsets of the block headers, [nb] = the EOF block). */
+typedef struct zr_index {
+    int32_t status;      /* ZXC_OK once the table is accepted, else the negative zxc_error_t every range of this index gets */
+    uint32_t nb;         /* blocks */
+    uint64_t total;      /* footer: decoded size */
+    uint32_t file_ck;    /* blocks carry 4-byte checksum trailers */
+    uint32_t dict_id;    /* file header: non-zero = written with a dictionary */
+    uint32_t block_size;
+    uint32_t seek;       /* open's progress: 1 the head stage passed, 2 the entries sum to the EOF block */
+    uint64_t eof_at;     /* archive offset of the EOF block header */
+    uint64_t rsv[3];
+} zr_index_t;
+
+/* A staged job's copy-out: slot[from, from + n) -> d_dst[dst_at, dst_at + n), when the block decoded to at least from + n bytes.
+ * n == 0: nothing to copy (an empty job, or a block decoded straight into the destination). */
+typedef struct zr_copy {
+    uint64_t dst_at;
+    uint32_t from, n;
+} zr_copy_t;
+
+ZC_FN int zr_block_size_ok(uint32_t bs) { return bs >= (1u << 12) && bs <= (1u << 21) && !(bs & (bs - 1u)); }
+ZC_FN uint64_t zr_index_size(uint32_t max_blocks) { return ZR_INDEX_HDR + 8ull * ((uint64_t)max_blocks + 1u); }
+ZC_FN uint32_t zr_open_tiles(uint32_t max_blocks) { return max_blocks ? (max_blocks + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS : 1u; }
+ZC_FN uint64_t* zr_offsets(void* index) { return (uint64_t*)((uint8_t*)index + ZR_INDEX_HDR); }
+ZC_FN const uint64_t* zr_coffsets(const void* index) { return (const uint64_t*)((const uint8_t*)index + ZR_INDEX_HDR); }
+
+/* ---- open. zxc_seekable_open over src[0, src_size), src_size >= 44: the file header, a non-zero footer size, a SEK header with
+ * a valid check byte and length 4 nb where the footer says it is, a valid EOF header right in front of it. Two additions: the
+ * header's block size is the argument's (the caller sized everything with it), and nb <= max_blocks (the index holds no more).
+ * -> status stays negative; seek = 1 when the entries are worth summing. */
+ZC_FN void zr_open_head(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint32_t max_blocks, zr_index_t* ix) {
+    uint32_t lg = 0, ck = 0, dict_id = 0;
+    ix->status = ZXC_ERROR_CORRUPT_DATA; ix->nb = 0; ix->total = 0; ix->file_ck = 0; ix->dict_id = 0; ix->block_size = block_size;
+    ix->seek = 0; ix->eof_at = 0; ix->rsv[0] = ix->rsv[1] = ix->rsv[2] = 0;
+    int rc = zc_file_header(src, &lg, &ck, &dict_id);
+    if (rc == ZXC_OK && (1u << lg) != block_size) rc = ZXC_ERROR_BAD_BLOCK_SIZE; /* departure, as zc_head */
+    if (rc != ZXC_OK) { ix->status = rc; return; }
+    const uint64_t total = zc_rd64(src + src_size - ZC_FOOTER);
+    if (total == 0) return;
+    const uint64_t nb = total / block_size + (total % block_size != 0);
+    if (nb > 0xFFFFFFFFull) return;
+    if (nb > max_blocks) { ix->status = ZXC_ERROR_MEMORY; return; }
+    /* [EOF header][SEK header][4 nb bytes][footer] at the end, at least the file header in front */
+    if (ZC_FILE_HDR + 2u * ZC_BLK_HDR + 4u * nb + ZC_FOOTER > src_size) return;
+    const uint64_t sek_at = src_size - ZC_FOOTER - 4u * nb - ZC_BLK_HDR, eof_at = sek_at - ZC_BLK_HDR;
+    const uint64_t sek = zc_rd64(src + sek_at), eof = zc_rd64(src + eof_at);
+    if (!zc_blk_hdr_ok(sek) || zc_blk_type(sek) != ZC_BLK_SEK || zc_blk_csz(sek) != 4u * nb) return;
+    if (!zc_blk_hdr_ok(eof) || zc_blk_type(eof) != ZC_BLK_EOF) return; /* (its size field is not looked at, as on the host) */
+    ix->nb = (uint32_t)nb; ix->total = total; ix->file_ck = ck; ix->dict_id = dict_id; ix->eof_at = eof_at;
+    ix->seek = 1;
+}
+ZC_FN const uint8_t* zr_entries(const uint8_t* src, const zr_index_t* ix) { return src + ix->eof_at + 2u * ZC_BLK_HDR; }
+/* seekable_build: an entry is at least a block header. Departure: none above ZC_SEEK_ENTRY_MAX (4 MiB; the tile sums are 32-bit;
+ * no legal block, at most 2 MiB of payload, is that large). The host's "entry and running sum <= archive size" follow from the
+ * sum landing on the EOF block. */
+ZC_FN int zr_entry_ok(uint32_t e) { return e >= ZC_BLK_HDR && e <= ZC_SEEK_ENTRY_MAX; }
+/* the entries summed from offset 16 land on the EOF block -> the table is accepted */
+ZC_FN void zr_open_judge(zr_index_t* ix, int any_bad, uint64_t sum) {
+    if (!any_bad && ZC_FILE_HDR + sum == ix->eof_at) { ix->status = ZXC_OK; ix->seek = 2; }
+}
+/* The passes in series (tests; the kernels run the same element functions over tiles). index: zr_index_size(max_blocks) bytes. */
+ZC_FN void zr_open_serial(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint32_t max_blocks, void* index) {
+    zr_index_t* ix = (zr_index_t*)index;
+    uint64_t* offs = zr_offsets(index);
+    zr_open_head(src, src_size, block_size, max_blocks, ix);
+    if (ix->seek != 1u) return;
+    const uint8_t* ent = zr_entries(src, ix);
+    uint64_t sum = 0;
+    int bad = 0;
+    for (uint32_t i = 0; i < ix->nb; i++) {
+        const uint32_t e = zc_rd32(ent + 4ull * i);
+        if (zr_entry_ok(e)) sum += e;
+        else bad = 1;
+    }
+    zr_open_judge(ix, bad, sum);
+    if (ix->status != ZXC_OK) return;
+    uint64_t run = ZC_FILE_HDR;
+    for (uint32_t i = 0; i < ix->nb; i++) { offs[i] = run; run += zc_rd32(ent + 4ull * i); }
+    offs[ix->nb] = run;
+}
+
+/* ---- a range. What is decided before any block is looked at, in zxc_seekable_decompress_range's order (seek_range_check, then
+ * range_source's bound): -> 1 and *result when the range is answered already, 0 when its blocks decide. */
+ZC_FN int zr_range_final(const zr_index_t* ix, zxc_dev_range_t r, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity,
+                         uint32_t block_size, int64_t* result) {
+    if (r.len == 0) { *result = 0; return 1; }
+    if (ix->status < 0) { *result = ix->status; return 1; }
+    if (ix->block_size != block_size) { *result = ZXC_ERROR_BAD_BLOCK_SIZE; return 1; } /* (an index opened with another size) */
+    /* max_len is the capacity the launch was sized for */
+    if (r.len > max_len || r.dst_off > dst_capacity || r.len > dst_capacity - r.dst_off) { *result = ZXC_ERROR_DST_TOO_SMALL; return 1; }
+    if (r.offset > ix->total || r.len > ix->total - r.offset) { *result = ZXC_ERROR_SRC_TOO_SMALL; return 1; }
+    if (ix->dict_id != 0) { *result = ZXC_ERROR_DICT_REQUIRED; return 1; }
+    if (ix->eof_at + ZC_BLK_HDR > src_size) { *result = ZXC_ERROR_SRC_TOO_SMALL; return 1; } /* fewer bytes than were opened */
+    return 0;
+}
+/* bytes [*from, *to) of block b (counted from the block's first byte) that a non-final range wants; from == to: not covered */
+ZC_FN void zr_wanted(zxc_dev_range_t r, uint64_t b, uint32_t block_size, uint32_t* from, uint32_t* to) {
+    const uint64_t lo = b * block_size, hi = lo + block_size, end = r.offset + r.len;
+    const uint64_t f = r.offset > lo ? r.offset : lo, t = end < hi ? end : hi;
+    *from = *to = 0;
+    if (t > f) { *from = (uint32_t)(f - lo); *to = (uint32_t)(t - lo); }
+}
+/* Block b of the range decodes straight to its place d_dst + dst_off + b bs - offset: all of it is wanted, the place is 16-byte
+ * aligned (d_dst is), and the slot plus the 32 bytes the decoders may store behind it end inside the range's own destination. */
+ZC_FN int zr_direct(zxc_dev_range_t r, uint64_t b, uint32_t block_size) {
+    const uint64_t lo = b * block_size;
+    if (lo < r.offset || lo + block_size + 32u > r.offset + r.len) return 0;
+    return ((r.dst_off + (lo - r.offset)) & 15u) == 0;
+}
+/* Job j of range r (job_index = r J + j): block offset / bs + j while the range reaches it, else an empty job (comp_size 0: the
+ * decoder answers with an error status and touches nothing). out_len is a whole block, as range_source has it. The launch's
+ * d_out is one base for both areas: d_dst = base + dst_rel, staged slot i = base + stage_rel + i slot_stride. */
+ZC_FN void zr_job(const void* index, zxc_dev_range_t r, uint32_t j, uint64_t job_index, uint64_t src_size, uint64_t max_len,
+                  uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel, zxc_dev_job_t* job, zr_copy_t* cp) {
+    const zr_index_t* ix = (const zr_index_t*)index;
+    const uint64_t* offs = zr_coffsets(index);
+    int64_t res;
+    uint32_t from, to;
+    job->comp_off = 0; job->out_off = stage_rel + job_index * ((uint64_t)block_size + ZR_SLOT_PAD); job->comp_size = 0; job->out_len = block_size;
+    cp->dst_at = 0; cp->from = 0; cp->n = 0;
+    if (zr_range_final(ix, r, src_size, max_len, dst_capacity, block_size, &res)) return;
+    const uint64_t b = r.offset / block_size + j;
+    zr_wanted(r, b, block_size, &from, &to);
+    if (to == from) return;
+    job->comp_off = offs[b];
+    job->comp_size = (uint32_t)(offs[b + 1u] - offs[b]);
+    const uint64_t dst_at = r.dst_off + (b * block_size + from - r.offset);
+    if (zr_direct(r, b, block_size)) job->out_off = dst_rel + dst_at;
+    else { cp->dst_at = dst_at; cp->from = from; cp->n = to - from; }
+}
+/* range_sink: a covered block's own error, or CORRUPT_DATA when it decoded short of what the range needs of it; 0 = fine */
+ZC_FN int32_t zr_block_verdict(int32_t status, uint32_t need_to) {
+    if (status < 0) return status;
+    return (uint32_t)status < need_to ? ZXC_ERROR_CORRUPT_DATA : 0;
+}
+/* The range's result from its J statuses: the first failing covered block in block order, else len. */
+ZC_FN int64_t zr_verdict(const void* index, zxc_dev_range_t r, uint32_t J, const int32_t* status, uint64_t src_size, uint64_t max_len,
+                         uint64_t dst_capacity, uint32_t block_size) {
+    int64_t res;
+    if (zr_range_final((const zr_index_t*)index, r, src_size, max_len, dst_capacity, block_size, &res)) return res;
+    const uint64_t b0 = r.offset / block_size;
+    for (uint32_t j = 0; j < J; j++) {
+        uint32_t from, to;
+        zr_wanted(r, b0 + j, block_size, &from, &to);
+        if (to == from) break;
+        const int32_t v = zr_block_verdict(status[j], to);
+        if (v != 0) return v;
+    }
+    return (int64_t)r.len;
+}
+
+/* ---- the call's shape, known to the host before any byte of the archive or of the range table */
+typedef struct zr_shape {
+    uint32_t J, n_jobs, slot_stride, copy_chunks; /* jobs per range; n_ranges J; bytes per slot; copy-out chunks per job */
+    uint64_t o_jobs, o_status, o_copy, o_stage, bytes; /* work-area offsets from its 256-byte aligned base */
+} zr_shape_t;
+/* -> 0, ZXC_ERROR_BAD_BLOCK_SIZE, or ZXC_ERROR_MEMORY (more jobs than a launch counts). A range of len <= max_len touches at
+ * most (max_len - 1) / bs + 2 blocks. */
+ZC_FN int zr_shape(uint32_t n_ranges, uint64_t max_len, uint32_t block_size, zr_shape_t* s) {
+    if (!zr_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    const uint64_t J = max_len ? (max_len - 1u) / block_size + 2u : 1u;
+    if (J > 0x7FFFFFFEull || J * n_ranges > 0x7FFFFFFEull) return ZXC_ERROR_MEMORY;
+    s->J = (uint32_t)J;
+    s->n_jobs = (uint32_t)(J * n_ranges);
+    s->slot_stride = block_size + ZR_SLOT_PAD;
+    s->copy_chunks = (block_size + 15u + ZR_COPY_CHUNK - 1u) / ZR_COPY_CHUNK; /* a copy of n bytes spans < n + 16 from its aligned start */
+    uint64_t o = 0;
+    s->o_jobs = o;   o = zc_round_up(o + (uint64_t)s->n_jobs * sizeof(zxc_dev_job_t), 256u);
+    s->o_status = o; o = zc_round_up(o + 4ull * s->n_jobs, 256u);
+    s->o_copy = o;   o = zc_round_up(o + (uint64_t)s->n_jobs * sizeof(zr_copy_t), 256u);
+    s->o_stage = o;  o += (uint64_t)s->n_jobs * s->slot_stride;
+    s->bytes = o + 256u; /* (the caller's d_work may have any alignment) */
+    return 0;
+}
+#endif

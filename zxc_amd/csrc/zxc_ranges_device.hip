@@ -1,0 +1,296 @@
+// zxc_ranges_device.hip — zxc_mi355x_seekable_open_device and zxc_mi355x_decompress_ranges_device: random access into a seekable
+// v8 archive that lies in device memory, results into device memory.
+//
+// The device-resident counterpart of zxc_seekable_open + zxc_seekable_decompress_range (zxc_host.c), batched: one range of a few
+// blocks cannot fill the device, a few thousand can. The rules are the inline C of zxc_ranges.h, which the CPU tests run as well.
+//
+// open, once per archive, in stream order:
+//   head     file header, footer, SEK and EOF headers                                      -> index header, status < 0
+//   tiles    per tile of 1024 entries: their sum and whether one is implausible, left in comp_offsets[first block of the tile]
+//   scan     one workgroup: those words become the tiles' archive offsets; the entries must sum from 16 to the EOF block -> status 0
+//   scatter  per tile: comp_offsets[b] for its blocks (the tile's first block is the word the scan left), [nb] behind the last
+//
+// ranges, per call, in stream order (the ranges are device data: the host only knows n_ranges and max_len, so it launches
+// J = (max_len - 1) / block_size + 2 jobs per range, of which a range uses as many as it covers blocks):
+//   plan     one thread per job: validates its range, writes the job and the copy descriptor
+//   decode   the existing decode launch, once, over all jobs: one d_out base below both d_dst and the staged slots
+//   copy     staged slot -> d_dst, one wavefront per 8 KiB of destination
+//   verdict  one thread per range: d_results[r]
+//
+// No workgroup waits for another: every dependency is the stream order between launches, and every stage is predicated on the index
+// status and the range's own verdict.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "zxc_ranges.h"
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+#define RNG_THREADS 256u
+#define RNG_PER_THREAD (ZC_TILE_BLOCKS / RNG_THREADS)
+#define RNG_BAD (1ull << 63)  // in a tile's word: one of its entries is implausible (a tile's sum is <= 2^32)
+
+// hidden entry point of zxc_hip_shim.hip (decode_launch)
+extern "C" int zxc_hip_decode_blocks(const void* d_comp, const zxc_dev_job_t* d_jobs, uint32_t n_jobs, void* d_out, int32_t* d_status,
+                                     uint32_t block_size, int verify_trailer, const void* d_dict, uint32_t dict_size,
+                                     const void* d_dict_huf, uint32_t cap_override, void* stream);
+
+// ---------------------------------------------------------------- device helpers (as in zxc_unframe_device.hip)
+__device__ __forceinline__ uint32_t rng_scan_add(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
+    return v;
+}
+__device__ __forceinline__ v4u rng_ld128(const uint8_t* p) { v4u v; __builtin_memcpy(&v, p, 16); return v; }  // any alignment
+
+// ---------------------------------------------------------------- open
+extern "C" __global__ void __launch_bounds__(64)
+zxc_seekidx_head_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size, uint32_t max_blocks, zr_index_t* __restrict__ ix) {
+    if (threadIdx.x == 0) zr_open_head(src, src_size, block_size, max_blocks, ix);
+}
+
+// Tile t covers entries [t * ZC_TILE_BLOCKS, ...), RNG_PER_THREAD consecutive entries per thread. Every tile of the grid writes its
+// word, also those behind the table (t * ZC_TILE_BLOCKS <= max_blocks: inside the index).
+extern "C" __global__ void __launch_bounds__(RNG_THREADS)
+zxc_seekidx_tiles_kernel(const uint8_t* __restrict__ src, const zr_index_t* __restrict__ ix, uint64_t* __restrict__ offs) {
+    __shared__ uint32_t w_sum[RNG_THREADS / 64u], w_bad[RNG_THREADS / 64u];
+    if (ix->seek != 1u) return;
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ix->nb;
+    const uint8_t* ent = zr_entries(src, ix);
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * RNG_PER_THREAD;
+    uint32_t sum = 0, bad = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+        const uint32_t b = b0 + j;
+        if (b >= nb) break;
+        const uint32_t e = zc_rd32(ent + 4ull * b);
+        if (zr_entry_ok(e)) sum += e;
+        else bad = 1u;
+    }
+    // (a thread's sum is <= 4 x 2^22, a wave's <= 2^30: 32 bits hold both)
+    sum = (uint32_t)__builtin_amdgcn_readlane((int)rng_scan_add(sum), 63);
+    bad = __any(bad) ? 1u : 0u;
+    if (lane == 0) { w_sum[wave] = sum; w_bad[wave] = bad; }
+    __syncthreads();
+    if (t == 0) {
+        uint64_t s = 0;
+        uint32_t d = 0;
+        for (uint32_t w = 0; w < RNG_THREADS / 64u; w++) { s += w_sum[w]; d |= w_bad[w]; }
+        offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS] = s | (d ? RNG_BAD : 0ull);
+    }
+}
+
+// One workgroup. Tile t's word becomes the archive offset of its first block (exclusive prefix + 16, in place); the table is
+// accepted only when no entry was implausible and the entries sum exactly to the EOF block the head stage found.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_seekidx_scan_kernel(uint64_t* __restrict__ offs, uint32_t n_tiles, zr_index_t* __restrict__ ix) {
+    __shared__ uint64_t w_tot[4];
+    __shared__ uint32_t w_bad[4];
+    if (ix->seek != 1u) return;
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t per = (n_tiles + 255u) / 256u;
+    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    uint64_t mine = 0;
+    uint32_t bad = 0;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint64_t w = offs[(uint64_t)i * ZC_TILE_BLOCKS];
+        mine += w & ~RNG_BAD;
+        bad |= (uint32_t)(w >> 63);
+    }
+    uint64_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(incl, (unsigned)d);
+        if ((int)lane >= d) incl += o;
+    }
+    bad = __any(bad) ? 1u : 0u;
+    if (lane == 63) w_tot[wave] = incl;
+    if (lane == 0) w_bad[wave] = bad;
+    __syncthreads();  // (every thread has read ix->seek by now)
+    uint64_t base = ZC_FILE_HDR, total = 0;
+    uint32_t gbad = 0;
+    for (uint32_t w = 0; w < 4u; w++) {
+        if (w < wave) base += w_tot[w];
+        total += w_tot[w];
+        gbad |= w_bad[w];
+    }
+    uint64_t run = base + incl - mine;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint64_t s = offs[(uint64_t)i * ZC_TILE_BLOCKS] & ~RNG_BAD;
+        offs[(uint64_t)i * ZC_TILE_BLOCKS] = run;
+        run += s;
+    }
+    if (t == 0) zr_open_judge(ix, (int)gbad, total);
+}
+
+// Per tile: block b's offset is the prefix sum of the entries. Every entry is plausible and the sum was checked, so every offset
+// lies in front of the EOF block.
+extern "C" __global__ void __launch_bounds__(RNG_THREADS)
+zxc_seekidx_scatter_kernel(const uint8_t* __restrict__ src, const zr_index_t* __restrict__ ix, uint64_t* __restrict__ offs) {
+    __shared__ uint32_t w_sum[RNG_THREADS / 64u];
+    __shared__ uint64_t tile_off;
+    if (ix->seek != 2u) return;
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ix->nb;
+    if ((uint64_t)blockIdx.x * ZC_TILE_BLOCKS >= nb) return;  // (a tile behind the table; [nb] is written by the last block's thread)
+    const uint8_t* ent = zr_entries(src, ix);
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * RNG_PER_THREAD;
+    uint32_t e[RNG_PER_THREAD], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+        e[j] = b0 + j < nb ? zc_rd32(ent + 4ull * (b0 + j)) : 0u;
+        sum += e[j];
+    }
+    const uint32_t incl = rng_scan_add(sum);
+    if (lane == 63) w_sum[wave] = incl;
+    if (t == 0) tile_off = offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS];
+    __syncthreads();  // (the tile's word is read before thread 0 writes its block's offset, the same value, over it)
+    uint64_t run = tile_off + incl - sum;
+    for (uint32_t w = 0; w < wave; w++) run += w_sum[w];
+#pragma unroll
+    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+        const uint32_t b = b0 + j;
+        if (b >= nb) break;
+        offs[b] = run;
+        run += e[j];
+        if (b + 1u == nb) offs[nb] = run;
+    }
+}
+
+// ---------------------------------------------------------------- ranges
+extern "C" __global__ void __launch_bounds__(256)
+zxc_ranges_plan_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
+                       uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel,
+                       zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_jobs) return;
+    const uint32_t r = i / J, j = i - r * J;
+    zxc_dev_job_t job;
+    zr_copy_t cp;
+    zr_job(index, ranges[r], j, i, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, &job, &cp);
+    jobs[i] = job;
+    copies[i] = cp;
+}
+
+// One wavefront per item = (job, chunk): chunk k of a job is the part of its copy whose destination addresses lie in
+// [A + k CHUNK, A + (k + 1) CHUNK), A = the copy's destination rounded down to 16. A lane moves 16-byte units of the destination:
+// an aligned 16-byte store fed by a 16-byte load of any alignment from the slot, bytes where the unit passes the copy's ends.
+// Most items are empty (direct and empty jobs, chunks behind a short copy) and end at once.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_ranges_copy_kernel(const uint8_t* __restrict__ stage, uint32_t slot_stride, const zr_copy_t* __restrict__ copies,
+                       const int32_t* __restrict__ status, uint32_t n_jobs, uint32_t chunks, uint8_t* __restrict__ dst) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t items = (uint64_t)n_jobs * chunks, waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t it = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); it < items; it += waves) {
+        const uint32_t i = (uint32_t)(it / chunks), k = (uint32_t)(it - (uint64_t)i * chunks);
+        const zr_copy_t cp = copies[i];
+        if (cp.n == 0 || (uint64_t)k * ZR_COPY_CHUNK >= (cp.dst_at & 15u) + cp.n) continue;
+        const int32_t st = status[i];
+        if (st < 0 || (uint32_t)st < cp.from + cp.n) continue;  // (the range fails: its bytes are undefined, nothing is copied)
+        const uint8_t* s = stage + (uint64_t)i * slot_stride + cp.from;
+        uint8_t* d = dst + cp.dst_at;
+        const int64_t n = (int64_t)cp.n;
+        // rel: position in the copy of this lane's first unit (negative in front of the head)
+        int64_t rel = (int64_t)k * ZR_COPY_CHUNK - (int64_t)(cp.dst_at & 15u) + 16 * (int64_t)lane;
+#pragma unroll 4
+        for (uint32_t u = 0; u < ZR_COPY_CHUNK / 1024u; u++, rel += 1024) {
+            if (rel >= n) break;
+            if (rel >= 0 && rel + 16 <= n) {
+                *(v4u*)(d + rel) = rng_ld128(s + rel);
+            } else {
+                const int64_t lo = rel < 0 ? 0 : rel, hi = rel + 16 < n ? rel + 16 : n;
+                for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+            }
+        }
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+zxc_ranges_verdict_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
+                          const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size,
+                          int64_t* __restrict__ results) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_ranges) return;
+    results[r] = zr_verdict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, dst_capacity, block_size);
+}
+
+// ---------------------------------------------------------------- host side
+namespace {
+bool launched() { return hipGetLastError() == hipSuccess; }
+bool have_device() {
+    int n_dev = 0, dev = -1;
+    return hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t zxc_mi355x_seekable_index_size(uint32_t max_blocks) { return zr_index_size(max_blocks); }
+
+int zxc_mi355x_seekable_open_device(const void* d_src, uint64_t src_size, uint32_t block_size, uint32_t max_blocks, void* d_index,
+                                    uint64_t index_size, void* stream) {
+    if (!d_src || !d_index) return ZXC_ERROR_NULL_INPUT;
+    if (src_size < ZR_OPEN_MIN) return ZXC_ERROR_SRC_TOO_SMALL;
+    if (!zr_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if ((uintptr_t)d_index & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (index_size < zr_index_size(max_blocks)) return ZXC_ERROR_MEMORY;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
+
+    const hipStream_t st = (hipStream_t)stream;
+    const uint8_t* src = (const uint8_t*)d_src;
+    zr_index_t* ix = (zr_index_t*)d_index;
+    uint64_t* offs = zr_offsets(d_index);
+    const uint32_t n_tiles = zr_open_tiles(max_blocks);
+    hipLaunchKernelGGL(zxc_seekidx_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, block_size, max_blocks, ix);
+    hipLaunchKernelGGL(zxc_seekidx_tiles_kernel, dim3(n_tiles), dim3(RNG_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
+    hipLaunchKernelGGL(zxc_seekidx_scan_kernel, dim3(1), dim3(256), 0, st, offs, n_tiles, ix);
+    hipLaunchKernelGGL(zxc_seekidx_scatter_kernel, dim3(n_tiles), dim3(RNG_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+uint64_t zxc_mi355x_decompress_ranges_device_work_size(uint32_t n_ranges, uint64_t max_len, uint32_t block_size) {
+    zr_shape_t s;
+    return zr_shape(n_ranges, max_len, block_size, &s) != 0 ? 0u : s.bytes;
+}
+
+int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges,
+                                        uint32_t n_ranges, uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                        void* d_work, uint64_t work_size, int64_t* d_results, void* stream) {
+    if (!d_src || !d_index || !d_work || !d_results || (!d_ranges && n_ranges > 0) || (!d_dst && dst_capacity > 0)) return ZXC_ERROR_NULL_INPUT;
+    zr_shape_t s;
+    const int shape_rc = zr_shape(n_ranges, max_len, block_size, &s);
+    if (shape_rc == ZXC_ERROR_BAD_BLOCK_SIZE) return shape_rc;
+    if ((uintptr_t)d_dst & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (shape_rc != 0 || work_size < s.bytes) return ZXC_ERROR_MEMORY;
+    if (n_ranges == 0) return ZXC_OK;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
+
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* base = (uint8_t*)zc_round_up((uint64_t)(uintptr_t)d_work, 256u);
+    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
+    int32_t* status = (int32_t*)(base + s.o_status);
+    zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);
+    uint8_t* stage = base + s.o_stage;
+    // One decode launch for both areas: job offsets are 64-bit and counted from d_out, so d_out is the lower of the two (both are
+    // 16-byte aligned, which keeps every out_off a multiple of 16).
+    uint8_t* out = (d_dst && (uint8_t*)d_dst < stage) ? (uint8_t*)d_dst : stage;
+    const uint64_t dst_rel = d_dst ? (uint64_t)((uint8_t*)d_dst - out) : 0u, stage_rel = (uint64_t)(stage - out);
+
+    hipLaunchKernelGGL(zxc_ranges_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
+                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, NULL, 0u, NULL, 0u, stream);
+    if (rc != ZXC_OK) return rc;
+    const uint64_t groups = ((uint64_t)s.n_jobs * s.copy_chunks + 3u) / 4u;
+    hipLaunchKernelGGL(zxc_ranges_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
+                       (const uint8_t*)stage, s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks,
+                       (uint8_t*)d_dst);
+    hipLaunchKernelGGL(zxc_ranges_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
+                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+}  // extern "C"

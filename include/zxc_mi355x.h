@@ -112,7 +112,7 @@ ZXC_EXPORT int zxc_mi355x_gather_blocks_device(const void* d_slots, uint32_t blo
  * block, seek table, footer, global hash) is written and the blocks are compacted, all on the device. The archive is byte for
  * byte the one zxc_compress writes for the same source, level, block_size, checksum_enabled and seekable.
  * Options are read like zxc_compress reads them (opts may be NULL); n_threads, progress_cb and user_data are ignored, and
- * opts->dict != NULL gives ZXC_ERROR_GPU_UNSUPPORTED.
+ * opts->dict != NULL gives ZXC_ERROR_GPU_UNSUPPORTED (a dictionary in device memory: zxc_mi355x_compress_dict_device below).
  * Reads exactly d_src[0, src_size) (the encoder's over-read is served from a staged copy of the last block or two), writes
  * nothing at or past d_dst + dst_capacity; d_dst may have any alignment. d_work is scratch of at least
  * zxc_mi355x_compress_device_work_size() bytes, any alignment, owned by the call until *d_result is written. */
@@ -191,8 +191,9 @@ ZXC_EXPORT int zxc_mi355x_frame_info_device(const void* d_src, uint64_t src_size
  * is read and judged on the device once (open), and then any number of calls fetch many ranges each, the ranges themselves lying
  * in device memory. Both calls return ZXC_OK once everything is enqueued, are asynchronous on `stream`, do not synchronise with
  * the host, allocate no device memory of their own (the decode launch keeps its per-stream buffers as it does for
- * zxc_mi355x_decode_blocks_device) and never write d_src. No dictionary support: an archive written with one gives every range
- * ZXC_ERROR_DICT_REQUIRED. Block checksum trailers are skipped, not verified, as in zxc_seekable_decompress_range. */
+ * zxc_mi355x_decode_blocks_device) and never write d_src. These calls take no dictionary: an archive written with one gives every
+ * range ZXC_ERROR_DICT_REQUIRED (zxc_mi355x_decompress_ranges_dict_device below takes one). Block checksum trailers are skipped,
+ * not verified, as in zxc_seekable_decompress_range. */
 
 /* One range to fetch (24 bytes, device-visible layout). */
 typedef struct zxc_dev_range {
@@ -255,6 +256,68 @@ ZXC_EXPORT int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t s
                                                    const zxc_dev_range_t* d_ranges, uint32_t n_ranges, uint64_t max_len,
                                                    void* d_dst, uint64_t dst_capacity, uint32_t block_size, void* d_work,
                                                    uint64_t work_size, int64_t* d_results, void* stream);
+
+/* ---- the same three calls with a dictionary that lies in device memory (zxc_amd/csrc/zxc_dict_device.hip and the three files
+ * above) ----
+ * opts->dict of zxc_compress / zxc_decompress and zxc_seekable_set_dict, for callers whose dictionary, like their data, is in
+ * device memory. A dictionary is described by a small host struct that every call reads when it is made and does not keep; what it
+ * points to must stay valid and unchanged until the call's result is written. */
+typedef struct zxc_dev_dict {          /* host struct; read at call time, not kept */
+    const void*     d_content;         /* dictionary content in device memory, 1..65535 bytes */
+    const void*     d_huf;             /* its 128-byte shared literal table in device memory, or NULL */
+    const uint32_t* d_id;              /* one word in device memory, written by zxc_mi355x_dict_prepare_device */
+    uint32_t        size;
+} zxc_dev_dict_t;
+/* No call reads d_content past `size` or d_huf past 128 bytes: the id pass loads inside the bytes it hashes, the encoder works on
+ * [dict | block] images that a byte-wise copy makes, and the dictionary decode kernel fetches dictionary bytes one at a time after
+ * checking the offset against `size`. (The host API allocates size + 128 + 64 for its own copy; nothing here needs that margin.
+ * This rests on reading the three kernels: a test cannot see an over-read inside an allocator's rounding.)
+ * A NULL zxc_dev_dict_t*, or one with size == 0, makes each call below behave exactly as its sibling without _dict. A host
+ * dictionary has no meaning here: opts->dict != NULL stays ZXC_ERROR_GPU_UNSUPPORTED. */
+
+/* *d_id = zxc_dict_id(content, size, huf), computed by one wavefront, asynchronously on `stream`, without synchronising with the
+ * host: once per dictionary, before the first call that uses it on that stream (or behind an event). d_huf may be NULL.
+ * Synchronous errors, in this order: NULL d_content or d_id -> ZXC_ERROR_NULL_INPUT; size == 0 -> ZXC_ERROR_NULL_INPUT;
+ * size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE. */
+ZXC_EXPORT int zxc_mi355x_dict_prepare_device(const void* d_content, uint32_t size, const void* d_huf, uint32_t* d_id, void* stream);
+
+/* zxc_mi355x_compress_device with a dictionary: the archive is byte for byte the one zxc_compress writes for the same source,
+ * options, dictionary and table. The file header carries the dictionary flag and *d_id, so its bytes 6..15 (flags, id, check
+ * bytes) are assembled on the device; as in zxc_compress the encoder is given the content only, the table enters the id alone.
+ * The blocks go through the [dict | block] images of zxc_mi355x_encode_blocks_dict_device in chunks of
+ * C = max(4096, 256 MiB / (block_size + dict_size)) blocks: one image area of min(nb, C) images is reused from chunk to chunk in
+ * stream order, a loop of enqueues without synchronisation. The work size is at most the sibling's plus
+ * min(nb, C) x (block_size + dict_size) + 4096. Reads exactly d_src[0, src_size): the images are copies already and their padding
+ * serves the encoder's over-read, so they take the place of the sibling's staged copy of the last blocks.
+ * Synchronous errors: the sibling's, in its order, with two additions behind the option checks: dict->size > 65535 ->
+ * ZXC_ERROR_DICT_TOO_LARGE; NULL d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_dict_device_work_size(uint64_t src_size, const zxc_compress_opts_t* opts, uint32_t dict_size);
+ZXC_EXPORT int zxc_mi355x_compress_dict_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity,
+                                               const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
+                                               uint64_t work_size, int64_t* d_result, void* stream);
+
+/* zxc_mi355x_decompress_device with a dictionary: same contract, same work size (zxc_mi355x_decompress_device_work_size), and
+ * *d_result is what zxc_decompress returns for the same bytes, capacity, options and dictionary. File-header errors and the
+ * block-size departure come first, as in the sibling; then a header with a dictionary id gives ZXC_ERROR_DICT_REQUIRED without a
+ * dictionary and ZXC_ERROR_DICT_MISMATCH with one whose *d_id differs, and no block is decoded in either case. A dictionary given
+ * for an archive written without one is handed to the decoder all the same, as the host does. The blocks are decoded by the
+ * dictionary kernel behind zxc_mi355x_decode_blocks_dict_device (one wavefront per block).
+ * Synchronous errors: the sibling's, with dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE and NULL d_content or d_id with size > 0
+ * -> ZXC_ERROR_NULL_INPUT behind the opts->dict check. */
+ZXC_EXPORT int zxc_mi355x_decompress_dict_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity,
+                                                 uint32_t block_size, const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict,
+                                                 void* d_work, uint64_t work_size, int64_t* d_result, void* stream);
+
+/* zxc_mi355x_decompress_ranges_device with a dictionary: same contract, index (zxc_mi355x_seekable_open_device stores the header's
+ * dictionary id) and work size. Where the sibling answers ZXC_ERROR_DICT_REQUIRED: that without a dictionary,
+ * ZXC_ERROR_DICT_MISMATCH when *d_id is not the index's id (every non-empty range, their destinations untouched), else the range is
+ * decoded with the dictionary. Synchronous errors: the sibling's, with dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE and NULL
+ * d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT behind the block_size check, as in the two calls above. */
+ZXC_EXPORT int zxc_mi355x_decompress_ranges_dict_device(const void* d_src, uint64_t src_size, const void* d_index,
+                                                        const zxc_dev_range_t* d_ranges, uint32_t n_ranges, uint64_t max_len,
+                                                        void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                                        const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size,
+                                                        int64_t* d_results, void* stream);
 
 #ifdef __cplusplus
 }

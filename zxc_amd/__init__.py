@@ -8,5 +8,6 @@ decoder behind it: if the library or a GPU is missing, calls raise.
 from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_size, decode_blocks_device,  # noqa: F401
                   compress_device, compress_device_work_size, decompress_device, decompress_device_work_size,
                   frame_info_device, seekable_index_size, seekable_open_device, decompress_ranges_device_work_size,
-                  decompress_ranges_device, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, error_name)
+                  decompress_ranges_device, dict_prepare_device, compress_dict_device, compress_dict_device_work_size,
+                  decompress_dict_device, decompress_ranges_dict_device, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, error_name)
 from . import api  # noqa: F401  (stream_* helpers live there)

@@ -348,6 +348,90 @@ def decompress_ranges_device(d_src, src_size, d_index, d_ranges, n_ranges, max_l
         raise ZxcError(rc, "zxc_mi355x_decompress_ranges_device")
 
 
+# ---- the device calls with a dictionary in device memory (include/zxc_mi355x.h: zxc_dev_dict_t)
+class _DevDict(C.Structure):  # zxc_dev_dict_t
+    _fields_ = [("d_content", C.c_void_p), ("d_huf", C.c_void_p), ("d_id", C.c_void_p), ("size", C.c_uint32)]
+
+
+def _dev_dict(dict_):
+    """dict_: None, or (d_content, size, d_huf or 0, d_id), raw device pointers as ints. -> a zxc_dev_dict_t pointer or None"""
+    if dict_ is None:
+        return None
+    d_content, size, d_huf, d_id = dict_
+    return C.byref(_DevDict(d_content or None, d_huf or None, d_id or None, size))
+
+
+def _bind_dict_device(L):
+    L.zxc_mi355x_dict_prepare_device.restype = C.c_int
+    L.zxc_mi355x_dict_prepare_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_compress_dict_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_dict_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
+    L.zxc_mi355x_compress_dict_device.restype = C.c_int
+    L.zxc_mi355x_compress_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts),
+                                                  C.POINTER(_DevDict), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_decompress_dict_device.restype = C.c_int
+    L.zxc_mi355x_decompress_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                                    C.POINTER(_DecompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_decompress_ranges_dict_device.restype = C.c_int
+    L.zxc_mi355x_decompress_ranges_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                           C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_DevDict), C.c_void_p,
+                                                           C.c_uint64, C.c_void_p, C.c_void_p]
+    return L
+
+
+def dict_prepare_device(d_content, size, d_huf, d_id, stream=0):
+    """zxc_mi355x_dict_prepare_device(): the uint32 at d_id receives zxc_dict_id of the content (and the 128-byte table at d_huf,
+    or 0 for none), computed on the device, asynchronously on `stream`. A synchronous failure raises ZxcError."""
+    rc = _bind_dict_device(lib()).zxc_mi355x_dict_prepare_device(C.c_void_p(d_content or None), size, C.c_void_p(d_huf or None),
+                                                                 C.c_void_p(d_id or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_dict_prepare_device")
+
+
+def compress_dict_device_work_size(src_size, dict_size, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_dict_device_work_size(): bytes of device scratch compress_dict_device needs with a dictionary of
+    dict_size bytes (0 for invalid options; dict_size 0 gives compress_device_work_size)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(_bind_dict_device(lib()).zxc_mi355x_compress_dict_device_work_size(src_size, C.byref(o), dict_size))
+
+
+def compress_dict_device(d_src, src_size, d_dst, dst_capacity, dict_, d_work, work_size, d_result, level=3, block_size=0,
+                         seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_dict_device(): compress_device with a dictionary in device memory, dict_ = (d_content, size, d_huf or 0,
+    d_id) with d_id prepared by dict_prepare_device, or None for no dictionary."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = _bind_dict_device(lib()).zxc_mi355x_compress_dict_device(
+        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, C.byref(o), _dev_dict(dict_),
+        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_dict_device")
+
+
+def decompress_dict_device(d_src, src_size, d_dst, dst_capacity, block_size, dict_, d_work, work_size, d_result, checksum=False,
+                           stream=0):
+    """zxc_mi355x_decompress_dict_device(): decompress_device with a dictionary in device memory (dict_ as in
+    compress_dict_device); the work size is decompress_device_work_size."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    rc = _bind_dict_device(lib()).zxc_mi355x_decompress_dict_device(
+        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, block_size, C.byref(o), _dev_dict(dict_),
+        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_dict_device")
+
+
+def decompress_ranges_dict_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, dict_,
+                                  d_work, work_size, d_results, stream=0):
+    """zxc_mi355x_decompress_ranges_dict_device(): decompress_ranges_device with a dictionary in device memory (dict_ as in
+    compress_dict_device); index and work size are the sibling's."""
+    rc = _bind_dict_device(lib()).zxc_mi355x_decompress_ranges_dict_device(
+        C.c_void_p(d_src or None), src_size, C.c_void_p(d_index or None), C.c_void_p(d_ranges or None), n_ranges, max_len,
+        C.c_void_p(d_dst or None), dst_capacity, block_size, _dev_dict(dict_), C.c_void_p(d_work or None), work_size,
+        C.c_void_p(d_results or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_ranges_dict_device")
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

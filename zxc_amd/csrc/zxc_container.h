@@ -98,9 +98,12 @@ ZC_FN zxc_dev_job_t zc_job(uint64_t comp_off, uint32_t i, uint32_t comp_size, ui
     return j;
 }
 
-/* ---- head: file header, footer, seek-table probe. src_size >= 28. n_jobs = ceil(dst_capacity / block_size) + 1. */
-ZC_FN void zc_head(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size, int want_verify, uint32_t n_jobs,
-                   zc_ctl_t* c) {
+/* ---- head: file header, footer, seek-table probe. src_size >= 28. n_jobs = ceil(dst_capacity / block_size) + 1.
+ * have_dict / dict_id: the caller's dictionary and its zxc_dict_id. A header with a dictionary id wants one, and that one
+ * (zxc_decompress, "zxc_dispatch.c:883-892"): DICT_REQUIRED without, DICT_MISMATCH with another; a dictionary given for a header
+ * without an id is not looked at here. */
+ZC_FN void zc_head_dict(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size, int want_verify, uint32_t n_jobs,
+                        zc_ctl_t* c, int have_dict, uint32_t have_id) {
     const uint8_t* foot = src + src_size - ZC_FOOTER;
     uint32_t lg = 0, dict_id = 0;
     c->head_result = 0; c->total = zc_rd64(foot); c->eof_at = 0; c->event = ZC_NO_EVENT; c->final = 0; c->file_ck = 0; c->verify = 0;
@@ -113,7 +116,10 @@ ZC_FN void zc_head(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity,
     }
     int rc = zc_file_header(src, &lg, &c->file_ck, &dict_id);
     if (rc == ZXC_OK && (1u << lg) != block_size) rc = ZXC_ERROR_BAD_BLOCK_SIZE; /* departure: the grids were sized by the argument */
-    if (rc == ZXC_OK && dict_id != 0) rc = ZXC_ERROR_DICT_REQUIRED;              /* (this call takes no dictionary) */
+    if (rc == ZXC_OK && dict_id != 0) {
+        if (!have_dict) rc = ZXC_ERROR_DICT_REQUIRED;
+        else if (have_id != dict_id) rc = ZXC_ERROR_DICT_MISMATCH;
+    }
     if (rc != ZXC_OK) { c->final = 1; c->head_result = rc; return; }
     c->verify = (c->file_ck && want_verify) ? 1u : 0u;
     c->sel = c->verify;
@@ -127,6 +133,11 @@ ZC_FN void zc_head(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity,
     if (zc_blk_type(eof) != ZC_BLK_EOF || !zc_blk_hdr_ok(eof) || zc_blk_csz(eof) != 0) return;
     c->eof_at = eof_at;
     c->seek = 1;
+}
+/* the head of the call that takes no dictionary */
+ZC_FN void zc_head(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size, int want_verify, uint32_t n_jobs,
+                   zc_ctl_t* c) {
+    zc_head_dict(src, src_size, dst_capacity, block_size, want_verify, n_jobs, c, 0, 0u);
 }
 
 /* ---- seek-table path. Entry i is block i's physical size. If every entry is plausible, the entries sum from offset 16 to the EOF

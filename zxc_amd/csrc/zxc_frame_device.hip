@@ -12,11 +12,15 @@
 //   result   *d_result = archive size or the error, written once, after everything above
 //
 // No workgroup waits for another: every dependency is the stream order between launches.
+//
+// zxc_mi355x_compress_dict_device is the same call with a dictionary in device memory. Two stages differ: the blocks are encoded
+// from [dict | block] images (zxc_mi355x_encode_blocks_dict_device), in chunks that reuse one image area in stream order, and
+// nothing is staged, because an image's padding serves the encoder's over-read; and the finish pass assembles bytes 6..15 of the
+// file header (dictionary flag, id, check bytes) itself, because the id is a word in device memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/zxc_error.h"
-#include "../../include/zxc_mi355x.h"
+#include "zxc_container.h"  // zc_hdr_hash16 on the device (and zxc_error.h, zxc_mi355x.h)
 
 #define FRAME_MAGIC 0x9CB02EF5u
 #define FRAME_VERSION 8u
@@ -29,6 +33,10 @@
 #define FRAME_PER_THREAD 4u
 #define FRAME_TILE_BLOCKS (FRAME_TILE_THREADS * FRAME_PER_THREAD)
 #define FRAME_ALIGN 256u
+#define FRAME_DICT_MAX 65535u
+#define FRAME_IMAGE_BYTES (256ull << 20)  // the image area of a chunk of the dictionary path stays near this ...
+#define FRAME_IMAGE_MIN_BLOCKS 4096u      // ... but a chunk is never fewer blocks than this
+#define FRAME_IMAGE_PAD 64u               // behind the last image (the encoder's over-read, as zxc_mi355x_encode_dict_work_size)
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
@@ -135,11 +143,13 @@ zxc_frame_tiles_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride, 
 // One workgroup. tile_sum[t] becomes the archive offset of tile t's first block (exclusive prefix + FRAME_HDR, in place); then the
 // archive size is checked against the capacity and, when it fits, the header, the EOF block, the SEK header and the footer are written.
 // hdr_lo / hdr_hi, eof and sek are the little-endian images of those 16 + 8 + 8 bytes, made on the host (they depend on options only).
+// dict_id != NULL (the dictionary call): the header gets the dictionary flag and *dict_id in bytes 7..10, and its check bytes are
+// computed here over that (zxc_compress: zxc_host.c, "HAS_DICTIONARY + dict_id").
 extern "C" __global__ void __launch_bounds__(256)
 zxc_frame_finish_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
                         uint32_t n_tiles, uint32_t nb, uint64_t src_size, uint8_t* __restrict__ dst, uint64_t dst_capacity,
                         uint64_t hdr_lo, uint64_t hdr_hi, uint64_t eof, uint64_t sek, uint32_t seekable, uint32_t checksum,
-                        FrameCtl* __restrict__ ctl) {
+                        FrameCtl* __restrict__ ctl, const uint32_t* __restrict__ dict_id) {
     __shared__ uint64_t w_tot[4];
     __shared__ uint32_t w_hash[4], w_bad[4];
     const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
@@ -179,6 +189,12 @@ zxc_frame_finish_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restr
     ctl->status = status;
     ctl->seek_at = eof_at + 2u * FRAME_BLK_HDR;
     if (status < 0) return;
+    if (dict_id) {  // bytes 6..15: flags | 0x40, the id in 7..10, zeros, the 16-bit check over the rest
+        const uint64_t id = *dict_id;
+        hdr_lo = (hdr_lo & 0x0000FFFFFFFFFFFFull) | (((hdr_lo >> 48) & 0xFFu) | 0x40u) << 48 | (id & 0xFFu) << 56;
+        hdr_hi = id >> 8;
+        hdr_hi |= (uint64_t)zc_hdr_hash16(hdr_lo, hdr_hi) << 48;
+    }
     fr_st_le(dst, hdr_lo, 8);
     fr_st_le(dst + 8, hdr_hi, 8);
     fr_st_le(dst + eof_at, eof, 8);
@@ -252,7 +268,7 @@ struct FramePlan {
     uint32_t block_size, lg, level, checksum, seekable, nb, n_tiles, k_direct, stride;
     uint64_t staged;  // source bytes of the staged blocks [k_direct, nb)
     // work-area offsets (relative to the 256-byte aligned base)
-    uint64_t o_tile_sum, o_tile_hash, o_tile_bad, o_sizes, o_offsets, o_stage, o_slots, bytes;
+    uint64_t o_tile_sum, o_tile_hash, o_tile_bad, o_sizes, o_offsets, o_stage, o_slots, o_images, bytes;  // o_images: the dictionary call's image area, behind the rest
 };
 
 uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1u) / a * a; }
@@ -287,7 +303,8 @@ int frame_plan(uint64_t src_size, const zxc_compress_opts_t* opts, FramePlan* p)
     p->o_sizes = o;     o = round_up(o + 4ull * nb, FRAME_ALIGN);
     p->o_offsets = o;   o = round_up(o + 8ull * nb, FRAME_ALIGN);
     p->o_stage = o;     o = round_up(o + (nb ? bs + FRAME_ENC_OVERREAD + FRAME_STAGE_PAD : 0u), FRAME_ALIGN);
-    p->o_slots = o;     o += nb * p->stride;
+    p->o_slots = o;     o = round_up(o + nb * p->stride, FRAME_ALIGN);
+    p->o_images = o;
     p->bytes = o + FRAME_ALIGN;  // (the caller's d_work may have any alignment)
     return ZXC_OK;
 }
@@ -299,6 +316,99 @@ uint64_t frame_known_size(const FramePlan& p) {
 }
 
 bool launched() { return hipGetLastError() == hipSuccess; }
+
+// The dictionary path's image area: blocks per chunk, and the area's bytes, added to p.bytes of the plain plan (0 blocks: none).
+uint64_t frame_chunk_blocks(const FramePlan& p, uint32_t dict_size) {
+    const uint64_t c = FRAME_IMAGE_BYTES / ((uint64_t)p.block_size + dict_size);
+    return c > FRAME_IMAGE_MIN_BLOCKS ? c : FRAME_IMAGE_MIN_BLOCKS;
+}
+uint64_t frame_image_bytes(const FramePlan& p, uint32_t dict_size) {
+    if (!p.nb) return 0u;
+    const uint64_t c = frame_chunk_blocks(p, dict_size), n = p.nb < c ? p.nb : c;
+    return round_up(n * ((uint64_t)p.block_size + dict_size) + FRAME_IMAGE_PAD, FRAME_ALIGN);
+}
+
+// Both calls behind their argument checks. dict == NULL: the plain call.
+int frame_enqueue(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, const FramePlan& p, const zxc_dev_dict_t* dict,
+                  void* d_work, int64_t* d_result, void* stream) {
+    int n_dev = 0, dev = -1;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || hipGetDevice(&dev) != hipSuccess || dev < 0)
+        return ZXC_ERROR_GPU_UNAVAILABLE;
+
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* base = (uint8_t*)round_up((uint64_t)(uintptr_t)d_work, FRAME_ALIGN);
+    FrameCtl* ctl = (FrameCtl*)base;
+    uint64_t* tile_sum = (uint64_t*)(base + p.o_tile_sum);
+    uint32_t* tile_hash = (uint32_t*)(base + p.o_tile_hash);
+    uint32_t* tile_bad = (uint32_t*)(base + p.o_tile_bad);
+    uint32_t* sizes = (uint32_t*)(base + p.o_sizes);
+    uint64_t* offsets = (uint64_t*)(base + p.o_offsets);
+    uint8_t* stage = base + p.o_stage;
+    uint8_t* slots = base + p.o_slots;
+    uint8_t* images = base + p.o_images;  // (dictionary call only: its work size adds frame_image_bytes() behind the plain plan)
+    uint8_t* dst = (uint8_t*)d_dst;
+
+    if (p.nb && dict) {
+        // Blocks are independent, so chunk by chunk gives the bytes of one launch over all of them. A chunk's images are built and
+        // consumed in stream order before the next chunk overwrites them. zxc_prepend_dict_kernel reads exactly the source's bytes.
+        const uint64_t chunk = frame_chunk_blocks(p, dict->size);
+        for (uint64_t b0 = 0; b0 < p.nb; b0 += chunk) {
+            const uint64_t n = p.nb - b0 < chunk ? p.nb - b0 : chunk, at = b0 * p.block_size;
+            const uint64_t bytes = src_size - at < n * p.block_size ? src_size - at : n * p.block_size;
+            const int rc = zxc_mi355x_encode_blocks_dict_device((const uint8_t*)d_src + at, bytes, p.block_size, (int)p.level, (int)p.checksum,
+                                                                dict->d_content, dict->size, images, slots + b0 * p.stride, sizes + b0, stream);
+            if (rc != ZXC_OK) return rc;
+        }
+    } else if (p.nb) {
+        const uint64_t direct = (uint64_t)p.k_direct * p.block_size;
+        hipLaunchKernelGGL(zxc_frame_stage_kernel, dim3((unsigned)((p.staged + FRAME_STAGE_PAD + 4095u) / 4096u)), dim3(256), 0, st,
+                           (const uint8_t*)d_src + direct, (uint32_t)p.staged, stage);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        int rc = ZXC_OK;
+        if (p.k_direct)
+            rc = zxc_mi355x_encode_blocks_device(d_src, direct, p.block_size, (int)p.level, (int)p.checksum, slots, sizes, stream);
+        if (rc == ZXC_OK)
+            rc = zxc_mi355x_encode_blocks_device(stage, p.staged, p.block_size, (int)p.level, (int)p.checksum,
+                                                 slots + (uint64_t)p.k_direct * p.stride, sizes + p.k_direct, stream);
+        if (rc != ZXC_OK) return rc;
+    }
+    if (p.nb) {
+        hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(p.n_tiles), dim3(FRAME_TILE_THREADS), 0, st, (const uint8_t*)slots, p.stride,
+                           (const uint32_t*)sizes, p.nb, p.block_size, p.checksum, tile_sum, tile_hash, tile_bad);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    uint8_t hdr[FRAME_HDR] = {0}, eof[FRAME_BLK_HDR] = {0}, sek[FRAME_BLK_HDR] = {0};
+    hdr[0] = (uint8_t)FRAME_MAGIC; hdr[1] = (uint8_t)(FRAME_MAGIC >> 8); hdr[2] = (uint8_t)(FRAME_MAGIC >> 16); hdr[3] = (uint8_t)(FRAME_MAGIC >> 24);
+    hdr[4] = FRAME_VERSION;
+    hdr[5] = (uint8_t)p.lg;
+    hdr[6] = p.checksum ? 0x80u : 0u;
+    if (!dict) {  // (with a dictionary the finish pass completes bytes 6..15)
+        const uint16_t h16 = fr_hdr_hash16(hdr);
+        hdr[14] = (uint8_t)h16;
+        hdr[15] = (uint8_t)(h16 >> 8);
+    }
+    eof[0] = 255u;  // BLK_EOF
+    eof[7] = fr_hdr_hash8(eof);
+    const uint32_t sek_len = p.nb * 4u;
+    sek[0] = 254u;  // BLK_SEK
+    sek[3] = (uint8_t)sek_len; sek[4] = (uint8_t)(sek_len >> 8); sek[5] = (uint8_t)(sek_len >> 16); sek[6] = (uint8_t)(sek_len >> 24);
+    sek[7] = fr_hdr_hash8(sek);
+    hipLaunchKernelGGL(zxc_frame_finish_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
+                       p.n_tiles, p.nb, src_size, dst, dst_capacity, fr_rd64(hdr), fr_rd64(hdr + 8), fr_rd64(eof), fr_rd64(sek), p.seekable, p.checksum, ctl,
+                       dict ? dict->d_id : (const uint32_t*)NULL);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    if (p.nb) {
+        hipLaunchKernelGGL(zxc_frame_scatter_kernel, dim3(p.n_tiles), dim3(FRAME_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,
+                           (const uint64_t*)tile_sum, offsets, dst, p.seekable, (const FrameCtl*)ctl);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        const uint32_t groups = (p.nb + 3u) / 4u < 65536u ? (p.nb + 3u) / 4u : 65536u;
+        hipLaunchKernelGGL(zxc_frame_gather_kernel, dim3(groups), dim3(256), 0, st, (const uint8_t*)slots, p.stride, (const uint32_t*)sizes,
+                           (const uint64_t*)offsets, dst, p.nb, (const FrameCtl*)ctl);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    hipLaunchKernelGGL(zxc_frame_result_kernel, dim3(1), dim3(64), 0, st, (const FrameCtl*)ctl, d_result);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
 
 }  // namespace
 
@@ -317,66 +427,27 @@ int zxc_mi355x_compress_device(const void* d_src, uint64_t src_size, void* d_dst
     if (prc != ZXC_OK) return prc;
     if (work_size < p.bytes) return ZXC_ERROR_MEMORY;
     if (dst_capacity < frame_known_size(p)) return ZXC_ERROR_DST_TOO_SMALL;
-    int n_dev = 0, dev = -1;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || hipGetDevice(&dev) != hipSuccess || dev < 0)
-        return ZXC_ERROR_GPU_UNAVAILABLE;
+    return frame_enqueue(d_src, src_size, d_dst, dst_capacity, p, NULL, d_work, d_result, stream);
+}
 
-    const hipStream_t st = (hipStream_t)stream;
-    uint8_t* base = (uint8_t*)round_up((uint64_t)(uintptr_t)d_work, FRAME_ALIGN);
-    FrameCtl* ctl = (FrameCtl*)base;
-    uint64_t* tile_sum = (uint64_t*)(base + p.o_tile_sum);
-    uint32_t* tile_hash = (uint32_t*)(base + p.o_tile_hash);
-    uint32_t* tile_bad = (uint32_t*)(base + p.o_tile_bad);
-    uint32_t* sizes = (uint32_t*)(base + p.o_sizes);
-    uint64_t* offsets = (uint64_t*)(base + p.o_offsets);
-    uint8_t* stage = base + p.o_stage;
-    uint8_t* slots = base + p.o_slots;
-    uint8_t* dst = (uint8_t*)d_dst;
+uint64_t zxc_mi355x_compress_dict_device_work_size(uint64_t src_size, const zxc_compress_opts_t* opts, uint32_t dict_size) {
+    FramePlan p;
+    if (frame_plan(src_size, opts, &p) != ZXC_OK || dict_size > FRAME_DICT_MAX) return 0u;
+    return p.bytes + (dict_size ? frame_image_bytes(p, dict_size) : 0u);
+}
 
-    if (p.nb) {
-        const uint64_t direct = (uint64_t)p.k_direct * p.block_size;
-        hipLaunchKernelGGL(zxc_frame_stage_kernel, dim3((unsigned)((p.staged + FRAME_STAGE_PAD + 4095u) / 4096u)), dim3(256), 0, st,
-                           (const uint8_t*)d_src + direct, (uint32_t)p.staged, stage);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-        int rc = ZXC_OK;
-        if (p.k_direct)
-            rc = zxc_mi355x_encode_blocks_device(d_src, direct, p.block_size, (int)p.level, (int)p.checksum, slots, sizes, stream);
-        if (rc == ZXC_OK)
-            rc = zxc_mi355x_encode_blocks_device(stage, p.staged, p.block_size, (int)p.level, (int)p.checksum,
-                                                 slots + (uint64_t)p.k_direct * p.stride, sizes + p.k_direct, stream);
-        if (rc != ZXC_OK) return rc;
-        hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(p.n_tiles), dim3(FRAME_TILE_THREADS), 0, st, (const uint8_t*)slots, p.stride,
-                           (const uint32_t*)sizes, p.nb, p.block_size, p.checksum, tile_sum, tile_hash, tile_bad);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    uint8_t hdr[FRAME_HDR] = {0}, eof[FRAME_BLK_HDR] = {0}, sek[FRAME_BLK_HDR] = {0};
-    hdr[0] = (uint8_t)FRAME_MAGIC; hdr[1] = (uint8_t)(FRAME_MAGIC >> 8); hdr[2] = (uint8_t)(FRAME_MAGIC >> 16); hdr[3] = (uint8_t)(FRAME_MAGIC >> 24);
-    hdr[4] = FRAME_VERSION;
-    hdr[5] = (uint8_t)p.lg;
-    hdr[6] = p.checksum ? 0x80u : 0u;
-    const uint16_t h16 = fr_hdr_hash16(hdr);
-    hdr[14] = (uint8_t)h16;
-    hdr[15] = (uint8_t)(h16 >> 8);
-    eof[0] = 255u;  // BLK_EOF
-    eof[7] = fr_hdr_hash8(eof);
-    const uint32_t sek_len = p.nb * 4u;
-    sek[0] = 254u;  // BLK_SEK
-    sek[3] = (uint8_t)sek_len; sek[4] = (uint8_t)(sek_len >> 8); sek[5] = (uint8_t)(sek_len >> 16); sek[6] = (uint8_t)(sek_len >> 24);
-    sek[7] = fr_hdr_hash8(sek);
-    hipLaunchKernelGGL(zxc_frame_finish_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
-                       p.n_tiles, p.nb, src_size, dst, dst_capacity, fr_rd64(hdr), fr_rd64(hdr + 8), fr_rd64(eof), fr_rd64(sek), p.seekable, p.checksum, ctl);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    if (p.nb) {
-        hipLaunchKernelGGL(zxc_frame_scatter_kernel, dim3(p.n_tiles), dim3(FRAME_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,
-                           (const uint64_t*)tile_sum, offsets, dst, p.seekable, (const FrameCtl*)ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-        const uint32_t groups = (p.nb + 3u) / 4u < 65536u ? (p.nb + 3u) / 4u : 65536u;
-        hipLaunchKernelGGL(zxc_frame_gather_kernel, dim3(groups), dim3(256), 0, st, (const uint8_t*)slots, p.stride, (const uint32_t*)sizes,
-                           (const uint64_t*)offsets, dst, p.nb, (const FrameCtl*)ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    hipLaunchKernelGGL(zxc_frame_result_kernel, dim3(1), dim3(64), 0, st, (const FrameCtl*)ctl, d_result);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+int zxc_mi355x_compress_dict_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, const zxc_compress_opts_t* opts,
+                                    const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, int64_t* d_result, void* stream) {
+    if (!d_dst || !d_result || !d_work || (src_size > 0 && !d_src)) return ZXC_ERROR_NULL_INPUT;
+    FramePlan p;
+    const int prc = frame_plan(src_size, opts, &p);
+    if (prc != ZXC_OK) return prc;
+    if (dict && dict->size > FRAME_DICT_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
+    if (dict && dict->size > 0 && (!dict->d_content || !dict->d_id)) return ZXC_ERROR_NULL_INPUT;
+    if (dict && dict->size == 0) dict = NULL;
+    if (work_size < p.bytes + (dict ? frame_image_bytes(p, dict->size) : 0u)) return ZXC_ERROR_MEMORY;
+    if (dst_capacity < frame_known_size(p)) return ZXC_ERROR_DST_TOO_SMALL;
+    return frame_enqueue(d_src, src_size, d_dst, dst_capacity, p, dict, d_work, d_result, stream);
 }
 
 }  // extern "C"

@@ -97,18 +97,25 @@ ZC_FN void zr_open_serial(const uint8_t* src, uint64_t src_size, uint32_t block_
 }
 
 /* ---- a range. What is decided before any block is looked at, in zxc_seekable_decompress_range's order (seek_range_check, then
- * range_source's bound): -> 1 and *result when the range is answered already, 0 when its blocks decide. */
-ZC_FN int zr_range_final(const zr_index_t* ix, zxc_dev_range_t r, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity,
-                         uint32_t block_size, int64_t* result) {
+ * range_source's bound): -> 1 and *result when the range is answered already, 0 when its blocks decide.
+ * have_dict / have_id: the caller's dictionary and its zxc_dict_id. An archive written with a dictionary wants one
+ * (seek_range_check) and that one (zxc_seekable_set_dict refuses another with DICT_MISMATCH; here the range is refused). */
+ZC_FN int zr_range_final_dict(const zr_index_t* ix, zxc_dev_range_t r, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity,
+                              uint32_t block_size, int have_dict, uint32_t have_id, int64_t* result) {
     if (r.len == 0) { *result = 0; return 1; }
     if (ix->status < 0) { *result = ix->status; return 1; }
     if (ix->block_size != block_size) { *result = ZXC_ERROR_BAD_BLOCK_SIZE; return 1; } /* (an index opened with another size) */
     /* max_len is the capacity the launch was sized for */
     if (r.len > max_len || r.dst_off > dst_capacity || r.len > dst_capacity - r.dst_off) { *result = ZXC_ERROR_DST_TOO_SMALL; return 1; }
     if (r.offset > ix->total || r.len > ix->total - r.offset) { *result = ZXC_ERROR_SRC_TOO_SMALL; return 1; }
-    if (ix->dict_id != 0) { *result = ZXC_ERROR_DICT_REQUIRED; return 1; }
+    if (ix->dict_id != 0 && !have_dict) { *result = ZXC_ERROR_DICT_REQUIRED; return 1; }
+    if (ix->dict_id != 0 && have_id != ix->dict_id) { *result = ZXC_ERROR_DICT_MISMATCH; return 1; }
     if (ix->eof_at + ZC_BLK_HDR > src_size) { *result = ZXC_ERROR_SRC_TOO_SMALL; return 1; } /* fewer bytes than were opened */
     return 0;
+}
+ZC_FN int zr_range_final(const zr_index_t* ix, zxc_dev_range_t r, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity,
+                         uint32_t block_size, int64_t* result) {
+    return zr_range_final_dict(ix, r, src_size, max_len, dst_capacity, block_size, 0, 0u, result);
 }
 /* bytes [*from, *to) of block b (counted from the block's first byte) that a non-final range wants; from == to: not covered */
 ZC_FN void zr_wanted(zxc_dev_range_t r, uint64_t b, uint32_t block_size, uint32_t* from, uint32_t* to) {
@@ -127,15 +134,16 @@ ZC_FN int zr_direct(zxc_dev_range_t r, uint64_t b, uint32_t block_size) {
 /* Job j of range r (job_index = r J + j): block offset / bs + j while the range reaches it, else an empty job (comp_size 0: the
  * decoder answers with an error status and touches nothing). out_len is a whole block, as range_source has it. The launch's
  * d_out is one base for both areas: d_dst = base + dst_rel, staged slot i = base + stage_rel + i slot_stride. */
-ZC_FN void zr_job(const void* index, zxc_dev_range_t r, uint32_t j, uint64_t job_index, uint64_t src_size, uint64_t max_len,
-                  uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel, zxc_dev_job_t* job, zr_copy_t* cp) {
+ZC_FN void zr_job_dict(const void* index, zxc_dev_range_t r, uint32_t j, uint64_t job_index, uint64_t src_size, uint64_t max_len,
+                       uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel, int have_dict, uint32_t have_id,
+                       zxc_dev_job_t* job, zr_copy_t* cp) {
     const zr_index_t* ix = (const zr_index_t*)index;
     const uint64_t* offs = zr_coffsets(index);
     int64_t res;
     uint32_t from, to;
     job->comp_off = 0; job->out_off = stage_rel + job_index * ((uint64_t)block_size + ZR_SLOT_PAD); job->comp_size = 0; job->out_len = block_size;
     cp->dst_at = 0; cp->from = 0; cp->n = 0;
-    if (zr_range_final(ix, r, src_size, max_len, dst_capacity, block_size, &res)) return;
+    if (zr_range_final_dict(ix, r, src_size, max_len, dst_capacity, block_size, have_dict, have_id, &res)) return;
     const uint64_t b = r.offset / block_size + j;
     zr_wanted(r, b, block_size, &from, &to);
     if (to == from) return;
@@ -145,16 +153,20 @@ ZC_FN void zr_job(const void* index, zxc_dev_range_t r, uint32_t j, uint64_t job
     if (zr_direct(r, b, block_size)) job->out_off = dst_rel + dst_at;
     else { cp->dst_at = dst_at; cp->from = from; cp->n = to - from; }
 }
+ZC_FN void zr_job(const void* index, zxc_dev_range_t r, uint32_t j, uint64_t job_index, uint64_t src_size, uint64_t max_len,
+                  uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel, zxc_dev_job_t* job, zr_copy_t* cp) {
+    zr_job_dict(index, r, j, job_index, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, 0, 0u, job, cp);
+}
 /* range_sink: a covered block's own error, or CORRUPT_DATA when it decoded short of what the range needs of it; 0 = fine */
 ZC_FN int32_t zr_block_verdict(int32_t status, uint32_t need_to) {
     if (status < 0) return status;
     return (uint32_t)status < need_to ? ZXC_ERROR_CORRUPT_DATA : 0;
 }
 /* The range's result from its J statuses: the first failing covered block in block order, else len. */
-ZC_FN int64_t zr_verdict(const void* index, zxc_dev_range_t r, uint32_t J, const int32_t* status, uint64_t src_size, uint64_t max_len,
-                         uint64_t dst_capacity, uint32_t block_size) {
+ZC_FN int64_t zr_verdict_dict(const void* index, zxc_dev_range_t r, uint32_t J, const int32_t* status, uint64_t src_size, uint64_t max_len,
+                              uint64_t dst_capacity, uint32_t block_size, int have_dict, uint32_t have_id) {
     int64_t res;
-    if (zr_range_final((const zr_index_t*)index, r, src_size, max_len, dst_capacity, block_size, &res)) return res;
+    if (zr_range_final_dict((const zr_index_t*)index, r, src_size, max_len, dst_capacity, block_size, have_dict, have_id, &res)) return res;
     const uint64_t b0 = r.offset / block_size;
     for (uint32_t j = 0; j < J; j++) {
         uint32_t from, to;
@@ -164,6 +176,10 @@ ZC_FN int64_t zr_verdict(const void* index, zxc_dev_range_t r, uint32_t J, const
         if (v != 0) return v;
     }
     return (int64_t)r.len;
+}
+ZC_FN int64_t zr_verdict(const void* index, zxc_dev_range_t r, uint32_t J, const int32_t* status, uint64_t src_size, uint64_t max_len,
+                         uint64_t dst_capacity, uint32_t block_size) {
+    return zr_verdict_dict(index, r, J, status, src_size, max_len, dst_capacity, block_size, 0, 0u);
 }
 
 /* ---- the call's shape, known to the host before any byte of the archive or of the range table */

@@ -19,6 +19,9 @@
 //
 // No workgroup waits for another: every dependency is the stream order between launches, and every stage is predicated on the index
 // status and the range's own verdict.
+//
+// zxc_mi355x_decompress_ranges_dict_device is the ranges call with a dictionary in device memory: plan and verdict compare the
+// index's dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launch gets the dictionary.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -164,13 +167,14 @@ zxc_seekidx_scatter_kernel(const uint8_t* __restrict__ src, const zr_index_t* __
 extern "C" __global__ void __launch_bounds__(256)
 zxc_ranges_plan_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
                        uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel,
-                       zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies) {
+                       zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies, const uint32_t* __restrict__ dict_id) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_jobs) return;
     const uint32_t r = i / J, j = i - r * J;
     zxc_dev_job_t job;
     zr_copy_t cp;
-    zr_job(index, ranges[r], j, i, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, &job, &cp);
+    zr_job_dict(index, ranges[r], j, i, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u,
+                &job, &cp);
     jobs[i] = job;
     copies[i] = cp;
 }
@@ -211,10 +215,11 @@ zxc_ranges_copy_kernel(const uint8_t* __restrict__ stage, uint32_t slot_stride, 
 extern "C" __global__ void __launch_bounds__(256)
 zxc_ranges_verdict_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
                           const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size,
-                          int64_t* __restrict__ results) {
+                          int64_t* __restrict__ results, const uint32_t* __restrict__ dict_id) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= n_ranges) return;
-    results[r] = zr_verdict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, dst_capacity, block_size);
+    results[r] = zr_verdict_dict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, dst_capacity, block_size, dict_id != nullptr,
+                                 dict_id ? *dict_id : 0u);
 }
 
 // ---------------------------------------------------------------- host side
@@ -256,19 +261,24 @@ uint64_t zxc_mi355x_decompress_ranges_device_work_size(uint32_t n_ranges, uint64
     return zr_shape(n_ranges, max_len, block_size, &s) != 0 ? 0u : s.bytes;
 }
 
-int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges,
-                                        uint32_t n_ranges, uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
-                                        void* d_work, uint64_t work_size, int64_t* d_results, void* stream) {
+// Both calls. dict == NULL: the call that takes no dictionary.
+static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges, uint32_t n_ranges,
+                       uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size, const zxc_dev_dict_t* dict, void* d_work,
+                       uint64_t work_size, int64_t* d_results, void* stream) {
     if (!d_src || !d_index || !d_work || !d_results || (!d_ranges && n_ranges > 0) || (!d_dst && dst_capacity > 0)) return ZXC_ERROR_NULL_INPUT;
     zr_shape_t s;
     const int shape_rc = zr_shape(n_ranges, max_len, block_size, &s);
     if (shape_rc == ZXC_ERROR_BAD_BLOCK_SIZE) return shape_rc;
+    if (dict && dict->size > 65535u) return ZXC_ERROR_DICT_TOO_LARGE;
+    if (dict && dict->size > 0 && (!dict->d_content || !dict->d_id)) return ZXC_ERROR_NULL_INPUT;
+    if (dict && dict->size == 0) dict = NULL;
     if ((uintptr_t)d_dst & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
     if (shape_rc != 0 || work_size < s.bytes) return ZXC_ERROR_MEMORY;
     if (n_ranges == 0) return ZXC_OK;
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
 
     const hipStream_t st = (hipStream_t)stream;
+    const uint32_t* d_id = dict ? dict->d_id : NULL;
     uint8_t* base = (uint8_t*)zc_round_up((uint64_t)(uintptr_t)d_work, 256u);
     zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
     int32_t* status = (int32_t*)(base + s.o_status);
@@ -280,17 +290,32 @@ int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, co
     const uint64_t dst_rel = d_dst ? (uint64_t)((uint8_t*)d_dst - out) : 0u, stage_rel = (uint64_t)(stage - out);
 
     hipLaunchKernelGGL(zxc_ranges_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
-                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies);
+                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies, d_id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, NULL, 0u, NULL, 0u, stream);
+    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, dict ? dict->d_content : NULL, dict ? dict->size : 0u,
+                                         dict ? dict->d_huf : NULL, 0u, stream);
     if (rc != ZXC_OK) return rc;
     const uint64_t groups = ((uint64_t)s.n_jobs * s.copy_chunks + 3u) / 4u;
     hipLaunchKernelGGL(zxc_ranges_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
                        (const uint8_t*)stage, s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks,
                        (uint8_t*)d_dst);
     hipLaunchKernelGGL(zxc_ranges_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
-                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results);
+                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results, d_id);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges,
+                                        uint32_t n_ranges, uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                        void* d_work, uint64_t work_size, int64_t* d_results, void* stream) {
+    return ranges_call(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, NULL, d_work, work_size, d_results,
+                       stream);
+}
+
+int zxc_mi355x_decompress_ranges_dict_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges,
+                                             uint32_t n_ranges, uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                             const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, int64_t* d_results, void* stream) {
+    return ranges_call(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, dict, d_work, work_size, d_results,
+                       stream);
 }
 
 }  // extern "C"

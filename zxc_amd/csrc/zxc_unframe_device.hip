@@ -21,6 +21,10 @@
 // Whether the blocks carry checksum trailers is known on the device only, and the decode launch takes it by value: a call that
 // asks for verification decodes two job tables, one with verify_trailer = 1 and one without, and the head stage picks the one
 // that gets the jobs (ctl.sel); the other stays empty.
+//
+// zxc_mi355x_decompress_dict_device is the same call with a dictionary in device memory: the head stage compares the header's
+// dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launches get the dictionary (the plan then is
+// the dictionary kernel, one wavefront per block).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -55,8 +59,8 @@ __device__ __forceinline__ uint32_t unf_wave_xor(uint32_t v) {
 // ---------------------------------------------------------------- kernels
 extern "C" __global__ void __launch_bounds__(64)
 zxc_unframe_head_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size, uint32_t want_verify,
-                        uint32_t n_jobs, zc_ctl_t* __restrict__ ctl) {
-    if (threadIdx.x == 0) zc_head(src, src_size, dst_capacity, block_size, (int)want_verify, n_jobs, ctl);
+                        uint32_t n_jobs, zc_ctl_t* __restrict__ ctl, const uint32_t* __restrict__ dict_id) {
+    if (threadIdx.x == 0) zc_head_dict(src, src_size, dst_capacity, block_size, (int)want_verify, n_jobs, ctl, dict_id != nullptr, dict_id ? *dict_id : 0u);
 }
 
 // Tile t covers entries [t * ZC_TILE_BLOCKS, ...), UNF_PER_THREAD consecutive entries per thread: the tile's sum and whether an entry is
@@ -263,13 +267,18 @@ uint64_t zxc_mi355x_decompress_device_work_size(uint64_t src_size, uint64_t dst_
     return s.bytes;
 }
 
-int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
-                                 const zxc_decompress_opts_t* opts, void* d_work, uint64_t work_size, int64_t* d_result, void* stream) {
+// Both calls. dict == NULL: the call that takes no dictionary.
+static int unframe_call(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                        const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, int64_t* d_result,
+                        void* stream) {
     if (!d_src || !d_work || !d_result || (!d_dst && dst_capacity > 0)) return ZXC_ERROR_NULL_INPUT;
     if (src_size < ZC_FILE_HDR + ZC_FOOTER) return ZXC_ERROR_SRC_TOO_SMALL;
     zc_shape_t s;
     if (zc_shape(dst_capacity, block_size, &s) != 0) return ZXC_ERROR_BAD_BLOCK_SIZE;
     if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (dict && dict->size > 65535u) return ZXC_ERROR_DICT_TOO_LARGE;
+    if (dict && dict->size > 0 && (!dict->d_content || !dict->d_id)) return ZXC_ERROR_NULL_INPUT;
+    if (dict && dict->size == 0) dict = NULL;
     if ((uintptr_t)d_dst & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
     if (work_size < s.bytes) return ZXC_ERROR_MEMORY;
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
@@ -287,8 +296,12 @@ int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_d
     const uint8_t* src = (const uint8_t*)d_src;
 
     if (hipMemsetAsync(jobs, 0, (size_t)tables * s.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
-    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, dst_capacity, block_size, want_verify, s.n_jobs, ctl);
+    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, dst_capacity, block_size, want_verify, s.n_jobs, ctl,
+                       dict ? dict->d_id : (const uint32_t*)NULL);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const void* d_dict = dict ? dict->d_content : NULL;
+    const void* d_huf = dict ? dict->d_huf : NULL;
+    const uint32_t dict_size = dict ? dict->size : 0u;
     if (dst_capacity > 0) {  // (the empty-frame probe is answered by the head stage alone)
         hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(s.n_tiles), dim3(UNF_THREADS), 0, st, src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
         hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_bad, s.n_tiles, ctl);
@@ -300,10 +313,10 @@ int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_d
         for (uint32_t tb = 0; tb < tables; tb++) {
             const zxc_dev_job_t* tab = jobs + (uint64_t)tb * s.n_jobs;
             int32_t* tst = status + (uint64_t)tb * s.n_jobs;
-            int rc = zxc_hip_decode_blocks(d_src, tab, s.k_direct, d_dst, tst, block_size, (int)tb, NULL, 0u, NULL, 0u, stream);
+            int rc = zxc_hip_decode_blocks(d_src, tab, s.k_direct, d_dst, tst, block_size, (int)tb, d_dict, dict_size, d_huf, 0u, stream);
             if (rc == ZXC_OK)
-                rc = zxc_hip_decode_blocks(d_src, tab + s.k_direct, s.n_jobs - s.k_direct, stage, tst + s.k_direct, block_size, (int)tb, NULL, 0u,
-                                           NULL, 0u, stream);
+                rc = zxc_hip_decode_blocks(d_src, tab + s.k_direct, s.n_jobs - s.k_direct, stage, tst + s.k_direct, block_size, (int)tb, d_dict,
+                                           dict_size, d_huf, 0u, stream);
             if (rc != ZXC_OK) return rc;
         }
         hipLaunchKernelGGL(zxc_unframe_tail_kernel, dim3(ZC_STAGED_MAX), dim3(256), 0, st, (const uint8_t*)stage, (const int32_t*)status,
@@ -314,6 +327,17 @@ int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_d
     }
     hipLaunchKernelGGL(zxc_unframe_result_kernel, dim3(1), dim3(64), 0, st, (const zc_ctl_t*)ctl, (const int32_t*)status, block_size, s.n_jobs, d_result);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                 const zxc_decompress_opts_t* opts, void* d_work, uint64_t work_size, int64_t* d_result, void* stream) {
+    return unframe_call(d_src, src_size, d_dst, dst_capacity, block_size, opts, NULL, d_work, work_size, d_result, stream);
+}
+
+int zxc_mi355x_decompress_dict_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, uint32_t block_size,
+                                      const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size,
+                                      int64_t* d_result, void* stream) {
+    return unframe_call(d_src, src_size, d_dst, dst_capacity, block_size, opts, dict, d_work, work_size, d_result, stream);
 }
 
 int zxc_mi355x_frame_info_device(const void* d_src, uint64_t src_size, uint32_t* block_size, uint64_t* decompressed_size, int* has_checksum,

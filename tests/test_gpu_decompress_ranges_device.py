@@ -410,3 +410,38 @@ def test_two_streams_share_one_index_and_the_call_is_ordered_behind_its_range_ta
         s.synchronize()
         _check_on_device(src, dst, a, ln, d, res.cpu().numpy()[:n], step=7)
         assert np.array_equal(dst[cap:].cpu().numpy(), _pattern(cap + CANARY)[cap:])
+
+
+def test_open_more_tiles_than_scan_threads(gpu):
+    """257 x 1024 + 5 blocks opened with room for three tiles more: more tiles than open's scan pass has threads, so each of its
+    threads sums several words of the index, and tiles behind the table run too. Each block starts with its own index, so a range
+    at a block's first byte shows whether comp_offsets[] of that block is right."""
+    import torch
+    bs, nb = 4096, 257 * 1024 + 5
+    n = nb * bs - 3
+    words = np.zeros(nb * (bs // 4), dtype="<u4")
+    words[:: bs // 4] = np.arange(nb, dtype="<u4")
+    data = words.view(np.uint8)[:n]
+    comp = gpu.compress(data.tobytes(), 1, bs, True, True)
+    arc = _to_dev(comp)
+    index = _open(gpu, arc, len(comp), bs, nb + 3 * 1024)
+    blocks = [0, 1, 1023, 1024, 1025, 256 * 1024 - 1, 256 * 1024, 256 * 1024 + 1, 257 * 1024 - 1, 257 * 1024, nb - 1]
+    ranges, at = [], 0
+    for b in blocks:
+        for odd in (0, 5, 11):   # destinations of every alignment class the copy-out has
+            ranges.append((b * bs, 8, at + odd))
+            at += 32
+    ranges.append((1024 * bs - 4, 8, at + 3))   # straddles blocks 1023 / 1024
+    cap = at + 32
+    got, dst = _fetch(gpu, arc, len(comp), index, ranges, 8, cap, bs)
+    assert _index_status(index) == 0
+    keep = np.zeros(len(dst), dtype=bool)
+    for (a, ln, d), rc in zip(ranges, got):
+        assert rc == ln, (a, rc)
+        assert np.array_equal(dst[d: d + ln], data[a: a + ln]), a
+        if a % bs == 0:
+            assert int(dst[d: d + 4].view("<u4")[0]) == a // bs, a
+        keep[d: d + ln] = True
+    assert np.array_equal(dst[~keep], _pattern(len(dst))[~keep])   # the gaps and the canary behind the destination
+    del arc, index, words, data
+    torch.cuda.empty_cache()

@@ -2,6 +2,8 @@
  * block-header validation, the seek-table rules, the header walk and the verdict's precedence. Plain inline C that hipcc and
  * a host C compiler both take, so that the kernels of zxc_unframe_device.hip and the CPU tests run the same lines. Every
  * function states what zxc_decompress (zxc_host.c) does for the same bytes; where the device call departs from it, it says so.
+ * The constants, the check bytes and the block-size and seek-table rules also serve zxc_mi355x_compress_device
+ * (zxc_frame_device.hip), which writes these bytes, and zxc_ranges.h.
  * Nothing here writes through a pointer it was not given, and every read lies inside src[0, src_size). */
 #ifndef ZXC_CONTAINER_H
 #define ZXC_CONTAINER_H
@@ -27,6 +29,7 @@
 #define ZC_SEEK_ENTRY_MAX (1u << 22)  /* a seek entry above this sends the archive to the walk (keeps a wave's sum in 32 bits) */
 #define ZC_STAGED_MAX 3u              /* blocks decoded into the work area: at most two slots that pass the capacity, and block n_max */
 #define ZC_NO_EVENT (~0ull)
+#define ZC_DICT_MAX 65535u            /* bytes of a dictionary (zxc_dev_dict_t.size) */
 
 /* Per-call state at the start of the work area. */
 typedef struct zc_ctl {
@@ -74,6 +77,26 @@ ZC_FN uint16_t zc_hdr_hash16(uint64_t lo, uint64_t hi) {
 ZC_FN int zc_blk_hdr_ok(uint64_t w) { return (uint8_t)(w >> 56) == zc_hdr_hash8(w); }
 ZC_FN uint32_t zc_blk_type(uint64_t w) { return (uint32_t)(w & 0xFFu); }
 ZC_FN uint32_t zc_blk_csz(uint64_t w) { return (uint32_t)(w >> 24); }
+/* ... and the word of a header with that type and payload size, check byte included */
+ZC_FN uint64_t zc_blk_hdr(uint32_t type, uint32_t csz) {
+    const uint64_t w = (uint64_t)type | (uint64_t)csz << 24;
+    return w | (uint64_t)zc_hdr_hash8(w) << 56;
+}
+/* a block size the format has: a power of two from 4 KiB to 2 MiB */
+ZC_FN int zc_block_size_ok(uint64_t bs) { return bs >= (1u << 12) && bs <= (1u << 21) && !(bs & (bs - 1u)); }
+/* A seek table is the last thing in front of the footer: [EOF header][SEK header][4 nb bytes][footer], at least the file header
+ * in front. -> 1 when both headers are valid, of their types, and the SEK header's size is 4 nb; then *eof_at is the EOF header's
+ * offset and *eof its word (whose size field is the caller's to judge). */
+ZC_FN int zc_seek_tail(const uint8_t* src, uint64_t src_size, uint64_t nb, uint64_t* eof_at, uint64_t* eof) {
+    if (ZC_FILE_HDR + 2u * ZC_BLK_HDR + 4u * nb + ZC_FOOTER > src_size) return 0;
+    const uint64_t sek_at = src_size - ZC_FOOTER - 4u * nb - ZC_BLK_HDR, at = sek_at - ZC_BLK_HDR;
+    const uint64_t sek = zc_rd64(src + sek_at), w = zc_rd64(src + at);
+    if (!zc_blk_hdr_ok(sek) || zc_blk_type(sek) != ZC_BLK_SEK || zc_blk_csz(sek) != 4u * nb) return 0;
+    if (!zc_blk_hdr_ok(w) || zc_blk_type(w) != ZC_BLK_EOF) return 0;
+    *eof_at = at;
+    *eof = w;
+    return 1;
+}
 
 /* read_file_header of zxc_host.c over the 16 header bytes. -> ZXC_OK or the error; block-size log2, checksum flag, dictionary id. */
 ZC_FN int zc_file_header(const uint8_t* h, uint32_t* lg, uint32_t* file_ck, uint32_t* dict_id) {
@@ -125,12 +148,8 @@ ZC_FN void zc_head_dict(const uint8_t* src, uint64_t src_size, uint64_t dst_capa
     c->sel = c->verify;
     const uint64_t nb = c->total / block_size + (c->total % block_size != 0);
     c->nb = nb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nb;
-    /* a seek table is the last thing in front of the footer: [EOF header][SEK header][4 nb bytes][footer] */
-    if (nb == 0 || nb > n_jobs || ZC_FILE_HDR + 2u * ZC_BLK_HDR + 4u * nb + ZC_FOOTER > src_size) return;
-    const uint64_t sek_at = src_size - ZC_FOOTER - 4u * nb - ZC_BLK_HDR, eof_at = sek_at - ZC_BLK_HDR;
-    const uint64_t sek = zc_rd64(src + sek_at), eof = zc_rd64(src + eof_at);
-    if (zc_blk_type(sek) != ZC_BLK_SEK || !zc_blk_hdr_ok(sek) || zc_blk_csz(sek) != 4u * nb) return;
-    if (zc_blk_type(eof) != ZC_BLK_EOF || !zc_blk_hdr_ok(eof) || zc_blk_csz(eof) != 0) return;
+    uint64_t eof_at = 0, eof = 0;
+    if (nb == 0 || nb > n_jobs || !zc_seek_tail(src, src_size, nb, &eof_at, &eof) || zc_blk_csz(eof) != 0) return;
     c->eof_at = eof_at;
     c->seek = 1;
 }
@@ -257,7 +276,7 @@ typedef struct zc_shape {
 ZC_FN uint64_t zc_round_up(uint64_t x, uint64_t a) { return (x + a - 1u) / a * a; }
 /* -> 0, or ZXC_ERROR_BAD_BLOCK_SIZE (block size, or more blocks than a launch counts) */
 ZC_FN int zc_shape(uint64_t dst_capacity, uint32_t block_size, zc_shape_t* s) {
-    if (block_size < (1u << 12) || block_size > (1u << 21) || (block_size & (block_size - 1u))) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     const uint64_t n_max = dst_capacity / block_size + (dst_capacity % block_size != 0);
     if (n_max + 1u > 0x7FFFFFFFull) return ZXC_ERROR_BAD_BLOCK_SIZE;
     s->n_jobs = (uint32_t)n_max + 1u;

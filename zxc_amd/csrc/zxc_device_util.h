@@ -1,0 +1,153 @@
+// zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
+// zxc_dict_device.hip): the wave primitives, the three tile passes every container stage is made of, the copy, and the host-side
+// plumbing of an entry point. HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h.
+//
+// A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
+// blocks per thread. Every helper with a barrier in it is called by all threads of the workgroup, outside divergent control flow.
+// The decode and encode kernels keep their own wave scans (wave_scan_add / e_scan_add): their sources do not include this file.
+#ifndef ZXC_DEVICE_UTIL_H
+#define ZXC_DEVICE_UTIL_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "zxc_container.h"
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+#define ZD_TILE_THREADS 256u
+#define ZD_WAVES (ZD_TILE_THREADS / 64u)
+#define ZD_PER_THREAD (ZC_TILE_BLOCKS / ZD_TILE_THREADS)
+#define ZD_WORK_ALIGN 256u  // every part of a work area starts on this, counted from the aligned base (zd_work_base)
+
+// ---------------------------------------------------------------- wave primitives
+// wave-wide inclusive prefix sum on the DPP crossbar (the same controls as wave_scan_add / e_scan_add of the kernel sources)
+__device__ __forceinline__ uint32_t zd_wave_scan_add(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
+    return v;
+}
+// xor butterfly: the xor of all 64 lanes' values, in every lane
+__device__ __forceinline__ uint32_t zd_wave_xor(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+
+// ---------------------------------------------------------------- tile passes
+struct zd_totals {
+    uint64_t sum;
+    uint32_t hash, bad;  // the hashes xored, the bad flags (0 / 1) ored
+};
+
+// Reduce over the workgroup: every thread hands in the sum, the hash and the bad flag of its own blocks; all threads get the
+// totals back. One barrier. A thread's sum is at most 2^24 (four entries of at most ZC_SEEK_ENTRY_MAX, or four block sizes of at
+// most 2 MiB + 64), a wave's then at most 2^30: 32 bits hold both, and the waves are added in 64.
+__device__ __forceinline__ zd_totals zd_tile_reduce(uint32_t sum, uint32_t hash, uint32_t bad) {
+    __shared__ uint32_t w_sum[ZD_WAVES], w_hash[ZD_WAVES], w_bad[ZD_WAVES];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    sum = (uint32_t)__builtin_amdgcn_readlane((int)zd_wave_scan_add(sum), 63);
+    hash = zd_wave_xor(hash);
+    bad = __any(bad) ? 1u : 0u;
+    if (lane == 0) { w_sum[wave] = sum; w_hash[wave] = hash; w_bad[wave] = bad; }
+    __syncthreads();
+    zd_totals r = {0, 0, 0};
+    for (uint32_t w = 0; w < ZD_WAVES; w++) { r.sum += w_sum[w]; r.hash ^= w_hash[w]; r.bad |= w_bad[w]; }
+    return r;
+}
+
+// Exclusive offsets inside a tile: sum = this thread's entries added up (the bound of zd_tile_reduce holds), base = the offset of
+// the tile's first block. -> base + the entries of all lower threads: the offset of this thread's first block. One barrier.
+__device__ __forceinline__ uint64_t zd_tile_offset(uint32_t sum, uint64_t base) {
+    __shared__ uint32_t w_incl[ZD_WAVES];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t incl = zd_wave_scan_add(sum);
+    if (lane == 63) w_incl[wave] = incl;
+    __syncthreads();
+    uint64_t at = base + incl - sum;
+    for (uint32_t w = 0; w < wave; w++) at += w_incl[w];
+    return at;
+}
+
+// One workgroup of 256 threads over the n_tiles words the reduce pass left, one per tile: load(i, hash, bad) returns tile i's sum
+// and folds its hash and bad flag into the two references; store(i, v) puts v where tile i's sum was. Thread t owns tiles
+// [t * per, (t + 1) * per): a serial sum, a 64-bit scan of the 256 sums (a tile's sum can pass 2^31), a serial write-back. Every
+// tile's word becomes base + the sums of the tiles in front of it; all threads get the totals (the sum without base). One barrier,
+// behind every thread's loads and in front of every store.
+template <class Load, class Store>
+__device__ __forceinline__ zd_totals zd_scan_tiles(uint32_t n_tiles, uint64_t base, Load load, Store store) {
+    __shared__ uint64_t w_tot[4];
+    __shared__ uint32_t w_hash[4], w_bad[4];
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t per = (n_tiles + 255u) / 256u;
+    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    uint64_t mine = 0;
+    uint32_t hash = 0, bad = 0;
+    for (uint32_t i = lo; i < hi; i++) mine += load(i, hash, bad);
+    uint64_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(incl, (unsigned)d);
+        if ((int)lane >= d) incl += o;
+    }
+    hash = zd_wave_xor(hash);
+    bad = __any(bad) ? 1u : 0u;
+    if (lane == 63) w_tot[wave] = incl;
+    if (lane == 0) { w_hash[wave] = hash; w_bad[wave] = bad; }
+    __syncthreads();
+    zd_totals r = {0, 0, 0};
+    uint64_t run = base + incl - mine;
+    for (uint32_t w = 0; w < 4u; w++) {
+        if (w < wave) run += w_tot[w];
+        r.sum += w_tot[w];
+        r.hash ^= w_hash[w];
+        r.bad |= w_bad[w];
+    }
+    for (uint32_t i = lo; i < hi; i++) {
+        uint32_t h = 0, b = 0;
+        const uint64_t s = load(i, h, b);
+        store(i, run);
+        run += s;
+    }
+    return r;
+}
+
+// d[0, n) = s[0, n) by `threads` threads, of which this is number t: 16-byte units of any alignment, bytes where the last unit
+// passes n. Reads and writes exactly those n bytes.
+__device__ __forceinline__ void zd_copy(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, uint32_t n, uint32_t t, uint32_t threads) {
+    for (uint32_t o = 16u * t; o < n; o += 16u * threads) {
+        if (o + 16u <= n) {
+            v4u v;
+            __builtin_memcpy(&v, s + o, 16);
+            __builtin_memcpy(d + o, &v, 16);
+        } else {
+            for (uint32_t k = o; k < n; k++) d[k] = s[k];
+        }
+    }
+}
+
+// ---------------------------------------------------------------- host side of an entry point
+// hidden entry point of zxc_hip_shim.hip (decode_launch)
+extern "C" int zxc_hip_decode_blocks(const void* d_comp, const zxc_dev_job_t* d_jobs, uint32_t n_jobs, void* d_out, int32_t* d_status,
+                                     uint32_t block_size, int verify_trailer, const void* d_dict, uint32_t dict_size,
+                                     const void* d_dict_huf, uint32_t cap_override, void* stream);
+
+static inline bool launched() { return hipGetLastError() == hipSuccess; }
+static inline bool have_device() {
+    int n_dev = 0, dev = -1;
+    return hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0;
+}
+// the caller's d_work may have any alignment: the work area starts at the next multiple of ZD_WORK_ALIGN (the *_work_size count it)
+static inline uint8_t* zd_work_base(void* d_work) { return (uint8_t*)zc_round_up((uint64_t)(uintptr_t)d_work, ZD_WORK_ALIGN); }
+// The dictionary argument of a *_dict_device call. -> ZXC_OK or the error; a dictionary of size 0 is no dictionary (*dict = NULL).
+static inline int dict_arg(const zxc_dev_dict_t** dict) {
+    const zxc_dev_dict_t* d = *dict;
+    if (d && d->size > ZC_DICT_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
+    if (d && d->size > 0 && (!d->d_content || !d->d_id)) return ZXC_ERROR_NULL_INPUT;
+    if (d && d->size == 0) *dict = NULL;
+    return ZXC_OK;
+}
+#endif

@@ -9,13 +9,8 @@
 // kept in this file because the decode and encode kernels include that one and their code does not change for this call.
 // The bulk loop is seven independent accumulators, one per lane, over at most 585 stripes of 112 bytes (65 535 bytes); the
 // <= 112-byte tail and the finaliser run wave-uniform. Every load lies inside p[0, len).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "zxc_device_util.h"  // the host-side plumbing; zxc_container.h: ZC_DICT_MAX
 
-#include "../../include/zxc_error.h"
-#include "../../include/zxc_mi355x.h"
-
-#define DI_DICT_MAX 65535u
 #define DI_HUF_BYTES 128u
 #define DI_DEPTH 8  // stripes of loads in flight per lane: the accumulator chain then runs at multiplier latency
 
@@ -112,11 +107,9 @@ zxc_dict_id_kernel(const uint8_t* __restrict__ content, uint32_t size, const uin
 
 extern "C" int zxc_mi355x_dict_prepare_device(const void* d_content, uint32_t size, const void* d_huf, uint32_t* d_id, void* stream) {
     if (!d_content || !d_id || size == 0u) return ZXC_ERROR_NULL_INPUT;
-    if (size > DI_DICT_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
-    int n_dev = 0, dev = -1;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || hipGetDevice(&dev) != hipSuccess || dev < 0)
-        return ZXC_ERROR_GPU_UNAVAILABLE;
+    if (size > ZC_DICT_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
     hipLaunchKernelGGL(zxc_dict_id_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)d_content, size,
                        (const uint8_t*)d_huf, d_id);
-    return hipGetLastError() == hipSuccess ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }

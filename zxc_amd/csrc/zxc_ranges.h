@@ -35,7 +35,6 @@ typedef struct zr_copy {
     uint32_t from, n;
 } zr_copy_t;
 
-ZC_FN int zr_block_size_ok(uint32_t bs) { return bs >= (1u << 12) && bs <= (1u << 21) && !(bs & (bs - 1u)); }
 ZC_FN uint64_t zr_index_size(uint32_t max_blocks) { return ZR_INDEX_HDR + 8ull * ((uint64_t)max_blocks + 1u); }
 ZC_FN uint32_t zr_open_tiles(uint32_t max_blocks) { return max_blocks ? (max_blocks + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS : 1u; }
 ZC_FN uint64_t* zr_offsets(void* index) { return (uint64_t*)((uint8_t*)index + ZR_INDEX_HDR); }
@@ -57,12 +56,8 @@ ZC_FN void zr_open_head(const uint8_t* src, uint64_t src_size, uint32_t block_si
     const uint64_t nb = total / block_size + (total % block_size != 0);
     if (nb > 0xFFFFFFFFull) return;
     if (nb > max_blocks) { ix->status = ZXC_ERROR_MEMORY; return; }
-    /* [EOF header][SEK header][4 nb bytes][footer] at the end, at least the file header in front */
-    if (ZC_FILE_HDR + 2u * ZC_BLK_HDR + 4u * nb + ZC_FOOTER > src_size) return;
-    const uint64_t sek_at = src_size - ZC_FOOTER - 4u * nb - ZC_BLK_HDR, eof_at = sek_at - ZC_BLK_HDR;
-    const uint64_t sek = zc_rd64(src + sek_at), eof = zc_rd64(src + eof_at);
-    if (!zc_blk_hdr_ok(sek) || zc_blk_type(sek) != ZC_BLK_SEK || zc_blk_csz(sek) != 4u * nb) return;
-    if (!zc_blk_hdr_ok(eof) || zc_blk_type(eof) != ZC_BLK_EOF) return; /* (its size field is not looked at, as on the host) */
+    uint64_t eof_at = 0, eof = 0;
+    if (!zc_seek_tail(src, src_size, nb, &eof_at, &eof)) return; /* (the EOF header's size field is not looked at, as on the host) */
     ix->nb = (uint32_t)nb; ix->total = total; ix->file_ck = ck; ix->dict_id = dict_id; ix->eof_at = eof_at;
     ix->seek = 1;
 }
@@ -70,7 +65,7 @@ ZC_FN const uint8_t* zr_entries(const uint8_t* src, const zr_index_t* ix) { retu
 /* seekable_build: an entry is at least a block header. Departure: none above ZC_SEEK_ENTRY_MAX (4 MiB; the tile sums are 32-bit;
  * no legal block, at most 2 MiB of payload, is that large). The host's "entry and running sum <= archive size" follow from the
  * sum landing on the EOF block. */
-ZC_FN int zr_entry_ok(uint32_t e) { return e >= ZC_BLK_HDR && e <= ZC_SEEK_ENTRY_MAX; }
+ZC_FN int zr_entry_ok(uint32_t e) { return zc_seek_entry_ok(e, 0u); }
 /* the entries summed from offset 16 land on the EOF block -> the table is accepted */
 ZC_FN void zr_open_judge(zr_index_t* ix, int any_bad, uint64_t sum) {
     if (!any_bad && ZC_FILE_HDR + sum == ix->eof_at) { ix->status = ZXC_OK; ix->seek = 2; }
@@ -190,7 +185,7 @@ typedef struct zr_shape {
 /* -> 0, ZXC_ERROR_BAD_BLOCK_SIZE, or ZXC_ERROR_MEMORY (more jobs than a launch counts). A range of len <= max_len touches at
  * most (max_len - 1) / bs + 2 blocks. */
 ZC_FN int zr_shape(uint32_t n_ranges, uint64_t max_len, uint32_t block_size, zr_shape_t* s) {
-    if (!zr_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     const uint64_t J = max_len ? (max_len - 1u) / block_size + 2u : 1u;
     if (J > 0x7FFFFFFEull || J * n_ranges > 0x7FFFFFFEull) return ZXC_ERROR_MEMORY;
     s->J = (uint32_t)J;

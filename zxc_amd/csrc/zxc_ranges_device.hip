@@ -22,32 +22,11 @@
 //
 // zxc_mi355x_decompress_ranges_dict_device is the ranges call with a dictionary in device memory: plan and verdict compare the
 // index's dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launch gets the dictionary.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "zxc_device_util.h"  // the tile passes, the host-side plumbing
 #include "zxc_ranges.h"
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-#define RNG_THREADS 256u
-#define RNG_PER_THREAD (ZC_TILE_BLOCKS / RNG_THREADS)
 #define RNG_BAD (1ull << 63)  // in a tile's word: one of its entries is implausible (a tile's sum is <= 2^32)
 
-// hidden entry point of zxc_hip_shim.hip (decode_launch)
-extern "C" int zxc_hip_decode_blocks(const void* d_comp, const zxc_dev_job_t* d_jobs, uint32_t n_jobs, void* d_out, int32_t* d_status,
-                                     uint32_t block_size, int verify_trailer, const void* d_dict, uint32_t dict_size,
-                                     const void* d_dict_huf, uint32_t cap_override, void* stream);
-
-// ---------------------------------------------------------------- device helpers (as in zxc_unframe_device.hip)
-__device__ __forceinline__ uint32_t rng_scan_add(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return v;
-}
 __device__ __forceinline__ v4u rng_ld128(const uint8_t* p) { v4u v; __builtin_memcpy(&v, p, 16); return v; }  // any alignment
 
 // ---------------------------------------------------------------- open
@@ -56,105 +35,62 @@ zxc_seekidx_head_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint
     if (threadIdx.x == 0) zr_open_head(src, src_size, block_size, max_blocks, ix);
 }
 
-// Tile t covers entries [t * ZC_TILE_BLOCKS, ...), RNG_PER_THREAD consecutive entries per thread. Every tile of the grid writes its
+// Tile t covers entries [t * ZC_TILE_BLOCKS, ...), ZD_PER_THREAD consecutive entries per thread. Every tile of the grid writes its
 // word, also those behind the table (t * ZC_TILE_BLOCKS <= max_blocks: inside the index).
-extern "C" __global__ void __launch_bounds__(RNG_THREADS)
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
 zxc_seekidx_tiles_kernel(const uint8_t* __restrict__ src, const zr_index_t* __restrict__ ix, uint64_t* __restrict__ offs) {
-    __shared__ uint32_t w_sum[RNG_THREADS / 64u], w_bad[RNG_THREADS / 64u];
     if (ix->seek != 1u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ix->nb;
+    const uint32_t t = threadIdx.x, nb = ix->nb;
     const uint8_t* ent = zr_entries(src, ix);
-    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * RNG_PER_THREAD;
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * ZD_PER_THREAD;
     uint32_t sum = 0, bad = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         const uint32_t b = b0 + j;
         if (b >= nb) break;
         const uint32_t e = zc_rd32(ent + 4ull * b);
         if (zr_entry_ok(e)) sum += e;
         else bad = 1u;
     }
-    // (a thread's sum is <= 4 x 2^22, a wave's <= 2^30: 32 bits hold both)
-    sum = (uint32_t)__builtin_amdgcn_readlane((int)rng_scan_add(sum), 63);
-    bad = __any(bad) ? 1u : 0u;
-    if (lane == 0) { w_sum[wave] = sum; w_bad[wave] = bad; }
-    __syncthreads();
-    if (t == 0) {
-        uint64_t s = 0;
-        uint32_t d = 0;
-        for (uint32_t w = 0; w < RNG_THREADS / 64u; w++) { s += w_sum[w]; d |= w_bad[w]; }
-        offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS] = s | (d ? RNG_BAD : 0ull);
-    }
+    const zd_totals tile = zd_tile_reduce(sum, 0u, bad);
+    if (t == 0) offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS] = tile.sum | (tile.bad ? RNG_BAD : 0ull);
 }
 
 // One workgroup. Tile t's word becomes the archive offset of its first block (exclusive prefix + 16, in place); the table is
 // accepted only when no entry was implausible and the entries sum exactly to the EOF block the head stage found.
 extern "C" __global__ void __launch_bounds__(256)
 zxc_seekidx_scan_kernel(uint64_t* __restrict__ offs, uint32_t n_tiles, zr_index_t* __restrict__ ix) {
-    __shared__ uint64_t w_tot[4];
-    __shared__ uint32_t w_bad[4];
     if (ix->seek != 1u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-    const uint32_t per = (n_tiles + 255u) / 256u;
-    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
-    uint64_t mine = 0;
-    uint32_t bad = 0;
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t w = offs[(uint64_t)i * ZC_TILE_BLOCKS];
-        mine += w & ~RNG_BAD;
-        bad |= (uint32_t)(w >> 63);
-    }
-    uint64_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(incl, (unsigned)d);
-        if ((int)lane >= d) incl += o;
-    }
-    bad = __any(bad) ? 1u : 0u;
-    if (lane == 63) w_tot[wave] = incl;
-    if (lane == 0) w_bad[wave] = bad;
-    __syncthreads();  // (every thread has read ix->seek by now)
-    uint64_t base = ZC_FILE_HDR, total = 0;
-    uint32_t gbad = 0;
-    for (uint32_t w = 0; w < 4u; w++) {
-        if (w < wave) base += w_tot[w];
-        total += w_tot[w];
-        gbad |= w_bad[w];
-    }
-    uint64_t run = base + incl - mine;
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t s = offs[(uint64_t)i * ZC_TILE_BLOCKS] & ~RNG_BAD;
-        offs[(uint64_t)i * ZC_TILE_BLOCKS] = run;
-        run += s;
-    }
-    if (t == 0) zr_open_judge(ix, (int)gbad, total);
+    const zd_totals all = zd_scan_tiles(  // (behind its barrier every thread has read ix->seek)
+        n_tiles, ZC_FILE_HDR,
+        [=](uint32_t i, uint32_t&, uint32_t& bad) {
+            const uint64_t w = offs[(uint64_t)i * ZC_TILE_BLOCKS];
+            bad |= (uint32_t)(w >> 63);
+            return w & ~RNG_BAD;
+        },
+        [=](uint32_t i, uint64_t off) { offs[(uint64_t)i * ZC_TILE_BLOCKS] = off; });
+    if (threadIdx.x == 0) zr_open_judge(ix, (int)all.bad, all.sum);
 }
 
 // Per tile: block b's offset is the prefix sum of the entries. Every entry is plausible and the sum was checked, so every offset
 // lies in front of the EOF block.
-extern "C" __global__ void __launch_bounds__(RNG_THREADS)
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
 zxc_seekidx_scatter_kernel(const uint8_t* __restrict__ src, const zr_index_t* __restrict__ ix, uint64_t* __restrict__ offs) {
-    __shared__ uint32_t w_sum[RNG_THREADS / 64u];
-    __shared__ uint64_t tile_off;
     if (ix->seek != 2u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ix->nb;
+    const uint32_t t = threadIdx.x, nb = ix->nb;
     if ((uint64_t)blockIdx.x * ZC_TILE_BLOCKS >= nb) return;  // (a tile behind the table; [nb] is written by the last block's thread)
     const uint8_t* ent = zr_entries(src, ix);
-    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * RNG_PER_THREAD;
-    uint32_t e[RNG_PER_THREAD], sum = 0;
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * ZD_PER_THREAD;
+    uint32_t e[ZD_PER_THREAD], sum = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         e[j] = b0 + j < nb ? zc_rd32(ent + 4ull * (b0 + j)) : 0u;
         sum += e[j];
     }
-    const uint32_t incl = rng_scan_add(sum);
-    if (lane == 63) w_sum[wave] = incl;
-    if (t == 0) tile_off = offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS];
-    __syncthreads();  // (the tile's word is read before thread 0 writes its block's offset, the same value, over it)
-    uint64_t run = tile_off + incl - sum;
-    for (uint32_t w = 0; w < wave; w++) run += w_sum[w];
+    // (thread 0 writes its first block's offset over the tile's word: the same value, so a thread reads the right one either way)
+    uint64_t run = zd_tile_offset(sum, offs[(uint64_t)blockIdx.x * ZC_TILE_BLOCKS]);
 #pragma unroll
-    for (uint32_t j = 0; j < RNG_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         const uint32_t b = b0 + j;
         if (b >= nb) break;
         offs[b] = run;
@@ -223,14 +159,6 @@ zxc_ranges_verdict_kernel(const void* __restrict__ index, const zxc_dev_range_t*
 }
 
 // ---------------------------------------------------------------- host side
-namespace {
-bool launched() { return hipGetLastError() == hipSuccess; }
-bool have_device() {
-    int n_dev = 0, dev = -1;
-    return hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0;
-}
-}  // namespace
-
 extern "C" {
 
 uint64_t zxc_mi355x_seekable_index_size(uint32_t max_blocks) { return zr_index_size(max_blocks); }
@@ -239,7 +167,7 @@ int zxc_mi355x_seekable_open_device(const void* d_src, uint64_t src_size, uint32
                                     uint64_t index_size, void* stream) {
     if (!d_src || !d_index) return ZXC_ERROR_NULL_INPUT;
     if (src_size < ZR_OPEN_MIN) return ZXC_ERROR_SRC_TOO_SMALL;
-    if (!zr_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     if ((uintptr_t)d_index & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
     if (index_size < zr_index_size(max_blocks)) return ZXC_ERROR_MEMORY;
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
@@ -250,9 +178,9 @@ int zxc_mi355x_seekable_open_device(const void* d_src, uint64_t src_size, uint32
     uint64_t* offs = zr_offsets(d_index);
     const uint32_t n_tiles = zr_open_tiles(max_blocks);
     hipLaunchKernelGGL(zxc_seekidx_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, block_size, max_blocks, ix);
-    hipLaunchKernelGGL(zxc_seekidx_tiles_kernel, dim3(n_tiles), dim3(RNG_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
+    hipLaunchKernelGGL(zxc_seekidx_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
     hipLaunchKernelGGL(zxc_seekidx_scan_kernel, dim3(1), dim3(256), 0, st, offs, n_tiles, ix);
-    hipLaunchKernelGGL(zxc_seekidx_scatter_kernel, dim3(n_tiles), dim3(RNG_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
+    hipLaunchKernelGGL(zxc_seekidx_scatter_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zr_index_t*)ix, offs);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
@@ -269,9 +197,8 @@ static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index
     zr_shape_t s;
     const int shape_rc = zr_shape(n_ranges, max_len, block_size, &s);
     if (shape_rc == ZXC_ERROR_BAD_BLOCK_SIZE) return shape_rc;
-    if (dict && dict->size > 65535u) return ZXC_ERROR_DICT_TOO_LARGE;
-    if (dict && dict->size > 0 && (!dict->d_content || !dict->d_id)) return ZXC_ERROR_NULL_INPUT;
-    if (dict && dict->size == 0) dict = NULL;
+    const int drc = dict_arg(&dict);
+    if (drc != ZXC_OK) return drc;
     if ((uintptr_t)d_dst & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
     if (shape_rc != 0 || work_size < s.bytes) return ZXC_ERROR_MEMORY;
     if (n_ranges == 0) return ZXC_OK;
@@ -279,7 +206,7 @@ static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index
 
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t* d_id = dict ? dict->d_id : NULL;
-    uint8_t* base = (uint8_t*)zc_round_up((uint64_t)(uintptr_t)d_work, 256u);
+    uint8_t* base = zd_work_base(d_work);
     zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
     int32_t* status = (int32_t*)(base + s.o_status);
     zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);

@@ -1,6 +1,6 @@
 // zxc_unframe_device.hip — zxc_mi355x_decompress_device: a whole v8 archive in device memory decoded into device memory.
 //
-// The mirror image of zxc_frame_device.hip. zxc_decompress (zxc_host.c) reads the container on the host around the device decoder;
+// The mirror image of zxc_mi355x_compress_device. zxc_decompress (zxc_host.c) reads the container on the host around the device decoder;
 // here the container is parsed, validated and judged on the device, so that an archive already in HBM never crosses the link. The
 // container rules are the inline C of zxc_container.h, which the CPU tests run as well. The stream order of one call:
 //
@@ -25,36 +25,7 @@
 // zxc_mi355x_decompress_dict_device is the same call with a dictionary in device memory: the head stage compares the header's
 // dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launches get the dictionary (the plan then is
 // the dictionary kernel, one wavefront per block).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "zxc_container.h"
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-#define UNF_THREADS 256u
-#define UNF_PER_THREAD (ZC_TILE_BLOCKS / UNF_THREADS)
-
-// hidden entry point of zxc_hip_shim.hip (decode_launch)
-extern "C" int zxc_hip_decode_blocks(const void* d_comp, const zxc_dev_job_t* d_jobs, uint32_t n_jobs, void* d_out, int32_t* d_status,
-                                     uint32_t block_size, int verify_trailer, const void* d_dict, uint32_t dict_size,
-                                     const void* d_dict_huf, uint32_t cap_override, void* stream);
-
-// ---------------------------------------------------------------- device helpers (as in zxc_frame_device.hip)
-__device__ __forceinline__ uint32_t unf_scan_add(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return v;
-}
-__device__ __forceinline__ uint32_t unf_wave_xor(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
+#include "zxc_device_util.h"  // the tile passes, the copy, the host-side plumbing; zxc_container.h: the container rules
 
 // ---------------------------------------------------------------- kernels
 extern "C" __global__ void __launch_bounds__(64)
@@ -63,36 +34,28 @@ zxc_unframe_head_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint
     if (threadIdx.x == 0) zc_head_dict(src, src_size, dst_capacity, block_size, (int)want_verify, n_jobs, ctl, dict_id != nullptr, dict_id ? *dict_id : 0u);
 }
 
-// Tile t covers entries [t * ZC_TILE_BLOCKS, ...), UNF_PER_THREAD consecutive entries per thread: the tile's sum and whether an entry is
+// Tile t covers entries [t * ZC_TILE_BLOCKS, ...), ZD_PER_THREAD consecutive entries per thread: the tile's sum and whether an entry is
 // implausible (such an entry is never added or used as a length). Every tile of the grid writes, also those behind the table.
-extern "C" __global__ void __launch_bounds__(UNF_THREADS)
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
 zxc_unframe_tiles_kernel(const uint8_t* __restrict__ src, const zc_ctl_t* __restrict__ ctl, uint64_t* __restrict__ tile_sum,
                          uint32_t* __restrict__ tile_bad) {
-    __shared__ uint32_t w_sum[UNF_THREADS / 64u], w_bad[UNF_THREADS / 64u];
     if (ctl->final || ctl->seek != 1u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ctl->nb, file_ck = ctl->file_ck;
+    const uint32_t t = threadIdx.x, nb = ctl->nb, file_ck = ctl->file_ck;
     const uint8_t* ent = zc_seek_entries(src, ctl);
-    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * UNF_PER_THREAD;
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * ZD_PER_THREAD;
     uint32_t sum = 0, bad = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < UNF_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         const uint32_t b = b0 + j;
         if (b >= nb) break;
         const uint32_t e = zc_rd32(ent + 4ull * b);
         if (zc_seek_entry_ok(e, file_ck)) sum += e;
         else bad = 1u;
     }
-    // (a thread's sum is <= 4 x 2^22, a wave's <= 2^30: 32 bits hold both)
-    sum = (uint32_t)__builtin_amdgcn_readlane((int)unf_scan_add(sum), 63);
-    bad = __any(bad) ? 1u : 0u;
-    if (lane == 0) { w_sum[wave] = sum; w_bad[wave] = bad; }
-    __syncthreads();
+    const zd_totals tile = zd_tile_reduce(sum, 0u, bad);
     if (t == 0) {
-        uint64_t s = 0;
-        uint32_t d = 0;
-        for (uint32_t w = 0; w < UNF_THREADS / 64u; w++) { s += w_sum[w]; d |= w_bad[w]; }
-        tile_sum[blockIdx.x] = s;
-        tile_bad[blockIdx.x] = d;
+        tile_sum[blockIdx.x] = tile.sum;
+        tile_bad[blockIdx.x] = tile.bad;
     }
 }
 
@@ -100,63 +63,34 @@ zxc_unframe_tiles_kernel(const uint8_t* __restrict__ src, const zc_ctl_t* __rest
 // (ctl.seek = 2) only when no entry was implausible and the entries sum exactly to the EOF block the head stage found.
 extern "C" __global__ void __launch_bounds__(256)
 zxc_unframe_scan_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_bad, uint32_t n_tiles, zc_ctl_t* __restrict__ ctl) {
-    __shared__ uint64_t w_tot[4];
-    __shared__ uint32_t w_bad[4];
     if (ctl->final || ctl->seek != 1u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-    const uint32_t per = (n_tiles + 255u) / 256u;
-    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
-    uint64_t mine = 0;
-    uint32_t bad = 0;
-    for (uint32_t i = lo; i < hi; i++) { mine += tile_sum[i]; bad |= tile_bad[i]; }
-    uint64_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(incl, (unsigned)d);
-        if ((int)lane >= d) incl += o;
-    }
-    bad = __any(bad) ? 1u : 0u;
-    if (lane == 63) w_tot[wave] = incl;
-    if (lane == 0) w_bad[wave] = bad;
-    __syncthreads();  // (every thread has read ctl->seek by now)
-    uint64_t base = ZC_FILE_HDR, total = 0;
-    uint32_t gbad = 0;
-    for (uint32_t w = 0; w < 4u; w++) {
-        if (w < wave) base += w_tot[w];
-        total += w_tot[w];
-        gbad |= w_bad[w];
-    }
-    uint64_t run = base + incl - mine;
-    for (uint32_t i = lo; i < hi; i++) { const uint64_t s = tile_sum[i]; tile_sum[i] = run; run += s; }
-    if (t == 0) ctl->seek = (!gbad && ZC_FILE_HDR + total == ctl->eof_at) ? 2u : 0u;
+    const zd_totals all = zd_scan_tiles(  // (behind its barrier every thread has read ctl->seek)
+        n_tiles, ZC_FILE_HDR, [=](uint32_t i, uint32_t&, uint32_t& bad) { const uint64_t s = tile_sum[i]; bad |= tile_bad[i]; return s; },
+        [=](uint32_t i, uint64_t off) { tile_sum[i] = off; });
+    if (threadIdx.x == 0) ctl->seek = (!all.bad && ZC_FILE_HDR + all.sum == ctl->eof_at) ? 2u : 0u;
 }
 
 // Per tile: block b's offset is the prefix sum of the entries; its thread checks the block header found there against the entry and
 // writes the job. Every offset + entry lies in front of the EOF block (the scan checked the sum), so every read is inside the archive.
-extern "C" __global__ void __launch_bounds__(UNF_THREADS)
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
 zxc_unframe_scatter_kernel(const uint8_t* __restrict__ src, const zc_ctl_t* __restrict__ ctl, const uint64_t* __restrict__ tile_off,
                            uint32_t block_size, uint32_t k_direct, uint32_t n_jobs, zxc_dev_job_t* __restrict__ jobs,
                            uint32_t* __restrict__ tile_hash, uint32_t* __restrict__ tile_bad) {
-    __shared__ uint32_t w_sum[UNF_THREADS / 64u], w_hash[UNF_THREADS / 64u], w_bad[UNF_THREADS / 64u];
     if (ctl->final || ctl->seek != 2u) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u, nb = ctl->nb, file_ck = ctl->file_ck, verify = ctl->verify;
+    const uint32_t t = threadIdx.x, nb = ctl->nb, file_ck = ctl->file_ck, verify = ctl->verify;
     const uint8_t* ent = zc_seek_entries(src, ctl);
     zxc_dev_job_t* tab = jobs + (uint64_t)ctl->sel * n_jobs;
-    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * UNF_PER_THREAD;
-    uint32_t e[UNF_PER_THREAD], sum = 0;
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + t * ZD_PER_THREAD;
+    uint32_t e[ZD_PER_THREAD], sum = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < UNF_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         e[j] = b0 + j < nb ? zc_rd32(ent + 4ull * (b0 + j)) : 0u;
         sum += e[j];
     }
-    const uint32_t incl = unf_scan_add(sum);
-    if (lane == 63) w_sum[wave] = incl;
-    __syncthreads();
-    uint64_t run = tile_off[blockIdx.x] + incl - sum;
-    for (uint32_t w = 0; w < wave; w++) run += w_sum[w];
+    uint64_t run = zd_tile_offset(sum, tile_off[blockIdx.x]);
     uint32_t hash = 0, bad = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < UNF_PER_THREAD; j++) {
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         const uint32_t b = b0 + j;
         if (b >= nb) break;
         if (!zc_seek_block_ok(src, run, e[j], file_ck)) bad = 1u;
@@ -164,15 +98,10 @@ zxc_unframe_scatter_kernel(const uint8_t* __restrict__ src, const zc_ctl_t* __re
         if (b < n_jobs) tab[b] = zc_job(run, b, e[j], block_size, k_direct);
         run += e[j];
     }
-    hash = unf_wave_xor(hash);
-    bad = __any(bad) ? 1u : 0u;
-    if (lane == 0) { w_hash[wave] = hash; w_bad[wave] = bad; }
-    __syncthreads();
+    const zd_totals tile = zd_tile_reduce(0u, hash, bad);
     if (t == 0) {
-        uint32_t h = 0, d = 0;
-        for (uint32_t w = 0; w < UNF_THREADS / 64u; w++) { h ^= w_hash[w]; d |= w_bad[w]; }
-        tile_hash[blockIdx.x] = h;
-        tile_bad[blockIdx.x] = d;
+        tile_hash[blockIdx.x] = tile.hash;
+        tile_bad[blockIdx.x] = tile.bad;
     }
 }
 
@@ -183,20 +112,16 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_unframe_walk_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size, uint32_t k_direct, uint32_t n_jobs,
                         const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad, zxc_dev_job_t* __restrict__ jobs,
                         zc_ctl_t* __restrict__ ctl) {
-    __shared__ uint32_t w_hash[4], w_bad[4];
     if (ctl->final) return;
-    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+    const uint32_t t = threadIdx.x;
     zxc_dev_job_t* tab = jobs + (uint64_t)ctl->sel * n_jobs;
     if (ctl->seek == 2u) {
         const uint32_t tiles = (ctl->nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS;  // (nb <= n_jobs: inside the grid of the scatter pass)
         uint32_t hash = 0, bad = 0;
         for (uint32_t i = t; i < tiles; i += 256u) { hash ^= tile_hash[i]; bad |= tile_bad[i]; }
-        hash = unf_wave_xor(hash);
-        bad = __any(bad) ? 1u : 0u;
-        if (lane == 0) { w_hash[wave] = hash; w_bad[wave] = bad; }
-        __syncthreads();
-        if (!(w_bad[0] | w_bad[1] | w_bad[2] | w_bad[3])) {
-            if (t == 0) zc_chain_from_table(ctl, w_hash[0] ^ w_hash[1] ^ w_hash[2] ^ w_hash[3]);
+        const zd_totals all = zd_tile_reduce(0u, hash, bad);
+        if (!all.bad) {
+            if (t == 0) zc_chain_from_table(ctl, all.hash);
             return;
         }
         uint64_t* words = (uint64_t*)tab;  // 24-byte jobs, 8-byte aligned
@@ -213,12 +138,7 @@ zxc_unframe_tail_kernel(const uint8_t* __restrict__ stage, const int32_t* __rest
     const uint32_t i = k_direct + blockIdx.x;
     if (ctl->final || i >= n_jobs) return;
     const uint32_t n = zc_tail_bytes(i, status[(uint64_t)ctl->sel * n_jobs + i], block_size, dst_capacity);
-    const uint8_t* s = stage + (uint64_t)blockIdx.x * block_size;  // both 16-byte aligned
-    uint8_t* d = dst + (uint64_t)i * block_size;
-    for (uint32_t o = 16u * threadIdx.x; o < n; o += 16u * 256u) {
-        if (o + 16u <= n) *(v4u*)(d + o) = *(const v4u*)(s + o);
-        else for (uint32_t b = o; b < n; b++) d[b] = s[b];
-    }
+    zd_copy(dst + (uint64_t)i * block_size, stage + (uint64_t)blockIdx.x * block_size, n, threadIdx.x, 256u);
 }
 
 // The first block, in archive order, whose status ends the call: zc_block_event is local to a block as long as no earlier block has
@@ -251,14 +171,6 @@ zxc_unframe_result_kernel(const zc_ctl_t* __restrict__ ctl, const int32_t* __res
 }
 
 // ---------------------------------------------------------------- host side
-namespace {
-bool launched() { return hipGetLastError() == hipSuccess; }
-bool have_device() {
-    int n_dev = 0, dev = -1;
-    return hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0;
-}
-}  // namespace
-
 extern "C" {
 
 uint64_t zxc_mi355x_decompress_device_work_size(uint64_t src_size, uint64_t dst_capacity, uint32_t block_size) {
@@ -276,16 +188,15 @@ static int unframe_call(const void* d_src, uint64_t src_size, void* d_dst, uint6
     zc_shape_t s;
     if (zc_shape(dst_capacity, block_size, &s) != 0) return ZXC_ERROR_BAD_BLOCK_SIZE;
     if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
-    if (dict && dict->size > 65535u) return ZXC_ERROR_DICT_TOO_LARGE;
-    if (dict && dict->size > 0 && (!dict->d_content || !dict->d_id)) return ZXC_ERROR_NULL_INPUT;
-    if (dict && dict->size == 0) dict = NULL;
+    const int drc = dict_arg(&dict);
+    if (drc != ZXC_OK) return drc;
     if ((uintptr_t)d_dst & 15u) return ZXC_ERROR_GPU_UNSUPPORTED;
     if (work_size < s.bytes) return ZXC_ERROR_MEMORY;
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
 
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t want_verify = (opts && opts->checksum_enabled) ? 1u : 0u, tables = 1u + want_verify;
-    uint8_t* base = (uint8_t*)zc_round_up((uint64_t)(uintptr_t)d_work, 256u);
+    uint8_t* base = zd_work_base(d_work);
     zc_ctl_t* ctl = (zc_ctl_t*)base;
     uint64_t* tile_sum = (uint64_t*)(base + s.o_tile_sum);
     uint32_t* tile_hash = (uint32_t*)(base + s.o_tile_hash);
@@ -303,9 +214,9 @@ static int unframe_call(const void* d_src, uint64_t src_size, void* d_dst, uint6
     const void* d_huf = dict ? dict->d_huf : NULL;
     const uint32_t dict_size = dict ? dict->size : 0u;
     if (dst_capacity > 0) {  // (the empty-frame probe is answered by the head stage alone)
-        hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(s.n_tiles), dim3(UNF_THREADS), 0, st, src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
+        hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(s.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
         hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_bad, s.n_tiles, ctl);
-        hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(s.n_tiles), dim3(UNF_THREADS), 0, st, src, (const zc_ctl_t*)ctl,
+        hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(s.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)ctl,
                            (const uint64_t*)tile_sum, block_size, s.k_direct, s.n_jobs, jobs, tile_hash, tile_bad);
         hipLaunchKernelGGL(zxc_unframe_walk_kernel, dim3(1), dim3(256), 0, st, src, src_size, block_size, s.k_direct, s.n_jobs,
                            (const uint32_t*)tile_hash, (const uint32_t*)tile_bad, jobs, ctl);

@@ -32,3 +32,22 @@ int64_t t_verdict(zc_ctl_t* c, const int32_t* status, uint32_t block_size, uint6
 uint32_t t_tail_bytes(uint32_t i, int32_t status, uint32_t block_size, uint64_t dst_capacity) {
     return zc_tail_bytes(i, status, block_size, dst_capacity);
 }
+
+/* ---- the writers, for tests/test_container_writers_cpu.py */
+int t_file_header(const uint8_t* h, uint32_t* lg, uint32_t* file_ck, uint32_t* dict_id) { return zc_file_header(h, lg, file_ck, dict_id); }
+void t_put_file_header(uint8_t* p, uint32_t lg, int file_ck, int has_dict, uint32_t dict_id) { zc_put_file_header(p, lg, file_ck, has_dict, dict_id); }
+void t_put_blk_hdr(uint8_t* p, uint32_t type, uint32_t csz) { zc_st_le(p, zc_blk_hdr(type, csz), ZC_BLK_HDR); }
+void t_put_footer(uint8_t* p, uint64_t total, uint32_t hash) { zc_put_footer(p, total, hash); }
+uint32_t t_block_size_lg(uint64_t bs) { return zc_block_size_lg(bs); }
+uint32_t t_hash_fold(uint32_t h, uint32_t trailer) { return zc_hash_fold(h, trailer); }
+/* -> 1 and the EOF header's offset when the archive ends in a seek table of nb entries */
+int t_seek_tail(const uint8_t* src, uint64_t src_size, uint64_t nb, uint64_t* eof_at) {
+    uint64_t eof = 0;
+    return zc_seek_tail(src, src_size, nb, eof_at, &eof);
+}
+/* the chain from offset 16 to its end: -> the offset of the EOF block it ends at without an error, else -1 */
+int64_t t_chain_eof(const uint8_t* src, uint64_t src_size, uint32_t file_ck) {
+    zc_chain_t c = {ZC_FILE_HDR, 0, 0, 0, 0};
+    while (!c.done) (void)zc_chain_next(src, src_size, file_ck, 0, &c);
+    return c.saw_eof && c.tail_err == 0 ? (int64_t)c.ip : -1;
+}

@@ -1,9 +1,8 @@
-/* zxc_container.h — the v8 container as zxc_mi355x_decompress_device reads it: header check bytes, file-header and
- * block-header validation, the seek-table rules, the header walk and the verdict's precedence. Plain inline C that hipcc and
- * a host C compiler both take, so that the kernels of zxc_unframe_device.hip and the CPU tests run the same lines. Every
- * function states what zxc_decompress (zxc_host.c) does for the same bytes; where the device call departs from it, it says so.
- * The constants, the check bytes and the block-size and seek-table rules also serve zxc_mi355x_compress_device
- * (zxc_frame_device.hip), which writes these bytes, and zxc_ranges.h.
+/* zxc_container.h — the v8 container, once: constants, little-endian reads and stores, header check bytes, the file header
+ * and the block header read and written, the footer, the seek-table rules, the block chain, the header walk and the verdict's
+ * precedence. Plain inline C that hipcc and a host C compiler both take: the host API (zxc_host.c and the files included into
+ * it), the kernels of the device-to-device calls and the CPU tests run the same lines, so "what zxc_decompress / zxc_compress
+ * does for the same bytes" holds by construction. Where a device call departs from the host API, the function says so.
  * Nothing here writes through a pointer it was not given, and every read lies inside src[0, src_size). */
 #ifndef ZXC_CONTAINER_H
 #define ZXC_CONTAINER_H
@@ -56,8 +55,14 @@ ZC_FN uint32_t zc_rd32(const uint8_t* p) {
 }
 ZC_FN uint64_t zc_rd64(const uint8_t* p) { return (uint64_t)zc_rd32(p) | ((uint64_t)zc_rd32(p + 4) << 32); }
 ZC_FN uint32_t zc_rotl(uint32_t x, uint32_t r) { return r ? (x << r) | (x >> (32u - r)) : x; }
+/* the low n bytes of v, little-endian */
+ZC_FN void zc_st_le(uint8_t* p, uint64_t v, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8u * i));
+}
+/* the global hash over the stored per-block checksums, one trailer at a time in stream order */
+ZC_FN uint32_t zc_hash_fold(uint32_t h, uint32_t trailer) { return zc_rotl(h, 1) ^ trailer; }
 
-/* header check bytes (zxc_host.c: hdr_hash8 / hdr_hash16), on the little-endian words with the check bytes zeroed */
+/* header check bytes (xorshift of the little-endian words; the functions mask the check bytes out themselves) */
 ZC_FN uint64_t zc_xs_mix(uint64_t h) {
     h ^= h << 13;
     h ^= h >> 7;
@@ -84,6 +89,11 @@ ZC_FN uint64_t zc_blk_hdr(uint32_t type, uint32_t csz) {
 }
 /* a block size the format has: a power of two from 4 KiB to 2 MiB */
 ZC_FN int zc_block_size_ok(uint64_t bs) { return bs >= (1u << 12) && bs <= (1u << 21) && !(bs & (bs - 1u)); }
+ZC_FN uint32_t zc_block_size_lg(uint64_t bs) { /* of a size zc_block_size_ok accepts */
+    uint32_t lg = 12;
+    while ((1ull << lg) < bs) lg++;
+    return lg;
+}
 /* A seek table is the last thing in front of the footer: [EOF header][SEK header][4 nb bytes][footer], at least the file header
  * in front. -> 1 when both headers are valid, of their types, and the SEK header's size is 4 nb; then *eof_at is the EOF header's
  * offset and *eof its word (whose size field is the caller's to judge). */
@@ -98,7 +108,8 @@ ZC_FN int zc_seek_tail(const uint8_t* src, uint64_t src_size, uint64_t nb, uint6
     return 1;
 }
 
-/* read_file_header of zxc_host.c over the 16 header bytes. -> ZXC_OK or the error; block-size log2, checksum flag, dictionary id. */
+/* The file header over its 16 bytes: magic, version, log2 of the block size, flags (0x80 per-block checksums, 0x40 a dictionary
+ * id in bytes 7..10, low nibble zero), zeros, two check bytes. -> ZXC_OK or the error; block-size log2, checksum flag, dictionary id. */
 ZC_FN int zc_file_header(const uint8_t* h, uint32_t* lg, uint32_t* file_ck, uint32_t* dict_id) {
     if (zc_rd32(h) != ZC_MAGIC) return ZXC_ERROR_BAD_MAGIC;
     if (h[4] != ZC_VERSION) return ZXC_ERROR_BAD_VERSION;
@@ -109,9 +120,27 @@ ZC_FN int zc_file_header(const uint8_t* h, uint32_t* lg, uint32_t* file_ck, uint
     *dict_id = (h[6] & 0x40u) ? zc_rd32(h + 7) : 0u;
     return ZXC_OK;
 }
+/* ... and the two little-endian words of the header with these fields, check bytes included (dict_id counts only with has_dict) */
+ZC_FN void zc_file_header_words(uint32_t lg, int file_ck, int has_dict, uint32_t dict_id, uint64_t* lo, uint64_t* hi) {
+    const uint64_t flags = (file_ck ? 0x80u : 0u) | (has_dict ? 0x40u : 0u), id = has_dict ? dict_id : 0u;
+    *lo = (uint64_t)ZC_MAGIC | (uint64_t)ZC_VERSION << 32 | (uint64_t)lg << 40 | flags << 48 | (id & 0xFFu) << 56;
+    *hi = id >> 8;
+    *hi |= (uint64_t)zc_hdr_hash16(*lo, *hi) << 48;
+}
+ZC_FN void zc_put_file_header(uint8_t* p, uint32_t lg, int file_ck, int has_dict, uint32_t dict_id) {
+    uint64_t lo, hi;
+    zc_file_header_words(lg, file_ck, has_dict, dict_id, &lo, &hi);
+    zc_st_le(p, lo, 8);
+    zc_st_le(p + 8, hi, 8);
+}
+/* the footer's 12 bytes: decoded size, global hash (the caller's 0 without checksums) */
+ZC_FN void zc_put_footer(uint8_t* p, uint64_t total, uint32_t hash) {
+    zc_st_le(p, total, 8);
+    zc_st_le(p + 8, hash, 4);
+}
 
 /* Block i of the archive: compressed bytes at comp_off, decoded into slot i of the destination while i < k_direct, else into
- * slot i - k_direct of the staged area (the k split of the caller). out_len is a whole block, as frame_source has it. */
+ * slot i - k_direct of the staged area (the k split of the caller). out_len is a whole block, as frame_source of zxc_host.c has it. */
 ZC_FN zxc_dev_job_t zc_job(uint64_t comp_off, uint32_t i, uint32_t comp_size, uint32_t block_size, uint32_t k_direct) {
     zxc_dev_job_t j;
     j.comp_off = comp_off;
@@ -201,35 +230,49 @@ ZC_FN int zc_seek_plan(const uint8_t* src, uint32_t block_size, uint32_t k_direc
     return 1;
 }
 
-/* ---- walk: frame_source of zxc_host.c from offset 16, for at most n_jobs blocks. Jobs behind the blocks found are left as they are
+/* ---- the block chain, as zxc_decompress (frame_source of zxc_host.c) and zc_walk below follow it from offset 16 */
+typedef struct zc_chain {
+    uint64_t ip;       /* offset of the next block header */
+    uint32_t ghash;    /* fold of the trailers of the whole blocks passed (verify only) */
+    uint32_t done;     /* the chain ended: EOF block, bad header or end of the bytes */
+    uint32_t saw_eof;
+    int32_t tail_err;  /* error of the chain itself, reported only when every block in front of it decodes */
+} zc_chain_t;
+/* One block. -> 0 when the chain ends at c->ip without one: at the end of the bytes, at a header that is cut or fails its check
+ * byte (BAD_HEADER), or at an EOF block (which must carry size 0, else BAD_HEADER). Else the block at c->ip is a job of the
+ * returned size: its physical 8 + csz (+4) bytes clamped to the bytes left and to 32 bits (the decoder sees "all remaining
+ * bytes"; any size >= the physical block is equivalent); its trailer is folded only when the block lies whole inside the
+ * bytes, and c->ip moves behind it, or to src_size with done set when the block reaches the end. */
+ZC_FN uint32_t zc_chain_next(const uint8_t* src, uint64_t src_size, uint32_t file_ck, uint32_t verify, zc_chain_t* c) {
+    if (c->ip >= src_size) { c->done = 1; return 0; }
+    const uint64_t rem = src_size - c->ip, w = rem < ZC_BLK_HDR ? 0u : zc_rd64(src + c->ip);
+    if (rem < ZC_BLK_HDR || !zc_blk_hdr_ok(w)) { c->tail_err = ZXC_ERROR_BAD_HEADER; c->done = 1; return 0; }
+    if (zc_blk_type(w) == ZC_BLK_EOF) {
+        if (zc_blk_csz(w) != 0) c->tail_err = ZXC_ERROR_BAD_HEADER;
+        c->saw_eof = 1;
+        c->done = 1;
+        return 0;
+    }
+    const uint64_t phys = (uint64_t)ZC_BLK_HDR + zc_blk_csz(w) + (file_ck ? 4u : 0u), cs = phys < rem ? phys : rem;
+    if (verify && phys <= rem) c->ghash = zc_hash_fold(c->ghash, zc_rd32(src + c->ip + ZC_BLK_HDR + zc_blk_csz(w)));
+    if (phys >= rem) { c->ip = src_size; c->done = 1; }
+    else c->ip += phys;
+    return cs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cs;
+}
+
+/* ---- walk: the chain from offset 16, for at most n_jobs blocks. Jobs behind the blocks found are left as they are
  * (the caller zeroed them: comp_size 0 is answered with an error status and nothing is read). */
 ZC_FN void zc_walk(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint32_t k_direct, uint32_t n_jobs, zc_ctl_t* c,
                    zxc_dev_job_t* jobs) {
-    uint64_t ip = ZC_FILE_HDR;
-    uint32_t n = 0, h = 0, done = 0, saw_eof = 0;
-    int32_t tail_err = 0;
+    zc_chain_t ch = {ZC_FILE_HDR, 0, 0, 0, 0};
+    uint32_t n = 0;
     while (n < n_jobs) {
-        if (ip >= src_size) { done = 1; break; }
-        const uint64_t rem = src_size - ip;
-        if (rem < ZC_BLK_HDR) { tail_err = ZXC_ERROR_BAD_HEADER; done = 1; break; }
-        const uint64_t w = zc_rd64(src + ip);
-        if (!zc_blk_hdr_ok(w)) { tail_err = ZXC_ERROR_BAD_HEADER; done = 1; break; }
-        if (zc_blk_type(w) == ZC_BLK_EOF) {
-            if (zc_blk_csz(w) != 0) tail_err = ZXC_ERROR_BAD_HEADER;
-            saw_eof = 1;
-            done = 1;
-            break;
-        }
-        const uint64_t phys = (uint64_t)ZC_BLK_HDR + zc_blk_csz(w) + (c->file_ck ? 4u : 0u);
-        /* the decoder sees "all remaining bytes"; any size >= the physical block is equivalent */
-        const uint64_t cs = phys < rem ? phys : rem;
-        jobs[n] = zc_job(ip, n, cs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cs, block_size, k_direct);
-        n++;
-        if (c->verify && phys <= rem) h = zc_rotl(h, 1) ^ zc_rd32(src + ip + ZC_BLK_HDR + zc_blk_csz(w));
-        if (phys >= rem) { done = 1; break; }
-        ip += phys;
+        const uint64_t at = ch.ip;
+        const uint32_t cs = zc_chain_next(src, src_size, c->file_ck, c->verify, &ch);
+        if (cs) { jobs[n] = zc_job(at, n, cs, block_size, k_direct); n++; }
+        if (ch.done) break;
     }
-    c->found = n; c->done = done; c->saw_eof = saw_eof; c->tail_err = tail_err; c->ghash = h;
+    c->found = n; c->done = ch.done; c->saw_eof = ch.saw_eof; c->tail_err = ch.tail_err; c->ghash = ch.ghash;
 }
 
 /* ---- verdict. What block i's status means for the call, given that no earlier block has an event (so every earlier block decoded

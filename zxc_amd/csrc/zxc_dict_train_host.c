@@ -24,7 +24,7 @@
 #define DT_HUF_MAX_LEN 8            /* ZXC_HUF_MAX_CODE_LEN_DENSITY, :602 */
 
 static uint32_t dt_hash(const uint8_t* p) { /* src/lib/zxc_dict.c:231-235 */
-    return ((rd32(p) ^ (uint32_t)p[4]) * 0x2D35182Du) >> (32 - DT_HASH_BITS);
+    return ((zc_rd32(p) ^ (uint32_t)p[4]) * 0x2D35182Du) >> (32 - DT_HASH_BITS);
 }
 
 typedef struct { uint32_t off; uint16_t len; uint32_t score; } dt_seg_t;
@@ -192,19 +192,19 @@ static int huf_lengths_limited(const uint32_t* freq, uint8_t* len_out) {
 
 /* literals of one encoded block -> freq (the block formats: SURVEY.md appendix A; RLE tokens: src/lib/zxc_decompress.c:906-975) */
 static void dt_count_block_literals(const uint8_t* blk, uint32_t size, const uint8_t* raw_src, size_t raw_len, uint32_t* freq) {
-    if (size < BLK_HDR) return;
-    const uint32_t csz = rd32(blk + 3);
-    if ((uint64_t)BLK_HDR + csz > size) return;
-    const uint8_t* p = blk + BLK_HDR;
+    if (size < ZC_BLK_HDR) return;
+    const uint32_t csz = zc_rd32(blk + 3);
+    if ((uint64_t)ZC_BLK_HDR + csz > size) return;
+    const uint8_t* p = blk + ZC_BLK_HDR;
     if (blk[0] == BLK_RAW) { /* stored: every byte of the slice is a literal */
         for (size_t i = 0; i < raw_len; i++) freq[raw_src[i]]++;
         return;
     }
     if (blk[0] != BLK_GLO || csz < 12) return;
-    const uint32_t n_lit = rd32(p + 4);
+    const uint32_t n_lit = zc_rd32(p + 4);
     const uint8_t enc_lit = p[8], enc_tok = p[9];
     uint32_t at = 12, lit_bytes = n_lit;
-    if (enc_lit != 0) { if (at + 4 > csz) return; lit_bytes = rd32(p + at); at += 4; }
+    if (enc_lit != 0) { if (at + 4 > csz) return; lit_bytes = zc_rd32(p + at); at += 4; }
     if (enc_tok == 2) at += 4;
     if ((uint64_t)at + lit_bytes > csz) return;
     const uint8_t* l = p + at;

@@ -15,8 +15,8 @@
 //
 // zxc_mi355x_compress_dict_device is the same call with a dictionary in device memory. Two stages differ: the blocks are encoded
 // from [dict | block] images (zxc_mi355x_encode_blocks_dict_device), in chunks that reuse one image area in stream order, and
-// nothing is staged, because an image's padding serves the encoder's over-read; and the finish pass assembles bytes 6..15 of the
-// file header (dictionary flag, id, check bytes) itself, because the id is a word in device memory.
+// nothing is staged, because an image's padding serves the encoder's over-read; and the finish pass makes the file header's words
+// (zc_file_header_words) itself, because the dictionary's id is a word in device memory.
 #include "zxc_device_util.h"  // the tile passes, the copy, the host-side plumbing; zxc_container.h: the container's constants and check bytes
 
 #define FRAME_ENC_OVERREAD 32u      // the encoder reads up to 32 bytes past its input (include/zxc_mi355x.h)
@@ -24,10 +24,6 @@
 #define FRAME_IMAGE_BYTES (256ull << 20)  // the image area of a chunk of the dictionary path stays near this ...
 #define FRAME_IMAGE_MIN_BLOCKS 4096u      // ... but a chunk is never fewer blocks than this
 #define FRAME_IMAGE_PAD 64u               // behind the last image (the encoder's over-read, as zxc_mi355x_encode_dict_work_size)
-
-__device__ __forceinline__ void fr_st_le(uint8_t* p, uint64_t v, uint32_t n) {
-    for (uint32_t i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8u * i));
-}
 
 // Per-call state at the start of the work area (one call owns it from the first launch to the last).
 struct FrameCtl {
@@ -77,13 +73,12 @@ zxc_frame_tiles_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride, 
 // One workgroup. tile_sum[t] becomes the archive offset of tile t's first block (exclusive prefix + ZC_FILE_HDR, in place); then the
 // archive size is checked against the capacity and, when it fits, the header, the EOF block, the SEK header and the footer are written.
 // hdr_lo / hdr_hi, eof and sek are the little-endian images of those 16 + 8 + 8 bytes, made on the host (they depend on options only).
-// dict_id != NULL (the dictionary call): the header gets the dictionary flag and *dict_id in bytes 7..10, and its check bytes are
-// computed here over that (zxc_compress: zxc_host.c, "HAS_DICTIONARY + dict_id").
+// dict_id != NULL (the dictionary call): the header carries *dict_id, so its words are made here, from lg and the checksum flag.
 extern "C" __global__ void __launch_bounds__(256)
 zxc_frame_finish_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
                         uint32_t n_tiles, uint32_t nb, uint64_t src_size, uint8_t* __restrict__ dst, uint64_t dst_capacity,
                         uint64_t hdr_lo, uint64_t hdr_hi, uint64_t eof, uint64_t sek, uint32_t seekable, uint32_t checksum,
-                        FrameCtl* __restrict__ ctl, const uint32_t* __restrict__ dict_id) {
+                        FrameCtl* __restrict__ ctl, uint32_t lg, const uint32_t* __restrict__ dict_id) {
     const zd_totals all = zd_scan_tiles(
         n_tiles, ZC_FILE_HDR,
         [=](uint32_t i, uint32_t& hash, uint32_t& bad) { const uint64_t s = tile_sum[i]; hash ^= tile_hash[i]; bad |= tile_bad[i]; return s; },
@@ -97,19 +92,13 @@ zxc_frame_finish_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restr
     ctl->status = status;
     ctl->seek_at = eof_at + 2u * ZC_BLK_HDR;
     if (status < 0) return;
-    if (dict_id) {  // bytes 6..15: flags | 0x40, the id in 7..10, zeros, the 16-bit check over the rest
-        const uint64_t id = *dict_id;
-        hdr_lo = (hdr_lo & 0x0000FFFFFFFFFFFFull) | (((hdr_lo >> 48) & 0xFFu) | 0x40u) << 48 | (id & 0xFFu) << 56;
-        hdr_hi = id >> 8;
-        hdr_hi |= (uint64_t)zc_hdr_hash16(hdr_lo, hdr_hi) << 48;
-    }
-    fr_st_le(dst, hdr_lo, 8);
-    fr_st_le(dst + 8, hdr_hi, 8);
-    fr_st_le(dst + eof_at, eof, 8);
-    if (seek_bytes) fr_st_le(dst + eof_at + ZC_BLK_HDR, sek, 8);
+    if (dict_id) zc_file_header_words(lg, (int)checksum, 1, *dict_id, &hdr_lo, &hdr_hi);
+    zc_st_le(dst, hdr_lo, 8);
+    zc_st_le(dst + 8, hdr_hi, 8);
+    zc_st_le(dst + eof_at, eof, 8);
+    if (seek_bytes) zc_st_le(dst + eof_at + ZC_BLK_HDR, sek, 8);
     uint8_t* foot = dst + size - ZC_FOOTER;
-    fr_st_le(foot, src_size, 8);
-    fr_st_le(foot + 8, checksum ? all.hash : 0u, 4);
+    zc_put_footer(foot, src_size, checksum ? all.hash : 0u);
 }
 
 // Per tile: offsets[b] = archive offset of block b; with a seek table also its entry (the block's size, 4 bytes LE).
@@ -132,7 +121,7 @@ zxc_frame_scatter_kernel(const uint32_t* __restrict__ sizes, uint32_t nb, const 
         if (b >= nb) break;
         offsets[b] = run;
         run += sz[j];
-        if (seekable) fr_st_le(seek + 4ull * b, sz[j], 4);
+        if (seekable) zc_st_le(seek + 4ull * b, sz[j], 4);
     }
 }
 
@@ -172,8 +161,7 @@ int frame_plan(uint64_t src_size, const zxc_compress_opts_t* opts, FramePlan* p)
     const uint64_t nb = (src_size + bs - 1u) / bs;
     if (nb > 0x7FFFFFFFull) return ZXC_ERROR_BAD_BLOCK_SIZE;
     p->block_size = (uint32_t)bs;
-    p->lg = 0;
-    while ((1ull << p->lg) < bs) p->lg++;
+    p->lg = zc_block_size_lg(bs);
     p->level = (uint32_t)level;
     p->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
     p->seekable = (opts && opts->seekable) ? 1u : 0u;
@@ -262,13 +250,13 @@ int frame_enqueue(const void* d_src, uint64_t src_size, void* d_dst, uint64_t ds
                            (const uint32_t*)sizes, p.nb, p.block_size, p.checksum, tile_sum, tile_hash, tile_bad);
         if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     }
-    // the little-endian words of the file header (magic, version, log2 of the block size, flags; with a dictionary the finish
-    // pass completes bytes 6..15), of the EOF block and of the SEK header
-    const uint64_t hdr_lo = (uint64_t)ZC_MAGIC | (uint64_t)ZC_VERSION << 32 | (uint64_t)p.lg << 40 | (uint64_t)(p.checksum ? 0x80u : 0u) << 48;
-    const uint64_t hdr_hi = dict ? 0u : (uint64_t)zc_hdr_hash16(hdr_lo, 0u) << 48;
+    // the little-endian words of the file header (with a dictionary the finish pass makes them, around the id), of the EOF block
+    // and of the SEK header
+    uint64_t hdr_lo = 0, hdr_hi = 0;
+    if (!dict) zc_file_header_words(p.lg, (int)p.checksum, 0, 0u, &hdr_lo, &hdr_hi);
     hipLaunchKernelGGL(zxc_frame_finish_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
                        p.n_tiles, p.nb, src_size, dst, dst_capacity, hdr_lo, hdr_hi, zc_blk_hdr(ZC_BLK_EOF, 0u), zc_blk_hdr(ZC_BLK_SEK, p.nb * 4u), p.seekable, p.checksum, ctl,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
+                       p.lg, dict ? dict->d_id : (const uint32_t*)NULL);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     if (p.nb) {
         hipLaunchKernelGGL(zxc_frame_scatter_kernel, dim3(p.n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,

@@ -21,39 +21,13 @@
 #include <time.h>
 
 #include "../../include/zxc.h"
+#include "zxc_container.h" /* the v8 container: constants, reads and stores, check bytes, headers, footer, the block chain */
 
-#define MAGIC 0x9CB02EF5u
-#define FORMAT_VERSION 8
-#define BLK_HDR 8
 #define TAIL_PAD 2112u /* ZXC_DECOMPRESS_TAIL_PAD, src/lib/zxc_internal.h:341 */
 #define HOST_BATCH_BYTES ((size_t)256 << 20) /* output slots per launch of the host Buffer API */
-enum { BLK_RAW = 0, BLK_GLO = 1, BLK_GHI = 2, BLK_SEK = 254, BLK_EOF = 255 };
+enum { BLK_RAW = 0, BLK_GLO = 1, BLK_GHI = 2 };
 
 static uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-static uint32_t rd32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-static uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
-static void wr32(uint8_t* p, uint32_t v) {
-    p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
-}
-
-/* header check bytes (src/lib/zxc_internal.h:1188-1214): xorshift of the LE words */
-static uint64_t xs_mix(uint64_t h) {
-    h ^= h << 13;
-    h ^= h >> 7;
-    h ^= h << 17;
-    return h;
-}
-static uint8_t hdr_hash8(const uint8_t* p) {
-    const uint64_t h = xs_mix(rd64(p) ^ 0x9E3779B97F4A7C15ull);
-    return (uint8_t)((h >> 32) ^ h);
-}
-static uint16_t hdr_hash16(const uint8_t* p) {
-    const uint64_t h = xs_mix(rd64(p) ^ rd64(p + 8) ^ 0xD2D84A61D2D84A61ull);
-    const uint32_t r = (uint32_t)((h >> 32) ^ h);
-    return (uint16_t)((r >> 16) ^ r);
-}
 
 /* ---------------------------------------------------------------- misc API */
 const char* zxc_error_name(const int code) {
@@ -117,8 +91,8 @@ static uint64_t host_rapidhash(const uint8_t* p, size_t len, uint64_t seed) {
     if (len <= 16) {
         if (len >= 4) {
             seed ^= len;
-            if (len >= 8) { a = rd64(p); b = rd64(p + len - 8); }
-            else { a = rd32(p); b = rd32(p + len - 4); }
+            if (len >= 8) { a = zc_rd64(p); b = zc_rd64(p + len - 8); }
+            else { a = zc_rd32(p); b = zc_rd32(p + len - 4); }
         } else if (len > 0) {
             a = ((uint64_t)p[0] << 45) | p[len - 1];
             b = p[len >> 1];
@@ -128,7 +102,7 @@ static uint64_t host_rapidhash(const uint8_t* p, size_t len, uint64_t seed) {
             uint64_t s[7];
             for (int k = 0; k < 7; k++) s[k] = seed;
             do {
-                for (int k = 0; k < 7; k++) s[k] = rh_mix(rd64(p + 16 * k) ^ RH_S[k], rd64(p + 16 * k + 8) ^ s[k]);
+                for (int k = 0; k < 7; k++) s[k] = rh_mix(zc_rd64(p + 16 * k) ^ RH_S[k], zc_rd64(p + 16 * k + 8) ^ s[k]);
                 p += 112;
                 i -= 112;
             } while (i > 112);
@@ -136,9 +110,9 @@ static uint64_t host_rapidhash(const uint8_t* p, size_t len, uint64_t seed) {
         }
         static const int sel[6] = {2, 2, 1, 1, 2, 1};
         for (int k = 0; k < 6 && i > (size_t)(16 * (k + 1)); k++)
-            seed = rh_mix(rd64(p + 16 * k) ^ RH_S[sel[k]], rd64(p + 16 * k + 8) ^ seed);
-        a = rd64(p + i - 16) ^ i;
-        b = rd64(p + i - 8);
+            seed = rh_mix(zc_rd64(p + 16 * k) ^ RH_S[sel[k]], zc_rd64(p + 16 * k + 8) ^ seed);
+        a = zc_rd64(p + i - 16) ^ i;
+        b = zc_rd64(p + i - 8);
     }
     a ^= RH_S[1];
     b ^= seed;
@@ -159,7 +133,9 @@ static uint32_t dict_id_of(const uint8_t* dict, size_t n, const uint8_t* huf) {
 #define DICT_MAGIC 0x9CB0D1C7u
 #define DICT_VERSION 1
 #define DICT_HDR 16
-static uint16_t hdr_hash16(const uint8_t* p);
+/* (the .zxd check covers bytes 0..11 only; zc_hdr_hash16 masks just the file header's own check bytes 14..15, so the second
+ *  word is cut to its low 32 bits here) */
+static uint16_t dict_hdr_check(const uint8_t* p) { return zc_hdr_hash16(zc_rd64(p), zc_rd64(p + 8) & 0xFFFFFFFFull); }
 
 uint32_t zxc_dict_id(const void* dict, size_t dict_size, const void* huf_lengths) {
     return dict_id_of((const uint8_t*)dict, dict_size, (const uint8_t*)huf_lengths);
@@ -167,7 +143,7 @@ uint32_t zxc_dict_id(const void* dict, size_t dict_size, const void* huf_lengths
 uint32_t zxc_dict_get_id(const void* buf, const size_t buf_size) {
     if (!buf || buf_size < DICT_HDR) return 0;
     const uint8_t* p = (const uint8_t*)buf;
-    return rd32(p) == DICT_MAGIC ? rd32(p + 8) : 0;
+    return zc_rd32(p) == DICT_MAGIC ? zc_rd32(p + 8) : 0;
 }
 size_t zxc_dict_save_bound(const size_t content_size) { return DICT_HDR + content_size + ZXC_HUF_TABLE_SIZE; }
 int64_t zxc_dict_save(const void* content, const size_t content_size, const void* huf_lengths, void* buf,
@@ -177,16 +153,13 @@ int64_t zxc_dict_save(const void* content, const size_t content_size, const void
     const size_t total = zxc_dict_save_bound(content_size);
     if (buf_capacity < total) return ZXC_ERROR_DST_TOO_SMALL;
     uint8_t* d = (uint8_t*)buf;
-    wr32(d, DICT_MAGIC);
+    zc_st_le(d, DICT_MAGIC, 4);
     d[4] = DICT_VERSION;
     d[5] = 0;
-    d[6] = (uint8_t)content_size;
-    d[7] = (uint8_t)(content_size >> 8);
-    wr32(d + 8, dict_id_of((const uint8_t*)content, content_size, (const uint8_t*)huf_lengths));
-    wr32(d + 12, 0);
-    const uint16_t crc = hdr_hash16(d);
-    d[14] = (uint8_t)crc;
-    d[15] = (uint8_t)(crc >> 8);
+    zc_st_le(d + 6, content_size, 2);
+    zc_st_le(d + 8, dict_id_of((const uint8_t*)content, content_size, (const uint8_t*)huf_lengths), 4);
+    zc_st_le(d + 12, 0, 4);
+    zc_st_le(d + 14, dict_hdr_check(d), 2);
     memcpy(d + DICT_HDR, content, content_size);
     memcpy(d + DICT_HDR + content_size, huf_lengths, ZXC_HUF_TABLE_SIZE);
     return (int64_t)total;
@@ -196,19 +169,16 @@ int zxc_dict_load(const void* buf, const size_t buf_size, const void** content_o
     if (!buf || !content_out || !content_size_out) return ZXC_ERROR_NULL_INPUT;
     if (buf_size < DICT_HDR) return ZXC_ERROR_SRC_TOO_SMALL;
     const uint8_t* src = (const uint8_t*)buf;
-    if (rd32(src) != DICT_MAGIC) return ZXC_ERROR_BAD_MAGIC;
+    if (zc_rd32(src) != DICT_MAGIC) return ZXC_ERROR_BAD_MAGIC;
     if (src[4] != DICT_VERSION) return ZXC_ERROR_BAD_VERSION;
     const size_t n = rd16(src + 6);
     if (n == 0) return ZXC_ERROR_CORRUPT_DATA;
     if (buf_size < DICT_HDR + n + ZXC_HUF_TABLE_SIZE) return ZXC_ERROR_SRC_TOO_SMALL;
-    uint8_t t[DICT_HDR];
-    memcpy(t, src, DICT_HDR);
-    t[12] = t[13] = t[14] = t[15] = 0;
-    if (rd16(src + 14) != hdr_hash16(t)) return ZXC_ERROR_BAD_HEADER;
+    if (rd16(src + 14) != dict_hdr_check(src)) return ZXC_ERROR_BAD_HEADER;
     const uint8_t* content = src + DICT_HDR;
     const uint8_t* huf = content + n;
     const uint32_t id = dict_id_of(content, n, huf);
-    if (rd32(src + 8) != id) return ZXC_ERROR_BAD_CHECKSUM;
+    if (zc_rd32(src + 8) != id) return ZXC_ERROR_BAD_CHECKSUM;
     *content_out = content;
     *content_size_out = n;
     if (huf_out) *huf_out = huf;
@@ -218,37 +188,21 @@ int zxc_dict_load(const void* buf, const size_t buf_size, const void** content_o
 const void* zxc_dict_huf(const void* buf, const size_t buf_size) {
     if (!buf || buf_size < DICT_HDR) return NULL;
     const uint8_t* src = (const uint8_t*)buf;
-    if (rd32(src) != DICT_MAGIC || src[4] != DICT_VERSION) return NULL;
+    if (zc_rd32(src) != DICT_MAGIC || src[4] != DICT_VERSION) return NULL;
     const size_t n = rd16(src + 6);
     if (n == 0 || buf_size < DICT_HDR + n + ZXC_HUF_TABLE_SIZE) return NULL;
     return src + DICT_HDR + n;
 }
 
 /* ------------------------------------------------------------- containers */
-static int read_file_header(const uint8_t* src, size_t n, uint32_t* block_size, int* has_checksum,
-                            uint32_t* dict_id) {
+/* zc_file_header behind the host's size check, in the host's types */
+static int host_file_header(const uint8_t* src, size_t n, uint32_t* block_size, int* has_checksum, uint32_t* dict_id) {
     if (n < ZXC_FILE_HEADER_SIZE) return ZXC_ERROR_SRC_TOO_SMALL;
-    if (rd32(src) != MAGIC) return ZXC_ERROR_BAD_MAGIC;
-    if (src[4] != FORMAT_VERSION) return ZXC_ERROR_BAD_VERSION;
-    uint8_t t[16];
-    memcpy(t, src, 16);
-    t[14] = t[15] = 0;
-    if (rd16(src + 14) != hdr_hash16(t) || (src[6] & 0x0F) != 0) return ZXC_ERROR_BAD_HEADER;
-    if (src[5] < ZXC_BLOCK_SIZE_MIN_LOG2 || src[5] > ZXC_BLOCK_SIZE_MAX_LOG2) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    *block_size = 1u << src[5];
-    *has_checksum = (src[6] & 0x80) ? 1 : 0;
-    *dict_id = (src[6] & 0x40) ? rd32(src + 7) : 0;
-    return ZXC_OK;
-}
-
-static int read_block_header(const uint8_t* src, size_t n, uint8_t* type, uint32_t* comp_size) {
-    if (n < BLK_HDR) return ZXC_ERROR_SRC_TOO_SMALL;
-    uint8_t t[8];
-    memcpy(t, src, 8);
-    t[7] = 0;
-    if (src[7] != hdr_hash8(t)) return ZXC_ERROR_BAD_HEADER;
-    *type = src[0];
-    *comp_size = rd32(src + 3);
+    uint32_t lg = 0, ck = 0;
+    const int rc = zc_file_header(src, &lg, &ck, dict_id);
+    if (rc != ZXC_OK) return rc;
+    *block_size = 1u << lg;
+    *has_checksum = (int)ck;
     return ZXC_OK;
 }
 
@@ -257,11 +211,11 @@ uint64_t zxc_get_decompressed_size(const void* src, const size_t src_size) {
     const uint8_t* p = (const uint8_t*)src;
     uint32_t bs, did;
     int cs;
-    if (read_file_header(p, src_size, &bs, &cs, &did) != ZXC_OK) return 0;
-    const uint64_t dsize = rd64(p + src_size - ZXC_FILE_FOOTER_SIZE);
+    if (host_file_header(p, src_size, &bs, &cs, &did) != ZXC_OK) return 0;
+    const uint64_t dsize = zc_rd64(p + src_size - ZXC_FILE_FOOTER_SIZE);
     /* plausibility cap: each block costs >= 8 compressed bytes (zxc_dispatch.c:1021-1027) */
     const uint64_t need = dsize / bs + (dsize % bs != 0);
-    return need <= (uint64_t)(src_size / BLK_HDR) ? dsize : 0;
+    return need <= (uint64_t)(src_size / ZC_BLK_HDR) ? dsize : 0;
 }
 
 /* ------------------------------------------------------- device round trip */
@@ -777,57 +731,41 @@ static int pipe_run(pipe_source_fn source, void* source_ctx, pipe_sink_fn sink, 
  * failure in stream order wins). */
 typedef struct {
     const uint8_t* src;
-    size_t src_size, ip;
+    size_t src_size;
     uint32_t block_size;
     int file_ck, verify;
-    int tail_err;         /* error to report after all queued blocks succeed */
-    int saw_eof, done;
-    uint32_t global_hash; /* rotl1-xor fold of the stored per-block checksums (zxc_internal.h:1390-1393) */
+    zc_chain_t c;         /* where the walk stands: position, global hash (zxc_internal.h:1390-1393), the error to report after all queued blocks succeed */
     size_t stop_ip;       /* != 0: a piece ends in front of this position (the block-by-block walk over an irregular piece stops where the piece did) */
 } frame_walk_t;
 static int frame_source(void* ctx, uint32_t max_blocks, pipe_piece_t* p) {
     frame_walk_t* w = (frame_walk_t*)ctx;
     zxc_dev_job_t* jobs = p->jobs;
     uint32_t n = 0;
-    const size_t span0 = w->ip;
-    const uint32_t hash0 = w->global_hash;
-    while (!w->done && n < max_blocks) {
-        if (w->ip >= w->src_size) { w->done = 1; break; }
-        if (w->stop_ip && w->ip >= w->stop_ip) break;
-        const size_t rem = w->src_size - w->ip;
-        uint8_t type;
-        uint32_t csz;
-        if (read_block_header(w->src + w->ip, rem, &type, &csz) != ZXC_OK) { w->tail_err = ZXC_ERROR_BAD_HEADER; w->done = 1; break; }
-        if (type == BLK_EOF) {
-            if (csz != 0) w->tail_err = ZXC_ERROR_BAD_HEADER;
-            w->saw_eof = 1;
-            w->done = 1;
-            break;
-        }
-        const uint64_t phys = (uint64_t)BLK_HDR + csz + (w->file_ck ? 4u : 0u);
-        jobs[n].comp_off = w->ip - span0;
-        /* the wrapper sees "all remaining bytes"; any size >= the physical block is equivalent */
-        { const uint64_t cs = phys < rem ? phys : rem; jobs[n].comp_size = cs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cs; }
+    const size_t span0 = (size_t)w->c.ip;
+    const uint32_t hash0 = w->c.ghash;
+    while (!w->c.done && n < max_blocks) {
+        if (w->stop_ip && w->c.ip >= w->stop_ip && w->c.ip < w->src_size) break; /* (at the end of the bytes the chain ends itself) */
+        const uint64_t at = w->c.ip;
+        const uint32_t cs = zc_chain_next(w->src, w->src_size, (uint32_t)w->file_ck, (uint32_t)w->verify, &w->c);
+        if (!cs) break;
+        jobs[n].comp_off = at - span0;
+        jobs[n].comp_size = cs;
         jobs[n].out_off = (uint64_t)n * w->block_size;
         jobs[n].out_len = w->block_size;
         n++;
-        if (w->verify && phys <= rem)
-            w->global_hash = ((w->global_hash << 1) | (w->global_hash >> 31)) ^ rd32(w->src + w->ip + BLK_HDR + csz);
-        if (phys >= rem) { w->ip = w->src_size; w->done = 1; break; }
-        w->ip += (size_t)phys;
     }
     if (n == 0) return 0;
     p->h_comp = w->src + span0;
-    p->comp_bytes = w->ip - span0;
+    p->comp_bytes = (size_t)w->c.ip - span0;
     p->n = n;
     p->out_bytes = (size_t)n * w->block_size;
     /* the walk in front of and behind this piece: the caller restarts from either when a piece turns out irregular */
     p->cookie[0] = span0;
     p->cookie[1] = hash0;
-    p->cookie[2] = w->ip;
-    p->cookie[3] = w->global_hash;
-    p->cookie[4] = (uint64_t)w->done | ((uint64_t)w->saw_eof << 1);
-    p->cookie[5] = (uint64_t)(uint32_t)w->tail_err;
+    p->cookie[2] = w->c.ip;
+    p->cookie[3] = w->c.ghash;
+    p->cookie[4] = (uint64_t)w->c.done | ((uint64_t)w->c.saw_eof << 1);
+    p->cookie[5] = (uint64_t)(uint32_t)w->c.tail_err;
     return 1;
 }
 typedef struct {
@@ -895,12 +833,12 @@ int64_t zxc_decompress(const void* src_v, const size_t src_size, void* dst_v, co
     if (!src || (!dst && dst_capacity != 0)) return ZXC_ERROR_NULL_INPUT;
     if (src_size < ZXC_FILE_HEADER_SIZE + ZXC_FILE_FOOTER_SIZE) return ZXC_ERROR_SRC_TOO_SMALL;
     if (!dst || dst_capacity == 0) { /* empty-frame probe, zxc_dispatch.c:848-853 */
-        if (rd32(src) != MAGIC) return ZXC_ERROR_BAD_MAGIC;
-        return rd64(src + src_size - ZXC_FILE_FOOTER_SIZE) == 0 ? 0 : (int64_t)ZXC_ERROR_DST_TOO_SMALL;
+        if (zc_rd32(src) != ZC_MAGIC) return ZXC_ERROR_BAD_MAGIC;
+        return zc_rd64(src + src_size - ZXC_FILE_FOOTER_SIZE) == 0 ? 0 : (int64_t)ZXC_ERROR_DST_TOO_SMALL;
     }
     uint32_t block_size, dict_id;
     int file_ck;
-    const int hrc = read_file_header(src, src_size, &block_size, &file_ck, &dict_id);
+    const int hrc = host_file_header(src, src_size, &block_size, &file_ck, &dict_id);
     if (hrc != ZXC_OK) return hrc;
     const int verify = file_ck && opts && opts->checksum_enabled;
     const uint8_t* dict = opts ? (const uint8_t*)opts->dict : NULL;
@@ -917,7 +855,7 @@ int64_t zxc_decompress(const void* src_v, const size_t src_size, void* dst_v, co
     memset(&w, 0, sizeof w);
     w.src = src;
     w.src_size = src_size;
-    w.ip = ZXC_FILE_HEADER_SIZE;
+    w.c.ip = ZC_FILE_HDR;
     w.block_size = block_size;
     w.file_ck = file_ck;
     w.verify = verify;
@@ -927,36 +865,36 @@ int64_t zxc_decompress(const void* src_v, const size_t src_size, void* dst_v, co
     k.dst_capacity = dst_capacity;
     k.block_size = block_size;
     /* (the footer's size is a hint for the slots' reservations only: bounded by the caller's capacity) */
-    uint64_t out_hint = rd64(src + src_size - ZXC_FILE_FOOTER_SIZE);
+    uint64_t out_hint = zc_rd64(src + src_size - ZXC_FILE_FOOTER_SIZE);
     if (out_hint > (uint64_t)dst_capacity) out_hint = dst_capacity;
     for (;;) {
         const int r = pipe_run(frame_source, &w, frame_sink, &k, block_size, verify, &dr, src_size, out_hint, 0, 0, PIPE_DECODE_SLOTS);
         if (r < 0) return r;
         if (r != PIPE_IRREGULAR) break;
         /* rewind the walk (it ran ahead of the sink) to the front of the irregular piece, take that piece block by block ... */
-        w.ip = (size_t)k.irr[0];
-        w.global_hash = (uint32_t)k.irr[1];
-        w.done = 0;
-        w.saw_eof = 0;
-        w.tail_err = 0;
+        w.c.ip = k.irr[0];
+        w.c.ghash = (uint32_t)k.irr[1];
+        w.c.done = 0;
+        w.c.saw_eof = 0;
+        w.c.tail_err = 0;
         uint32_t nb = (uint32_t)(PIPE_PIECE_BYTES / block_size); /* (at most what a piece can hold: the walk stops where the piece did) */
         { const char* ev = getenv("ZXC_MI355X_FRAME_BATCH_MIB"); if (ev && atoi(ev) >= 1 && atoi(ev) <= 1024) nb = (uint32_t)(((size_t)atoi(ev) << 20) / block_size); }
         if (nb < 16u) nb = 16u;
         /* the piece had exactly this many blocks or fewer: walk block by block up to where it ended */
         w.stop_ip = (size_t)k.irr[2];
-        while (w.ip < (size_t)k.irr[2] && !w.done) {
+        while (w.c.ip < k.irr[2] && !w.c.done) {
             const int rc = frame_irregular_piece(&w, &k, &dr, nb);
             if (rc != ZXC_OK) return rc;
         }
         w.stop_ip = 0;
         /* ... and go on behind it */
-        if (w.done) break;
+        if (w.c.done) break;
     }
-    if (w.tail_err) return w.tail_err;
-    if (w.saw_eof) { /* footer: stored size must equal what was produced (zxc_dispatch.c:936-943) */
+    if (w.c.tail_err) return w.c.tail_err;
+    if (w.c.saw_eof) { /* footer: stored size must equal what was produced (zxc_dispatch.c:936-943) */
         const uint8_t* footer = src + src_size - ZXC_FILE_FOOTER_SIZE;
-        if (rd64(footer) != (uint64_t)k.total) return ZXC_ERROR_CORRUPT_DATA;
-        if (verify && rd32(footer + 8) != w.global_hash) return ZXC_ERROR_BAD_CHECKSUM; /* :945-952 */
+        if (zc_rd64(footer) != (uint64_t)k.total) return ZXC_ERROR_CORRUPT_DATA;
+        if (verify && zc_rd32(footer + 8) != w.c.ghash) return ZXC_ERROR_BAD_CHECKSUM; /* :945-952 */
     }
     return (int64_t)k.total;
 }
@@ -967,16 +905,16 @@ int64_t zxc_decompress(const void* src_v, const size_t src_size, void* dst_v, co
  * uploaded batch by batch before their output comes back, and a batch's output ends where the sequential decoder's
  * would, so the same bound holds. */
 static int inplace_probe(const uint8_t* comp, size_t comp_size, uint64_t* dsize, uint64_t* margin, uint64_t* floor_) {
-    if (rd32(comp) != MAGIC) return ZXC_ERROR_BAD_MAGIC;
+    if (zc_rd32(comp) != ZC_MAGIC) return ZXC_ERROR_BAD_MAGIC;
     uint32_t bs, did;
     int ck;
-    if (read_file_header(comp, comp_size, &bs, &ck, &did) != ZXC_OK) return ZXC_ERROR_BAD_HEADER;
-    const uint64_t d = rd64(comp + comp_size - ZXC_FILE_FOOTER_SIZE);
+    if (host_file_header(comp, comp_size, &bs, &ck, &did) != ZXC_OK) return ZXC_ERROR_BAD_HEADER;
+    const uint64_t d = zc_rd64(comp + comp_size - ZXC_FILE_FOOTER_SIZE);
     const uint64_t need = d / bs + (d % bs != 0);
-    if (need > (uint64_t)(comp_size / BLK_HDR)) return ZXC_ERROR_CORRUPT_DATA;
+    if (need > (uint64_t)(comp_size / ZC_BLK_HDR)) return ZXC_ERROR_CORRUPT_DATA;
     const uint64_t nblocks = (d + bs - 1) / bs;
-    const uint64_t per_block = BLK_HDR + (ck ? 4u : 0u);
-    const uint64_t trailing = BLK_HDR + (BLK_HDR + nblocks * 4u) + ZXC_FILE_FOOTER_SIZE;
+    const uint64_t per_block = ZC_BLK_HDR + (ck ? 4u : 0u);
+    const uint64_t trailing = ZC_BLK_HDR + (ZC_BLK_HDR + nblocks * 4u) + ZXC_FILE_FOOTER_SIZE;
     *dsize = d;
     *margin = (uint64_t)bs + nblocks * per_block + trailing + TAIL_PAD;
     *floor_ = (uint64_t)bs + TAIL_PAD;
@@ -1007,11 +945,6 @@ int64_t zxc_decompress_inplace(void* buffer, const size_t buffer_capacity, const
 }
 
 /* ------------------------------------------------------------ zxc_compress */
-static void wr64(uint8_t* p, uint64_t v) {
-    wr32(p, (uint32_t)v);
-    wr32(p + 4, (uint32_t)(v >> 32));
-}
-
 /* zxc_compress over pieces of blocks, through the piece pipeline above (round 5): two producer threads upload the source pieces
  * and launch their encodes (a piece's encode takes ~3.5 ms whatever its size — one round of wavefronts — so three pieces sit in
  * flight and fill the chip), the calling thread turns a finished piece's block sizes into offsets, compacts its slots
@@ -1088,7 +1021,7 @@ static int comp_sink(void* ctx, const pipe_piece_t* p, const int32_t* st, const 
     if (rc != ZXC_OK) return rc;
     if (k->checksum) /* fold the block trailers in stream order (zxc_dispatch.c:754-759) */
         for (uint32_t i = 0; i < n; i++)
-            k->global_hash = ((k->global_hash << 1) | (k->global_hash >> 31)) ^ rd32(k->dst + k->op + k->offs[i] + k->sizes[f + i] - 4);
+            k->global_hash = zc_hash_fold(k->global_hash, zc_rd32(k->dst + k->op + k->offs[i] + k->sizes[f + i] - 4));
     k->op += (size_t)total;
     return 0;
 }
@@ -1134,27 +1067,13 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
     const size_t block_size = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
     const size_t dict_size = (opts && opts->dict) ? opts->dict_size : 0;
     if (dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
-    if (block_size < ZXC_BLOCK_SIZE_MIN || block_size > ZXC_BLOCK_SIZE_MAX || (block_size & (block_size - 1)))
-        return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     const uint8_t* dict = dict_size ? (const uint8_t*)opts->dict : NULL;
     const uint8_t* dict_huf = dict_size ? (const uint8_t*)opts->dict_huf : NULL;
     if (dst_capacity < ZXC_FILE_HEADER_SIZE) return ZXC_ERROR_DST_TOO_SMALL;
 
-    /* file header (src/lib/zxc_common.c:534-558) */
-    memset(dst, 0, ZXC_FILE_HEADER_SIZE);
-    wr32(dst, MAGIC);
-    dst[4] = FORMAT_VERSION;
-    uint8_t lg = 0;
-    while (((size_t)1 << lg) < block_size) lg++;
-    dst[5] = lg;
-    dst[6] = checksum_enabled ? 0x80 : 0; /* HAS_CHECKSUM | algo 0 (rapidhash) */
-    if (dict_size) { /* HAS_DICTIONARY + dict_id binding content (and shared table), src/lib/zxc_common.c:546-553 */
-        dst[6] |= 0x40;
-        wr32(dst + 7, dict_id_of(dict, dict_size, dict_huf));
-    }
-    const uint16_t crc = hdr_hash16(dst);
-    dst[14] = (uint8_t)crc;
-    dst[15] = (uint8_t)(crc >> 8);
+    /* file header (src/lib/zxc_common.c:534-558): with a dictionary, the id that binds its content (and shared table) */
+    zc_put_file_header(dst, zc_block_size_lg(block_size), checksum_enabled, dict_size != 0, dict_id_of(dict, dict_size, dict_huf));
     size_t op = ZXC_FILE_HEADER_SIZE;
 
     const uint64_t nb64 = ((uint64_t)src_size + block_size - 1) / block_size;
@@ -1170,7 +1089,7 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
         if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
         sizes = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t));
         if (!sizes) return ZXC_ERROR_MEMORY;
-        const size_t tail_need = BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
+        const size_t tail_need = ZC_BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
         const int rc = compress_pieces((const uint8_t*)src, src_size, block_size, level, checksum_enabled, tail_need, dst, dst_capacity,
                                        &op, sizes, nb, (size_t)batch_blocks * block_size, &global_hash);
         if (rc != ZXC_OK) { free(sizes); return rc; }
@@ -1200,7 +1119,7 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
             uint64_t total = 0;
             if (rc == ZXC_OK) {
                 for (uint32_t i = 0; i < nb; i++) { offs[i] = total; total += sizes[i]; }
-                const uint64_t need = op + total + BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
+                const uint64_t need = op + total + ZC_BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
                 if (need > dst_capacity) rc = ZXC_ERROR_DST_TOO_SMALL;
             }
             if (rc == ZXC_OK) {
@@ -1215,7 +1134,7 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
             if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(dst + op, d_out, (size_t)total);
             if (rc == ZXC_OK && checksum_enabled) /* fold the block trailers in stream order (zxc_dispatch.c:754-759) */
                 for (uint32_t i = 0; i < nb; i++)
-                    global_hash = ((global_hash << 1) | (global_hash >> 31)) ^ rd32(dst + op + offs[i] + sizes[i] - 4);
+                    global_hash = zc_hash_fold(global_hash, zc_rd32(dst + op + offs[i] + sizes[i] - 4));
             if (rc == ZXC_OK) op += (size_t)total;
         }
         zxc_mi355x_free(d_src);
@@ -1229,11 +1148,9 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
         if (rc != ZXC_OK) { free(sizes); return rc; }
     }
     /* EOF block, optional seek table, footer (src/lib/zxc_dispatch.c:784-815) */
-    if (dst_capacity - op < BLK_HDR) { free(sizes); return ZXC_ERROR_DST_TOO_SMALL; }
-    memset(dst + op, 0, BLK_HDR);
-    dst[op] = BLK_EOF;
-    dst[op + 7] = hdr_hash8(dst + op);
-    op += BLK_HDR;
+    if (dst_capacity - op < ZC_BLK_HDR) { free(sizes); return ZXC_ERROR_DST_TOO_SMALL; }
+    zc_st_le(dst + op, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
+    op += ZC_BLK_HDR;
     if (seekable && nb > 0) {
         const int64_t st = zxc_write_seek_table(dst + op, dst_capacity - op, sizes, nb);
         if (st < 0) { free(sizes); return st; }
@@ -1241,8 +1158,7 @@ int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const 
     }
     free(sizes);
     if (dst_capacity - op < ZXC_FILE_FOOTER_SIZE) return ZXC_ERROR_DST_TOO_SMALL;
-    wr64(dst + op, (uint64_t)src_size);
-    wr32(dst + op + 8, checksum_enabled ? global_hash : 0); /* zero when checksums are off */
+    zc_put_footer(dst + op, src_size, checksum_enabled ? global_hash : 0); /* zero when checksums are off */
     op += ZXC_FILE_FOOTER_SIZE;
     return (int64_t)op;
 }
@@ -1265,7 +1181,7 @@ struct zxc_seekable_s {
     int has_dict_huf;
 };
 
-size_t zxc_seek_table_size(const uint32_t num_blocks) { return BLK_HDR + (size_t)num_blocks * 4; }
+size_t zxc_seek_table_size(const uint32_t num_blocks) { return ZC_BLK_HDR + (size_t)num_blocks * 4; }
 
 int64_t zxc_write_seek_table(uint8_t* dst, const size_t dst_capacity, const uint32_t* comp_sizes,
                              const uint32_t num_blocks) {
@@ -1273,12 +1189,8 @@ int64_t zxc_write_seek_table(uint8_t* dst, const size_t dst_capacity, const uint
     const size_t total = zxc_seek_table_size(num_blocks);
     if (dst_capacity < total) return ZXC_ERROR_DST_TOO_SMALL;
     if (!dst || !comp_sizes) return ZXC_ERROR_NULL_INPUT;
-    dst[0] = BLK_SEK;
-    dst[1] = dst[2] = 0;
-    wr32(dst + 3, num_blocks * 4);
-    dst[7] = 0;
-    dst[7] = hdr_hash8(dst);
-    for (uint32_t i = 0; i < num_blocks; i++) wr32(dst + BLK_HDR + 4 * (size_t)i, comp_sizes[i]);
+    zc_st_le(dst, zc_blk_hdr(ZC_BLK_SEK, num_blocks * 4), ZC_BLK_HDR);
+    for (uint32_t i = 0; i < num_blocks; i++) zc_st_le(dst + ZC_BLK_HDR + 4 * (size_t)i, comp_sizes[i], 4);
     return (int64_t)total;
 }
 
@@ -1326,8 +1238,8 @@ static zxc_seekable* seekable_build(uint32_t block_size, int has_ck, uint32_t di
     if (!s->comp_sizes || !s->comp_offsets) { zxc_seekable_free(s); return NULL; }
     uint64_t acc = ZXC_FILE_HEADER_SIZE;
     for (uint32_t i = 0; i < nb; i++) {
-        const uint32_t cs = rd32(entries + 4 * (size_t)i);
-        if (cs < BLK_HDR || cs > archive_size) { zxc_seekable_free(s); return NULL; }
+        const uint32_t cs = zc_rd32(entries + 4 * (size_t)i);
+        if (cs < ZC_BLK_HDR || cs > archive_size) { zxc_seekable_free(s); return NULL; }
         s->comp_sizes[i] = cs;
         s->comp_offsets[i] = acc;
         acc += cs;
@@ -1339,28 +1251,22 @@ static zxc_seekable* seekable_build(uint32_t block_size, int has_ck, uint32_t di
 
 zxc_seekable* zxc_seekable_open(const void* src_v, const size_t n) {
     const uint8_t* data = (const uint8_t*)src_v;
-    if (!data || n < ZXC_FILE_HEADER_SIZE + 2 * BLK_HDR + ZXC_FILE_FOOTER_SIZE) return NULL;
+    if (!data || n < ZXC_FILE_HEADER_SIZE + 2 * ZC_BLK_HDR + ZXC_FILE_FOOTER_SIZE) return NULL;
     uint32_t bs, did;
     int ck;
-    if (read_file_header(data, n, &bs, &ck, &did) != ZXC_OK) return NULL;
-    const uint64_t total = rd64(data + n - ZXC_FILE_FOOTER_SIZE);
+    if (host_file_header(data, n, &bs, &ck, &did) != ZXC_OK) return NULL;
+    const uint64_t total = zc_rd64(data + n - ZXC_FILE_FOOTER_SIZE);
     if (total == 0) return NULL;
     const uint64_t nb = (total + bs - 1) / bs;
     if (nb > UINT32_MAX) return NULL;
-    const uint64_t entries = nb * 4;
-    if (entries + BLK_HDR + ZXC_FILE_FOOTER_SIZE > n) return NULL;
-    const uint8_t* sek = data + n - ZXC_FILE_FOOTER_SIZE - BLK_HDR - (size_t)entries;
-    uint8_t type;
-    uint32_t csz;
-    if (read_block_header(sek, BLK_HDR + (size_t)entries, &type, &csz) != ZXC_OK) return NULL;
-    if (type != BLK_SEK || csz != (uint32_t)entries) return NULL;
-    zxc_seekable* s = seekable_build(bs, ck, did, total, (uint32_t)nb, sek + BLK_HDR, n);
+    /* the tail [EOF header][SEK header of 4 nb bytes][entries][footer] behind at least the file header */
+    uint64_t eof_at = 0, eof = 0;
+    if (!zc_seek_tail(data, n, nb, &eof_at, &eof)) return NULL;
+    zxc_seekable* s = seekable_build(bs, ck, did, total, (uint32_t)nb, data + eof_at + 2 * ZC_BLK_HDR, n);
     if (!s) return NULL;
     s->src = data;
-    /* the prefix sum must land on a real EOF block right in front of the SEK block */
-    const uint64_t acc = s->comp_offsets[nb];
-    if (acc != (uint64_t)(sek - data) - BLK_HDR || read_block_header(data + acc, BLK_HDR, &type, &csz) != ZXC_OK ||
-        type != BLK_EOF) {
+    /* the prefix sum must land on that EOF block */
+    if (s->comp_offsets[nb] != eof_at) {
         zxc_seekable_free(s);
         return NULL;
     }
@@ -1369,28 +1275,28 @@ zxc_seekable* zxc_seekable_open(const void* src_v, const size_t n) {
 
 zxc_seekable* zxc_seekable_open_reader(const zxc_reader_t* r) {
     if (!r || !r->read_at || r->size == 0) return NULL;
-    if (r->size < ZXC_FILE_HEADER_SIZE + 2 * BLK_HDR + ZXC_FILE_FOOTER_SIZE) return NULL;
+    if (r->size < ZXC_FILE_HEADER_SIZE + 2 * ZC_BLK_HDR + ZXC_FILE_FOOTER_SIZE) return NULL;
     uint8_t hdr[ZXC_FILE_HEADER_SIZE], foot[ZXC_FILE_FOOTER_SIZE];
     if (r->read_at(r->ctx, hdr, sizeof hdr, 0) != (int64_t)sizeof hdr) return NULL;
     uint32_t bs, did;
     int ck;
-    if (read_file_header(hdr, sizeof hdr, &bs, &ck, &did) != ZXC_OK) return NULL;
+    if (host_file_header(hdr, sizeof hdr, &bs, &ck, &did) != ZXC_OK) return NULL;
     if (r->read_at(r->ctx, foot, sizeof foot, r->size - sizeof foot) != (int64_t)sizeof foot) return NULL;
-    const uint64_t total = rd64(foot);
+    const uint64_t total = zc_rd64(foot);
     if (total == 0) return NULL;
     const uint64_t nb = (total + bs - 1) / bs;
     if (nb > UINT32_MAX) return NULL;
     const uint64_t entries = nb * 4;
-    if (entries + BLK_HDR + ZXC_FILE_FOOTER_SIZE > r->size) return NULL;
-    const size_t sek_total = BLK_HDR + (size_t)entries;
+    if (entries + ZC_BLK_HDR + ZXC_FILE_FOOTER_SIZE > r->size) return NULL;
+    const size_t sek_total = ZC_BLK_HDR + (size_t)entries;
     uint8_t* buf = (uint8_t*)malloc(sek_total);
     if (!buf) return NULL;
     zxc_seekable* s = NULL;
-    uint8_t type;
-    uint32_t csz;
+    /* (a shorter rule than zxc_seekable_open's zc_seek_tail: the EOF header in front of the SEK header is never read here, nor is
+     *  the prefix sum held against it; the SEK header alone must be valid, of its type and 4 nb long) */
     if (r->read_at(r->ctx, buf, sek_total, r->size - ZXC_FILE_FOOTER_SIZE - sek_total) == (int64_t)sek_total &&
-        read_block_header(buf, sek_total, &type, &csz) == ZXC_OK && type == BLK_SEK && csz == (uint32_t)entries) {
-        s = seekable_build(bs, ck, did, total, (uint32_t)nb, buf + BLK_HDR, r->size);
+        zc_blk_hdr_ok(zc_rd64(buf)) && zc_blk_type(zc_rd64(buf)) == ZC_BLK_SEK && zc_blk_csz(zc_rd64(buf)) == (uint32_t)entries) {
+        s = seekable_build(bs, ck, did, total, (uint32_t)nb, buf + ZC_BLK_HDR, r->size);
         if (s) s->reader = *r;
     }
     free(buf);
@@ -1621,13 +1527,13 @@ struct zxc_dctx_s { int in_workspace; size_t block_size; };
 uint32_t zxc_get_dict_id(const void* src, const size_t src_size) {
     if (!src || src_size < ZXC_FILE_HEADER_SIZE) return 0;
     const uint8_t* p = (const uint8_t*)src;
-    if (rd32(p) != MAGIC) return 0;
-    return (p[6] & 0x40) ? rd32(p + 7) : 0;
+    if (zc_rd32(p) != ZC_MAGIC) return 0;
+    return (p[6] & 0x40) ? zc_rd32(p + 7) : 0;
 }
 
 uint64_t zxc_compress_block_bound(const size_t input_size) {
     if (input_size == 0 || input_size > ZXC_BLOCK_SIZE_MAX) return 0;
-    return (uint64_t)BLK_HDR + (uint64_t)input_size + BLOCK_FORMAT_OVERHEAD + 4u;
+    return (uint64_t)ZC_BLK_HDR + (uint64_t)input_size + BLOCK_FORMAT_OVERHEAD + 4u;
 }
 
 uint64_t zxc_decompress_block_bound(const size_t uncompressed_size) {
@@ -1675,10 +1581,9 @@ void zxc_free_dctx(zxc_dctx* dctx) { if (dctx && !dctx->in_workspace) free(dctx)
  * contract that matters to callers is the reference's: block_size locked (ZXC_ERROR_BAD_BLOCK_SIZE), a raise into levels 6-7 on
  * a workspace carved below them refused (ZXC_ERROR_BAD_LEVEL), level / checksum otherwise per call, zxc_free_* no-ops. */
 #define STATIC_LINE 64u
-static int valid_block_size(size_t bs) { return bs >= ZXC_BLOCK_SIZE_MIN && bs <= ZXC_BLOCK_SIZE_MAX && !(bs & (bs - 1)); }
 
 size_t zxc_static_cctx_workspace_size(const size_t block_size, const int level) {
-    if (!valid_block_size(block_size) || level < ZXC_LEVEL_FASTEST || level > ZXC_LEVEL_ULTRA) return 0;
+    if (!zc_block_size_ok(block_size) || level < ZXC_LEVEL_FASTEST || level > ZXC_LEVEL_ULTRA) return 0;
     return STATIC_LINE * (level >= ZXC_LEVEL_DENSITY ? 2u : 1u);
 }
 
@@ -1698,10 +1603,10 @@ zxc_cctx* zxc_init_static_cctx(void* workspace, const size_t workspace_size, con
     return c;
 }
 
-size_t zxc_static_dctx_workspace_size(const size_t block_size) { return valid_block_size(block_size) ? STATIC_LINE : 0; }
+size_t zxc_static_dctx_workspace_size(const size_t block_size) { return zc_block_size_ok(block_size) ? STATIC_LINE : 0; }
 
 zxc_dctx* zxc_init_static_dctx(void* workspace, const size_t workspace_size, const size_t block_size) {
-    if (!workspace || !valid_block_size(block_size) || workspace_size < STATIC_LINE || ((uintptr_t)workspace & (_Alignof(zxc_dctx) - 1)))
+    if (!workspace || !zc_block_size_ok(block_size) || workspace_size < STATIC_LINE || ((uintptr_t)workspace & (_Alignof(zxc_dctx) - 1)))
         return NULL;
     zxc_dctx* d = (zxc_dctx*)workspace;
     memset(d, 0, sizeof(*d));
@@ -1739,7 +1644,7 @@ int64_t zxc_decompress_dctx(zxc_dctx* dctx, const void* src, const size_t src_si
         if (!src || !dst || src_size < ZXC_FILE_HEADER_SIZE) return ZXC_ERROR_NULL_INPUT;
         uint32_t bs = 0, did = 0;
         int ck = 0;
-        if (read_file_header((const uint8_t*)src, src_size, &bs, &ck, &did) != ZXC_OK) return ZXC_ERROR_BAD_HEADER;
+        if (host_file_header((const uint8_t*)src, src_size, &bs, &ck, &did) != ZXC_OK) return ZXC_ERROR_BAD_HEADER;
         if (bs != dctx->block_size) return ZXC_ERROR_BAD_BLOCK_SIZE;
     }
     return zxc_decompress(src, src_size, dst, dst_capacity, opts);
@@ -1828,8 +1733,8 @@ static int64_t decompress_one_block(const void* src, size_t src_size, void* dst,
     dev_bufs_t b;
     /* only the block itself is uploaded: header + payload (+ trailer), never more than the caller's buffer */
     size_t up = src_size;
-    if (src_size >= BLK_HDR) {
-        const uint64_t phys = (uint64_t)BLK_HDR + rd32((const uint8_t*)src + 3) + 4u;
+    if (src_size >= ZC_BLK_HDR) {
+        const uint64_t phys = (uint64_t)ZC_BLK_HDR + zc_rd32((const uint8_t*)src + 3) + 4u;
         if (phys < up) up = (size_t)phys;
     }
     int rc = run_jobs_cap((const uint8_t*)src, up, &job, 1, ((size_t)job.out_len + 15u) & ~(size_t)15u, (uint32_t)bs, cap_override,
@@ -1849,14 +1754,14 @@ static int64_t decompress_one_block(const void* src, size_t src_size, void* dst,
 
 int64_t zxc_decompress_block(zxc_dctx* dctx, const void* src, const size_t src_size, void* dst, const size_t dst_capacity,
                              const zxc_decompress_opts_t* opts) {
-    if (!dctx || !src || !dst || src_size < BLK_HDR || dst_capacity == 0) return ZXC_ERROR_NULL_INPUT;
+    if (!dctx || !src || !dst || src_size < ZC_BLK_HDR || dst_capacity == 0) return ZXC_ERROR_NULL_INPUT;
     if (dst_capacity > (size_t)ZXC_BLOCK_SIZE_MAX + TAIL_PAD) return ZXC_ERROR_BAD_BLOCK_SIZE;
     return decompress_one_block(src, src_size, dst, dst_capacity, opts, 0u);
 }
 
 int64_t zxc_decompress_block_safe(zxc_dctx* dctx, const void* src, const size_t src_size, void* dst,
                                   const size_t dst_capacity, const zxc_decompress_opts_t* opts) {
-    if (!dctx || !src || !dst || src_size < BLK_HDR || dst_capacity == 0) return ZXC_ERROR_NULL_INPUT;
+    if (!dctx || !src || !dst || src_size < ZC_BLK_HDR || dst_capacity == 0) return ZXC_ERROR_NULL_INPUT;
     if (dst_capacity > ZXC_BLOCK_SIZE_MAX) return ZXC_ERROR_BAD_BLOCK_SIZE;
     /* dictionary inputs and RAW blocks take the bounce-capable path (zxc_dispatch.c:1823-1832) */
     if ((opts && opts->dict && opts->dict_size > 0) || ((const uint8_t*)src)[0] == BLK_RAW)

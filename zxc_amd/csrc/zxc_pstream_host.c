@@ -69,7 +69,7 @@ zxc_cstream* zxc_cstream_create(const zxc_compress_opts_t* opts) {
     /* dictionaries are refused, not dropped: the push format has no dict_id (src/lib/zxc_pstream.c:275-280) */
     if (opts && (opts->dict || opts->dict_size || opts->dict_huf)) return NULL;
     const size_t bs = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    if (bs < ZXC_BLOCK_SIZE_MIN || bs > ZXC_BLOCK_SIZE_MAX || (bs & (bs - 1))) return NULL;
+    if (!zc_block_size_ok(bs)) return NULL;
     zxc_cstream* cs = (zxc_cstream*)calloc(1, sizeof(*cs));
     if (!cs) return NULL;
     int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
@@ -183,30 +183,17 @@ static int cs_drain(zxc_cstream* cs, zxc_outbuf_t* out) {
     return cs->pending_pos == cs->pending_len;
 }
 static void cs_stage_file_header(zxc_cstream* cs) { /* 16 bytes, src/lib/zxc_common.c:534-558 (no dictionary) */
-    uint8_t* h = cs->pending;
-    memset(h, 0, ZXC_FILE_HEADER_SIZE);
-    wr32(h, MAGIC);
-    h[4] = FORMAT_VERSION;
-    uint8_t lg = 0;
-    while (((size_t)1 << lg) < cs->block_size) lg++;
-    h[5] = lg;
-    h[6] = cs->checksum ? 0x80 : 0;
-    const uint16_t crc = hdr_hash16(h);
-    h[14] = (uint8_t)crc;
-    h[15] = (uint8_t)(crc >> 8);
+    zc_put_file_header(cs->pending, zc_block_size_lg(cs->block_size), cs->checksum, 0, 0);
     cs->pending_len = ZXC_FILE_HEADER_SIZE;
     cs->pending_pos = 0;
 }
 static void cs_stage_eof(zxc_cstream* cs) {
-    memset(cs->pending, 0, BLK_HDR);
-    cs->pending[0] = BLK_EOF;
-    cs->pending[7] = hdr_hash8(cs->pending);
-    cs->pending_len = BLK_HDR;
+    zc_st_le(cs->pending, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
+    cs->pending_len = ZC_BLK_HDR;
     cs->pending_pos = 0;
 }
 static void cs_stage_footer(zxc_cstream* cs) {
-    wr64(cs->pending, cs->total_in);
-    wr32(cs->pending + 8, cs->checksum ? cs->global_hash : 0);
+    zc_put_footer(cs->pending, cs->total_in, cs->checksum ? cs->global_hash : 0);
     cs->pending_len = ZXC_FILE_FOOTER_SIZE;
     cs->pending_pos = 0;
 }
@@ -553,7 +540,7 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 if (!ds_pull_scratch(ds, in)) return (int64_t)produced;
                 uint32_t bs = 0, did = 0;
                 int ck = 0;
-                const int rc = read_file_header(ds->scratch, ds->scratch_used, &bs, &ck, &did);
+                const int rc = host_file_header(ds->scratch, ds->scratch_used, &bs, &ck, &did);
                 if (rc != ZXC_OK) return ds_fail(ds, rc);
                 ds->block_size = bs;
                 ds->file_ck = ck;
@@ -563,18 +550,18 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 if (!ds->jobs) return ds_fail(ds, ZXC_ERROR_MEMORY);
                 ds->state = DS_BLOCK_HEADER;
                 ds->scratch_used = 0;
-                ds->scratch_need = BLK_HDR;
+                ds->scratch_need = ZC_BLK_HDR;
                 break;
             }
             case DS_BLOCK_HEADER: {
                 const size_t avail = in->size - in->pos;
                 const uint8_t* hdr;
                 int direct = 0;
-                if (ds->scratch_used == 0 && avail >= BLK_HDR) {
+                if (ds->scratch_used == 0 && avail >= ZC_BLK_HDR) {
                     hdr = (const uint8_t*)in->src + in->pos;
                     direct = 1;
                 } else {
-                    if (ds->n > 0 && avail < BLK_HDR - ds->scratch_used) { /* the input ends here: the collected blocks first */
+                    if (ds->n > 0 && avail < ZC_BLK_HDR - ds->scratch_used) { /* the input ends here: the collected blocks first */
                         ds->next_state = DS_BLOCK_HEADER;
                         ds->state = DS_FLUSH;
                         break;
@@ -582,13 +569,13 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                     if (!ds_pull_scratch(ds, in)) return (int64_t)produced;
                     hdr = ds->scratch;
                 }
-                uint8_t type = 0;
-                uint32_t csz = 0;
-                int herr = read_block_header(hdr, BLK_HDR, &type, &csz);
-                if (herr == ZXC_OK && type == BLK_EOF) {
+                const uint64_t hw = zc_rd64(hdr);
+                const uint32_t csz = zc_blk_hdr_ok(hw) ? zc_blk_csz(hw) : 0u;
+                int herr = zc_blk_hdr_ok(hw) ? ZXC_OK : ZXC_ERROR_BAD_HEADER;
+                if (herr == ZXC_OK && zc_blk_type(hw) == ZC_BLK_EOF) {
                     if (csz != 0) herr = ZXC_ERROR_BAD_BLOCK_SIZE; /* src/lib/zxc_pstream.c:991 */
                     else {
-                        if (direct) in->pos += BLK_HDR;
+                        if (direct) in->pos += ZC_BLK_HDR;
                         ds->scratch_used = 0;
                         ds->next_state = DS_PEEK_TAIL;
                         ds->state = DS_FLUSH;
@@ -598,13 +585,13 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 const uint64_t need = (uint64_t)csz + (ds->file_ck ? 4u : 0u);
                 if (herr == ZXC_OK && need > zxc_compress_block_bound(ds->block_size)) herr = ZXC_ERROR_BAD_BLOCK_SIZE; /* :1001 */
                 if (herr != ZXC_OK) { /* what was collected in front of it decodes (and may fail) first */
-                    if (direct) in->pos += BLK_HDR; /* (the reference has pulled the header it rejects) */
+                    if (direct) in->pos += ZC_BLK_HDR; /* (the reference has pulled the header it rejects) */
                     ds->scratch_used = 0;
                     ds->tail_err = herr;
                     ds->state = DS_FLUSH;
                     break;
                 }
-                const size_t phys = BLK_HDR + (size_t)need;
+                const size_t phys = ZC_BLK_HDR + (size_t)need;
                 if (direct && avail >= phys) { /* the frame lies whole in the caller's input: it joins the span where it is */
                     if (ds->n == ds->jobs_cap) {
                         zxc_dev_job_t* nj = (zxc_dev_job_t*)realloc(ds->jobs, (size_t)ds->jobs_cap * 2 * sizeof(zxc_dev_job_t));
@@ -618,7 +605,7 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                     ds->n++;
                     ds->span_len += phys;
                     in->pos += phys;
-                    if (ds->want_verify && ds->file_ck) ds->global_hash = ((ds->global_hash << 1) | (ds->global_hash >> 31)) ^ rd32(hdr + BLK_HDR + csz);
+                    if (ds->want_verify && ds->file_ck) ds->global_hash = zc_hash_fold(ds->global_hash, zc_rd32(hdr + ZC_BLK_HDR + csz));
                     /* a window is a batch — unless the caller's out has room for more: then everything the input holds (what does
                      * not land in out has to fit the staging buffer) */
                     if (ds->n >= ds->max_blocks && (uint64_t)(ds->n + 1) * ds->block_size > (uint64_t)(out->size - out->pos)) {
@@ -633,10 +620,10 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                     break;
                 }
                 if (ps_host_reserve(&ds->carry, &ds->carry_cap, phys, 0) != ZXC_OK) return ds_fail(ds, ZXC_ERROR_MEMORY);
-                memcpy(ds->carry, hdr, BLK_HDR);
-                if (direct) in->pos += BLK_HDR;
+                memcpy(ds->carry, hdr, ZC_BLK_HDR);
+                if (direct) in->pos += ZC_BLK_HDR;
                 ds->scratch_used = 0;
-                ds->carry_used = BLK_HDR;
+                ds->carry_used = ZC_BLK_HDR;
                 ds->carry_need = phys;
                 ds->state = DS_PAYLOAD;
                 break;
@@ -655,7 +642,7 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 ds->jobs[0].comp_size = (uint32_t)ds->carry_need;
                 ds->n = 1;
                 ds->has_carry = 1;
-                if (ds->want_verify && ds->file_ck) ds->global_hash = ((ds->global_hash << 1) | (ds->global_hash >> 31)) ^ rd32(ds->carry + ds->carry_need - 4);
+                if (ds->want_verify && ds->file_ck) ds->global_hash = zc_hash_fold(ds->global_hash, zc_rd32(ds->carry + ds->carry_need - 4));
                 ds->state = DS_BLOCK_HEADER;
                 break;
             }
@@ -678,15 +665,14 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 if (ds->decoded_pos < ds->decoded_size) return (int64_t)produced;
                 if (ds->tail_err) return ds_fail(ds, ds->tail_err);
                 ds->state = ds->next_state;
-                if (ds->state == DS_PEEK_TAIL) { ds->scratch_used = 0; ds->scratch_need = BLK_HDR; }
+                if (ds->state == DS_PEEK_TAIL) { ds->scratch_used = 0; ds->scratch_need = ZC_BLK_HDR; }
                 break;
             }
             case DS_PEEK_TAIL: { /* behind the EOF block: a SEK block, or the first 8 bytes of the footer (src/lib/zxc_pstream.c:1122-1137) */
                 if (!ds_pull_scratch(ds, in)) return (int64_t)produced;
-                uint8_t type = 0;
-                uint32_t csz = 0;
-                if (read_block_header(ds->scratch, BLK_HDR, &type, &csz) == ZXC_OK && type == BLK_SEK) {
-                    ds->sek_remaining = csz;
+                const uint64_t hw = zc_rd64(ds->scratch);
+                if (zc_blk_hdr_ok(hw) && zc_blk_type(hw) == ZC_BLK_SEK) {
+                    ds->sek_remaining = zc_blk_csz(hw);
                     ds->state = DS_SEK;
                 } else {
                     ds->scratch_need = ZXC_FILE_FOOTER_SIZE; /* keep the 8, 4 more */
@@ -710,8 +696,8 @@ int64_t zxc_dstream_decompress(zxc_dstream* ds, zxc_outbuf_t* out, zxc_inbuf_t* 
                 ds->state = DS_VALIDATE;
                 break;
             case DS_VALIDATE:
-                if (rd64(ds->scratch) != ds->total_out) return ds_fail(ds, ZXC_ERROR_CORRUPT_DATA);
-                if (ds->want_verify && ds->file_ck && rd32(ds->scratch + 8) != ds->global_hash) return ds_fail(ds, ZXC_ERROR_BAD_CHECKSUM);
+                if (zc_rd64(ds->scratch) != ds->total_out) return ds_fail(ds, ZXC_ERROR_CORRUPT_DATA);
+                if (ds->want_verify && ds->file_ck && zc_rd32(ds->scratch + 8) != ds->global_hash) return ds_fail(ds, ZXC_ERROR_BAD_CHECKSUM);
                 ds->state = DS_DONE;
                 return (int64_t)produced;
             default:

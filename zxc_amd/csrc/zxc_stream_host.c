@@ -35,10 +35,10 @@ int64_t zxc_stream_get_decompressed_size(FILE* f_in) {
     uint8_t hdr[ZXC_FILE_HEADER_SIZE], foot[ZXC_FILE_FOOTER_SIZE];
     if (size < (off_t)(ZXC_FILE_HEADER_SIZE + ZXC_FILE_FOOTER_SIZE)) ret = ZXC_ERROR_SRC_TOO_SMALL;
     else if (fseeko(f_in, 0, SEEK_SET) != 0 || fread(hdr, 1, sizeof hdr, f_in) != sizeof hdr) ret = ZXC_ERROR_IO;
-    else if (rd32(hdr) != MAGIC) ret = ZXC_ERROR_BAD_MAGIC;
+    else if (zc_rd32(hdr) != ZC_MAGIC) ret = ZXC_ERROR_BAD_MAGIC;
     else if (fseeko(f_in, size - (off_t)ZXC_FILE_FOOTER_SIZE, SEEK_SET) != 0 || fread(foot, 1, sizeof foot, f_in) != sizeof foot)
         ret = ZXC_ERROR_IO;
-    else ret = (int64_t)rd64(foot);
+    else ret = (int64_t)zc_rd64(foot);
     if (fseeko(f_in, saved, SEEK_SET) != 0 && ret >= 0) ret = ZXC_ERROR_IO;
     return ret;
 }
@@ -163,7 +163,7 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
     if (fread(hdr, 1, sizeof hdr, f_in) != sizeof hdr) return ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
     uint32_t block_size, dict_id;
     int file_ck;
-    const int hrc = read_file_header(hdr, sizeof hdr + ZXC_FILE_FOOTER_SIZE, &block_size, &file_ck, &dict_id);
+    const int hrc = host_file_header(hdr, sizeof hdr + ZXC_FILE_FOOTER_SIZE, &block_size, &file_ck, &dict_id);
     if (hrc != ZXC_OK) return hrc;
     const int verify = file_ck && opts && opts->checksum_enabled;
     const uint8_t* dict = opts ? (const uint8_t*)opts->dict : NULL;
@@ -206,14 +206,14 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
     int saw_eof = 0;
     for (;;) {
         stream_batch_t* b = &B[cur];
-        uint8_t bh[BLK_HDR];
-        const size_t got = fread(bh, 1, BLK_HDR, f_in);
-        uint8_t type = 0;
-        uint32_t csz = 0;
+        uint8_t bh[ZC_BLK_HDR];
+        const size_t got = fread(bh, 1, ZC_BLK_HDR, f_in);
+        const uint64_t hw = got == ZC_BLK_HDR ? zc_rd64(bh) : 0u;
+        const uint32_t csz = zc_blk_csz(hw);
         int herr = ZXC_OK;
-        if (got != BLK_HDR) herr = ferror(f_in) ? ZXC_ERROR_IO : (got == 0 ? ZXC_ERROR_SRC_TOO_SMALL : ZXC_ERROR_BAD_HEADER);
-        else herr = read_block_header(bh, BLK_HDR, &type, &csz);
-        if (herr == ZXC_OK && type == BLK_EOF) {
+        if (got != ZC_BLK_HDR) herr = ferror(f_in) ? ZXC_ERROR_IO : (got == 0 ? ZXC_ERROR_SRC_TOO_SMALL : ZXC_ERROR_BAD_HEADER);
+        else if (!zc_blk_hdr_ok(hw)) herr = ZXC_ERROR_BAD_HEADER;
+        if (herr == ZXC_OK && zc_blk_type(hw) == ZC_BLK_EOF) {
             if (csz != 0) herr = ZXC_ERROR_BAD_HEADER;
             else saw_eof = 1;
         }
@@ -222,25 +222,25 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
             herr = ZXC_ERROR_CORRUPT_DATA;
         const size_t want = herr == ZXC_OK && !saw_eof ? (size_t)csz + (file_ck ? 4u : 0u) : 0;
         if (herr == ZXC_OK && !saw_eof) {
-            if (b->comp_used + BLK_HDR + want + 64 > b->comp_cap) {
+            if (b->comp_used + ZC_BLK_HDR + want + 64 > b->comp_cap) {
                 size_t nc_cap = b->comp_cap;
-                while (b->comp_used + BLK_HDR + want + 64 > nc_cap) nc_cap *= 2;
+                while (b->comp_used + ZC_BLK_HDR + want + 64 > nc_cap) nc_cap *= 2;
                 uint8_t* nc = (uint8_t*)realloc(b->comp, nc_cap);
                 if (!nc) { herr = ZXC_ERROR_MEMORY; }
                 else { b->comp = nc; b->comp_cap = nc_cap; }
             }
         }
         if (herr == ZXC_OK && !saw_eof) {
-            memcpy(b->comp + b->comp_used, bh, BLK_HDR);
-            if (fread(b->comp + b->comp_used + BLK_HDR, 1, want, f_in) != want) herr = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
+            memcpy(b->comp + b->comp_used, bh, ZC_BLK_HDR);
+            if (fread(b->comp + b->comp_used + ZC_BLK_HDR, 1, want, f_in) != want) herr = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
         }
         if (herr == ZXC_OK && !saw_eof) {
             b->jobs[b->n].comp_off = b->comp_used;
-            b->jobs[b->n].comp_size = (uint32_t)(BLK_HDR + want);
+            b->jobs[b->n].comp_size = (uint32_t)(ZC_BLK_HDR + want);
             b->jobs[b->n].out_off = (uint64_t)b->n * slot;
             b->jobs[b->n].out_len = slot;
-            if (verify) global_hash = ((global_hash << 1) | (global_hash >> 31)) ^ rd32(b->comp + b->comp_used + BLK_HDR + csz);
-            b->comp_used += BLK_HDR + want;
+            if (verify) global_hash = zc_hash_fold(global_hash, zc_rd32(b->comp + b->comp_used + ZC_BLK_HDR + csz));
+            b->comp_used += ZC_BLK_HDR + want;
             b->n++;
         }
         if (herr != ZXC_OK || saw_eof || b->n == batch_blocks) { /* queued blocks first: an earlier block's error wins */
@@ -278,12 +278,10 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
         /* what follows the EOF block is (a) the 12-byte footer, or (b) a SEK block then the footer; like the
          * reference (zxc_driver.c:959-992) peek 8 bytes and see whether they are a SEK block header */
         uint8_t foot[ZXC_FILE_FOOTER_SIZE];
-        uint8_t t2 = 0;
-        uint32_t c2 = 0;
-        if (fread(foot, 1, BLK_HDR, f_in) != BLK_HDR) ret = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
-        else if (read_block_header(foot, BLK_HDR, &t2, &c2) == ZXC_OK && t2 == BLK_SEK) {
+        if (fread(foot, 1, ZC_BLK_HDR, f_in) != ZC_BLK_HDR) ret = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
+        else if (zc_blk_hdr_ok(zc_rd64(foot)) && zc_blk_type(zc_rd64(foot)) == ZC_BLK_SEK) {
             uint8_t buf[4096];
-            uint64_t skip = c2;
+            uint64_t skip = zc_blk_csz(zc_rd64(foot));
             while (ret == 0 && skip > 0) {  /* drain the table */
                 const size_t k = skip < sizeof buf ? (size_t)skip : sizeof buf;
                 if (fread(buf, 1, k, f_in) != k) ret = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
@@ -291,12 +289,12 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
             }
             if (ret == 0 && fread(foot, 1, ZXC_FILE_FOOTER_SIZE, f_in) != ZXC_FILE_FOOTER_SIZE)
                 ret = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
-        } else if (fread(foot + BLK_HDR, 1, ZXC_FILE_FOOTER_SIZE - BLK_HDR, f_in) != ZXC_FILE_FOOTER_SIZE - BLK_HDR) {
+        } else if (fread(foot + ZC_BLK_HDR, 1, ZXC_FILE_FOOTER_SIZE - ZC_BLK_HDR, f_in) != ZXC_FILE_FOOTER_SIZE - ZC_BLK_HDR) {
             ret = ferror(f_in) ? ZXC_ERROR_IO : ZXC_ERROR_SRC_TOO_SMALL;
         }
         if (ret == 0) {
-            if (rd64(foot) != (uint64_t)total) ret = ZXC_ERROR_CORRUPT_DATA;
-            else if (verify && rd32(foot + 8) != global_hash) ret = ZXC_ERROR_BAD_CHECKSUM;
+            if (zc_rd64(foot) != (uint64_t)total) ret = ZXC_ERROR_CORRUPT_DATA;
+            else if (verify && zc_rd32(foot + 8) != global_hash) ret = ZXC_ERROR_BAD_CHECKSUM;
         }
     }
     for (int k = 0; k < 2; k++) { free(B[k].jobs); free(B[k].comp); free(writer.host_out[k]); }
@@ -312,8 +310,7 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
     int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
     if (level > ZXC_LEVEL_ULTRA) level = ZXC_LEVEL_ULTRA;
     const size_t block_size = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    if (block_size < ZXC_BLOCK_SIZE_MIN || block_size > ZXC_BLOCK_SIZE_MAX || (block_size & (block_size - 1)))
-        return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     const size_t dict_size = (opts && opts->dict) ? opts->dict_size : 0;
     if (dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
     const uint8_t* dict = dict_size ? (const uint8_t*)opts->dict : NULL;
@@ -321,20 +318,7 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
     if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
 
     uint8_t fh[ZXC_FILE_HEADER_SIZE];
-    memset(fh, 0, sizeof fh);
-    wr32(fh, MAGIC);
-    fh[4] = FORMAT_VERSION;
-    uint8_t lg = 0;
-    while (((size_t)1 << lg) < block_size) lg++;
-    fh[5] = lg;
-    fh[6] = checksum_enabled ? 0x80 : 0;
-    if (dict_size) { /* HAS_DICTIONARY + dict_id, like zxc_compress (src/lib/zxc_common.c:546-553) */
-        fh[6] |= 0x40;
-        wr32(fh + 7, dict_id_of(dict, dict_size, dict_huf));
-    }
-    const uint16_t crc = hdr_hash16(fh);
-    fh[14] = (uint8_t)crc;
-    fh[15] = (uint8_t)(crc >> 8);
+    zc_put_file_header(fh, zc_block_size_lg(block_size), checksum_enabled, dict_size != 0, dict_id_of(dict, dict_size, dict_huf)); /* like zxc_compress */
     if (f_out && fwrite(fh, 1, sizeof fh, f_out) != sizeof fh) return ZXC_ERROR_IO;
     int64_t out_total = ZXC_FILE_HEADER_SIZE;
 
@@ -389,7 +373,7 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
         if (rc != ZXC_OK) { ret = rc; break; }
         if (checksum_enabled)
             for (uint32_t i = 0; i < nb; i++)
-                global_hash = ((global_hash << 1) | (global_hash >> 31)) ^ rd32(h_out + h_offs[i] + h_sizes[i] - 4);
+                global_hash = zc_hash_fold(global_hash, zc_rd32(h_out + h_offs[i] + h_sizes[i] - 4));
         if (seekable) {
             if (all_n + nb > all_cap) {
                 all_cap = all_cap ? all_cap * 2 : 4096;
@@ -411,12 +395,10 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
         }
     }
     if (ret == 0) { /* EOF block, optional seek table, footer */
-        uint8_t eofb[BLK_HDR];
-        memset(eofb, 0, sizeof eofb);
-        eofb[0] = BLK_EOF;
-        eofb[7] = hdr_hash8(eofb);
+        uint8_t eofb[ZC_BLK_HDR];
+        zc_st_le(eofb, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
         if (f_out && fwrite(eofb, 1, sizeof eofb, f_out) != sizeof eofb) ret = ZXC_ERROR_IO;
-        else out_total += BLK_HDR;
+        else out_total += ZC_BLK_HDR;
         if (ret == 0 && seekable && all_n > 0) {
             if (all_n > 0x3FFFFFFFu) ret = ZXC_ERROR_OVERFLOW;
             else {
@@ -434,8 +416,7 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
         }
         if (ret == 0) {
             uint8_t foot[ZXC_FILE_FOOTER_SIZE];
-            wr64(foot, src_total);
-            wr32(foot + 8, checksum_enabled ? global_hash : 0);
+            zc_put_footer(foot, src_total, checksum_enabled ? global_hash : 0);
             if (f_out && (fwrite(foot, 1, sizeof foot, f_out) != sizeof foot || fflush(f_out) != 0)) ret = ZXC_ERROR_IO;
             else out_total += ZXC_FILE_FOOTER_SIZE;
         }

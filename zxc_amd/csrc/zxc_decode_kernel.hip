@@ -34,11 +34,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "zxc_dev.h"
+#include "zxc_kernels.h"  // the kernels defined here, as the shim launches them; zxc_dev.h
+#include "zxc_wave.h"
 
 typedef unsigned __int128 u128;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef v4u __attribute__((aligned(1))) v4u_unaligned;
 
 #include "zxc_lds.h"
 
@@ -84,12 +83,6 @@ struct __attribute__((aligned(16))) WaveLds : RingLds {
 };
 
 // ---------------------------------------------------------------- small helpers
-__device__ __forceinline__ uint32_t ld8(const uint8_t* p) { return *p; }
-__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
-__device__ __forceinline__ v4u ld128(const uint8_t* p) { v4u v; __builtin_memcpy(&v, p, 16); return v; }
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 // Arguments of an out-of-line device function arrive in VGPRs and count as divergent; this tells
 // the compiler a pointer is wave-uniform again (scalar address arithmetic and branches).
 template <typename T>
@@ -98,26 +91,6 @@ __device__ __forceinline__ T* uni_ptr(T* p) {
     return (T*)(((uint64_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a));
 }
 
-// wave-wide inclusive prefix sum (64 lanes) on the DPP crossbar: row_shr 1,2,4,8 scan each
-// 16-lane row, row_bcast:15 / row_bcast:31 carry the row totals across (gfx9 DPP controls).
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v, int lane) {
-    (void)lane;
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t t = __shfl_xor(v, d);
-        v = t < v ? t : v;
-    }
-    return v;
-}
 // LDS traffic between lanes of the one wave. One wave's DS instructions execute in program order, so a read issued
 // after another lane's write sees it: only the COMPILER must keep the order (wavefront-scope fence: no instruction,
 // where a workgroup-scope one drains the LDS queue with s_waitcnt lgkmcnt(0), ~10 times per batch).
@@ -346,7 +319,7 @@ __device__ __forceinline__ uint32_t parse_varints(const uint8_t* ext, uint32_t e
         }
     }
     const uint32_t cnt = __popc(starts);
-    const uint32_t rank0 = wave_scan_add(cnt, lane) - cnt;
+    const uint32_t rank0 = wave_scan_add(cnt) - cnt;
     const u128 W = (u128)lo8 | ((u128)hi4 << 64);
     uint32_t minbad = 0xFFFFFFFFu;
 #pragma unroll
@@ -528,8 +501,8 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
 
         // cursors: inclusive scans of (ll+ml) and ll
         uint32_t len = ll + ml;
-        const uint32_t Eincl0 = wave_scan_add(len, lane);
-        const uint32_t Lincl0 = wave_scan_add(ll, lane);
+        const uint32_t Eincl0 = wave_scan_add(len);
+        const uint32_t Lincl0 = wave_scan_add(ll);
         const uint32_t est = p + (Eincl0 - len);  // where this sequence's literals land
         const uint32_t lst = lp + (Lincl0 - ll);  // its first literal
         // bounds (reference: OVERFLOW src/lib/zxc_decompress.c:1184, BAD_OFFSET :1190), all lanes, no branches

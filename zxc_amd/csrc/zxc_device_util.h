@@ -1,41 +1,22 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_dict_device.hip): the wave primitives, the three tile passes every container stage is made of, the copy, and the host-side
-// plumbing of an entry point. HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h.
+// zxc_dict_device.hip): the three tile passes every container stage is made of and the host-side plumbing of an entry point.
+// HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h.
 //
 // A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
 // blocks per thread. Every helper with a barrier in it is called by all threads of the workgroup, outside divergent control flow.
-// The decode and encode kernels keep their own wave scans (wave_scan_add / e_scan_add): their sources do not include this file.
+// The wave primitives and the copy are those of zxc_wave.h, the same ones the decode and encode kernels use.
 #ifndef ZXC_DEVICE_UTIL_H
 #define ZXC_DEVICE_UTIL_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "zxc_container.h"
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+#include "zxc_wave.h"
 
 #define ZD_TILE_THREADS 256u
 #define ZD_WAVES (ZD_TILE_THREADS / 64u)
 #define ZD_PER_THREAD (ZC_TILE_BLOCKS / ZD_TILE_THREADS)
 #define ZD_WORK_ALIGN 256u  // every part of a work area starts on this, counted from the aligned base (zd_work_base)
-
-// ---------------------------------------------------------------- wave primitives
-// wave-wide inclusive prefix sum on the DPP crossbar (the same controls as wave_scan_add / e_scan_add of the kernel sources)
-__device__ __forceinline__ uint32_t zd_wave_scan_add(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return v;
-}
-// xor butterfly: the xor of all 64 lanes' values, in every lane
-__device__ __forceinline__ uint32_t zd_wave_xor(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
 
 // ---------------------------------------------------------------- tile passes
 struct zd_totals {
@@ -49,8 +30,8 @@ struct zd_totals {
 __device__ __forceinline__ zd_totals zd_tile_reduce(uint32_t sum, uint32_t hash, uint32_t bad) {
     __shared__ uint32_t w_sum[ZD_WAVES], w_hash[ZD_WAVES], w_bad[ZD_WAVES];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    sum = (uint32_t)__builtin_amdgcn_readlane((int)zd_wave_scan_add(sum), 63);
-    hash = zd_wave_xor(hash);
+    sum = wave_sum(sum);
+    hash = wave_xor(hash);
     bad = __any(bad) ? 1u : 0u;
     if (lane == 0) { w_sum[wave] = sum; w_hash[wave] = hash; w_bad[wave] = bad; }
     __syncthreads();
@@ -64,7 +45,7 @@ __device__ __forceinline__ zd_totals zd_tile_reduce(uint32_t sum, uint32_t hash,
 __device__ __forceinline__ uint64_t zd_tile_offset(uint32_t sum, uint64_t base) {
     __shared__ uint32_t w_incl[ZD_WAVES];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t incl = zd_wave_scan_add(sum);
+    const uint32_t incl = wave_scan_add(sum);
     if (lane == 63) w_incl[wave] = incl;
     __syncthreads();
     uint64_t at = base + incl - sum;
@@ -93,7 +74,7 @@ __device__ __forceinline__ zd_totals zd_scan_tiles(uint32_t n_tiles, uint64_t ba
         const uint64_t o = __shfl_up(incl, (unsigned)d);
         if ((int)lane >= d) incl += o;
     }
-    hash = zd_wave_xor(hash);
+    hash = wave_xor(hash);
     bad = __any(bad) ? 1u : 0u;
     if (lane == 63) w_tot[wave] = incl;
     if (lane == 0) { w_hash[wave] = hash; w_bad[wave] = bad; }
@@ -113,20 +94,6 @@ __device__ __forceinline__ zd_totals zd_scan_tiles(uint32_t n_tiles, uint64_t ba
         run += s;
     }
     return r;
-}
-
-// d[0, n) = s[0, n) by `threads` threads, of which this is number t: 16-byte units of any alignment, bytes where the last unit
-// passes n. Reads and writes exactly those n bytes.
-__device__ __forceinline__ void zd_copy(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, uint32_t n, uint32_t t, uint32_t threads) {
-    for (uint32_t o = 16u * t; o < n; o += 16u * threads) {
-        if (o + 16u <= n) {
-            v4u v;
-            __builtin_memcpy(&v, s + o, 16);
-            __builtin_memcpy(d + o, &v, 16);
-        } else {
-            for (uint32_t k = o; k < n; k++) d[k] = s[k];
-        }
-    }
 }
 
 // ---------------------------------------------------------------- host side of an entry point

@@ -36,11 +36,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "zxc_dev.h"
+#include "zxc_container.h"  // the block header's check byte
 #include "zxc_encode_levels.h"
+#include "zxc_kernels.h"  // the kernels defined here, as the shim launches them; zxc_dev.h
+#include "zxc_wave.h"
 #include "zxc_rapidhash.inc"
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // The head table + chain ring are the LDS footprint, i.e. the occupancy (sizes per level: table at the bottom;
 // measured trade-offs: profiles/r2o_encode_table_sizes_ab.log).
@@ -50,12 +50,6 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // i - ((i - entry) & 0xFFFF); a stale or never-written entry just names some older position, and
 // every candidate is verified against the bytes. Half the LDS of 32-bit entries -> twice the waves.
 
-__device__ __forceinline__ uint32_t e_ld8(const uint8_t* p) { return *p; }
-__device__ __forceinline__ uint32_t e_ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint64_t e_ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
-__device__ __forceinline__ v4u e_ld128(const uint8_t* p) { v4u v; __builtin_memcpy(&v, p, 16); return v; }
-__device__ __forceinline__ uint32_t e_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // LDS traffic between the lanes of the ONE wave of a workgroup: order it (lgkmcnt only). __syncthreads() would also wait
 // for every global store and load in flight (vmcnt(0)), i.e. for the token / literal stores of the previous chunk.
 __device__ __forceinline__ void enc_lds_fence() {
@@ -63,23 +57,6 @@ __device__ __forceinline__ void enc_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ uint32_t e_scan_add(uint32_t v) {  // wave inclusive prefix sum (DPP)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-__device__ __forceinline__ uint32_t e_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
-}
 __device__ __forceinline__ uint32_t varint_len(uint32_t x) { return 1u + (x >= 128u) + (x >= 16384u); }
 // prefix varint, docs/FORMAT.md §6 (decoder: src/lib/zxc_decompress.c:51-88)
 __device__ __forceinline__ void put_varint(uint8_t* p, uint32_t x) {
@@ -94,15 +71,6 @@ __device__ __forceinline__ void put_varint(uint8_t* p, uint32_t x) {
         p[2] = (uint8_t)(x >> 13);
     }
 }
-// zxc_hash8 (src/lib/zxc_internal.h:1188-1195): block header check byte
-__device__ __forceinline__ uint8_t hdr_hash8(uint64_t v) {
-    uint64_t h = v ^ 0x9E3779B97F4A7C15ull;
-    h ^= h << 13;
-    h ^= h >> 7;
-    h ^= h << 17;
-    return (uint8_t)((h >> 32) ^ h);
-}
-
 // wave copy of n bytes, forward, dst below src (regions may overlap that way). Every step moves 1 KiB: the
 // wave's loads of a step precede its stores (one instruction each), and a step's stores end below the next
 // step's loads because dst < src — no waits beyond the data dependence are needed.
@@ -111,7 +79,7 @@ __device__ __forceinline__ void wave_move_down(uint8_t* dst, const uint8_t* src,
     for (uint32_t base = 0; base < full; base += 1024u) {
         const uint32_t o = base + 16u * (uint32_t)lane;
         v4u v = {0, 0, 0, 0};
-        if (o < full) v = e_ld128(src + o);
+        if (o < full) v = ld128(src + o);
         __builtin_amdgcn_wave_barrier();
         if (o < full) __builtin_memcpy(dst + o, &v, 16);
         __builtin_amdgcn_wave_barrier();
@@ -241,7 +209,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
         const bool ins = i < D && i < limit;
         uint32_t h = 0, d0 = 0;
         if (ins) {
-            h = hash_of(e_ld64(in + i));
+            h = hash_of(ld64(in + i));
             d0 = (i - (uint32_t)ht[h]) & 0xFFFFu;
             if (d0 > i) d0 = 0;
         }
@@ -273,7 +241,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
         for (uint32_t u = 0; u < U; u++) {
             iA[u] = c0 + 64u * u + (uint32_t)lane;
             canA[u] = iA[u] < limit && iA[u] >= D && iA[u] >= skip_until;
-            if (!fresh && iA[u] < n) v_next[u] = e_ld128(in + iA[u]);  // (a long match skipped ahead: the prefetch was for other chunks)
+            if (!fresh && iA[u] < n) v_next[u] = ld128(in + iA[u]);  // (a long match skipped ahead: the prefetch was for other chunks)
         }
         // request the following chunks' bytes now; they arrive while these are matched, parsed and emitted
         c_next = c0 + 64u * U;
@@ -283,10 +251,10 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             vA[u] = (uint64_t)v_next[u].x | ((uint64_t)v_next[u].y << 32);
             vhA[u] = (uint64_t)v_next[u].z | ((uint64_t)v_next[u].w << 32);
             const uint32_t i2 = c_next + 64u * u + (uint32_t)lane;
-            if (i2 < n) v_next[u] = e_ld128(in + i2);  // (every position of the block: its low byte is the literal the emission stores)
+            if (i2 < n) v_next[u] = ld128(in + i2);  // (every position of the block: its low byte is the literal the emission stores)
             // my own second 16 bytes: the same for every round of the walk (may reach up to 16 bytes past the block: lengths
             // are clamped to it below)
-            own2A[u] = e_ld128((canA[u] ? in + iA[u] : in) + 16u);
+            own2A[u] = ld128((canA[u] ? in + iA[u] : in) + 16u);
         }
         // ---- 1. hash -> head candidate, then publish: chunk by chunk, so that a chunk's lookup sees the chunks before it
 #pragma unroll
@@ -343,7 +311,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
                 dkA[u][0] = actA[u] ? dA[u] : 0u;
 #pragma unroll
                 for (uint32_t k = 0; k < NC; k++) {
-                    c1A[u][k] = e_ld128(pme - dkA[u][k]);
+                    c1A[u][k] = ld128(pme - dkA[u][k]);
                     dkA[u][k + 1] = next(u, dkA[u][k], triedA[u] + k + 1u < depth);
                 }
             }
@@ -367,7 +335,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
 #pragma unroll
                     for (uint32_t k = 0; k < NC; k++) {
                         v4u c2 = {0, 0, 0, 0};
-                        if (mk[k] == 16u) c2 = e_ld128(pme - dkA[u][k] + 16u);
+                        if (mk[k] == 16u) c2 = ld128(pme - dkA[u][k] + 16u);
                         if (mk[k] == 16u) mk[k] += prefix16(o2lo, o2hi, c2);
                     }
                 }
@@ -389,12 +357,12 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
                                 if (lk[k]) { mk[k] = L; while (i + mk[k] < n && in[i + mk[k]] == in[i - dkA[u][k] + mk[k]]) mk[k]++; lk[k] = false; }
                             break;
                         }
-                        const v4u own = e_ld128(in + i + L);
+                        const v4u own = ld128(in + i + L);
                         v4u xk[NC];
 #pragma unroll
                         for (uint32_t k = 0; k < NC; k++) {
                             xk[k] = own;
-                            if (lk[k]) xk[k] = e_ld128(in + i - dkA[u][k] + L);
+                            if (lk[k]) xk[k] = ld128(in + i - dkA[u][k] + L);
                         }
                         const uint64_t olo = (uint64_t)own.x | ((uint64_t)own.y << 32), ohi = (uint64_t)own.z | ((uint64_t)own.w << 32);
                         anylive = false;
@@ -425,8 +393,8 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             // next to nothing — identical archive sizes at levels 1-4 in tests/wave_emu — and is kept for the deep levels)
             uint32_t bk = 0;
             if (depth > 8u && lenA[u] && i >= 16u && i - distA[u] >= 16u) {
-                const uint64_t y = e_ld64(in + i - 8u) ^ e_ld64(in + i - distA[u] - 8u);
-                const uint64_t y2 = e_ld64(in + i - 16u) ^ e_ld64(in + i - distA[u] - 16u);
+                const uint64_t y = ld64(in + i - 8u) ^ ld64(in + i - distA[u] - 8u);
+                const uint64_t y2 = ld64(in + i - 16u) ^ ld64(in + i - distA[u] - 16u);
                 bk = y ? (uint32_t)(__builtin_clzll(y) >> 3) : (y2 ? 8u + (uint32_t)(__builtin_clzll(y2) >> 3) : 16u);
             }
             bkA[u] = bk;
@@ -508,7 +476,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             const uint32_t mlm = issel ? len + ext_v - 5u : 0u;
             uint32_t eb = 0;
             if (issel) eb = (ll >= esc ? varint_len(ll - esc) : 0u) + (mlm >= esc ? varint_len(mlm - esc) : 0u);
-            const uint32_t eincl = e_scan_add(eb);
+            const uint32_t eincl = wave_scan_add(eb);
             const uint32_t etot = (uint32_t)__builtin_amdgcn_readlane((int)eincl, 63);
             const uint32_t nsel = __popcll(sel);
             if (seq_count + nsel > max_seq || ext_count + etot > ext_cap) { overflow = true; break; }
@@ -606,8 +574,8 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             uint32_t run_start = 0;    // start of the run of equal bytes the walk is inside
             for (uint32_t t0 = 0; t0 < lit_count; t0 += 64u) {
                 const uint32_t j = t0 + (uint32_t)lane;
-                const uint32_t b0 = j < lit_count ? e_ld8(lit_out + j) : 0x100u;
-                const uint32_t b1 = j + 1u < lit_count ? e_ld8(lit_out + j + 1u) : 0x200u;
+                const uint32_t b0 = j < lit_count ? ld8(lit_out + j) : 0x100u;
+                const uint32_t b1 = j + 1u < lit_count ? ld8(lit_out + j + 1u) : 0x200u;
                 const uint64_t E = __ballot(b0 == b1);
                 // run boundaries inside this tile: positions whose byte differs from the next one end a run
                 uint64_t ends = ~E;
@@ -714,12 +682,12 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     if (overflow || 8u + payload >= nblk || nblk < 64u) {
         // RAW block (reference: zxc_encode_block_raw, src/lib/zxc_compress.c:2004-2023)
         for (uint32_t o = 16u * lane; o < nblk; o += 1024u) {
-            if (o + 16u <= nblk) { const v4u t = e_ld128(in + D + o); __builtin_memcpy(slot + 8 + o, &t, 16); }
+            if (o + 16u <= nblk) { const v4u t = ld128(in + D + o); __builtin_memcpy(slot + 8 + o, &t, 16); }
             else for (uint32_t k = o; k < nblk; k++) slot[8 + k] = in[D + k];
         }
         if (lane == 0) {
             uint64_t hv = (uint64_t)0 | ((uint64_t)nblk << 24);  // type 0, flags 0, reserved 0, comp_size le32 @3
-            const uint8_t crc = hdr_hash8(hv);
+            const uint8_t crc = zc_hdr_hash8(hv);
             hv |= (uint64_t)crc << 56;
             __builtin_memcpy(slot, &hv, 8);
         }
@@ -739,7 +707,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     auto wave_copy = [&](uint8_t* dstp, const uint8_t* srcp, uint32_t nbytes) {
         for (uint32_t o = 0; o < nbytes; o += 1024u) {
             const uint32_t q = o + 16u * (uint32_t)lane;
-            if (q + 16u <= nbytes) { const v4u t = e_ld128(srcp + q); __builtin_memcpy(dstp + q, &t, 16); }
+            if (q + 16u <= nbytes) { const v4u t = ld128(srcp + q); __builtin_memcpy(dstp + q, &t, 16); }
             else for (uint32_t k = q; k < nbytes; k++) dstp[k] = srcp[k];
         }
     };
@@ -770,7 +738,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     if ((uint32_t)lane < pad) w[lane] = 0;
     if (lane == 0) {
         uint64_t hv = (GHI ? 2ull : 1ull) | ((uint64_t)payload << 24);  // type 1 = GLO, 2 = GHI
-        hv |= (uint64_t)hdr_hash8(hv) << 56;
+        hv |= (uint64_t)zc_hdr_hash8(hv) << 56;
         __builtin_memcpy(slot, &hv, 8);
         // n_sequences, n_literals, enc_lit (0 raw / 1 RLE / 2 PivCo), enc_tok (0 / 2 PivCo), enc_mlen 0, enc_off
         uint32_t gh[3] = {seq_count, lit_count, (lit_huf ? 2u : (use_rle ? 1u : 0u)) | (tok_huf ? 2u << 8 : 0u) | ((uint32_t)(off8 ? 1u : 0u) << 24)};
@@ -889,8 +857,5 @@ zxc_gather_blocks_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride
     const uint8_t* s = slots + (uint64_t)b * slot_stride;
     uint8_t* d = out + offsets[b];
     const uint32_t n = sizes[b];
-    for (uint32_t o = 16u * lane; o < n; o += 1024u) {
-        if (o + 16u <= n) { const v4u t = e_ld128(s + o); __builtin_memcpy(d + o, &t, 16); }
-        else for (uint32_t k = o; k < n; k++) d[k] = s[k];
-    }
+    copy_bytes(d, s, n, (uint32_t)lane, 64u);
 }

@@ -133,7 +133,7 @@ zxc_frame_gather_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride,
     if (ctl->status < 0) return;
     const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
     for (uint64_t b = (uint64_t)blockIdx.x * waves + (threadIdx.x >> 6); b < nb; b += (uint64_t)gridDim.x * waves) {
-        zd_copy(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
+        copy_bytes(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
     }
 }
 

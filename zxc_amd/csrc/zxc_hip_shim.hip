@@ -8,49 +8,10 @@
 #include <stdlib.h>
 
 #include "../../include/zxc_error.h"
-#include "zxc_dev.h"
-
-extern "C" __global__ void zxc_decode_blocks_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
-                                                    uint8_t* out, int32_t* status, uint32_t block_size,
-                                                    uint32_t trailer_bytes, uint8_t* scratch, uint32_t scratch_stride, uint32_t dbg,
-                                                    uint32_t* slot_busy, uint32_t n_slots, const uint32_t* order,
-                                                    uint32_t cap_override, uint32_t* list);
-extern "C" __global__ void zxc_decode_blocks_lean_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
-                                                         uint8_t* out, int32_t* status, uint32_t block_size,
-                                                         const uint32_t* order, uint32_t cap_override, uint32_t trailer_bytes,
-                                                         const zxc_dev_pre_t* pre, uint8_t* rscratch);
-extern "C" __global__ void zxc_decode_blocks_lean_pre_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint8_t* out, int32_t* status,
-                                                             uint32_t block_size, uint32_t cap_override, uint32_t trailer_bytes,
-                                                             const zxc_dev_pre_t* pre, const uint8_t* pscratch, const uint32_t* hdr,
-                                                             const uint32_t* entries);
-extern "C" __global__ void zxc_rle_expand_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, zxc_dev_pre_t* pre, uint8_t* rscratch,
-                                                 const uint32_t* hdr, const uint32_t* entries_last);
-#define ZXC_SECTIONS_KERNEL(name)                                                                                              \
-    extern "C" __global__ void name(const uint8_t* comp, const zxc_dev_sec_t* secs, uint32_t* hdr, zxc_dev_pre_t* pre, uint8_t* pscratch)
-ZXC_SECTIONS_KERNEL(zxc_pivco_sections_small_kernel);
-ZXC_SECTIONS_KERNEL(zxc_pivco_sections_medium_kernel);
-ZXC_SECTIONS_KERNEL(zxc_pivco_sections_large_kernel);
-extern "C" __global__ void zxc_order_hist_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
-                                                 uint32_t block_size, uint32_t* hist);
-extern "C" __global__ void zxc_order_scatter_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
-                                                    uint32_t block_size, uint32_t* hist, uint32_t* order, uint32_t* list, uint32_t trailer_bytes,
-                                                    zxc_dev_pre_t* pre, uint32_t* ctl, uint32_t* pre_entries, zxc_dev_sec_t* secs,
-                                                    uint32_t pscratch_cap16, uint32_t cap, uint32_t rscratch_cap16);
-extern "C" __global__ void zxc_decode_blocks_dict_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
-                                                         uint8_t* out, int32_t* status, uint32_t block_size,
-                                                         uint32_t trailer_bytes, uint8_t* scratch, uint32_t scratch_stride,
-                                                         uint32_t dbg, uint32_t* slot_busy, uint32_t n_slots,
-                                                         const uint32_t* order, uint32_t cap_override, const uint8_t* dict,
-                                                         uint32_t dict_size, const uint8_t* dict_huf);
-
 #include "zxc_encode_levels.h"
-#define ZXC_ENCODE_DECL(name)                                                                                          \
-    extern "C" __global__ void name(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint8_t* slots,        \
-                                    uint32_t slot_stride, uint32_t* sizes, uint32_t n_blocks, uint32_t with_checksum,  \
-                                    uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,        \
-                                    uint8_t* huf_scratch, uint32_t huf);
+#include "zxc_kernels.h"  // every kernel launched here and its workgroup size; zxc_dev.h
+
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
-extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 extern "C" __attribute__((visibility("default"))) int zxc_mi355x_exp_enc_clocks(unsigned long long* out8) {
     unsigned long long* d = NULL;
     if (hipMalloc((void**)&d, 64) != hipSuccess) return -1;
@@ -60,19 +21,6 @@ extern "C" __attribute__((visibility("default"))) int zxc_mi355x_exp_enc_clocks(
     return e == hipSuccess ? 0 : -1;
 }
 #endif
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l1)
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l2)
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l3)
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l4)
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l57)
-ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l67)
-extern "C" __global__ void zxc_prepend_dict_kernel(const uint8_t* src, uint64_t src_size, uint32_t block_size, const uint8_t* dict,
-                                                   uint32_t dict_size, uint8_t* work, uint32_t n_blocks);
-extern "C" __global__ void zxc_block_checksum_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs, const uint32_t* order, uint8_t* ck_bad);
-extern "C" __global__ void zxc_checksum_merge_kernel(const uint8_t* ck_bad, int32_t* status, uint32_t n_jobs);
-extern "C" __global__ void zxc_block_offsets_kernel(uint32_t* sizes, uint64_t* offsets, uint32_t n_blocks, uint32_t max_size);
-extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32_t slot_stride, const uint32_t* sizes,
-                                                    const uint64_t* offsets, uint8_t* out, uint32_t n_blocks);
 
 // Per-device scratch for expanded literal / token sections: one slot per resident
 // workgroup. Grown on demand, never shrunk; freed at process exit by the driver.
@@ -385,11 +333,11 @@ static int enqueue_two_pass_pre(const Launch& L) {
     hipLaunchKernelGGL(zxc_decode_blocks_lean_kernel, dim3(L.n), dim3(64), 0, s1, L.comp, L.jobs, L.n, L.out, L.status, L.bs, L.order,
                        L.cap_override, L.plan.trailer_bytes, L.pre, L.rscratch);
     // (the small class runs beside the medium / large ones, on its own stream: +1 % level 7, +4 % level 6)
-    hipLaunchKernelGGL(zxc_pivco_sections_small_kernel, grid(10), dim3(128), 0, s2, L.comp, L.secs, sec_hdr, L.pre, L.pscratch);
+    hipLaunchKernelGGL(zxc_pivco_sections_small_kernel, grid(10), dim3(PDIR_SMALL_THREADS), 0, s2, L.comp, L.secs, sec_hdr, L.pre, L.pscratch);
     if (forked && hipEventRecord(o.small_done, s2) != hipSuccess) return fail(o);
     launch_full(L, s2, L.n < L.max_slots ? L.n : L.max_slots);
-    hipLaunchKernelGGL(zxc_pivco_sections_medium_kernel, grid(3), dim3(256), 0, s0, L.comp, L.secs + 2u * (size_t)L.n, sec_hdr + 2, L.pre, L.pscratch);
-    hipLaunchKernelGGL(zxc_pivco_sections_large_kernel, grid(2), dim3(512), 0, s0, L.comp, L.secs + 4u * (size_t)L.n, sec_hdr + 4, L.pre, L.pscratch);
+    hipLaunchKernelGGL(zxc_pivco_sections_medium_kernel, grid(3), dim3(PDIR_MEDIUM_THREADS), 0, s0, L.comp, L.secs + 2u * (size_t)L.n, sec_hdr + 2, L.pre, L.pscratch);
+    hipLaunchKernelGGL(zxc_pivco_sections_large_kernel, grid(2), dim3(PDIR_LARGE_THREADS), 0, s0, L.comp, L.secs + 4u * (size_t)L.n, sec_hdr + 4, L.pre, L.pscratch);
     if (forked && hipStreamWaitEvent(s0, o.small_done, 0) != hipSuccess) return fail(o);
     hipLaunchKernelGGL(zxc_decode_blocks_lean_pre_kernel, dim3(L.n), dim3(64), 0, s0, L.comp, L.jobs, L.out, L.status, L.bs,
                        L.cap_override, L.plan.trailer_bytes, L.pre, L.pscratch, L.ctl + ZXC_DEV_CTL_PRE, L.pre_entries);

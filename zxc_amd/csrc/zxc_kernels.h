@@ -1,0 +1,76 @@
+// zxc_kernels.h — every kernel that is launched from another translation unit, declared once. HIP only. Included by
+// zxc_hip_shim.hip, which launches them, AND by the files that define them (zxc_decode_kernel.hip with zxc_pivco_dir.inc,
+// zxc_encode_kernel.hip): the names are extern "C", so a definition whose argument list departs from the declaration here is a
+// conflicting redeclaration and does not compile, where two hand-kept copies would link and launch with a shifted argument
+// block. __launch_bounds__ stay on the definitions; the workgroup sizes the shim launches with are the ones below.
+#ifndef ZXC_KERNELS_H
+#define ZXC_KERNELS_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "zxc_dev.h"
+
+// threads of the three builds of the section decoder (zxc_pivco_dir.inc): launch bounds, loop strides and the shim's launches
+#define PDIR_SMALL_THREADS 128
+#define PDIR_MEDIUM_THREADS 256
+#define PDIR_LARGE_THREADS 512
+
+// ---------------------------------------------------------------- zxc_decode_kernel.hip
+extern "C" __global__ void zxc_decode_blocks_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
+                                                    uint8_t* out, int32_t* status, uint32_t block_size,
+                                                    uint32_t trailer_bytes, uint8_t* scratch, uint32_t scratch_stride, uint32_t dbg,
+                                                    uint32_t* slot_busy, uint32_t n_slots, const uint32_t* order,
+                                                    uint32_t cap_override, uint32_t* list);
+extern "C" __global__ void zxc_decode_blocks_dict_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
+                                                         uint8_t* out, int32_t* status, uint32_t block_size,
+                                                         uint32_t trailer_bytes, uint8_t* scratch, uint32_t scratch_stride,
+                                                         uint32_t dbg, uint32_t* slot_busy, uint32_t n_slots,
+                                                         const uint32_t* order, uint32_t cap_override, const uint8_t* dict,
+                                                         uint32_t dict_size, const uint8_t* dict_huf);
+extern "C" __global__ void zxc_decode_blocks_lean_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
+                                                         uint8_t* out, int32_t* status, uint32_t block_size,
+                                                         const uint32_t* order, uint32_t cap_override, uint32_t trailer_bytes,
+                                                         const zxc_dev_pre_t* pre, const uint8_t* rscratch);
+extern "C" __global__ void zxc_decode_blocks_lean_pre_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint8_t* out, int32_t* status,
+                                                             uint32_t block_size, uint32_t cap_override, uint32_t trailer_bytes,
+                                                             const zxc_dev_pre_t* pre, const uint8_t* pscratch, const uint32_t* hdr,
+                                                             const uint32_t* entries);
+extern "C" __global__ void zxc_rle_expand_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, zxc_dev_pre_t* pre, uint8_t* rscratch,
+                                                 const uint32_t* hdr, const uint32_t* entries_last);
+extern "C" __global__ void zxc_order_hist_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
+                                                 uint32_t block_size, uint32_t* hist);
+extern "C" __global__ void zxc_order_scatter_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs,
+                                                    uint32_t block_size, uint32_t* hist, uint32_t* order, uint32_t* list, uint32_t trailer_bytes,
+                                                    zxc_dev_pre_t* pre, uint32_t* ctl, uint32_t* pre_entries, zxc_dev_sec_t* secs,
+                                                    uint32_t pscratch_cap16, uint32_t cap, uint32_t rscratch_cap16);
+#define ZXC_SECTIONS_KERNEL(name)                                                                                              \
+    extern "C" __global__ void name(const uint8_t* comp, const zxc_dev_sec_t* secs, uint32_t* hdr, zxc_dev_pre_t* pre, uint8_t* pscratch)
+ZXC_SECTIONS_KERNEL(zxc_pivco_sections_small_kernel);
+ZXC_SECTIONS_KERNEL(zxc_pivco_sections_medium_kernel);
+ZXC_SECTIONS_KERNEL(zxc_pivco_sections_large_kernel);
+#undef ZXC_SECTIONS_KERNEL
+extern "C" __global__ void zxc_block_checksum_kernel(const uint8_t* comp, const zxc_dev_job_t* jobs, uint32_t n_jobs, const uint32_t* order, uint8_t* ck_bad);
+extern "C" __global__ void zxc_checksum_merge_kernel(const uint8_t* ck_bad, int32_t* status, uint32_t n_jobs);
+
+// ---------------------------------------------------------------- zxc_encode_kernel.hip
+#define ZXC_ENCODE_DECL(name)                                                                                          \
+    extern "C" __global__ void name(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint8_t* slots,        \
+                                    uint32_t slot_stride, uint32_t* sizes, uint32_t n_blocks, uint32_t with_checksum,  \
+                                    uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,        \
+                                    uint8_t* huf_scratch, uint32_t huf)
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l1);
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l2);
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l3);
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l4);
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l57);
+ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l67);
+#undef ZXC_ENCODE_DECL
+extern "C" __global__ void zxc_prepend_dict_kernel(const uint8_t* src, uint64_t src_size, uint32_t block_size, const uint8_t* dict,
+                                                   uint32_t dict_size, uint8_t* work, uint32_t n_blocks);
+extern "C" __global__ void zxc_block_offsets_kernel(uint32_t* sizes, uint64_t* offsets, uint32_t n_blocks, uint32_t max_size);
+extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32_t slot_stride, const uint32_t* sizes,
+                                                    const uint64_t* offsets, uint8_t* out, uint32_t n_blocks);
+#ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
+extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
+#endif
+#endif

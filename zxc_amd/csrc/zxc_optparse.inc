@@ -168,7 +168,7 @@ __device__ void opt_backtrack(const uint32_t* __restrict__ mp, uint32_t nblk, ui
         for (uint32_t i = lane; i <= pos - wb; i += 64u) win[i] = (wb + i) >= 1u ? mp[wb + i] : 0u;
         enc_lds_fence();
         while (pos > 0u && pos >= wb) {
-            const uint32_t e = e_uni(win[pos - wb]);
+            const uint32_t e = uni(win[pos - wb]);
             const uint32_t len = 0xFFFFu - (e >> 16);
             if (len == 0u) {
                 uint32_t run = e & 0xFFFFu;
@@ -201,7 +201,7 @@ __device__ bool opt_emit(const uint8_t* __restrict__ blk, const uint32_t* __rest
         const uint32_t w0 = (base >> 5) + 2u * (uint32_t)lane;
         uint32_t blo = w0 < n_words ? ends[w0] : 0u, bhi = w0 + 1u < n_words ? ends[w0 + 1u] : 0u;
         const uint32_t cnt = (uint32_t)__popc(blo) + (uint32_t)__popc(bhi);
-        const uint32_t incl = e_scan_add(cnt);
+        const uint32_t incl = wave_scan_add(cnt);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         uint32_t at = incl - cnt;
         while (blo) { list[at++] = base + 64u * (uint32_t)lane + (uint32_t)__builtin_ctz(blo); blo &= blo - 1u; }
@@ -221,9 +221,9 @@ __device__ bool opt_emit(const uint8_t* __restrict__ blk, const uint32_t* __rest
             const uint32_t mlm = has ? L - 5u : 0u;
             uint32_t eb = 0;
             if (has) eb = (ll >= 15u ? varint_len(ll - 15u) : 0u) + (mlm >= 15u ? varint_len(mlm - 15u) : 0u);
-            const uint32_t eincl = e_scan_add(eb);
+            const uint32_t eincl = wave_scan_add(eb);
             const uint32_t etot = (uint32_t)__builtin_amdgcn_readlane((int)eincl, 63);
-            const uint32_t lincl = e_scan_add(ll);
+            const uint32_t lincl = wave_scan_add(ll);
             const uint32_t ltot = (uint32_t)__builtin_amdgcn_readlane((int)lincl, 63);
             if (seq_count + nsel > max_seq || ext_count + etot > ext_cap) return false;
             if (has) {
@@ -245,7 +245,7 @@ __device__ bool opt_emit(const uint8_t* __restrict__ blk, const uint32_t* __rest
                 const bool fastok = has && prev_end + 32u <= nblk;
                 const uint8_t* sp = blk + (fastok ? prev_end : 0u);
                 const bool shortrun = fastok && ll != 0u && ll <= 32u;
-                const v4u a0 = e_ld128(nblk >= 32u ? sp : blk), a1 = e_ld128(nblk >= 32u ? sp + 16 : blk);
+                const v4u a0 = ld128(nblk >= 32u ? sp : blk), a1 = ld128(nblk >= 32u ? sp + 16 : blk);
                 const uint32_t wv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
                 for (uint32_t k = 0; k < 32u; k++) {

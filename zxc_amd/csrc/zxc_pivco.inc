@@ -49,9 +49,6 @@ struct PivLds {  // overlays WaveLds (the ring is idle while a section is being 
     uint32_t ib[PIV_MAXLEN + 2];     // index of the first internal node of a depth
 };
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v, int lane) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(v, lane), 63);
-}
 __device__ __forceinline__ uint32_t nt_ld8(const uint8_t* p) { return __builtin_nontemporal_load(p); }
 // The same through a pointer the compiler knows to be global memory: inside this out-of-line function the
 // buffers are generic pointers, i.e. FLAT accesses, which count against both vmcnt and lgkmcnt and make every
@@ -63,9 +60,8 @@ __device__ __forceinline__ void g_st8(uint8_t* p, uint32_t v) { *(gptr_t)(uintpt
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 typedef const u32_unaligned __attribute__((address_space(1))) * gcptr32_t;
 typedef u32_unaligned __attribute__((address_space(1))) * gptr32_t;
-typedef v4u __attribute__((aligned(1))) v4u_una;
 typedef uint64_t __attribute__((aligned(1))) u64_una;
-__device__ __forceinline__ v4u g_ld128(const uint8_t* p) { return *(const v4u_una __attribute__((address_space(1)))*)(uintptr_t)p; }
+__device__ __forceinline__ v4u g_ld128(const uint8_t* p) { return *(const v4u_unaligned __attribute__((address_space(1)))*)(uintptr_t)p; }
 __device__ __forceinline__ uint64_t g_ld64(const uint8_t* p) { return *(const u64_una __attribute__((address_space(1)))*)(uintptr_t)p; }
 __device__ __forceinline__ uint32_t g_nt_ld32(const uint8_t* p) { return __builtin_nontemporal_load((gcptr32_t)(uintptr_t)p); }
 __device__ __forceinline__ void g_st32(uint8_t* p, uint32_t v) { *(gptr32_t)(uintptr_t)p = v; }
@@ -126,7 +122,7 @@ __device__ __forceinline__ void piv_level(PivLds& P, int d, const uint8_t* __res
         const uint32_t nro = nnf & 0xFFFFFFu;
         const uint32_t nso = nemit ? P.seqoff[nii] : 0u;
         const uint32_t ncs = nc <= 64u ? nc : 0u;
-        const uint32_t nincl = wave_scan_add(ncs, lane);
+        const uint32_t nincl = wave_scan_add(ncs);
         const uint32_t ntotal = (uint32_t)__builtin_amdgcn_readlane((int)nincl, 63);
         // every small bitmap node's whole run (<= 64 bits) is fetched once by the node's lane: the steps below take it
         // from that lane's registers (two cross-lane reads) instead of a memory round trip per step
@@ -428,7 +424,7 @@ __device__ __forceinline__ int piv_tree(const uint8_t* __restrict__ lens128, PL&
 #pragma unroll
     for (int l = 1; l <= PIV_MAXLEN; l++) {
         const uint32_t mine = (myl[0] == (uint32_t)l) + (myl[1] == (uint32_t)l) + (myl[2] == (uint32_t)l) + (myl[3] == (uint32_t)l);
-        const uint32_t incl = wave_scan_add(mine, lane);
+        const uint32_t incl = wave_scan_add(mine);
         const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         blc[l] = tot;
         if (tot) maxlen = l;
@@ -549,7 +545,7 @@ __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, 
             const uint32_t c = emit ? P.cnt[ii] : 0u;
             const uint32_t D = emit ? ((nf >> 24) & 15u) : 0u;
             const uint32_t nbytes = emit ? (D ? (uint32_t)(((uint64_t)c * D + 7u) >> 3) : ((c + 7u) >> 3)) : 0u;
-            const uint32_t incl = wave_scan_add(nbytes, lane);
+            const uint32_t incl = wave_scan_add(nbytes);
             const uint32_t ro = pcur + incl - nbytes;
             if (__ballot(emit && (ro > bsize || nbytes > bsize - ro))) return E_CORRUPT;
             if (emit) P.runoff[ii] = nf | ro;
@@ -606,7 +602,7 @@ __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, 
                         part += __popcll(x[t] & (left >= 64u ? ~0ull : ((1ull << left) - 1ull)));
                     }
                 }
-                const uint32_t tot = wave_sum(part, lane);
+                const uint32_t tot = wave_sum(part);
                 if (lane == bl) ones = tot;
             }
             if (bitmap) {  // children 2j, 2j+1 of depth d+1: only internal ones keep a count
@@ -627,7 +623,7 @@ __device__ __forceinline__ int piv_prepare(const uint8_t* __restrict__ payload, 
             const uint32_t ii = Bi + (j < Id ? j : 0u);
             const bool emit = j < Id && !(P.runoff[ii] & 0x80000000u);
             const uint32_t c = emit ? P.cnt[ii] : 0u;
-            const uint32_t incl = wave_scan_add(c, lane);
+            const uint32_t incl = wave_scan_add(c);
             if (emit) P.seqoff[ii] = acc + incl - c;
             acc += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         }

@@ -27,11 +27,8 @@
 
 #define PDIR_N_MAX 65535u  // symbols per section (16-bit ranks)
 #define PDIR_BODY_OF(THREADS, ITERS) (8u * ((uint32_t)(ITERS) * ((uint32_t)(THREADS) - 64u) - 1u))
-#define PDIR_SMALL_THREADS 128
-#define PDIR_SMALL_ITERS 16
-#define PDIR_MEDIUM_THREADS 256
+#define PDIR_SMALL_ITERS 16  // (PDIR_*_THREADS: zxc_kernels.h, the shim launches with them)
 #define PDIR_MEDIUM_ITERS 24
-#define PDIR_LARGE_THREADS 512
 #define PDIR_LARGE_ITERS 16
 #define PDIR_SMALL_BODY PDIR_BODY_OF(PDIR_SMALL_THREADS, PDIR_SMALL_ITERS)      //  8184 bytes of section body
 #define PDIR_MEDIUM_BODY PDIR_BODY_OF(PDIR_MEDIUM_THREADS, PDIR_MEDIUM_ITERS)   // 36856
@@ -87,7 +84,7 @@ __device__ __forceinline__ int pdir_pass1(PL& P, int lane, uint32_t n, uint32_t 
             const uint32_t c = emit ? P.cnt[ii] : 0u;
             const uint32_t D = emit ? ((nf >> 24) & 15u) : 0u;
             const uint32_t nbytes = emit ? (D ? (uint32_t)(((uint64_t)c * D + 7u) >> 3) : ((c + 7u) >> 3)) : 0u;
-            const uint32_t incl = wave_scan_add(nbytes, lane);
+            const uint32_t incl = wave_scan_add(nbytes);
             const uint32_t ro = pcur + incl - nbytes;
             if (__ballot(emit && (ro > bsize || nbytes > bsize - ro))) return E_CORRUPT;
             pcur += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -121,7 +118,7 @@ __device__ __forceinline__ void pdir_tables(PL& P, int lane, uint32_t maxlen, ui
             const uint32_t nf = P.runoff[Bi + (have ? j : 0u)];  // (wave 0 is filling in the offset bits meanwhile: the flags do not change)
             const uint32_t D = (have && !(nf & 0x80000000u)) ? ((nf >> 24) & 15u) : 0u;
             const uint32_t size = D ? 1u << D : 0u;
-            const uint32_t incl = wave_scan_add(size, lane);
+            const uint32_t incl = wave_scan_add(size);
             const uint32_t base = tb + incl - size;
             if (D && tw == 0u) P.c2sb[Bi + j] = (uint16_t)base;
             tb += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -226,7 +223,7 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
                     for (uint32_t k = 0; 8u * i + k < bsize; k++) w |= (uint64_t)ld8(body + 8u * i + k) << (8u * k);
                 P.W[i] = w;
                 const uint32_t pc = (uint32_t)__popcll(w);
-                const uint32_t incl = wave_scan_add(pc, lane);
+                const uint32_t incl = wave_scan_add(pc);
                 excl[it] = incl - pc;
                 if (lane == 63) P.wsum[(uint32_t)it * PL::kSlices + (wave - 1u)] = incl;
             }
@@ -238,7 +235,7 @@ __device__ __forceinline__ int pdir_decode(const uint8_t* __restrict__ payload_,
         for (uint32_t c0 = 0; c0 < nit * PL::kSlices; c0 += 64u) {
             const uint32_t idx = c0 + (uint32_t)lane;
             const uint32_t v = idx < nit * PL::kSlices ? P.wsum[idx] : 0u;
-            const uint32_t incl = wave_scan_add(v, lane);
+            const uint32_t incl = wave_scan_add(v);
             if (idx < nit * PL::kSlices) P.wsum[idx] = carry + incl - v;
             carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         }

@@ -36,18 +36,7 @@ __device__ __forceinline__ void pe_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
 }
-__device__ __forceinline__ uint32_t pe_scan_add(uint32_t v) { return e_scan_add(v); }
 __device__ __forceinline__ uint32_t pe_total(uint32_t incl) { return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63); }
-// wave-wide minimum of 64-bit keys (every lane gets it)
-__device__ __forceinline__ uint64_t pe_wave_min(uint64_t k) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)k, d), hi = __shfl_xor((uint32_t)(k >> 32), d);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        k = o < k ? o : k;
-    }
-    return k;
-}
 
 // Encodes sym[0..n) into out (128-byte length table + runs). tmpA / tmpB: n bytes of scratch each. Returns the section
 // size, or 0 when it would not be smaller than `budget` bytes (nothing usable is written then).
@@ -69,7 +58,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
     uint32_t mine_present = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { myf[k] = P.freq[4 * lane + k]; mine_present += myf[k] != 0u; }
-    const uint32_t present = pe_total(pe_scan_add(mine_present));
+    const uint32_t present = wave_sum(mine_present);
     uint32_t myl[4] = {0, 0, 0, 0};
     if (present == 1u) {
         // degenerate table: one symbol of code length 1, the root's run is n zero bits (docs/FORMAT.md §5.2.1)
@@ -99,7 +88,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
                 const uint64_t key = ((uint64_t)P.weight[i] << 16) | i;
                 best = key < best ? key : best;
             }
-            best = pe_wave_min(best);
+            best = wave_min(best);
             const uint32_t idx = (uint32_t)best & 0xFFFFu;
             wsum += (uint32_t)(best >> 16);
             if (lane == 0) {
@@ -131,7 +120,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
                 uint32_t s = 0;
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (myl[k]) s += 1u << (PE_MAXLEN - myl[k]);
-                return pe_total(pe_scan_add(s));
+                return wave_sum(s);
             };
             uint32_t K = kraft();
             while (K > (1u << PE_MAXLEN)) {  // lengthen the deepest code that is not at the limit (rarest first)
@@ -142,7 +131,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
                         const uint64_t key = ((uint64_t)(PE_MAXLEN - myl[k]) << 48) | ((uint64_t)myf[k] << 16) | (4u * lane + k);
                         best = key < best ? key : best;
                     }
-                best = pe_wave_min(best);
+                best = wave_min(best);
                 const uint32_t idx = (uint32_t)best & 0xFFFFu;
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (4u * (uint32_t)lane + (uint32_t)k == idx) myl[k]++;
@@ -157,7 +146,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
                         const uint64_t key = ((uint64_t)(0xFFFFFFFFu - myf[k]) << 16) | (4u * lane + k);
                         best = key < best ? key : best;
                     }
-                best = pe_wave_min(best);  // (a code at the limit always fits a slack >= 1, so one is found)
+                best = wave_min(best);  // (a code at the limit always fits a slack >= 1, so one is found)
                 const uint32_t idx = (uint32_t)best & 0xFFFFu;
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (4u * (uint32_t)lane + (uint32_t)k == idx) myl[k]--;
@@ -176,7 +165,7 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
 #pragma unroll
     for (int l = 1; l <= PE_MAXLEN; l++) {
         const uint32_t mine = (myl[0] == (uint32_t)l) + (myl[1] == (uint32_t)l) + (myl[2] == (uint32_t)l) + (myl[3] == (uint32_t)l);
-        const uint32_t incl = pe_scan_add(mine);
+        const uint32_t incl = wave_scan_add(mine);
         const uint32_t tot = pe_total(incl);
         blc[l] = tot;
         if (tot) maxlen = l;
@@ -255,10 +244,10 @@ __device__ uint32_t pivco_encode(const uint8_t* __restrict__ sym, uint32_t n, ui
             const uint32_t c = emit ? P.cnt[ii] : 0u;
             const uint32_t D = (nf >> 24) & 15u;
             const uint32_t nbytes = emit ? (D ? (uint32_t)(((uint64_t)c * D + 7u) >> 3) : ((c + 7u) >> 3)) : 0u;
-            const uint32_t incl = pe_scan_add(nbytes);
+            const uint32_t incl = wave_scan_add(nbytes);
             if (emit) P.runoff[ii] = nf | (pcur + incl - nbytes);
             pcur += pe_total(incl);
-            const uint32_t sincl = pe_scan_add(c);
+            const uint32_t sincl = wave_scan_add(c);
             if (emit) P.seqoff[ii] = acc + sincl - c;
             acc += pe_total(sincl);
         }

@@ -4,16 +4,6 @@
 // seven independent 16-byte lanes per 112-byte stripe — here literally seven SIMD lanes, each
 // carrying one accumulator (the algorithm has no more parallelism than that: every accumulator is a
 // serial chain over the stripes); the <= 112-byte tail and the finaliser run wave-uniform.
-__device__ __forceinline__ uint64_t rh_ld64(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-__device__ __forceinline__ uint64_t rh_ld32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 __device__ __forceinline__ uint64_t rh_mix(uint64_t a, uint64_t b) { return (a * b) ^ __umul64hi(a, b); }
 
 __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len, int lane) {
@@ -25,8 +15,8 @@ __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len,
     if (len <= 16u) {
         if (len >= 4u) {
             seed ^= len;
-            if (len >= 8u) { a = rh_ld64(p); b = rh_ld64(p + len - 8); }
-            else { a = rh_ld32(p); b = rh_ld32(p + len - 4); }
+            if (len >= 8u) { a = ld64(p); b = ld64(p + len - 8); }
+            else { a = ld32(p); b = ld32(p + len - 4); }
         } else if (len > 0u) {
             a = ((uint64_t)p[0] << 45) | p[len - 1];
             b = p[len >> 1];
@@ -46,11 +36,11 @@ __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len,
                 for (; t + 8u <= T; t += 8u, q += 896) {
                     uint64_t lo[8], hi[8];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) { lo[j] = rh_ld64(q + 112 * j); hi[j] = rh_ld64(q + 112 * j + 8); }
+                    for (int j = 0; j < 8; j++) { lo[j] = ld64(q + 112 * j); hi[j] = ld64(q + 112 * j + 8); }
 #pragma unroll
                     for (int j = 0; j < 8; j++) s = rh_mix(lo[j] ^ sk, hi[j] ^ s);
                 }
-                for (; t < T; t++, q += 112) s = rh_mix(rh_ld64(q) ^ sk, rh_ld64(q + 8) ^ s);
+                for (; t < T; t++, q += 112) s = rh_mix(ld64(q) ^ sk, ld64(q + 8) ^ s);
             }
             uint64_t x = (lane < 7) ? s : 0ull;  // seed ^= see1..see6 (all seven XORed together)
 #pragma unroll
@@ -64,23 +54,23 @@ __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len,
             i -= 112ull * T;
         }
         if (i > 16) {
-            seed = rh_mix(rh_ld64(p) ^ S[2], rh_ld64(p + 8) ^ seed);
+            seed = rh_mix(ld64(p) ^ S[2], ld64(p + 8) ^ seed);
             if (i > 32) {
-                seed = rh_mix(rh_ld64(p + 16) ^ S[2], rh_ld64(p + 24) ^ seed);
+                seed = rh_mix(ld64(p + 16) ^ S[2], ld64(p + 24) ^ seed);
                 if (i > 48) {
-                    seed = rh_mix(rh_ld64(p + 32) ^ S[1], rh_ld64(p + 40) ^ seed);
+                    seed = rh_mix(ld64(p + 32) ^ S[1], ld64(p + 40) ^ seed);
                     if (i > 64) {
-                        seed = rh_mix(rh_ld64(p + 48) ^ S[1], rh_ld64(p + 56) ^ seed);
+                        seed = rh_mix(ld64(p + 48) ^ S[1], ld64(p + 56) ^ seed);
                         if (i > 80) {
-                            seed = rh_mix(rh_ld64(p + 64) ^ S[2], rh_ld64(p + 72) ^ seed);
-                            if (i > 96) seed = rh_mix(rh_ld64(p + 80) ^ S[1], rh_ld64(p + 88) ^ seed);
+                            seed = rh_mix(ld64(p + 64) ^ S[2], ld64(p + 72) ^ seed);
+                            if (i > 96) seed = rh_mix(ld64(p + 80) ^ S[1], ld64(p + 88) ^ seed);
                         }
                     }
                 }
             }
         }
-        a = rh_ld64(p + i - 16) ^ i;
-        b = rh_ld64(p + i - 8);
+        a = ld64(p + i - 16) ^ i;
+        b = ld64(p + i - 8);
     }
     a ^= S[1];
     b ^= seed;
@@ -90,7 +80,6 @@ __device__ uint32_t wave_checksum32(const uint8_t* __restrict__ p, uint32_t len,
 }
 
 // ------------------------------------------------------------------ nine blocks per wavefront (round 6)
-typedef uint32_t rh_v4u __attribute__((ext_vector_type(4)));
 #define RH_GROUP_DEPTH 8   // stripes of loads in flight per lane. (Round 6 also tried to fit the kernel BESIDE six lean waves per SIMD — 32 VGPRs: depth 1
                            // still needs 34-36, one granule too many — so its waves take the place of decode waves while they run.)
 // The bulk loop has seven accumulators per block and no more: hashed inside the decode kernels, 57 of a wave's 64 lanes idle through
@@ -136,18 +125,18 @@ __device__ __forceinline__ uint32_t group_checksum32(const uint8_t* __restrict__
 #define RH_FIRST (lane - sub)
 #define RH_R (ph & 3u)
         for (uint32_t t = 0; t < Tmax; t += RH_GROUP_DEPTH) {
-            rh_v4u A[RH_GROUP_DEPTH + 1];
+            v4u A[RH_GROUP_DEPTH + 1];
 #pragma unroll
             for (int j = 0; j < RH_GROUP_DEPTH + 1; j++) {
                 // (stripe T = the chunk behind the bulk loop's last byte: only the group's first lane needs it, and its 16 bytes end at most
                 //  15 bytes behind the payload; every other lane stays inside the bulk loop's bytes)
                 const uint32_t tend = sub == 0 ? T : T - 1u;
                 const uint32_t tj = t + (uint32_t)j < tend ? t + (uint32_t)j : tend;
-                A[j] = T ? *(const rh_v4u*)(pa + 112ull * tj) : (rh_v4u){0, 0, 0, 0};
+                A[j] = T ? *(const v4u*)(pa + 112ull * tj) : (v4u){0, 0, 0, 0};
             }
 #pragma unroll
             for (int j = 0; j < RH_GROUP_DEPTH; j++) {
-                rh_v4u B;  // the chunk behind mine
+                v4u B;  // the chunk behind mine
                 {
                     const uint32_t n0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)A[j].x, 0x130, 0xf, 0xf, false), n1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)A[j].y, 0x130, 0xf, 0xf, false),
                                    n2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)A[j].z, 0x130, 0xf, 0xf, false), n3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)A[j].w, 0x130, 0xf, 0xf, false);  // wave_shl:1
@@ -174,31 +163,31 @@ __device__ __forceinline__ uint32_t group_checksum32(const uint8_t* __restrict__
     if (len <= 16u) {
         if (len >= 4u) {
             seed ^= len;
-            if (len >= 8u) { a = rh_ld64(p); b = rh_ld64(p + len - 8); }
-            else { a = rh_ld32(p); b = rh_ld32(p + len - 4); }
+            if (len >= 8u) { a = ld64(p); b = ld64(p + len - 8); }
+            else { a = ld32(p); b = ld32(p + len - 4); }
         } else if (len > 0u) {
             a = ((uint64_t)p[0] << 45) | p[len - 1];
             b = p[len >> 1];
         }
     } else {
         if (i > 16) {
-            seed = rh_mix(rh_ld64(p) ^ S[2], rh_ld64(p + 8) ^ seed);
+            seed = rh_mix(ld64(p) ^ S[2], ld64(p + 8) ^ seed);
             if (i > 32) {
-                seed = rh_mix(rh_ld64(p + 16) ^ S[2], rh_ld64(p + 24) ^ seed);
+                seed = rh_mix(ld64(p + 16) ^ S[2], ld64(p + 24) ^ seed);
                 if (i > 48) {
-                    seed = rh_mix(rh_ld64(p + 32) ^ S[1], rh_ld64(p + 40) ^ seed);
+                    seed = rh_mix(ld64(p + 32) ^ S[1], ld64(p + 40) ^ seed);
                     if (i > 64) {
-                        seed = rh_mix(rh_ld64(p + 48) ^ S[1], rh_ld64(p + 56) ^ seed);
+                        seed = rh_mix(ld64(p + 48) ^ S[1], ld64(p + 56) ^ seed);
                         if (i > 80) {
-                            seed = rh_mix(rh_ld64(p + 64) ^ S[2], rh_ld64(p + 72) ^ seed);
-                            if (i > 96) seed = rh_mix(rh_ld64(p + 80) ^ S[1], rh_ld64(p + 88) ^ seed);
+                            seed = rh_mix(ld64(p + 64) ^ S[2], ld64(p + 72) ^ seed);
+                            if (i > 96) seed = rh_mix(ld64(p + 80) ^ S[1], ld64(p + 88) ^ seed);
                         }
                     }
                 }
             }
         }
-        a = rh_ld64(p + i - 16) ^ i;
-        b = rh_ld64(p + i - 8);
+        a = ld64(p + i - 16) ^ i;
+        b = ld64(p + i - 8);
     }
     a ^= S[1];
     b ^= seed;

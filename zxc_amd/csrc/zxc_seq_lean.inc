@@ -141,8 +141,8 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
 
         // cursors: inclusive scans of (ll+ml) and ll
         uint32_t len = ll + ml;
-        const uint32_t Ei = wave_scan_add(len, lane);
-        const uint32_t Li = wave_scan_add(ll, lane);
+        const uint32_t Ei = wave_scan_add(len);
+        const uint32_t Li = wave_scan_add(ll);
         const uint32_t est = p + (Ei - len);  // where this sequence's literals land
         const uint32_t lst = lp + (Li - ll);  // its first literal
         const bool bad_off = real && off > est + ll;

@@ -138,7 +138,7 @@ zxc_unframe_tail_kernel(const uint8_t* __restrict__ stage, const int32_t* __rest
     const uint32_t i = k_direct + blockIdx.x;
     if (ctl->final || i >= n_jobs) return;
     const uint32_t n = zc_tail_bytes(i, status[(uint64_t)ctl->sel * n_jobs + i], block_size, dst_capacity);
-    zd_copy(dst + (uint64_t)i * block_size, stage + (uint64_t)blockIdx.x * block_size, n, threadIdx.x, 256u);
+    copy_bytes(dst + (uint64_t)i * block_size, stage + (uint64_t)blockIdx.x * block_size, n, threadIdx.x, 256u);
 }
 
 // The first block, in archive order, whose status ends the call: zc_block_event is local to a block as long as no earlier block has

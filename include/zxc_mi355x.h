@@ -319,6 +319,78 @@ ZXC_EXPORT int zxc_mi355x_decompress_ranges_dict_device(const void* d_src, uint6
                                                         const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size,
                                                         int64_t* d_results, void* stream);
 
+/* ---- many archives per call, device to device (zxc_amd/csrc/zxc_batch_device.hip, rules in zxc_amd/csrc/zxc_batch.h) ----
+ * zxc_mi355x_decompress_device for many small, independent archives that already live in device memory (cache pages, shards,
+ * column chunks, records compressed against one dictionary): one archive of a few blocks cannot fill the device and costs about
+ * ten launches, a few thousand in one call cost four passes. The archives lie in one source area, the decoded bytes go to one
+ * destination area, and a table in device memory says where each one lies and goes. */
+
+/* One archive to decode (32 bytes, device-visible layout). */
+typedef struct zxc_dev_item {
+    uint64_t src_off;      /* the archive is d_src[src_off, src_off + src_size) */
+    uint64_t src_size;
+    uint64_t dst_off;      /* decoded bytes go to d_dst + dst_off, any alignment */
+    uint64_t dst_capacity; /* at most this many */
+} zxc_dev_item_t;
+
+/* Bytes of device scratch the call below needs; 0 for arguments it would refuse (block_size, n_items x J > 2^31 - 2). Does not
+ * depend on opts. The host never sees the items, only the promise that none decodes to more than max_capacity bytes: the call
+ * launches J = ceil(max_capacity / block_size) + 1 jobs per item (the n_max + 1 of zxc_mi355x_decompress_device, for the same
+ * reason), and every job has a slot of its own. The size is at most
+ * n_items x J x (block_size + 64) + 56 x n_items x J + 128 x n_items + 1536: the slots, two job tables and two status tables
+ * (see checksum_enabled below), a record per item. That is the price of not knowing the items on the host; keep it down with a
+ * tight max_capacity. */
+ZXC_EXPORT uint64_t zxc_mi355x_decompress_batch_device_work_size(uint32_t n_items, uint64_t max_capacity, uint32_t block_size);
+
+/* For r in [0, n_items): the complete v8 archive d_src[src_off_r, src_off_r + src_size_r) is decoded to d_dst + dst_off_r,
+ * asynchronously on `stream`; d_results[r] (device memory) receives, once, after that item's last byte, what zxc_decompress
+ * returns for the same bytes, options and the capacity cap_r = min(dst_capacity_r, max_capacity, dst_capacity - dst_off_r) (0 when
+ * dst_off_r > dst_capacity): the decoded size or the negative zxc_error_t, with the precedence zxc_mi355x_decompress_device
+ * documents (file header; the first failing block in archive order; a bad block header only behind decoded blocks;
+ * DST_TOO_SMALL; footer size; global hash). cap_r == 0 is the empty-frame probe. That call's two departures hold per item: a
+ * header block size other than block_size is ZXC_ERROR_BAD_BLOCK_SIZE, an irregular frame ZXC_ERROR_GPU_UNSUPPORTED. Two more,
+ * decided on the device with nothing read for the item: src_size_r < 28 -> ZXC_ERROR_SRC_TOO_SMALL; src_off_r + src_size_r >
+ * src_capacity (compared without overflow) -> ZXC_ERROR_SRC_TOO_SMALL. An archive written with a dictionary is
+ * ZXC_ERROR_DICT_REQUIRED here (zxc_mi355x_decompress_batch_dict_device below takes one).
+ * d_items lies in device memory and is read on the stream: a kernel enqueued before the call may write it, a replayed graph may
+ * see other items each time. One thread per item walks that item's block headers, as zxc_decompress does (a seek table is not
+ * looked at), for at most ceil(cap_r / block_size) + 1 blocks; all items' blocks are decoded by one launch behind
+ * zxc_mi355x_decode_blocks_device. An archive of many blocks belongs in zxc_mi355x_decompress_device: here its walk is serial,
+ * and every item pays for J job slots, of which the unused ones cost a wavefront that exits at once.
+ * opts may be NULL; only checksum_enabled and dict are read. opts->checksum_enabled verifies per item, when that item's header
+ * carries checksums: every block's trailer by the decode launch, the footer's global hash folded while the headers are walked.
+ * Items with and without checksums may be mixed: such a call enqueues the decode launch over two job tables, of which each item
+ * fills one.
+ * Synchronous errors, in this order, before any device is touched: NULL d_src / d_work / d_results, NULL d_items with
+ * n_items > 0, NULL d_dst with dst_capacity > 0 -> ZXC_ERROR_NULL_INPUT; block_size not a power of two in [4 KiB, 2 MiB] ->
+ * ZXC_ERROR_BAD_BLOCK_SIZE; opts->dict != NULL -> ZXC_ERROR_GPU_UNSUPPORTED; d_dst not 16-byte aligned ->
+ * ZXC_ERROR_GPU_UNSUPPORTED; n_items x J above 2^31 - 2, or work_size too small -> ZXC_ERROR_MEMORY; n_items == 0 is ZXC_OK
+ * here and enqueues nothing; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE.
+ * Guarantees: nothing is written outside [dst_off_r, dst_off_r + cap_r) of each item and d_work (a block is decoded straight
+ * into d_dst only when its place d_dst + dst_off_r + i x block_size is 16-byte aligned and (i + 1) x block_size + 32 <= cap_r;
+ * every other block goes through its slot of d_work and a copy of min(decoded size, capacity left) bytes). An item that fails
+ * leaves its own destination bytes undefined and every other item untouched. Items whose destinations overlap are the caller's
+ * error: undefined bytes, no fault. d_src must be READABLE up to src_capacity + 64 (as d_comp of
+ * zxc_mi355x_decode_blocks_device) and is never written. No host synchronisation and no device allocation of its own (the decode
+ * launch keeps its per-stream buffers as it does for zxc_mi355x_decode_blocks_device). d_work: any alignment, owned by the call
+ * until the last result is written. Calls on different streams with different work areas may overlap. */
+ZXC_EXPORT int zxc_mi355x_decompress_batch_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                                  uint32_t n_items, uint64_t max_capacity, void* d_dst, uint64_t dst_capacity,
+                                                  uint32_t block_size, const zxc_decompress_opts_t* opts, void* d_work,
+                                                  uint64_t work_size, int64_t* d_results, void* stream);
+
+/* The call above with a dictionary in device memory that the whole batch shares: same contract and work size. Per item, behind
+ * the file-header errors and the block-size departure: a header with a dictionary id gives ZXC_ERROR_DICT_REQUIRED without a
+ * dictionary and ZXC_ERROR_DICT_MISMATCH with one whose *d_id differs, and no block of that item is decoded; a dictionary given
+ * to an item written without one is handed to the decoder all the same, as the host does. Synchronous errors: the sibling's,
+ * with dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE and NULL d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT behind
+ * the opts->dict check. */
+ZXC_EXPORT int zxc_mi355x_decompress_batch_dict_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                                       uint32_t n_items, uint64_t max_capacity, void* d_dst,
+                                                       uint64_t dst_capacity, uint32_t block_size,
+                                                       const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict,
+                                                       void* d_work, uint64_t work_size, int64_t* d_results, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ _LIB = None
 JOB_DTYPE = np.dtype([("comp_off", "<u8"), ("out_off", "<u8"), ("comp_size", "<u4"), ("out_len", "<u4")])
 # zxc_dev_range_t (include/zxc_mi355x.h)
 RANGE_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("dst_off", "<u8")])
+# zxc_dev_item_t (include/zxc_mi355x.h)
+ITEM_DTYPE = np.dtype([("src_off", "<u8"), ("src_size", "<u8"), ("dst_off", "<u8"), ("dst_capacity", "<u8")])
 
 
 class ZxcError(RuntimeError):
@@ -430,6 +432,51 @@ def decompress_ranges_dict_device(d_src, src_size, d_index, d_ranges, n_ranges, 
         C.c_void_p(d_results or None), C.c_void_p(stream or None))
     if rc < 0:
         raise ZxcError(rc, "zxc_mi355x_decompress_ranges_dict_device")
+
+
+# ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)
+def _bind_decompress_batch_device(L):
+    L.zxc_mi355x_decompress_batch_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_decompress_batch_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
+    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_DecompressOpts)]
+    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_decompress_batch_device.restype = C.c_int
+    L.zxc_mi355x_decompress_batch_device.argtypes = head + tail
+    L.zxc_mi355x_decompress_batch_dict_device.restype = C.c_int
+    L.zxc_mi355x_decompress_batch_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
+    return L
+
+
+def decompress_batch_device_work_size(n_items, max_capacity, block_size):
+    """zxc_mi355x_decompress_batch_device_work_size(): bytes of device scratch the call needs (0 for refused arguments)."""
+    return int(_bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_device_work_size(n_items, max_capacity, block_size))
+
+
+def decompress_batch_device(d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity, block_size, d_work, work_size,
+                            d_results, checksum=False, stream=0):
+    """zxc_mi355x_decompress_batch_device(): raw device pointers (ints); d_items is n_items x ITEM_DTYPE in device memory, d_results
+    n_items x int64, each what zxc_decompress would return for that item. Asynchronous on `stream`; a synchronous failure raises
+    ZxcError."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    rc = _bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_capacity, C.c_void_p(d_dst or None),
+        dst_capacity, block_size, C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
+        C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_batch_device")
+
+
+def decompress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity, block_size, dict_, d_work,
+                                 work_size, d_results, checksum=False, stream=0):
+    """zxc_mi355x_decompress_batch_dict_device(): decompress_batch_device with one dictionary in device memory for the whole batch
+    (dict_ as in compress_dict_device); the work size is the sibling's."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    rc = _bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_dict_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_capacity, C.c_void_p(d_dst or None),
+        dst_capacity, block_size, C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
+        C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_batch_dict_device")
 
 
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.

@@ -1,6 +1,7 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_dict_device.hip): the three tile passes every container stage is made of and the host-side plumbing of an entry point.
-// HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h.
+// zxc_batch_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
+// slot and the host-side plumbing of an entry point.
+// HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h.
 //
 // A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
 // blocks per thread. Every helper with a barrier in it is called by all threads of the workgroup, outside divergent control flow.
@@ -94,6 +95,28 @@ __device__ __forceinline__ zd_totals zd_scan_tiles(uint32_t n_tiles, uint64_t ba
         run += s;
     }
     return r;
+}
+
+// ---------------------------------------------------------------- staged slot -> destination
+#define ZD_COPY_CHUNK 8192u  // destination bytes one wavefront moves (ZB_COPY_CHUNK)
+
+// One wavefront's part of the copy s[0, n) -> d[0, n), d of any alignment: chunk k is the part whose destination addresses lie in
+// [A + k CHUNK, A + (k + 1) CHUNK), A = d rounded down to 16. A lane moves 16-byte units of the destination: an aligned 16-byte
+// store fed by a 16-byte load of any alignment from the slot, bytes where the unit passes the copy's ends. (The loop of
+// zxc_ranges_copy_kernel, which keeps its own copy: that kernel is left exactly as it was.)
+__device__ __forceinline__ void zd_copy_chunk(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int64_t n, uint32_t k, uint32_t lane) {
+    // rel: position in the copy of this lane's first unit (negative in front of the head)
+    int64_t rel = (int64_t)k * ZD_COPY_CHUNK - (int64_t)((uintptr_t)d & 15u) + 16 * (int64_t)lane;
+#pragma unroll 4
+    for (uint32_t u = 0; u < ZD_COPY_CHUNK / 1024u; u++, rel += 1024) {
+        if (rel >= n) break;
+        if (rel >= 0 && rel + 16 <= n) {
+            *(v4u*)(d + rel) = ld128(s + rel);
+        } else {
+            const int64_t lo = rel < 0 ? 0 : rel, hi = rel + 16 < n ? rel + 16 : n;
+            for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+        }
+    }
 }
 
 // ---------------------------------------------------------------- host side of an entry point

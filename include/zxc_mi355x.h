@@ -391,6 +391,70 @@ ZXC_EXPORT int zxc_mi355x_decompress_batch_dict_device(const void* d_src, uint64
                                                        const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict,
                                                        void* d_work, uint64_t work_size, int64_t* d_results, void* stream);
 
+/* ---- many buffers per call, device to device (zxc_amd/csrc/zxc_cbatch_device.hip, rules in zxc_amd/csrc/zxc_cbatch.h) ----
+ * zxc_mi355x_compress_device for many small, independent buffers that already live in device memory: the write side of the
+ * calls above. One source of a few blocks fills a sliver of the device and costs about eight launches and a work area of its own;
+ * a few thousand in one call cost a handful of launches. The buffers lie in one source area, the archives go to one destination
+ * area, and a zxc_dev_item_t table in device memory says where each one lies and goes: src_off / src_size are the buffer to
+ * compress, dst_off / dst_capacity where its archive goes and how large it may be (size each with zxc_compress_bound). With
+ * d_results as the sizes, the item table of a compress call is therefore almost the item table of the decompress call. */
+
+/* Bytes of device scratch the call below needs; 0 for arguments it would refuse (options as zxc_mi355x_compress_device_work_size,
+ * n_items x J > 2^31 - 2). The host never sees the items, only the promise that none is larger than max_size bytes: the call
+ * launches J = max(1, ceil(max_size / block_size)) jobs per item, of which an item uses as many as it has blocks, and every job
+ * has an encoder slot of S = zxc_mi355x_encode_slot_stride(block_size) bytes. The size is at most
+ * n_items x J x (S + 28) + 64 x n_items + 1536: the slots, per job a table entry, a size and an archive offset, a record per item.
+ * That is the price of not knowing the items on the host; keep it down with a tight max_size. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_batch_device_work_size(uint32_t n_items, uint64_t max_size, const zxc_compress_opts_t* opts);
+
+/* For r in [0, n_items): d_src[src_off_r, src_off_r + src_size_r) is compressed into a complete v8 archive at d_dst + dst_off_r,
+ * asynchronously on `stream`; d_results[r] (device memory) receives, once, after that item's last byte, the archive size or a
+ * negative zxc_error_t. The archive is byte for byte the one zxc_compress of this library (and zxc_mi355x_compress_device) writes
+ * for the same source, level, block_size, checksum_enabled and seekable; it does not depend on the bytes around the item.
+ * Per item, decided on the device in this order, with cap_r = min(dst_capacity_r, dst_capacity - dst_off_r) (0 when dst_off_r >
+ * dst_capacity): src_off_r + src_size_r > src_capacity (compared without overflow) -> ZXC_ERROR_SRC_TOO_SMALL; src_size_r >
+ * max_size -> ZXC_ERROR_OVERFLOW; cap_r below the part of the archive known before encoding (header, 8 (+4 with checksums) bytes
+ * per block, EOF block, seek table, footer) -> ZXC_ERROR_DST_TOO_SMALL; none of these items' bytes is read and no block of theirs
+ * is encoded. Behind the encoder: a block size outside [8 (+4), block_size + 64] -> ZXC_ERROR_CORRUPT_DATA; an archive larger
+ * than cap_r -> ZXC_ERROR_DST_TOO_SMALL. An item that fails has nothing written to its destination.
+ * d_items lies in device memory and is read on the stream: a kernel or copy enqueued before the call may write it, a replayed
+ * graph may see other items each time. All items' blocks are encoded by one launch of the level's encoder over a job table (one
+ * wavefront per job; the unused ones of an item's J exit at once); one thread per item then writes the container around them,
+ * serially over the item's blocks, so this call is for items of few blocks: a source of many blocks belongs in
+ * zxc_mi355x_compress_device. The archives are not packed back to back: each goes where its item says.
+ * Options are read like zxc_mi355x_compress_device reads them (opts may be NULL: level 3, 512 KiB blocks); n_threads, progress_cb
+ * and user_data are ignored.
+ * Synchronous errors, in this order, before any device is touched: NULL d_src / d_work / d_results, NULL d_items with
+ * n_items > 0, NULL d_dst with dst_capacity > 0 -> ZXC_ERROR_NULL_INPUT; block_size not a power of two in [4 KiB, 2 MiB] ->
+ * ZXC_ERROR_BAD_BLOCK_SIZE; opts->dict != NULL -> ZXC_ERROR_GPU_UNSUPPORTED (a dictionary in device memory: the call below);
+ * n_items x J above 2^31 - 2, or work_size too small -> ZXC_ERROR_MEMORY; n_items == 0 is ZXC_OK here and enqueues nothing;
+ * then, without a device, ZXC_ERROR_GPU_UNAVAILABLE.
+ * Guarantees: nothing is written outside [dst_off_r, dst_off_r + size_r) of the items that succeed and d_work; a failing item
+ * leaves every other item untouched. d_dst and dst_off_r may have any alignment. Items whose destinations overlap are the
+ * caller's error: undefined bytes, no fault. d_src must be READABLE up to src_capacity + 64 (the encoder compares 16 bytes at a
+ * time and reads up to 32 bytes past a block; the bytes themselves are never used) and is never written. No host synchronisation
+ * and no device allocation (beyond the encoder's stream-ordered scratch at levels 6-7). d_work: any alignment, owned by the call
+ * until the last result is written. Calls on different streams with different work areas may overlap. */
+ZXC_EXPORT int zxc_mi355x_compress_batch_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                                uint32_t n_items, uint64_t max_size, void* d_dst, uint64_t dst_capacity,
+                                                const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size,
+                                                int64_t* d_results, void* stream);
+
+/* The call above with a dictionary in device memory that the whole batch shares: every archive is the one zxc_compress writes
+ * with that dictionary, its file header carrying the dictionary flag and *d_id (zxc_mi355x_compress_dict_device). The blocks are
+ * encoded from [dict | block] images in chunks of C = max(4096, 256 MiB / (block_size + dict_size)) jobs: one image area of
+ * min(n_items x J, C) images is reused from chunk to chunk in stream order. The work size is at most the sibling's plus
+ * min(n_items x J, C) x (block_size + dict_size) + 320 (0 also for dict_size > 65535); with dict_size 0, and in the call with a
+ * NULL dict or one of size 0, everything is the sibling's. The images are copies of exactly the items' bytes.
+ * Synchronous errors: the sibling's, with dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE and NULL d_content or d_id with size > 0
+ * -> ZXC_ERROR_NULL_INPUT behind the opts->dict check. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_batch_dict_device_work_size(uint32_t n_items, uint64_t max_size,
+                                                                   const zxc_compress_opts_t* opts, uint32_t dict_size);
+ZXC_EXPORT int zxc_mi355x_compress_batch_dict_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                                     uint32_t n_items, uint64_t max_size, void* d_dst, uint64_t dst_capacity,
+                                                     const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
+                                                     uint64_t work_size, int64_t* d_results, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

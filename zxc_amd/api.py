@@ -479,6 +479,56 @@ def decompress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_capa
         raise ZxcError(rc, "zxc_mi355x_decompress_batch_dict_device")
 
 
+# ---- many buffers per call: the write side (zxc_dev_item_t: src_* the buffer to compress, dst_* where its archive goes)
+def _bind_compress_batch_device(L):
+    L.zxc_mi355x_compress_batch_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_batch_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
+    L.zxc_mi355x_compress_batch_dict_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_batch_dict_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
+    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts)]
+    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_compress_batch_device.restype = C.c_int
+    L.zxc_mi355x_compress_batch_device.argtypes = head + tail
+    L.zxc_mi355x_compress_batch_dict_device.restype = C.c_int
+    L.zxc_mi355x_compress_batch_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
+    return L
+
+
+def compress_batch_device_work_size(n_items, max_size, level=3, block_size=0, seekable=False, checksum=False, dict_size=0):
+    """zxc_mi355x_compress_batch_device_work_size(), or with dict_size the _dict call's: bytes of device scratch the call needs
+    (0 for refused arguments)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    L = _bind_compress_batch_device(lib())
+    if dict_size:
+        return int(L.zxc_mi355x_compress_batch_dict_device_work_size(n_items, max_size, C.byref(o), dict_size))
+    return int(L.zxc_mi355x_compress_batch_device_work_size(n_items, max_size, C.byref(o)))
+
+
+def compress_batch_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, d_work, work_size, d_results, level=3,
+                          block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_batch_device(): raw device pointers (ints); d_items is n_items x ITEM_DTYPE in device memory (src_* the
+    buffer to compress, dst_* where its archive goes), d_results n_items x int64, each the item's archive size or a negative
+    zxc_error_t. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = _bind_compress_batch_device(lib()).zxc_mi355x_compress_batch_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
+        C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_batch_device")
+
+
+def compress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, dict_, d_work, work_size, d_results,
+                               level=3, block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_batch_dict_device(): compress_batch_device with one dictionary in device memory for the whole batch
+    (dict_ as in compress_dict_device); the work size is compress_batch_device_work_size(..., dict_size=size)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = _bind_compress_batch_device(lib()).zxc_mi355x_compress_batch_dict_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
+        C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_batch_dict_device")
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

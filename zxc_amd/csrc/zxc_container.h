@@ -30,6 +30,11 @@
 #define ZC_NO_EVENT (~0ull)
 #define ZC_DICT_MAX 65535u            /* bytes of a dictionary (zxc_dev_dict_t.size) */
 
+/* The dictionary compress calls encode from [dict | block] images, in chunks that reuse one image area in stream order: */
+#define ZC_IMAGE_BYTES (256ull << 20) /* the image area of a chunk stays near this ... */
+#define ZC_IMAGE_MIN_BLOCKS 4096u     /* ... but a chunk is never fewer blocks than this */
+#define ZC_IMAGE_PAD 64u              /* behind the last image (the encoder's over-read, as zxc_mi355x_encode_dict_work_size) */
+
 /* Per-call state at the start of the work area. */
 typedef struct zc_ctl {
     int64_t head_result;  /* final != 0: the call's result, decided by the head stage (file-header error, empty-frame probe) */
@@ -87,6 +92,11 @@ ZC_FN uint64_t zc_blk_hdr(uint32_t type, uint32_t csz) {
     const uint64_t w = (uint64_t)type | (uint64_t)csz << 24;
     return w | (uint64_t)zc_hdr_hash8(w) << 56;
 }
+/* blocks per chunk of the dictionary compress calls */
+ZC_FN uint64_t zc_image_chunk(uint32_t block_size, uint32_t dict_size) {
+    const uint64_t c = ZC_IMAGE_BYTES / ((uint64_t)block_size + dict_size);
+    return c > ZC_IMAGE_MIN_BLOCKS ? c : ZC_IMAGE_MIN_BLOCKS;
+}
 /* a block size the format has: a power of two from 4 KiB to 2 MiB */
 ZC_FN int zc_block_size_ok(uint64_t bs) { return bs >= (1u << 12) && bs <= (1u << 21) && !(bs & (bs - 1u)); }
 ZC_FN uint32_t zc_block_size_lg(uint64_t bs) { /* of a size zc_block_size_ok accepts */
@@ -137,6 +147,11 @@ ZC_FN void zc_put_file_header(uint8_t* p, uint32_t lg, int file_ck, int has_dict
 ZC_FN void zc_put_footer(uint8_t* p, uint64_t total, uint32_t hash) {
     zc_st_le(p, total, 8);
     zc_st_le(p + 8, hash, 4);
+}
+
+/* What an archive of nb blocks needs whatever the encoder writes: header, the smallest block per block, EOF, seek table, footer. */
+ZC_FN uint64_t zc_known_size(uint64_t nb, int file_ck, int seekable) {
+    return ZC_FILE_HDR + nb * (ZC_BLK_HDR + (file_ck ? 4u : 0u)) + ZC_BLK_HDR + ((seekable && nb) ? ZC_BLK_HDR + 4u * nb : 0u) + ZC_FOOTER;
 }
 
 /* Block i of the archive: compressed bytes at comp_off, decoded into slot i of the destination while i < k_direct, else into

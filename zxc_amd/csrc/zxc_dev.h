@@ -10,6 +10,14 @@
 #define ZXC_DEV_DEFER (-103)      /* lean kernel only, never stored: the block goes to the full kernel's list */
 #define ZXC_DEV_E_INTERNAL (-102) /* kernel self-check tripped (a bug, never an input property) */
 
+/* One workgroup's input of the job-table encode entries (zxc_encode_jobs_kernel_*, zxc_encode_kernel.hip): len bytes, at most a
+ * block, at the launch's base pointer + src_off (with a dictionary: a [dict | block] image there). len 0: an unused job. */
+typedef struct zxc_enc_job {
+    uint64_t src_off;
+    uint32_t len;
+    uint32_t pad;
+} zxc_enc_job_t;
+
 /* Levels 6-7, launches without a dictionary: the launch-order pass (zxc_order_scatter_kernel) sorts every block into one
  * of three classes. The PivCo sections of PRE blocks are decoded by the workgroup section kernels (zxc_pivco_dir.inc) into a
  * per-launch scratch buffer, one work record per section; the blocks are then executed by the lean kernel's second entry

@@ -123,12 +123,14 @@ extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out) {
 //   GHI: 4-byte words), offsets (GLO), extras
 // HB = log2(head entries), CWB = log2(chain ring entries) or 0 for "head only". depth / sufficient / lazy: the
 // reference's search_depth / sufficient_len / lazy probes (src/lib/zxc_internal.h:965-979), see the table below.
+// The body works on one block wherever it lies: `in` = the block's bytes (behind dict_size dictionary bytes, see below; any
+// alignment, every load goes through ld64 / ld128), nblk = the block's own byte count, slot = its slot, *size_out = where its size
+// goes, b = its index into huf_scratch. The two kinds of entry below (by value, job table) differ only in how they find these.
 template <uint32_t HSZ, uint32_t CWB, bool GHI, uint32_t NC, uint32_t U>
-__device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size,
-                                                 uint8_t* __restrict__ slots, uint32_t slot_stride,
-                                                 uint32_t* __restrict__ sizes, uint32_t n_blocks, uint32_t with_checksum,
-                                                 uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,
-                                                 uint8_t* __restrict__ huf_scratch, uint32_t huf) {
+__device__ __forceinline__ void encode_block_body(const uint8_t* __restrict__ in, uint32_t nblk, uint8_t* __restrict__ slot,
+                                                  uint32_t* __restrict__ size_out, uint32_t b, uint32_t block_size,
+                                                  uint32_t with_checksum, uint32_t depth, uint32_t sufficient, uint32_t lazy,
+                                                  uint32_t dict_size, uint8_t* __restrict__ huf_scratch, uint32_t huf) {
     constexpr uint32_t HSIZE = HSZ;  // head entries: any even number (the hash's top bits are scaled onto it), so that the tables can be
                                      // cut to the LDS that buys one more workgroup per CU (160 KiB / 7 = 22.8 KiB)
     constexpr uint32_t CW = CWB ? (1u << CWB) : 1u;
@@ -137,18 +139,12 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     __shared__ __attribute__((aligned(16))) uint16_t ht[HSIZE];  // head: low 16 bits of the most recent position with this hash
     __shared__ __attribute__((aligned(16))) uint16_t chain[CW];  // chain[q & CWM]: distance from q to the previous position with q's hash (0: none)
     const int lane = threadIdx.x;
-    const uint32_t b = blockIdx.x;
-    if (b >= n_blocks) return;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     // With a dictionary (reference: zxc_lz_seed_dict + the [dict | block] buffer of zxc_compress_block,
-    // src/lib/zxc_dispatch.c:1688-1697) `src` holds one [dict | block] image per block (zxc_prepend_dict_kernel):
+    // src/lib/zxc_dispatch.c:1688-1697) `in` is a [dict | block] image (zxc_prepend_dict_kernel, zxc_encode_job_images_kernel):
     // positions [0, D) are the dictionary — inserted into the tables, never parsed — and the block starts at D.
     const uint32_t D = dict_size;
-    const uint8_t* in = src + (uint64_t)b * ((uint64_t)block_size + D);
-    const uint64_t remain = src_size - (uint64_t)b * block_size;
-    const uint32_t nblk = remain < block_size ? (uint32_t)remain : block_size;  // bytes of the block itself
     const uint32_t n = D + nblk;
-    uint8_t* slot = slots + (uint64_t)b * slot_stride;
     // literals are gathered behind room for the widest descriptor set (levels 6-7: lit_comp + tok_comp) and slid down at the end
     const uint32_t lit_base = (DEEP && huf != 0u) ? 28u : 20u;
     uint8_t* lit_out = slot + lit_base;
@@ -700,7 +696,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
             if (lane == 0) __builtin_memcpy(slot + total, &ck, 4);
             total += 4u;
         }
-        if (lane == 0) sizes[b] = total;
+        if (lane == 0) *size_out = total;
         return;
     }
     // a wave copy between regions that do not overlap
@@ -755,7 +751,39 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
         if (lane == 0) __builtin_memcpy(slot + total, &ck, 4);
         total += 4u;
     }
-    if (lane == 0) sizes[b] = total;
+    if (lane == 0) *size_out = total;
+}
+
+// Block b = blockIdx.x of a contiguous source (with a dictionary: of one [dict | block] image per block): its input and length
+// follow from b, so every block but the last is block_size bytes.
+template <uint32_t HSZ, uint32_t CWB, bool GHI, uint32_t NC, uint32_t U>
+__device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size,
+                                                 uint8_t* __restrict__ slots, uint32_t slot_stride,
+                                                 uint32_t* __restrict__ sizes, uint32_t n_blocks, uint32_t with_checksum,
+                                                 uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,
+                                                 uint8_t* __restrict__ huf_scratch, uint32_t huf) {
+    const uint32_t b = blockIdx.x;
+    if (b >= n_blocks) return;
+    const uint8_t* in = src + (uint64_t)b * ((uint64_t)block_size + dict_size);
+    const uint64_t remain = src_size - (uint64_t)b * block_size;
+    const uint32_t nblk = remain < block_size ? (uint32_t)remain : block_size;  // bytes of the block itself
+    encode_block_body<HSZ, CWB, GHI, NC, U>(in, nblk, slots + (uint64_t)b * slot_stride, sizes + b, b, block_size, with_checksum, depth,
+                                            sufficient, lazy, dict_size, huf_scratch, huf);
+}
+// Job b = blockIdx.x of a table: jobs[b].len bytes (at most block_size; the table's writer sees to that, and it is clamped here so
+// that a slot is never overrun) at src + jobs[b].src_off, behind dict_size dictionary bytes when there is a dictionary.
+template <uint32_t HSZ, uint32_t CWB, bool GHI, uint32_t NC, uint32_t U>
+__device__ __forceinline__ void encode_one_job(const uint8_t* __restrict__ src, const zxc_enc_job_t* __restrict__ jobs, uint32_t block_size,
+                                               uint8_t* __restrict__ slots, uint32_t slot_stride, uint32_t* __restrict__ sizes,
+                                               uint32_t n_jobs, uint32_t with_checksum, uint32_t depth, uint32_t sufficient,
+                                               uint32_t lazy, uint32_t dict_size, uint8_t* __restrict__ huf_scratch, uint32_t huf) {
+    const uint32_t b = blockIdx.x;
+    if (b >= n_jobs) return;
+    const uint32_t len = uni(jobs[b].len);
+    if (len == 0u) return;
+    const uint64_t off = ((uint64_t)uni((uint32_t)(jobs[b].src_off >> 32)) << 32) | uni((uint32_t)jobs[b].src_off);
+    encode_block_body<HSZ, CWB, GHI, NC, U>(src + off, len < block_size ? len : block_size, slots + (uint64_t)b * slot_stride, sizes + b, b,
+                                            block_size, with_checksum, depth, sufficient, lazy, dict_size, huf_scratch, huf);
 }
 
 // Level -> search effort. Reference table (src/lib/zxc_internal.h:965-979): search_depth 3/3/3/3/64/64/128,
@@ -773,32 +801,44 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
 //     7     2^13     2^15        66          6                   256        lazy 2    GLO + PivCo literals and tokens
 // Every entry runs ONE chunk of 64 positions per loop iteration (U = 1; A/B, profiles/r3p_encu.log: 1 / 2 / 3 / 4 all within 2 % at
 // level 3 — a wave issues in order, only the memory round trips overlap — and 1 keeps the archives of round 2 byte for byte).
-#define ZXC_ENCODE_ENTRY(name, hb, cwb, ghi, waves, nc)                                                                    \
+// Two entries per table geometry. By value (name): block b = blockIdx.x of a contiguous source, so only the last block of a launch may
+// be short. Job table (jobs_name): workgroup b encodes jobs[b].len bytes at src + jobs[b].src_off, for launches in which every
+// item ends in a short block (zxc_cbatch_device.hip); a job of len 0 is unused: its wave leaves before it touches the LDS
+// tables, the source or the slot, and sizes[b] stays what the caller made it.
+#define ZXC_ENCODE_ENTRY(name, jobs_name, hb, cwb, ghi, waves, nc)                                                     \
     extern "C" __global__ void __launch_bounds__(64, waves) name(                                                      \
         const uint8_t* __restrict__ src, uint64_t src_size, uint32_t block_size, uint8_t* __restrict__ slots,          \
         uint32_t slot_stride, uint32_t* __restrict__ sizes, uint32_t n_blocks, uint32_t with_checksum, uint32_t depth, \
         uint32_t sufficient, uint32_t lazy, uint32_t dict_size, uint8_t* __restrict__ huf_scratch, uint32_t huf) {     \
         encode_one_block<hb, cwb, ghi, nc, 1u>(src, src_size, block_size, slots, slot_stride, sizes, n_blocks, with_checksum,  \
                                        depth, sufficient, lazy, dict_size, huf_scratch, huf);                          \
+    }                                                                                                                  \
+    extern "C" __global__ void __launch_bounds__(64, waves) jobs_name(                                                 \
+        const uint8_t* __restrict__ src, const zxc_enc_job_t* __restrict__ jobs, uint32_t block_size,                  \
+        uint8_t* __restrict__ slots, uint32_t slot_stride, uint32_t* __restrict__ sizes, uint32_t n_jobs,              \
+        uint32_t with_checksum, uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,                \
+        uint8_t* __restrict__ huf_scratch, uint32_t huf) {                                                             \
+        encode_one_job<hb, cwb, ghi, nc, 1u>(src, jobs, block_size, slots, slot_stride, sizes, n_jobs, with_checksum,  \
+                                     depth, sufficient, lazy, dict_size, huf_scratch, huf);                            \
     }
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l1, 4096u, 0u, true, 5, 3u)    // level 1 (A/B: one candidate per round instead of three: -3 %)
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l2, 4096u, 11u, true, 3, 3u)   // level 2
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l1, zxc_encode_jobs_kernel_l1, 4096u, 0u, true, 5, 3u)    // level 1 (A/B: one candidate per round instead of three: -3 %)
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l2, zxc_encode_jobs_kernel_l2, 4096u, 11u, true, 3, 3u)   // level 2
 // Level 3 (round 4): head 2^13 + ring 2^11 = 20 KiB -> EIGHT workgroups per CU = two waves on every SIMD instead of six (two SIMDs
 // with one wave and nothing to hide its round trips behind): +40 % at the same search effort, for 1.25 % of ratio (the ring's far
 // hops); four candidates in ONE round and two lazy probes buy 0.8 % back for 9 % of the time (profiles/r4f_encoder_ablations.log).
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l3, 8192u, 11u, false, 2, 4u) // level 3
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l3, zxc_encode_jobs_kernel_l3, 8192u, 11u, false, 2, 4u) // level 3
 // Level 4: a ring of 2^12 = 24 KiB -> six per CU: level 4's size bound (1.05 x the reference, today 1.047 x) has nothing to spend on a
 // smaller ring; all six candidates in one round: +3 % over two rounds of three, sizes -0.08 %.
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l4, 8192u, 12u, false, 2, 6u) // level 4
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l4, zxc_encode_jobs_kernel_l4, 8192u, 12u, false, 2, 6u) // level 4
 // Level 5 (A/B on text, head / ring: 2^14 / 2^14 3.70 GB/s ratio 2.301; 2^13 / 2^14 4.76, 2.287; 2^14 / 2^13 4.99, 2.275; 2^13 / 2^13
 // 6.30, 2.249: the head table is the cheaper one to halve). Six candidates per round of the deep levels (18 / 33 / 66 per position:
 // half the round trips of 3).
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l57, 8192u, 14u, false, 1, 6u) // level 5
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l57, zxc_encode_jobs_kernel_l57, 8192u, 14u, false, 1, 6u) // level 5
 // Levels 6-7 (round 5): a chain ring of 2^15 entries. The reference's chain reaches 65 536 positions back (ZXC_LZ_WINDOW_SIZE,
 // src/lib/zxc_common.c:199); with 2^14 the ultra levels came out 2.2-2.5 % larger than the reference's on text, with 2^15 0.8-0.9 %
 // (2^16: 0.3 %, but 144 KiB of tables = one workgroup per CU): 80 KiB of tables = two workgroups per CU instead of three —
 // the ultra tiers buy ratio with speed (tests/test_wave_emu.py, profiles/r5f_*).
-ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l67, 8192u, 15u, false, 1, 6u) // levels 6-7
+ZXC_ENCODE_ENTRY(zxc_encode_blocks_kernel_l67, zxc_encode_jobs_kernel_l67, 8192u, 15u, false, 1, 6u) // levels 6-7
 
 // [dict | block b] images for the dictionary path: work + b * (block_size + dict_size)
 extern "C" __global__ void __launch_bounds__(64)
@@ -813,6 +853,25 @@ zxc_prepend_dict_kernel(const uint8_t* __restrict__ src, uint64_t src_size, uint
     const uint32_t n = remain < block_size ? (uint32_t)remain : block_size;
     const uint8_t* s = src + (uint64_t)b * block_size;
     for (uint32_t o = lane; o < n; o += 64u) w[dict_size + o] = s[o];
+}
+
+// The same images for a job table (zxc_cbatch_device.hip): workgroup w makes job w's image at work + w * (block_size + dict_size),
+// [dict | the job's len bytes], and then points the job at it: src_off becomes the image's offset from `work`, which the
+// job-table encode entries are given as their base. Reads exactly the job's len bytes of src; a job of len 0 is unused and skipped.
+extern "C" __global__ void __launch_bounds__(64)
+zxc_encode_job_images_kernel(const uint8_t* __restrict__ src, zxc_enc_job_t* __restrict__ jobs, uint32_t n, uint32_t block_size,
+                             const uint8_t* __restrict__ dict, uint32_t dict_size, uint8_t* __restrict__ work) {
+    const uint32_t wg = blockIdx.x;
+    if (wg >= n) return;
+    zxc_enc_job_t* job = jobs + wg;
+    const uint32_t asked = uni(job->len), len = asked < block_size ? asked : block_size;
+    if (len == 0u) return;
+    const uint64_t off = ((uint64_t)uni((uint32_t)(job->src_off >> 32)) << 32) | uni((uint32_t)job->src_off);
+    const uint32_t lane = threadIdx.x;
+    const uint64_t at = (uint64_t)wg * ((uint64_t)block_size + dict_size);
+    copy_bytes(work + at, dict, dict_size, lane, 64u);
+    copy_bytes(work + at + dict_size, src + off, len, lane, 64u);
+    if (lane == 0) job->src_off = at;  // (every lane has read the old value: uni() above)
 }
 
 // offsets[b] = sizes[0] + ... + sizes[b - 1] (one workgroup; a piece of the host API's pipeline is at most a few thousand blocks):

@@ -21,9 +21,7 @@
 
 #define FRAME_ENC_OVERREAD 32u      // the encoder reads up to 32 bytes past its input (include/zxc_mi355x.h)
 #define FRAME_STAGE_PAD 64u         // zero bytes behind the staged blocks (covers the over-read)
-#define FRAME_IMAGE_BYTES (256ull << 20)  // the image area of a chunk of the dictionary path stays near this ...
-#define FRAME_IMAGE_MIN_BLOCKS 4096u      // ... but a chunk is never fewer blocks than this
-#define FRAME_IMAGE_PAD 64u               // behind the last image (the encoder's over-read, as zxc_mi355x_encode_dict_work_size)
+#define FRAME_IMAGE_PAD ZC_IMAGE_PAD  // behind the last image; the chunk constants are zxc_container.h's, shared with zxc_cbatch.h
 
 // Per-call state at the start of the work area (one call owns it from the first launch to the last).
 struct FrameCtl {
@@ -187,15 +185,11 @@ int frame_plan(uint64_t src_size, const zxc_compress_opts_t* opts, FramePlan* p)
 }
 
 // What the archive needs whatever the encoder writes: header, the smallest block per block, EOF, seek table, footer.
-uint64_t frame_known_size(const FramePlan& p) {
-    return ZC_FILE_HDR + (uint64_t)p.nb * (8u + 4u * p.checksum) + ZC_BLK_HDR +
-           ((p.seekable && p.nb) ? ZC_BLK_HDR + 4ull * p.nb : 0u) + ZC_FOOTER;
-}
+uint64_t frame_known_size(const FramePlan& p) { return zc_known_size(p.nb, (int)p.checksum, (int)p.seekable); }
 
 // The dictionary path's image area: blocks per chunk, and the area's bytes, added to p.bytes of the plain plan (0 blocks: none).
 uint64_t frame_chunk_blocks(const FramePlan& p, uint32_t dict_size) {
-    const uint64_t c = FRAME_IMAGE_BYTES / ((uint64_t)p.block_size + dict_size);
-    return c > FRAME_IMAGE_MIN_BLOCKS ? c : FRAME_IMAGE_MIN_BLOCKS;
+    return zc_image_chunk(p.block_size, dict_size);
 }
 uint64_t frame_image_bytes(const FramePlan& p, uint32_t dict_size) {
     if (!p.nb) return 0u;

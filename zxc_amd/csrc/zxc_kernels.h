@@ -65,8 +65,23 @@ ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l4);
 ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l57);
 ZXC_ENCODE_DECL(zxc_encode_blocks_kernel_l67);
 #undef ZXC_ENCODE_DECL
+// ... and the job-table entries beside them: one zxc_enc_job_t per workgroup instead of a contiguous source
+#define ZXC_ENCODE_JOBS_DECL(name)                                                                                     \
+    extern "C" __global__ void name(const uint8_t* src, const zxc_enc_job_t* jobs, uint32_t block_size, uint8_t* slots, \
+                                    uint32_t slot_stride, uint32_t* sizes, uint32_t n_jobs, uint32_t with_checksum,    \
+                                    uint32_t depth, uint32_t sufficient, uint32_t lazy, uint32_t dict_size,            \
+                                    uint8_t* huf_scratch, uint32_t huf)
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l1);
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l2);
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l3);
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l4);
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l57);
+ZXC_ENCODE_JOBS_DECL(zxc_encode_jobs_kernel_l67);
+#undef ZXC_ENCODE_JOBS_DECL
 extern "C" __global__ void zxc_prepend_dict_kernel(const uint8_t* src, uint64_t src_size, uint32_t block_size, const uint8_t* dict,
                                                    uint32_t dict_size, uint8_t* work, uint32_t n_blocks);
+extern "C" __global__ void zxc_encode_job_images_kernel(const uint8_t* src, zxc_enc_job_t* jobs, uint32_t n, uint32_t block_size,
+                                                        const uint8_t* dict, uint32_t dict_size, uint8_t* work);
 extern "C" __global__ void zxc_block_offsets_kernel(uint32_t* sizes, uint64_t* offsets, uint32_t n_blocks, uint32_t max_size);
 extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32_t slot_stride, const uint32_t* sizes,
                                                     const uint64_t* offsets, uint8_t* out, uint32_t n_blocks);

@@ -455,6 +455,68 @@ ZXC_EXPORT int zxc_mi355x_compress_batch_dict_device(const void* d_src, uint64_t
                                                      const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
                                                      uint64_t work_size, int64_t* d_results, void* stream);
 
+/* ---- one archive from many pieces, device to device (zxc_amd/csrc/zxc_append_device.hip, rules in zxc_amd/csrc/zxc_append.h) ----
+ * zxc_mi355x_compress_device wants the whole source in one device buffer, a work area of about twice the source and a destination
+ * of zxc_compress_bound: compressing S bytes that lie in HBM costs about 3 S more HBM, and a list of tensors (a state dict,
+ * optimizer shards, pages produced step by step) has to be concatenated first. A session takes the source in pieces, as
+ * zxc_cstream_* does for host memory, and writes one archive: its work area is sized by the largest piece, not by the source. */
+
+/* The session: a host struct the caller owns, with no allocation behind it. begin fills it, end spends it; it may be dropped at
+ * any time (what is enqueued runs on). One session is one thread's at a time. */
+typedef struct zxc_dev_cappend { uint64_t opaque[16]; } zxc_dev_cappend_t;
+
+/* Bytes of device scratch a session needs; 0 for arguments begin would refuse (options as zxc_mi355x_compress_device_work_size,
+ * max_piece < block_size, more than 2^31 - 1 blocks in max_total or jobs in a piece). max_total is the most bytes the session
+ * will be given in all, max_piece the most it works on at a time: an append of more is processed in pieces of at most max_piece
+ * bytes. A piece has J = max_piece / block_size + 2 jobs, each with an encoder slot of S = zxc_mi355x_encode_slot_stride(block_size)
+ * bytes, which every piece reuses. With NB = ceil(max_total / block_size) the size is at most
+ * J x (S + 28) + 16 x ceil(J / 1024) + 3 x (block_size + 64) + 4096, and with opts->seekable + 4 x NB: the slots, per job a table
+ * entry, a size and an archive offset, three words per tile of 1024 jobs, two carry areas and a stage area, the seek-table entries
+ * until end puts them behind the blocks. Without a seek table it does not depend on max_total. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_append_device_work_size(uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts);
+
+/* begin, any number of appends, end: afterwards d_dst holds byte for byte the archive zxc_mi355x_compress_device (and zxc_compress
+ * of this library) writes for the concatenation of the appended bytes with the same level, block_size, checksum_enabled and
+ * seekable, however the source was cut: appends of 0 bytes, of less than a block, many of those in a row, appends that end inside
+ * a block. *d_result (device memory) is written once, last, by end: the archive size, or the negative zxc_error_t
+ * zxc_mi355x_compress_device would have stored for that source and dst_capacity (where that call refuses a capacity below the
+ * part of the archive known before encoding synchronously, the session, which cannot know the source at begin, stores
+ * ZXC_ERROR_DST_TOO_SMALL). begin + end gives the archive of the empty source.
+ * Everything is asynchronous on `stream`: no host synchronisation, no device allocation (beyond the encoder's stream-ordered
+ * scratch at levels 6-7). The calls of one session must be in stream order with each other (one stream, or the caller's events);
+ * sessions with different work areas and destinations may run concurrently. d_work (any alignment) and d_dst are the session's
+ * from begin until *d_result is written.
+ * An append reads exactly d_src[0, n), whatever its alignment; d_src may be reused or freed, in stream order, behind the call.
+ * The host knows every n, so it knows the carry, (bytes so far) mod block_size, and each piece's exact grid; nothing about the
+ * shape is decided on the device. The trailing partial block of an append is copied into a carry area of d_work, the next
+ * append's first block is assembled there from the carry and the head of the new bytes, and end encodes what is left there as the
+ * short last block. A whole block is encoded where it lies in d_src when the encoder's 32-byte over-read stays inside the piece,
+ * else (the last whole block of a piece, at most) from a zero-padded copy, as zxc_mi355x_compress_device stages its last blocks.
+ * An append of more than max_piece bytes is a loop of enqueues over pieces cut on the archive's block boundaries, which reuse
+ * the slots in stream order. Per piece, on the device: every block size is checked against [8 (+4), block_size + 64]
+ * (ZXC_ERROR_CORRUPT_DATA); the blocks are gathered right behind the previous piece's; the seek-table entries join an array in
+ * d_work; the global hash is carried on. Once the blocks so far, plus the EOF block, the seek table for them and the footer, exceed
+ * dst_capacity the session's status is ZXC_ERROR_DST_TOO_SMALL and no further block is gathered: the archive only grows, so this
+ * is exactly zxc_mi355x_compress_device's size > dst_capacity. Both errors stay and end reports them. Nothing is written at or
+ * past d_dst + dst_capacity; d_dst may have any alignment; after an error its bytes are undefined.
+ * Options are read like zxc_mi355x_compress_device reads them (opts may be NULL: level 3, 512 KiB blocks). opts->dict != NULL is
+ * ZXC_ERROR_GPU_UNSUPPORTED, and there is no sibling that takes a zxc_dev_dict_t yet: a session with a dictionary in device
+ * memory is left for later.
+ * Synchronous errors, before any device is touched, in this order. begin: NULL cs / d_dst / d_work -> ZXC_ERROR_NULL_INPUT;
+ * opts->dict -> ZXC_ERROR_GPU_UNSUPPORTED; block_size not a power of two in [4 KiB, 2 MiB], max_piece < block_size, more than
+ * 2^31 - 1 blocks in max_total (or jobs in a piece) -> ZXC_ERROR_BAD_BLOCK_SIZE; work_size too small -> ZXC_ERROR_MEMORY;
+ * dst_capacity below the empty archive -> ZXC_ERROR_DST_TOO_SMALL; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE. append:
+ * NULL cs, NULL d_src with n > 0 -> ZXC_ERROR_NULL_INPUT; a session that was never begun or is ended -> ZXC_ERROR_NULL_INPUT;
+ * bytes so far + n > max_total (compared without overflow) -> ZXC_ERROR_OVERFLOW, with nothing enqueued and the session as it
+ * was. end: NULL cs / d_result, a session never begun or ended -> ZXC_ERROR_NULL_INPUT; afterwards the struct is spent. A launch
+ * failure (ZXC_ERROR_GPU_UNAVAILABLE, ZXC_ERROR_MEMORY) in append or end leaves part of the work enqueued: the session is spent,
+ * *d_result is not written, and the bytes of d_dst are undefined. */
+ZXC_EXPORT int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total,
+                                                uint64_t max_piece, const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size,
+                                                void* stream);
+ZXC_EXPORT int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, uint64_t n, void* stream);
+ZXC_EXPORT int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

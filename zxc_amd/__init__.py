@@ -11,6 +11,7 @@ from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_siz
                   decompress_ranges_device, dict_prepare_device, compress_dict_device, compress_dict_device_work_size,
                   decompress_dict_device, decompress_ranges_dict_device, decompress_batch_device_work_size,
                   decompress_batch_device, decompress_batch_dict_device, compress_batch_device_work_size, compress_batch_device,
-                  compress_batch_dict_device, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, ITEM_DTYPE,
+                  compress_batch_dict_device, compress_append_device_work_size, compress_begin_device,
+                  CompressAppendSession, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, ITEM_DTYPE,
                   error_name)
 from . import api  # noqa: F401  (stream_* helpers live there)

@@ -529,6 +529,65 @@ def compress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_size, 
         raise ZxcError(rc, "zxc_mi355x_compress_batch_dict_device")
 
 
+# ---- one archive from many pieces: a session (zxc_dev_cappend_t is a host struct of 16 words, caller-owned)
+class _DevCappend(C.Structure):  # zxc_dev_cappend_t
+    _fields_ = [("opaque", C.c_uint64 * 16)]
+
+
+def _bind_compress_append_device(L):
+    L.zxc_mi355x_compress_append_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_append_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(_CompressOpts)]
+    L.zxc_mi355x_compress_begin_device.restype = C.c_int
+    L.zxc_mi355x_compress_begin_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                   C.POINTER(_CompressOpts), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_compress_append_device.restype = C.c_int
+    L.zxc_mi355x_compress_append_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_compress_end_device.restype = C.c_int
+    L.zxc_mi355x_compress_end_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_void_p]
+    return L
+
+
+def compress_append_device_work_size(max_total, max_piece, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_append_device_work_size(): bytes of device scratch a session needs (0 for refused arguments)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_append_device_work_size(max_total, max_piece, C.byref(o)))
+
+
+class CompressAppendSession:
+    """A session of zxc_mi355x_compress_begin_device(): .append(d_src, n) any number of times, then .end(d_result) once. Raw device
+    pointers (ints), asynchronous on `stream`; the calls of one session must be in stream order with each other. The archive
+    size or a negative zxc_error_t lands in the int64 at d_result; a synchronous failure raises ZxcError."""
+
+    def __init__(self, cs):
+        self._cs = cs
+
+    def append(self, d_src, n, stream=0):
+        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_append_device(C.byref(self._cs), C.c_void_p(d_src or None), n,
+                                                                                   C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_compress_append_device")
+
+    def end(self, d_result, stream=0):
+        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_end_device(C.byref(self._cs), C.c_void_p(d_result or None),
+                                                                                C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_compress_end_device")
+
+
+def compress_begin_device(d_dst, dst_capacity, max_total, max_piece, d_work, work_size, level=3, block_size=0, seekable=False,
+                          checksum=False, stream=0):
+    """zxc_mi355x_compress_begin_device(): -> a CompressAppendSession that writes one archive to d_dst from the pieces it is
+    given; the work size is compress_append_device_work_size(max_total, max_piece, ...)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    cs = _DevCappend()
+    rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_begin_device(
+        C.byref(cs), C.c_void_p(d_dst or None), dst_capacity, max_total, max_piece, C.byref(o), C.c_void_p(d_work or None), work_size,
+        C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_begin_device")
+    return CompressAppendSession(cs)
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

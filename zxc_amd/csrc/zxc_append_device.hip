@@ -1,0 +1,296 @@
+// zxc_append_device.hip — zxc_mi355x_compress_begin_device / _append_device / _end_device: one v8 archive in device memory from a
+// source that arrives in pieces, each in device memory. The device counterpart of zxc_cstream_* (zxc_stream_host.c).
+//
+// zxc_mi355x_compress_device (zxc_frame_device.hip) wants the whole source in one buffer and a slot per block of it. Here a session
+// keeps the archive's running state (offset, blocks, global hash, status) in its work area between calls, and a set of J slots
+// that every piece reuses in stream order, so the work area does not grow with the source. The host knows every n, so it knows the
+// carry and each piece's exact grid: the plan of a piece, its advance and the finish are the inline C of zxc_append.h, which the
+// CPU tests run as well. The stream order of one piece (an append of at most max_piece bytes; a longer one is a loop of these):
+//
+//   prep     head of the source -> carry area (completes the waiting block), last whole block -> stage area when its over-read
+//            would leave the source, tail -> the other carry area; zero padding behind each; the job table
+//   encode   the job-table entry of the level over the piece's blocks, in archive order (a piece that completes no block ends at prep)
+//   tiles    zxc_frame_tiles_kernel: per tile the sum of the sizes, the size check, the piece's part of the global hash
+//   advance  one workgroup: tile offsets from the running offset; status, offset, block count and hash move on (zap_advance)
+//   scatter  per tile: block offsets, seek-table entries into the array in the work area  (only while the status is no error)
+//   gather   one wave per block: slot -> archive                                           (idem)
+//
+// and of `end`: the piece above for what waits in the carry area, as the short last block; then
+//
+//   finish   file header, EOF block, SEK header, footer (zap_finish)
+//   seek     the entries from the work area to their unaligned place, 4 byte stores each
+//   result   *d_result = archive size or the error, written once, after everything above
+//
+// No workgroup waits for another: every dependency is the stream order between launches.
+#include <string.h>
+
+#include "zxc_device_util.h"  // the tile passes, copy_bytes (zxc_wave.h), zxc_frame_tiles_kernel, the host-side plumbing
+#include "zxc_append.h"
+
+static_assert(sizeof(zxc_enc_job_t) + 4 + 8 == ZAP_JOB_BYTES && 8 + 4 + 4 == ZAP_TILE_BYTES, "the documented work size");
+static_assert(sizeof(zap_ctl_t) <= 256, "the state's place at the start of the work area");
+
+// hidden entry point of zxc_hip_shim.hip (the encode launch over a job table)
+extern "C" int zxc_hip_encode_jobs(const void* d_base, zxc_enc_job_t* d_jobs, uint32_t n_jobs, uint32_t block_size, int level,
+                                   int with_checksum, const void* d_dict, uint32_t dict_size, void* d_images, void* d_slots,
+                                   uint32_t* d_sizes, void* stream);
+
+// ---------------------------------------------------------------- kernels
+extern "C" __global__ void zxc_append_begin_kernel(zap_ctl_t* __restrict__ ctl) {
+    if (threadIdx.x == 0) zap_begin(ctl);
+}
+
+// The copies of the piece's plan, each with ZAP_PAD zero bytes behind it, and the job table: job j's src_off is the address of its
+// bytes (the encode launch is given the base 0), since a piece's jobs read the source and the areas. Reads exactly the source bytes
+// the plan's copies name; the areas hold block_size + ZAP_PAD bytes and no copy with its padding passes that (zap_plan_piece).
+extern "C" __global__ void __launch_bounds__(256)
+zxc_append_prep_kernel(const uint8_t* __restrict__ src, zap_piece_t p, uint8_t* __restrict__ carry, uint8_t* __restrict__ next,
+                       uint8_t* __restrict__ stage, zxc_enc_job_t* __restrict__ jobs) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, threads = gridDim.x * blockDim.x;
+    for (uint32_t c = 0; c < 3u; c++) {
+        const zap_copy_t cp = p.cp[c];
+        if (cp.area == ZAP_SRC) continue;
+        uint8_t* d = (cp.area == ZAP_CARRY ? carry : cp.area == ZAP_NEXT ? next : stage) + cp.at;
+        copy_bytes(d, src + cp.from, cp.len, t, threads);
+        if (t < ZAP_PAD) d[cp.len + t] = 0u;
+    }
+    for (uint32_t j = t; j < p.nb; j += threads) {
+        const zap_src_t s = zap_job(&p, j);
+        const uint8_t* at = (s.area == ZAP_SRC ? src : s.area == ZAP_CARRY ? (const uint8_t*)carry : (const uint8_t*)stage) + s.off;
+        zxc_enc_job_t job = {(uint64_t)(uintptr_t)at, s.len, 0u};
+        jobs[j] = job;
+    }
+}
+
+// One workgroup. tile_sum[t] becomes the archive offset of tile t's first block (exclusive prefix + the running offset, in place);
+// then the session's state moves on. Every thread reads the running offset in front of the barrier of zd_scan_tiles, thread 0
+// writes the state behind it.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_append_advance_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
+                          uint32_t n_tiles, uint32_t nb_piece, uint64_t dst_capacity, uint32_t checksum, uint32_t seekable,
+                          zap_ctl_t* __restrict__ ctl) {
+    const uint64_t base = ctl->off;
+    const zd_totals all = zd_scan_tiles(
+        n_tiles, base,
+        [=](uint32_t i, uint32_t& hash, uint32_t& bad) { const uint64_t s = tile_sum[i]; hash ^= tile_hash[i]; bad |= tile_bad[i]; return s; },
+        [=](uint32_t i, uint64_t off) { tile_sum[i] = off; });
+    if (threadIdx.x == 0) zap_advance(ctl, nb_piece, all.sum, all.hash, all.bad, dst_capacity, (int)checksum, (int)seekable);
+}
+
+// Per tile: offsets[b] = archive offset of the piece's block b; with a seek table also its entry, ctl->first + b of the array.
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
+zxc_append_scatter_kernel(const uint32_t* __restrict__ sizes, uint32_t nb_piece, const uint64_t* __restrict__ tile_off,
+                          uint64_t* __restrict__ offsets, uint32_t* __restrict__ seek, uint32_t seekable, const zap_ctl_t* __restrict__ ctl) {
+    if (ctl->status < 0) return;
+    const uint32_t b0 = blockIdx.x * ZC_TILE_BLOCKS + threadIdx.x * ZD_PER_THREAD;
+    uint32_t sz[ZD_PER_THREAD], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
+        sz[j] = b0 + j < nb_piece ? sizes[b0 + j] : 0u;
+        sum += sz[j];
+    }
+    uint64_t run = zd_tile_offset(sum, tile_off[blockIdx.x]);
+    const uint64_t first = ctl->first;
+#pragma unroll
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
+        const uint32_t b = b0 + j;
+        if (b >= nb_piece) break;
+        offsets[b] = run;
+        run += sz[j];
+        if (seekable) seek[first + b] = sz[j];
+    }
+}
+
+// Compaction, one wave per block: block b's sizes[b] bytes at its slot -> dst + offsets[b]. While the status is no error every
+// size of the piece lies in [8, block_size + 64] and the blocks so far, this piece's included, end in front of the capacity
+// (zap_advance): nothing is written at or past offsets[b] + sizes[b].
+extern "C" __global__ void __launch_bounds__(256)
+zxc_append_gather_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride, const uint32_t* __restrict__ sizes,
+                         const uint64_t* __restrict__ offsets, uint8_t* __restrict__ dst, uint32_t nb_piece, const zap_ctl_t* __restrict__ ctl) {
+    if (ctl->status < 0) return;
+    const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
+    for (uint64_t b = (uint64_t)blockIdx.x * waves + (threadIdx.x >> 6); b < nb_piece; b += (uint64_t)gridDim.x * waves) {
+        copy_bytes(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
+    }
+}
+
+extern "C" __global__ void zxc_append_finish_kernel(zap_ctl_t* __restrict__ ctl, uint8_t* __restrict__ dst, uint64_t dst_capacity,
+                                                    uint64_t total, uint32_t block_size, uint32_t checksum, uint32_t seekable) {
+    if (threadIdx.x == 0) zap_finish(ctl, dst, dst_capacity, total, block_size, (int)checksum, (int)seekable);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+zxc_append_seek_kernel(const zap_ctl_t* __restrict__ ctl, uint8_t* __restrict__ dst, const uint32_t* __restrict__ seek, uint32_t nb) {
+    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += (uint64_t)gridDim.x * blockDim.x)
+        zap_put_seek_entry(ctl, dst, seek, b);
+}
+
+extern "C" __global__ void zxc_append_result_kernel(const zap_ctl_t* __restrict__ ctl, int64_t* __restrict__ result) {
+    if (threadIdx.x == 0) *result = ctl->status;
+}
+
+// ---------------------------------------------------------------- host side
+namespace {
+
+#define SESS_LIVE 0x7a78632d61707064ull  // a session between begin and end
+
+// What zxc_dev_cappend_t holds: the arguments of begin and the bytes appended. The work area's layout follows from them.
+struct Sess {
+    uint64_t magic;
+    uint8_t* dst;
+    uint64_t dst_capacity, max_total, max_piece;
+    uint8_t* base;  // the work area's aligned base
+    uint64_t total;
+    uint32_t block_size, level, checksum, seekable;
+    uint32_t cur;   // which of the two carry areas holds the waiting bytes
+    uint32_t rsv;
+};
+static_assert(sizeof(Sess) <= sizeof(zxc_dev_cappend_t), "the session fits the caller's struct");
+
+// Options as zxc_mi355x_compress_device reads them (frame_plan of zxc_frame_device.hip), in its order.
+int ap_opts(const zxc_compress_opts_t* opts, Sess* s) {
+    if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    int level = (opts && opts->level > 0) ? opts->level : 3;
+    if (level > 7) level = 7;
+    const uint64_t bs = (opts && opts->block_size > 0) ? (uint64_t)opts->block_size : 512u * 1024u;
+    if (!zc_block_size_ok(bs)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    s->block_size = (uint32_t)bs;
+    s->level = (uint32_t)level;
+    s->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
+    s->seekable = (opts && opts->seekable) ? 1u : 0u;
+    return ZXC_OK;
+}
+int ap_shape(const Sess& s, zap_shape_t* sh) {
+    return zap_shape(s.max_total, s.max_piece, s.block_size, zxc_mi355x_encode_slot_stride(s.block_size), (int)s.seekable, sh);
+}
+
+// One piece behind its plan: src is the piece's first byte (not read when the plan has no copy and no direct job).
+int ap_piece(const Sess& s, const zap_shape_t& sh, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+    uint8_t* base = s.base;
+    zap_ctl_t* ctl = (zap_ctl_t*)base;
+    uint64_t* tile_sum = (uint64_t*)(base + sh.o_tile_sum);
+    uint32_t* tile_hash = (uint32_t*)(base + sh.o_tile_hash);
+    uint32_t* tile_bad = (uint32_t*)(base + sh.o_tile_bad);
+    zxc_enc_job_t* jobs = (zxc_enc_job_t*)(base + sh.o_jobs);
+    uint32_t* sizes = (uint32_t*)(base + sh.o_sizes);
+    uint64_t* offsets = (uint64_t*)(base + sh.o_offsets);
+    uint32_t* seek = (uint32_t*)(base + sh.o_seek);
+    uint8_t* slots = base + sh.o_slots;
+
+    const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
+    const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
+    hipLaunchKernelGGL(zxc_append_prep_kernel, dim3(groups), dim3(256), 0, st, src, p, base + sh.o_carry[s.cur], base + sh.o_carry[s.cur ^ 1u],
+                       base + sh.o_stage, jobs);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    if (!p.nb) return ZXC_OK;
+    const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
+    if (rc != ZXC_OK) return rc;
+    const uint32_t n_tiles = (p.nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS;
+    hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint8_t*)slots, sh.slot_stride,
+                       (const uint32_t*)sizes, p.nb, s.block_size, s.checksum, tile_sum, tile_hash, tile_bad);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_append_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
+                       n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_append_scatter_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,
+                       (const uint64_t*)tile_sum, offsets, seek, s.seekable, (const zap_ctl_t*)ctl);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const uint32_t waves = (p.nb + 3u) / 4u < 65536u ? (p.nb + 3u) / 4u : 65536u;
+    hipLaunchKernelGGL(zxc_append_gather_kernel, dim3(waves), dim3(256), 0, st, (const uint8_t*)slots, sh.slot_stride, (const uint32_t*)sizes,
+                       (const uint64_t*)offsets, s.dst, p.nb, (const zap_ctl_t*)ctl);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t zxc_mi355x_compress_append_device_work_size(uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts) {
+    Sess s;
+    zap_shape_t sh;
+    if (ap_opts(opts, &s) != ZXC_OK) return 0u;
+    s.max_total = max_total; s.max_piece = max_piece;
+    return ap_shape(s, &sh) == 0 ? sh.bytes : 0u;
+}
+
+int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total, uint64_t max_piece,
+                                     const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size, void* stream) {
+    if (!cs || !d_dst || !d_work) return ZXC_ERROR_NULL_INPUT;
+    Sess s = {};
+    const int orc = ap_opts(opts, &s);
+    if (orc != ZXC_OK) return orc;
+    s.dst = (uint8_t*)d_dst; s.dst_capacity = dst_capacity; s.max_total = max_total; s.max_piece = max_piece;
+    s.base = zd_work_base(d_work);
+    zap_shape_t sh;
+    const int src = ap_shape(s, &sh);
+    if (src != 0) return src;
+    if (work_size < sh.bytes) return ZXC_ERROR_MEMORY;
+    if (dst_capacity < zc_known_size(0u, (int)s.checksum, (int)s.seekable)) return ZXC_ERROR_DST_TOO_SMALL;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_append_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (zap_ctl_t*)s.base);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    s.magic = SESS_LIVE;
+    memset(cs, 0, sizeof *cs);
+    memcpy(cs, &s, sizeof s);
+    return ZXC_OK;
+}
+
+int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, uint64_t n, void* stream) {
+    if (!cs || (n > 0 && !d_src)) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, cs, sizeof s);
+    if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (n > s.max_total - s.total) return ZXC_ERROR_OVERFLOW;
+    if (n == 0) return ZXC_OK;
+    zap_shape_t sh;
+    if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    // Pieces are independent but for the state, so piece by piece gives the archive of one piece over all the bytes. A piece's
+    // areas, jobs and slots are written and consumed in stream order before the next piece overwrites them. Every piece but the
+    // last ends on a block boundary of the archive.
+    const uint8_t* src = (const uint8_t*)d_src;
+    uint64_t left = n;
+    int rc = ZXC_OK;
+    while (left && rc == ZXC_OK) {
+        const uint32_t carry = (uint32_t)(s.total % s.block_size);
+        const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
+        zap_piece_t p;
+        zap_plan_piece(carry, m, s.block_size, &p);
+        rc = ap_piece(s, sh, src, p, (hipStream_t)stream);
+        if (p.swap) s.cur ^= 1u;
+        s.total += m; src += m; left -= m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;  // part of the append may be enqueued: the session cannot go on
+    memcpy(cs, &s, sizeof s);
+    return rc;
+}
+
+int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream) {
+    if (!cs || !d_result) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, cs, sizeof s);
+    if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
+    memset(cs, 0, sizeof *cs);  // spent, whatever happens below
+    zap_shape_t sh;
+    if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;
+    const hipStream_t st = (hipStream_t)stream;
+    zap_ctl_t* ctl = (zap_ctl_t*)s.base;
+    zap_piece_t p;
+    zap_plan_end((uint32_t)(s.total % s.block_size), s.block_size, &p);
+    if (p.nb) {
+        const int rc = ap_piece(s, sh, NULL, p, st);
+        if (rc != ZXC_OK) return rc;
+    }
+    hipLaunchKernelGGL(zxc_append_finish_kernel, dim3(1), dim3(64), 0, st, ctl, s.dst, s.dst_capacity, s.total, s.block_size, s.checksum, s.seekable);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const uint64_t nb = s.total / s.block_size + (s.total % s.block_size != 0);  // <= 2^31 - 1 (begin)
+    if (s.seekable && nb) {
+        const uint32_t groups = (nb + 255u) / 256u < 4096u ? (uint32_t)((nb + 255u) / 256u) : 4096u;
+        hipLaunchKernelGGL(zxc_append_seek_kernel, dim3(groups), dim3(256), 0, st, (const zap_ctl_t*)ctl, s.dst,
+                           (const uint32_t*)(s.base + sh.o_seek), (uint32_t)nb);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    hipLaunchKernelGGL(zxc_append_result_kernel, dim3(1), dim3(64), 0, st, (const zap_ctl_t*)ctl, d_result);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
+// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
 // slot and the host-side plumbing of an entry point.
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //
@@ -118,6 +118,13 @@ __device__ __forceinline__ void zd_copy_chunk(uint8_t* __restrict__ d, const uin
         }
     }
 }
+
+// ---------------------------------------------------------------- a kernel two files launch
+// zxc_frame_device.hip defines it; zxc_append_device.hip launches it per piece. Declared once, here, which both include: a
+// definition that departs from this is a conflicting redeclaration and does not compile (as zxc_kernels.h).
+extern "C" __global__ void zxc_frame_tiles_kernel(const uint8_t* slots, uint32_t slot_stride, const uint32_t* sizes, uint32_t nb,
+                                                  uint32_t block_size, uint32_t checksum, uint64_t* tile_sum, uint32_t* tile_hash,
+                                                  uint32_t* tile_bad);
 
 // ---------------------------------------------------------------- host side of an entry point
 // hidden entry point of zxc_hip_shim.hip (decode_launch)

@@ -517,6 +517,87 @@ ZXC_EXPORT int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_d
 ZXC_EXPORT int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, uint64_t n, void* stream);
 ZXC_EXPORT int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream);
 
+/* ---- one archive into many pieces, device to device (zxc_amd/csrc/zxc_take_device.hip, rules in zxc_amd/csrc/zxc_take.h) ----
+ * zxc_mi355x_decompress_device wants one contiguous, 16-byte aligned destination of the whole decoded size: whoever wrote an
+ * archive from a list of tensors with the session above needs a second copy of everything in HBM to read it back, and a device
+ * copy per tensor. A take session is the mirror image of the append session and the device counterpart of pulling from
+ * zxc_dstream_*: begin parses the archive once, every take delivers the next n decoded bytes to a destination of its own (the
+ * tensors of a state dict, or one buffer that is reused layer by layer), end writes one result word. */
+
+/* The session: a host struct the caller owns, with no allocation behind it. begin fills it, end spends it; it may be dropped at
+ * any time (what is enqueued runs on). One session is one thread's at a time. */
+typedef struct zxc_dev_dtake { uint64_t opaque[16]; } zxc_dev_dtake_t;
+
+/* Bytes of device scratch a session needs; 0 for arguments begin would refuse (src_size < 28, block_size, max_piece < block_size,
+ * more than 2^31 - 2 blocks in dst_capacity or jobs in a chunk). Does not depend on opts or a dictionary. dst_capacity is the
+ * number of bytes the takes will ask for in all, max_piece the most a take works on at a time: a take of more is processed in
+ * chunks of at most max_piece bytes. With n_jobs = ceil(dst_capacity / block_size) + 1 and J = max_piece / block_size + 2 the size
+ * is at most 56 x n_jobs + 16 x ceil(n_jobs / 1024) + J x (block_size + 64 + 48) + 2 x (block_size + 64) + 4096: per block of the
+ * capacity what zxc_mi355x_decompress_device keeps (two job tables and two status tables, see checksum_enabled there; three
+ * words per tile of 1024 jobs), per job of a chunk a slot and its entry in two chunk tables, two carry slots. It grows with
+ * dst_capacity exactly as zxc_mi355x_decompress_device_work_size does. */
+ZXC_EXPORT uint64_t zxc_mi355x_decompress_take_device_work_size(uint64_t src_size, uint64_t dst_capacity, uint64_t max_piece,
+                                                                uint32_t block_size);
+
+/* begin, takes of dst_capacity bytes in all, end: the session decodes the complete v8 archive d_src[0, src_size) as if into one
+ * destination of dst_capacity bytes that the caller hands over in pieces. dst_capacity plays exactly the role it has in
+ * zxc_mi355x_decompress_device: the caller knows it as the writer, or from zxc_mi355x_frame_info_device. Take k delivers decoded
+ * bytes [pos_k, pos_k + n_k) to d_dst_k[0, n_k), pos_k being the sum of the earlier n. *d_result (device memory) is written once,
+ * last, by end: what zxc_mi355x_decompress_device (after the _dict begin: zxc_mi355x_decompress_dict_device) stores for the same
+ * archive, dst_capacity, block_size, options and dictionary, that is the decoded size or the negative zxc_error_t with that
+ * call's precedence and its two departures (a header block size other than block_size is ZXC_ERROR_BAD_BLOCK_SIZE, an irregular
+ * frame ZXC_ERROR_GPU_UNSUPPORTED). On success the pieces, concatenated, are the bytes that call writes. dst_capacity == 0 is the
+ * empty-frame probe: begin, then end.
+ * Everything is asynchronous on `stream`: no host synchronisation, no device allocation of the session's own (the decode launch
+ * keeps its per-stream buffers as it does for zxc_mi355x_decode_blocks_device). The calls of one session must be in stream order
+ * with each other (one stream, or the caller's events); sessions with different work areas may run concurrently. d_work (any
+ * alignment) is the session's from begin until *d_result is written. d_src is never written and must be READABLE up to src_size
+ * + 64, as for zxc_mi355x_decompress_device, until then. A d_dst may be reused or freed, in stream order, behind its take.
+ * begin enqueues the container stages of zxc_mi355x_decompress_device once, for n_jobs = ceil(dst_capacity / block_size) + 1
+ * (clear, head, tiles, scan, scatter, walk; a non-seekable archive, or one whose table disagrees with its headers, takes the
+ * header walk); the block index and one status word per block stay in d_work for the session. The host knows block_size, pos and
+ * every n, so the plan of every take is the host's and nothing about the shape is decided on the device. d_dst of a take may have
+ * any alignment. A block is decoded straight into the piece only when it lies wholly inside the piece, its place
+ * d_dst + (i x block_size - pos) is 16-byte aligned and its slot plus 32 bytes ends inside the piece,
+ * (i + 1) x block_size - pos + 32 <= n (the decoders store 16 bytes at a time; the rule of zxc_mi355x_decompress_batch_device);
+ * every other block goes through a slot of d_work and a copy of min(decoded size, bytes wanted of it) bytes. A block that a take
+ * ends inside is decoded once, into one of two carry slots that take turns; that take copies the block's head out and the next
+ * takes copy their parts out of the same slot (any number of takes may lie wholly inside one block: they only copy). A take of
+ * more than max_piece bytes is a loop of enqueues over chunks cut on the archive's block boundaries, each with at most J jobs and,
+ * where the blocks cannot be decoded in place, J slots reused in stream order. Every block of the archive is decoded exactly once
+ * per session. All copies of a chunk are enqueued behind its decode launches. With opts->checksum_enabled every chunk enqueues
+ * the decode launch over two tables (verify_trailer 0 and 1), of which the head stage filled one, as in that call.
+ * end decodes the one job behind the capacity, block n_max, into a slot (only its status counts: it lets a failing block behind
+ * a full destination keep its precedence over DST_TOO_SMALL), then runs that call's events pass over the whole status table and
+ * its result kernel. The verdict is taken at end because it is the first event in archive order over all blocks.
+ * Guarantees: nothing is written outside [d_dst, d_dst + n) of each take and d_work. After an error, or at and past the decoded
+ * size when the archive is shorter than dst_capacity, the bytes inside the pieces are undefined. After a file-header error
+ * (dictionary errors included) no block is decoded and no piece is written.
+ * opts may be NULL; only checksum_enabled and dict are read. opts->dict != NULL is ZXC_ERROR_GPU_UNSUPPORTED: a dictionary in
+ * device memory goes through zxc_mi355x_decompress_begin_dict_device, with the DICT_REQUIRED / DICT_MISMATCH rules of
+ * zxc_mi355x_decompress_dict_device; a NULL dict, or one of size 0, behaves as the sibling.
+ * Synchronous errors, before any device is touched, in this order. begin: NULL ds / d_src / d_work -> ZXC_ERROR_NULL_INPUT;
+ * src_size < 28 -> ZXC_ERROR_SRC_TOO_SMALL; block_size not a power of two in [4 KiB, 2 MiB], max_piece < block_size, more than
+ * 2^31 - 2 blocks in dst_capacity or jobs in a chunk -> ZXC_ERROR_BAD_BLOCK_SIZE; opts->dict -> ZXC_ERROR_GPU_UNSUPPORTED; the
+ * _dict begin: dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE, NULL d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT;
+ * work_size too small -> ZXC_ERROR_MEMORY; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE. A refused begin leaves the struct
+ * alone. take: NULL ds, NULL d_dst with n > 0 -> ZXC_ERROR_NULL_INPUT; a session that was never begun or is ended ->
+ * ZXC_ERROR_NULL_INPUT; bytes so far + n > dst_capacity (compared without overflow) -> ZXC_ERROR_OVERFLOW, with nothing enqueued
+ * and the session as it was; n == 0 is ZXC_OK and enqueues nothing. end: NULL ds / d_result, a session never begun or ended ->
+ * ZXC_ERROR_NULL_INPUT; fewer than dst_capacity bytes taken -> ZXC_ERROR_DST_TOO_SMALL, with nothing enqueued and the session as
+ * it was (the verdict needs every block's status: the caller may take the rest and end again); afterwards the struct is spent. A
+ * launch failure (ZXC_ERROR_GPU_UNAVAILABLE, ZXC_ERROR_MEMORY) in take or end leaves part of the work enqueued: the session is
+ * spent and *d_result is not written. */
+ZXC_EXPORT int zxc_mi355x_decompress_begin_device(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size, uint64_t dst_capacity,
+                                                  uint64_t max_piece, uint32_t block_size, const zxc_decompress_opts_t* opts,
+                                                  void* d_work, uint64_t work_size, void* stream);
+ZXC_EXPORT int zxc_mi355x_decompress_begin_dict_device(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size,
+                                                       uint64_t dst_capacity, uint64_t max_piece, uint32_t block_size,
+                                                       const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
+                                                       uint64_t work_size, void* stream);
+ZXC_EXPORT int zxc_mi355x_decompress_take_device(zxc_dev_dtake_t* ds, void* d_dst, uint64_t n, void* stream);
+ZXC_EXPORT int zxc_mi355x_decompress_end_device(zxc_dev_dtake_t* ds, int64_t* d_result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

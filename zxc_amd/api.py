@@ -588,6 +588,83 @@ def compress_begin_device(d_dst, dst_capacity, max_total, max_piece, d_work, wor
     return CompressAppendSession(cs)
 
 
+# ---- one archive into many pieces: a session (zxc_dev_dtake_t is a host struct of 16 words, caller-owned)
+class _DevDtake(C.Structure):  # zxc_dev_dtake_t
+    _fields_ = [("opaque", C.c_uint64 * 16)]
+
+
+def _bind_decompress_take_device(L):
+    L.zxc_mi355x_decompress_take_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_decompress_take_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
+    L.zxc_mi355x_decompress_begin_device.restype = C.c_int
+    L.zxc_mi355x_decompress_begin_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                     C.POINTER(_DecompressOpts), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_decompress_begin_dict_device.restype = C.c_int
+    L.zxc_mi355x_decompress_begin_dict_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                          C.POINTER(_DecompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64,
+                                                          C.c_void_p]
+    L.zxc_mi355x_decompress_take_device.restype = C.c_int
+    L.zxc_mi355x_decompress_take_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_decompress_end_device.restype = C.c_int
+    L.zxc_mi355x_decompress_end_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_void_p]
+    return L
+
+
+def decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_size):
+    """zxc_mi355x_decompress_take_device_work_size(): bytes of device scratch a session needs (0 for refused arguments)."""
+    return int(_bind_decompress_take_device(lib()).zxc_mi355x_decompress_take_device_work_size(src_size, dst_capacity, max_piece,
+                                                                                                block_size))
+
+
+class DecompressTakeSession:
+    """A session of zxc_mi355x_decompress_begin_device(): .take(d_dst, n) until dst_capacity bytes are taken, then .end(d_result)
+    once. Raw device pointers (ints), asynchronous on `stream`; the calls of one session must be in stream order with each other.
+    The decoded size or the negative zxc_error_t decompress_device would store lands in the int64 at d_result; a synchronous
+    failure raises ZxcError."""
+
+    def __init__(self, ds):
+        self._ds = ds
+
+    def take(self, d_dst, n, stream=0):
+        rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_take_device(C.byref(self._ds), C.c_void_p(d_dst or None), n,
+                                                                                   C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_decompress_take_device")
+
+    def end(self, d_result, stream=0):
+        rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_end_device(C.byref(self._ds), C.c_void_p(d_result or None),
+                                                                                  C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_decompress_end_device")
+
+
+def decompress_begin_device(d_src, src_size, dst_capacity, max_piece, block_size, d_work, work_size, checksum=False, stream=0):
+    """zxc_mi355x_decompress_begin_device(): -> a DecompressTakeSession that delivers the archive at d_src in the pieces it is
+    asked for; the work size is decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_size)."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    ds = _DevDtake()
+    rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_begin_device(
+        C.byref(ds), C.c_void_p(d_src or None), src_size, dst_capacity, max_piece, block_size, C.byref(o), C.c_void_p(d_work or None),
+        work_size, C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_begin_device")
+    return DecompressTakeSession(ds)
+
+
+def decompress_begin_dict_device(d_src, src_size, dst_capacity, max_piece, block_size, dict_, d_work, work_size, checksum=False,
+                                 stream=0):
+    """zxc_mi355x_decompress_begin_dict_device(): decompress_begin_device with a dictionary in device memory (dict_ as in
+    compress_dict_device); the work size is the sibling's."""
+    o = _DecompressOpts(checksum_enabled=int(checksum))
+    ds = _DevDtake()
+    rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_begin_dict_device(
+        C.byref(ds), C.c_void_p(d_src or None), src_size, dst_capacity, max_piece, block_size, C.byref(o), _dev_dict(dict_),
+        C.c_void_p(d_work or None), work_size, C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_decompress_begin_dict_device")
+    return DecompressTakeSession(ds)
+
+
 # ---- FILE* callers (include/zxc_stream.h). ctypes has no FILE*, so the C library's fopen/fclose are used.
 _LIBC = None
 

@@ -1,5 +1,5 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
+// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_take_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
 // slot and the host-side plumbing of an entry point.
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "zxc_container.h"  // zc_ctl_t
 #include "zxc_dev.h"
 
 // threads of the three builds of the section decoder (zxc_pivco_dir.inc): launch bounds, loop strides and the shim's launches
@@ -85,6 +86,23 @@ extern "C" __global__ void zxc_encode_job_images_kernel(const uint8_t* src, zxc_
 extern "C" __global__ void zxc_block_offsets_kernel(uint32_t* sizes, uint64_t* offsets, uint32_t n_blocks, uint32_t max_size);
 extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32_t slot_stride, const uint32_t* sizes,
                                                     const uint64_t* offsets, uint8_t* out, uint32_t n_blocks);
+
+// ---------------------------------------------------------------- zxc_unframe_device.hip
+// The container stages of zxc_mi355x_decompress_device, which the take session (zxc_take_device.hip) launches as they are.
+extern "C" __global__ void zxc_unframe_head_kernel(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size,
+                                                   uint32_t want_verify, uint32_t n_jobs, zc_ctl_t* ctl, const uint32_t* dict_id);
+extern "C" __global__ void zxc_unframe_tiles_kernel(const uint8_t* src, const zc_ctl_t* ctl, uint64_t* tile_sum, uint32_t* tile_bad);
+extern "C" __global__ void zxc_unframe_scan_kernel(uint64_t* tile_sum, const uint32_t* tile_bad, uint32_t n_tiles, zc_ctl_t* ctl);
+extern "C" __global__ void zxc_unframe_scatter_kernel(const uint8_t* src, const zc_ctl_t* ctl, const uint64_t* tile_off, uint32_t block_size,
+                                                      uint32_t k_direct, uint32_t n_jobs, zxc_dev_job_t* jobs, uint32_t* tile_hash,
+                                                      uint32_t* tile_bad);
+extern "C" __global__ void zxc_unframe_walk_kernel(const uint8_t* src, uint64_t src_size, uint32_t block_size, uint32_t k_direct,
+                                                   uint32_t n_jobs, const uint32_t* tile_hash, const uint32_t* tile_bad, zxc_dev_job_t* jobs,
+                                                   zc_ctl_t* ctl);
+extern "C" __global__ void zxc_unframe_events_kernel(const int32_t* status, uint32_t block_size, uint32_t n_jobs, uint64_t dst_capacity,
+                                                     zc_ctl_t* ctl);
+extern "C" __global__ void zxc_unframe_result_kernel(const zc_ctl_t* ctl, const int32_t* status, uint32_t block_size, uint32_t n_jobs,
+                                                     int64_t* result);
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
 extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 #endif

@@ -1,0 +1,265 @@
+// zxc_take_device.hip — zxc_mi355x_decompress_begin_device / _take_device / _end_device: one v8 archive in device memory decoded
+// into a destination that is handed over in pieces, each in device memory. The device counterpart of pulling from zxc_dstream_*
+// (zxc_pstream_host.c) and the mirror image of the append session (zxc_append_device.hip).
+//
+// zxc_mi355x_decompress_device (zxc_unframe_device.hip) wants one contiguous, 16-byte aligned destination of the whole decoded
+// size. Here a session parses the container once, keeps the block index and one status word per block in its work area, and every
+// take decodes the next n bytes to a destination of its own. The host knows block_size, the position and every n, so it knows which
+// block lands where and each launch's exact grid: the plan of a chunk and its advance are the inline C of zxc_take.h, which the
+// CPU tests run as well. The container rules are zxc_container.h's and the container kernels zxc_unframe_device.hip's, as they are.
+//
+//   begin    clear, head, tiles, scan, scatter, walk: the stages of zxc_mi355x_decompress_device over n_jobs = ceil(capacity / bs) + 1
+//            jobs, whose out_off nobody reads                                                  -> control word, block index
+//
+// the stream order of one chunk (a take of at most max_piece bytes; a longer one is a loop of these):
+//
+//   plan     one thread per block the chunk decodes: its index entry with out_off into the piece, a slot or the next carry slot
+//   decode   the existing decode launch over the chunk's table (two tables with verification, as in that call); the statuses go
+//            to the blocks' words of the session's status table
+//   copy     carry slot -> head of the piece, slots -> piece, next carry slot -> tail of the piece: min(decoded size, bytes wanted)
+//            of each, one wavefront per 8 KiB of destination. Behind the decode launches: a block decoded straight into the piece
+//            may store up to 32 bytes behind itself, into what a copy fills.
+//
+// and of `end`: block n_max, the one job behind the capacity, decoded into a slot for its status; then
+//
+//   events   zxc_unframe_events_kernel over the whole status table
+//   result   zxc_unframe_result_kernel: *d_result, written once, after everything above
+//
+// No workgroup waits for another: every dependency is the stream order between launches, and every stage is predicated on the
+// control word.
+#include <string.h>
+
+#include "zxc_device_util.h"  // zd_copy_chunk, the host-side plumbing
+#include "zxc_kernels.h"      // the container stages of zxc_unframe_device.hip
+#include "zxc_take.h"
+
+static_assert(ZT_COPY_CHUNK == ZD_COPY_CHUNK, "the shape counts the chunks zd_copy_chunk moves");
+static_assert(2 * sizeof(zxc_dev_job_t) + 2 * 4 == ZT_BLOCK_BYTES && 2 * sizeof(zxc_dev_job_t) == ZT_JOB_BYTES, "the documented work size");
+static_assert(sizeof(zc_ctl_t) <= 256, "the state's place at the start of the work area");
+
+// ---------------------------------------------------------------- kernels
+// Job j of the chunk is block c.first + j of the index (both tables: the head stage left one of them empty), decoded where the
+// plan says. The launch's d_out is one base below the piece and the work area: piece = base + dst_rel, carry slot s = base +
+// carry_rel[s], slot i = base + slots_rel + i slot_stride. c.first + c.nb <= n_jobs (the takes end at the capacity; `end` asks
+// for the last job), c.nb <= J.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_take_plan_kernel(const zxc_dev_job_t* __restrict__ index, uint32_t n_jobs, uint32_t tables, zt_chunk_t c, uint64_t dst_rel,
+                     uint64_t carry_rel0, uint64_t carry_rel1, uint64_t slots_rel, uint32_t slot_stride, uint32_t J,
+                     zxc_dev_job_t* __restrict__ cjobs) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= c.nb || j >= J || c.first + j >= n_jobs) return;
+    const zt_place_t p = zt_job_place(&c, j);
+    const uint64_t out_off = p.kind == ZT_DIRECT ? dst_rel + p.at
+                             : p.kind == ZT_SLOT ? slots_rel + (uint64_t)p.slot * slot_stride
+                                                 : (p.slot ? carry_rel1 : carry_rel0);
+    for (uint32_t tb = 0; tb < tables; tb++) {
+        zxc_dev_job_t job = index[(uint64_t)tb * n_jobs + c.first + j];
+        job.out_off = out_off;
+        cjobs[(uint64_t)tb * J + j] = job;
+    }
+}
+
+// One wavefront per (copy, 8 KiB of destination), as in zxc_batch_copy_kernel: copy k of the plan moves min(decoded size, bytes
+// wanted) of its block from the slot or carry slot to its place in the piece, at any alignment. Most units are empty (blocks
+// decoded straight, chunks behind a short copy) and end at once. A block the chain does not have moves nothing.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_take_copy_kernel(const uint8_t* __restrict__ carry0, const uint8_t* __restrict__ carry1, const uint8_t* __restrict__ slots,
+                     uint32_t slot_stride, zt_chunk_t c, const int32_t* __restrict__ status, uint32_t n_jobs,
+                     const zc_ctl_t* __restrict__ ctl, uint32_t chunks, uint8_t* __restrict__ dst) {
+    if (ctl->final) return;
+    const uint32_t lane = threadIdx.x & 63u, found = ctl->found;
+    const int32_t* st = status + (uint64_t)ctl->sel * n_jobs;
+    const uint64_t units = ((uint64_t)c.nb + 1u) * chunks, waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t it = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); it < units; it += waves) {
+        const uint32_t k = (uint32_t)(it / chunks), ch = (uint32_t)(it - (uint64_t)k * chunks);
+        const zt_copy_t cp = zt_copy(&c, k);
+        if (cp.kind == ZT_NONE || cp.block >= found) continue;
+        const uint32_t n = zt_copy_bytes(&cp, st[cp.block], c.block_size);
+        uint8_t* d = dst + cp.to;
+        if (n == 0 || (uint64_t)ch * ZT_COPY_CHUNK >= ((uintptr_t)d & 15u) + n) continue;
+        const uint8_t* s = (cp.kind == ZT_SLOT ? slots + (uint64_t)cp.slot * slot_stride : cp.slot ? carry1 : carry0) + cp.from;
+        zd_copy_chunk(d, s, (int64_t)n, ch, lane);
+    }
+}
+
+// ---------------------------------------------------------------- host side
+namespace {
+
+#define TAKE_LIVE 0x7a78632d74616b65ull  // a session between begin and end
+
+// What zxc_dev_dtake_t holds: the arguments of begin and the bytes taken. The work area's layout follows from them.
+struct Sess {
+    uint64_t magic;
+    const uint8_t* src;
+    uint64_t src_size, dst_capacity, max_piece;
+    uint8_t* base;  // the work area's aligned base
+    uint64_t pos;   // bytes taken so far
+    const void *d_dict, *d_huf;
+    uint32_t dict_size, block_size, tables;
+    uint32_t cur;   // which of the two carry slots holds block pos / block_size
+};
+static_assert(sizeof(Sess) <= sizeof(zxc_dev_dtake_t), "the session fits the caller's struct");
+
+// plan and decode of one chunk: d = where its first byte goes (not touched when no block is decoded straight)
+int tk_decode(const Sess& s, const zt_shape_t& sh, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
+    if (!c.nb) return ZXC_OK;
+    uint8_t* base = s.base;
+    const zxc_dev_job_t* index = (const zxc_dev_job_t*)(base + sh.o_jobs);
+    zxc_dev_job_t* cjobs = (zxc_dev_job_t*)(base + sh.o_cjobs);
+    int32_t* status = (int32_t*)(base + sh.o_status);
+    // One decode launch for the piece and the work area: job offsets are 64-bit and counted from d_out, so d_out is the lower of
+    // the two; the piece's side is rounded down to 16, which keeps d_out and the out_off of every slot and of every block decoded
+    // straight (whose place is 16-byte aligned) multiples of 16.
+    uint8_t* work = base + sh.o_carry[0];
+    uint8_t* lo = (uint8_t*)((uintptr_t)d & ~(uintptr_t)15u);
+    uint8_t* out = (c.n_direct && lo < work) ? lo : work;
+    const uint64_t dst_rel = c.n_direct ? (uint64_t)(d - out) : 0u;
+    hipLaunchKernelGGL(zxc_take_plan_kernel, dim3((c.nb + 255u) / 256u), dim3(256), 0, st, index, sh.n_jobs, s.tables, c, dst_rel,
+                       (uint64_t)(base + sh.o_carry[0] - out), (uint64_t)(base + sh.o_carry[1] - out), (uint64_t)(base + sh.o_slots - out),
+                       sh.slot_stride, sh.J, cjobs);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    for (uint32_t tb = 0; tb < s.tables; tb++) {
+        const int rc = zxc_hip_decode_blocks(s.src, cjobs + (uint64_t)tb * sh.J, c.nb, out, status + (uint64_t)tb * sh.n_jobs + c.first,
+                                             s.block_size, (int)tb, s.d_dict, s.dict_size, s.d_huf, 0u, (void*)st);
+        if (rc != ZXC_OK) return rc;
+    }
+    return ZXC_OK;
+}
+
+// One chunk behind its plan: decode, then the copies.
+int tk_chunk(const Sess& s, const zt_shape_t& sh, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
+    const int rc = tk_decode(s, sh, d, c, st);
+    if (rc != ZXC_OK) return rc;
+    if (!c.head && c.nb == c.n_direct) return ZXC_OK;  // every byte lies in a block decoded straight
+    uint8_t* base = s.base;
+    const uint64_t groups = (((uint64_t)c.nb + 1u) * sh.copy_chunks + 3u) / 4u;
+    hipLaunchKernelGGL(zxc_take_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
+                       (const uint8_t*)(base + sh.o_carry[0]), (const uint8_t*)(base + sh.o_carry[1]), (const uint8_t*)(base + sh.o_slots),
+                       sh.slot_stride, c, (const int32_t*)(base + sh.o_status), sh.n_jobs, (const zc_ctl_t*)base, sh.copy_chunks, d);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+// Both begins. dict == NULL: the one that takes no dictionary.
+int tk_begin(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size, uint64_t dst_capacity, uint64_t max_piece, uint32_t block_size,
+             const zxc_decompress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, void* stream) {
+    if (!ds || !d_src || !d_work) return ZXC_ERROR_NULL_INPUT;
+    if (src_size < ZC_FILE_HDR + ZC_FOOTER) return ZXC_ERROR_SRC_TOO_SMALL;
+    zt_shape_t sh;
+    if (zt_shape(dst_capacity, max_piece, block_size, &sh) != 0) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    const int drc = dict_arg(&dict);
+    if (drc != ZXC_OK) return drc;
+    if (work_size < sh.bytes) return ZXC_ERROR_MEMORY;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
+
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t want_verify = (opts && opts->checksum_enabled) ? 1u : 0u;
+    Sess s = {};
+    s.src = (const uint8_t*)d_src; s.src_size = src_size; s.dst_capacity = dst_capacity; s.max_piece = max_piece;
+    s.base = zd_work_base(d_work);
+    s.d_dict = dict ? dict->d_content : NULL; s.d_huf = dict ? dict->d_huf : NULL; s.dict_size = dict ? dict->size : 0u;
+    s.block_size = block_size; s.tables = 1u + want_verify;
+    uint8_t* base = s.base;
+    zc_ctl_t* ctl = (zc_ctl_t*)base;
+    uint64_t* tile_sum = (uint64_t*)(base + sh.o_tile_sum);
+    uint32_t* tile_hash = (uint32_t*)(base + sh.o_tile_hash);
+    uint32_t* tile_bad = (uint32_t*)(base + sh.o_tile_bad);
+    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + sh.o_jobs);
+
+    // The container stages of zxc_mi355x_decompress_device. k_direct = n_jobs: every entry's out_off is its block's place in one
+    // destination, which no take reads (the chunk plan writes its own).
+    if (hipMemsetAsync(jobs, 0, (size_t)s.tables * sh.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, s.src, src_size, dst_capacity, block_size, want_verify, sh.n_jobs, ctl,
+                       dict ? dict->d_id : (const uint32_t*)NULL);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    if (dst_capacity > 0) {  // (the empty-frame probe is answered by the head stage alone)
+        hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(sh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, s.src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
+        hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_bad, sh.n_tiles, ctl);
+        hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(sh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, s.src, (const zc_ctl_t*)ctl,
+                           (const uint64_t*)tile_sum, block_size, sh.n_jobs, sh.n_jobs, jobs, tile_hash, tile_bad);
+        hipLaunchKernelGGL(zxc_unframe_walk_kernel, dim3(1), dim3(256), 0, st, s.src, src_size, block_size, sh.n_jobs, sh.n_jobs,
+                           (const uint32_t*)tile_hash, (const uint32_t*)tile_bad, jobs, ctl);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    s.magic = TAKE_LIVE;
+    memset(ds, 0, sizeof *ds);
+    memcpy(ds, &s, sizeof s);
+    return ZXC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t zxc_mi355x_decompress_take_device_work_size(uint64_t src_size, uint64_t dst_capacity, uint64_t max_piece, uint32_t block_size) {
+    zt_shape_t sh;
+    if (src_size < ZC_FILE_HDR + ZC_FOOTER || zt_shape(dst_capacity, max_piece, block_size, &sh) != 0) return 0u;
+    return sh.bytes;
+}
+
+int zxc_mi355x_decompress_begin_device(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size, uint64_t dst_capacity, uint64_t max_piece,
+                                       uint32_t block_size, const zxc_decompress_opts_t* opts, void* d_work, uint64_t work_size,
+                                       void* stream) {
+    return tk_begin(ds, d_src, src_size, dst_capacity, max_piece, block_size, opts, NULL, d_work, work_size, stream);
+}
+
+int zxc_mi355x_decompress_begin_dict_device(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size, uint64_t dst_capacity,
+                                            uint64_t max_piece, uint32_t block_size, const zxc_decompress_opts_t* opts,
+                                            const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, void* stream) {
+    return tk_begin(ds, d_src, src_size, dst_capacity, max_piece, block_size, opts, dict, d_work, work_size, stream);
+}
+
+int zxc_mi355x_decompress_take_device(zxc_dev_dtake_t* ds, void* d_dst, uint64_t n, void* stream) {
+    if (!ds || (n > 0 && !d_dst)) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, ds, sizeof s);
+    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (n > s.dst_capacity - s.pos) return ZXC_ERROR_OVERFLOW;
+    if (n == 0) return ZXC_OK;
+    zt_shape_t sh;
+    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    // Chunk by chunk: a chunk's table and slots are written and consumed in stream order before the next chunk overwrites them.
+    // Every chunk but the last ends on a block boundary of the archive. The 32 bytes a block decoded straight may store behind
+    // itself stay inside the take: a copy of the same chunk or a later chunk fills them afterwards.
+    uint8_t* d = (uint8_t*)d_dst;
+    uint64_t left = n;
+    int rc = ZXC_OK;
+    while (left && rc == ZXC_OK) {
+        const uint64_t m = zt_chunk_len(s.pos, left, s.max_piece, s.block_size);
+        zt_chunk_t c;
+        zt_plan_chunk(s.pos, m, left, (uint32_t)((uintptr_t)d & 15u), s.block_size, s.cur, &c);
+        rc = tk_chunk(s, sh, d, c, (hipStream_t)stream);
+        zt_advance(&c, &s.pos, &s.cur);
+        d += m; left -= m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;  // part of the take may be enqueued: the session cannot go on
+    memcpy(ds, &s, sizeof s);
+    return rc;
+}
+
+int zxc_mi355x_decompress_end_device(zxc_dev_dtake_t* ds, int64_t* d_result, void* stream) {
+    if (!ds || !d_result) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, ds, sizeof s);
+    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (s.pos < s.dst_capacity) return ZXC_ERROR_DST_TOO_SMALL;  // the verdict needs every block's status: take the rest, end again
+    memset(ds, 0, sizeof *ds);  // spent, whatever happens below
+    zt_shape_t sh;
+    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0) return ZXC_ERROR_NULL_INPUT;
+    const hipStream_t st = (hipStream_t)stream;
+    zc_ctl_t* ctl = (zc_ctl_t*)s.base;
+    const int32_t* status = (const int32_t*)(s.base + sh.o_status);
+    if (s.dst_capacity > 0) {
+        zt_chunk_t c;
+        zt_plan_extra(sh.n_jobs - 1u, s.block_size, s.cur, &c);
+        const int rc = tk_decode(s, sh, NULL, c, st);
+        if (rc != ZXC_OK) return rc;
+        const uint32_t groups = sh.n_tiles * 4u < 1024u ? sh.n_tiles * 4u : 1024u;
+        hipLaunchKernelGGL(zxc_unframe_events_kernel, dim3(groups), dim3(256), 0, st, status, s.block_size, sh.n_jobs, s.dst_capacity, ctl);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    hipLaunchKernelGGL(zxc_unframe_result_kernel, dim3(1), dim3(64), 0, st, (const zc_ctl_t*)ctl, status, s.block_size, sh.n_jobs, d_result);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 // dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launches get the dictionary (the plan then is
 // the dictionary kernel, one wavefront per block).
 #include "zxc_device_util.h"  // the tile passes, the copy, the host-side plumbing; zxc_container.h: the container rules
+#include "zxc_kernels.h"      // the stages the take session launches as well are declared there
 
 // ---------------------------------------------------------------- kernels
 extern "C" __global__ void __launch_bounds__(64)

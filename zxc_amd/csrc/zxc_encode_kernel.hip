@@ -91,6 +91,29 @@ __device__ __forceinline__ void wave_move_down(uint8_t* dst, const uint8_t* src,
     __builtin_amdgcn_wave_barrier();
 }
 
+// ... and the other way: dst above src (regions may overlap that way), from the top down, so that a step's stores lie above
+// every byte the following steps still load. Only the RLE path's rare relocation of the staging uses it.
+__device__ __forceinline__ void wave_move_up(uint8_t* dst, const uint8_t* src, uint32_t n, int lane) {
+    const uint32_t full = n & ~15u;
+    uint32_t tb = 0;
+    if (full + (uint32_t)lane < n) tb = src[full + lane];
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (full + (uint32_t)lane < n) dst[full + lane] = (uint8_t)tb;
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t hi = full; hi != 0u;) {
+        const uint32_t lo = hi > 1024u ? hi - 1024u : 0u;
+        const uint32_t o = lo + 16u * (uint32_t)lane;
+        v4u v = {0, 0, 0, 0};
+        if (o < hi) v = ld128(src + o);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        if (o < hi) __builtin_memcpy(dst + o, &v, 16);
+        __builtin_amdgcn_wave_barrier();
+        hi = lo;
+    }
+}
+
 // common prefix (bytes, 0..16) of two 16-byte groups (branch-free: the lanes of a wave all take different ways)
 __device__ __forceinline__ uint32_t prefix16(uint64_t a_lo, uint64_t a_hi, const v4u c) {
     const uint64_t x = a_lo ^ ((uint64_t)c.x | ((uint64_t)c.y << 32));
@@ -124,10 +147,10 @@ extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out) {
 // HB = log2(head entries), CWB = log2(chain ring entries) or 0 for "head only". depth / sufficient / lazy: the
 // reference's search_depth / sufficient_len / lazy probes (src/lib/zxc_internal.h:965-979), see the table below.
 // The body works on one block wherever it lies: `in` = the block's bytes (behind dict_size dictionary bytes, see below; any
-// alignment, every load goes through ld64 / ld128), nblk = the block's own byte count, slot = its slot, *size_out = where its size
+// alignment, every load goes through ld64 / ld128), nblk = the block's own byte count, slot = its slot of slot_bytes bytes, *size_out = where its size
 // goes, b = its index into huf_scratch. The two kinds of entry below (by value, job table) differ only in how they find these.
 template <uint32_t HSZ, uint32_t CWB, bool GHI, uint32_t NC, uint32_t U>
-__device__ __forceinline__ void encode_block_body(const uint8_t* __restrict__ in, uint32_t nblk, uint8_t* __restrict__ slot,
+__device__ __forceinline__ void encode_block_body(const uint8_t* __restrict__ in, uint32_t nblk, uint8_t* __restrict__ slot, uint32_t slot_bytes,
                                                   uint32_t* __restrict__ size_out, uint32_t b, uint32_t block_size,
                                                   uint32_t with_checksum, uint32_t depth, uint32_t sufficient, uint32_t lazy,
                                                   uint32_t dict_size, uint8_t* __restrict__ huf_scratch, uint32_t huf) {
@@ -552,16 +575,38 @@ __device__ __forceinline__ void encode_block_body(const uint8_t* __restrict__ in
     // (a remainder of 1-3 bytes is a raw token of its own), everything between them raw tokens of <= 128 bytes.
     uint32_t rle_size = 0;
     bool use_rle = false;
-    if (!GHI && !overflow && lit_count >= 64u) {
+    if (!GHI && !overflow && lit_count != 0u) {  // (any literal count, like the reference: zxc_compress.c:1275)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the literal section is read back with cached loads
         uint8_t* rle_out = lit_out + lit_count + 4u;         // (temp behind the literals; moved down when chosen)
-        const bool room = lit_base + 4u + 2u * lit_count + 8u <= block_size + 64u;
         // pass 0 sizes, pass 1 writes
-        for (uint32_t pass = 0; pass < 2u && room; pass++) {
+        for (uint32_t pass = 0; pass < 2u; pass++) {
             if (pass == 1u) {
                 const uint32_t tax = (lit_count * 8u) >> 8;  // ZXC_SS_TAX(lit_c, 8)
                 if (!(rle_size + tax < lit_count)) break;
+                // The coded section is written behind the literals, in front of the staging. Where the literals fill more than half
+                // the block it does not fit there: the staging then moves to the top of the slot first (tokens, offsets, extras packed,
+                // highest first: each lands above everything not yet moved). It always fits a slot of >= 2 block_size + 512 bytes
+                // (zxc_mi355x_encode_slot_stride; every caller sizes its slots with it): rle_size < lit_count, a sequence covers
+                // >= 5 bytes and owns <= 9 staged bytes, so 2 lit_count + 3 seq_count + ext_count < 2 block_size, and the fixed
+                // parts (28 + 4 + 16 + 32) stay below 512. A smaller slot cannot take this block's RLE section at all: the block
+                // then goes RAW through the overflow path instead of quietly keeping raw literals.
+                const uint32_t need = lit_base + lit_count + 4u + rle_size + 16u;
+                if (need > block_size + 64u) {
+                    const uint32_t staged = 3u * seq_count + ext_count;
+                    const uint32_t at = slot_bytes >= staged + 32u ? (slot_bytes - 16u - staged) & ~15u : 0u;
+                    if (at < need || at < block_size + 64u) { overflow = true; break; }
+                    __builtin_amdgcn_s_waitcnt(0);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the staging was written with ordinary stores
+                    wave_move_up(slot + at + 3u * seq_count, ext_st, ext_count, lane);
+                    wave_move_up(slot + at + seq_count, off_st, 2u * seq_count, lane);
+                    wave_move_up(slot + at, tok_st, seq_count, lane);
+                    tok_st = slot + at; off_st = tok_st + seq_count; ext_st = off_st + 2u * seq_count;
+                    __builtin_amdgcn_s_waitcnt(0);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                }
                 use_rle = true;
             }
             // wave-uniform walk over maximal runs: E bit j of a 64-byte tile = "byte j equals byte j + 1"
@@ -667,7 +712,7 @@ __device__ __forceinline__ void encode_block_body(const uint8_t* __restrict__ in
     }
     // ---- assemble: [8 B block header][12 B GLO/GHI header][4 B literal descriptor if RLE][literals]
     //      GLO: [tokens][offsets][extras][pad]   GHI: [sequence words][extras][pad]
-    const bool off8 = !GHI && max_off <= 256u && max_off != 0u;
+    const bool off8 = !GHI && max_off <= 256u;  // (reference: max biased offset <= 255, which a block without sequences meets too, zxc_compress.c:1632)
     const uint32_t sz_tok = GHI ? 4u * seq_count : (tok_huf ? huf_tok_size : seq_count);
     const uint32_t sz_off = GHI ? 0u : (off8 ? seq_count : 2u * seq_count);
     const uint32_t lit_sec = lit_huf ? huf_lit_size : (use_rle ? rle_size : lit_count);
@@ -767,7 +812,7 @@ __device__ __forceinline__ void encode_one_block(const uint8_t* __restrict__ src
     const uint8_t* in = src + (uint64_t)b * ((uint64_t)block_size + dict_size);
     const uint64_t remain = src_size - (uint64_t)b * block_size;
     const uint32_t nblk = remain < block_size ? (uint32_t)remain : block_size;  // bytes of the block itself
-    encode_block_body<HSZ, CWB, GHI, NC, U>(in, nblk, slots + (uint64_t)b * slot_stride, sizes + b, b, block_size, with_checksum, depth,
+    encode_block_body<HSZ, CWB, GHI, NC, U>(in, nblk, slots + (uint64_t)b * slot_stride, slot_stride, sizes + b, b, block_size, with_checksum, depth,
                                             sufficient, lazy, dict_size, huf_scratch, huf);
 }
 // Job b = blockIdx.x of a table: jobs[b].len bytes (at most block_size; the table's writer sees to that, and it is clamped here so
@@ -782,7 +827,7 @@ __device__ __forceinline__ void encode_one_job(const uint8_t* __restrict__ src, 
     const uint32_t len = uni(jobs[b].len);
     if (len == 0u) return;
     const uint64_t off = ((uint64_t)uni((uint32_t)(jobs[b].src_off >> 32)) << 32) | uni((uint32_t)jobs[b].src_off);
-    encode_block_body<HSZ, CWB, GHI, NC, U>(src + off, len < block_size ? len : block_size, slots + (uint64_t)b * slot_stride, sizes + b, b,
+    encode_block_body<HSZ, CWB, GHI, NC, U>(src + off, len < block_size ? len : block_size, slots + (uint64_t)b * slot_stride, slot_stride, sizes + b, b,
                                             block_size, with_checksum, depth, sufficient, lazy, dict_size, huf_scratch, huf);
 }
 

@@ -8,5 +8,7 @@ HIPCC=/opt/rocm/bin/hipcc
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-function -DZXC_EXPERIMENT"
 $HIPCC $F "$@" -c zxc_decode_kernel.hip -o build/var_$name/dk.o
 $HIPCC $F "$@" -c zxc_hip_shim.hip -o build/var_$name/shim.o   # (-DZXC_EXPERIMENT exports zxc_mi355x__set_debug)
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libzxc_$name.so build/var_$name/dk.o build/zxc_encode_kernel.o build/var_$name/shim.o build/zxc_host.o
+# (every other object as the product build left it: make -C zxc_amd/csrc first)
+others=$(ls build/*.o | grep -v -e zxc_decode_kernel.o -e zxc_hip_shim.o)
+$HIPCC --offload-arch=gfx950 -shared -fPIC -pthread -o ../libzxc_$name.so build/var_$name/dk.o build/var_$name/shim.o $others
 echo built ../libzxc_$name.so

@@ -1409,16 +1409,18 @@ zxc_decode_blocks_lean_pre_kernel(const uint8_t* __restrict__ comp, const zxc_de
 }
 
 // ------------------------------------------------------------------ per-block checksums beside the decode (round 6)
-// Nine blocks per wavefront (zxc_rapidhash.inc: group_checksum32), in launch order (neighbours are of similar weight). ck_bad[b] = 1 when
+// Nine blocks per wavefront (zxc_rapidhash.inc: group_checksum32), in SORTED order (neighbours are of similar weight, a wavefront lasts as
+// long as its largest block): slot s is sorted position s, found in order[] through zxc_dev_order_mix like the launch-order pass put it
+// there, so the mixed head of a long launch does not hand a wavefront nine weight classes. ck_bad[b] = 1 when
 // block b carries a checksum that does not match its payload — and only then: a block whose header the decode kernels refuse before they
 // would look at the checksum (too small, size beyond its bytes) keeps THEIR verdict (reference order: zxc_decompress.c:1655-1666).
 extern "C" __global__ void __launch_bounds__(64)
 zxc_block_checksum_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* __restrict__ jobs, uint32_t n_jobs,
-                          const uint32_t* __restrict__ order, uint8_t* __restrict__ ck_bad) {
+                          const uint32_t* __restrict__ order, uint8_t* __restrict__ ck_bad, uint32_t mix_slots) {
     const int lane = threadIdx.x;
     const uint32_t slot = blockIdx.x * 9u + (uint32_t)lane / 7u;
     const bool in = lane < 63 && slot < n_jobs;
-    const uint32_t b = in ? (order ? order[slot] : slot) : 0u;
+    const uint32_t b = in ? (order ? order[zxc_dev_order_mix(slot, n_jobs, mix_slots)] : slot) : 0u;
     const uint8_t* src = comp + jobs[b].comp_off;
     const uint32_t src_sz = in ? jobs[b].comp_size : 0u;
     uint32_t comp_sz = 0;
@@ -1439,9 +1441,11 @@ zxc_checksum_merge_kernel(const uint8_t* __restrict__ ck_bad, int32_t* __restric
 
 // ------------------------------------------------------------------ launch order
 // A launch ends when its slowest block ends, and block cost varies ~3x with the number of
-// sequences and the literal coding. For launches of many rounds the blocks are dispatched
-// heaviest-first (longest-processing-time order): a 64-bucket counting sort on a cost estimate
-// read from each block header. order[0 .. n) = job indices; hist[0..64) counts, hist[64..128) cursors.
+// sequences and the literal coding. The blocks are sorted heaviest-first (a 64-bucket counting sort on a
+// cost estimate read from each block header); a launch of at most two residencies of the lean kernel is
+// dispatched in that order (longest-processing-time order), a longer one keeps it for its last two
+// residencies only and deals the head so that every weight class is resident all the time
+// (zxc_dev_order_mix, zxc_dev.h). order[0 .. n) = job indices; hist[0..64) counts, hist[64..128) cursors.
 __device__ __forceinline__ uint32_t order_bucket(const uint8_t* __restrict__ comp, const zxc_dev_job_t& j, uint32_t block_size) {
     uint32_t cost = 0;
     if (j.comp_size >= 8u + 12u) {
@@ -1476,7 +1480,7 @@ zxc_order_scatter_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* 
                          uint32_t block_size, uint32_t* __restrict__ hist, uint32_t* __restrict__ order,
                          uint32_t* __restrict__ list, uint32_t trailer_bytes, zxc_dev_pre_t* __restrict__ pre,
                          uint32_t* __restrict__ ctl, uint32_t* __restrict__ pre_entries, zxc_dev_sec_t* __restrict__ secs,
-                         uint32_t pscratch_cap16, uint32_t cap, uint32_t rscratch_cap16) {
+                         uint32_t pscratch_cap16, uint32_t cap, uint32_t rscratch_cap16, uint32_t mix_slots) {
     __shared__ uint32_t cnt[64], base[64];
     __shared__ uint32_t wg_cnt[8], wg_base[8];  // 0: scratch units, 1: PRE blocks, 2: FULL blocks, 3..5: sections per size class, 6: RLE scratch units, 7: LEAN_RLE blocks
     __shared__ uint32_t wg_fit, wg_rle_fit;
@@ -1496,7 +1500,12 @@ zxc_order_scatter_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* 
         base[threadIdx.x] = cnt[threadIdx.x] ? s + atomicAdd(hist + 64u + threadIdx.x, cnt[threadIdx.x]) : 0u;
     }
     __syncthreads();
-    if (i < n_jobs) order[base[bk] + rank] = i;
+    // (sorted position -> launch index: the head of a long launch is mixed, its tail stays heaviest-first, zxc_dev.h)
+    uint32_t pos = i < n_jobs ? zxc_dev_order_mix(base[bk] + rank, n_jobs, mix_slots) : 0u;
+#ifdef ZXC_EXPERIMENT  // (tools/ordermix.py: file order under the two-pass plans)
+    if (mix_slots == 0xFFFFFFFFu) pos = i;
+#endif
+    if (i < n_jobs) order[pos] = i;
     if (!list) return;
     BlockClass c = {ZXC_DEV_CLS_LEAN, 0, 0, 3, 3, 0, 0, 0, 0, 0, 0};
     uint32_t my_off = 0, my_pre = 0, my_full = 0, my_lit = 0, my_tok = 0;
@@ -1589,7 +1598,7 @@ zxc_order_scatter_kernel(const uint8_t* __restrict__ comp, const zxc_dev_job_t* 
     pre[i].rc_tok = 0;
     pre[i].cls = cls;
     if (cls == ZXC_DEV_CLS_FULL) {
-        list[2u + wg_base[2] + my_full] = base[bk] + rank;
+        list[2u + wg_base[2] + my_full] = pos;
     } else if (cls == ZXC_DEV_CLS_PRE) {
         pre_entries[wg_base[1] + my_pre] = i;
         if (c.lit_cls < 3u) {

@@ -71,6 +71,33 @@ static inline zxc_dev_ord_layout_t zxc_dev_ord_layout(uint32_t n_jobs) {
     return l;
 }
 
+/* Launch order of a long launch, shared by the launch-order pass, the shim and the CPU emulator: sorted position pos (heaviest
+ * first, zxc_order_scatter_kernel's counting sort) -> index in order[]. The last T = min(n, 2 slots) sorted positions, the
+ * lightest blocks, stay where they are: they are the launch's tail, where heaviest-first still decides when it ends. The head
+ * H = n - T is dealt like a deck: its sorted run cut into ZXC_DEV_ORDER_MIX_ROWS rows (the first q of C, the others of C - 1
+ * positions, H = rows (C - 1) + q), read column by column, so every window of the launch holds every weight class. The row
+ * count is an odd prime: workgroup ids go round-robin to the 8 XCDs, and index c rows + r lands on XCD (5 c + r) mod 8, no
+ * XCD keeps a row. A bijection on [0, n); the identity for n <= 2 slots and for slots == 0 (no mixing). */
+#ifndef EXP_ORDER_MIX_ROWS
+#define ZXC_DEV_ORDER_MIX_ROWS 61u
+#else /* (A/B builds only, behind the gate of zxc_experiments.h) */
+#define ZXC_DEV_ORDER_MIX_ROWS EXP_ORDER_MIX_ROWS
+#endif
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline uint32_t zxc_dev_order_mix(uint32_t pos, uint32_t n, uint32_t slots) {
+    const uint64_t tail = 2ull * slots;
+    if (slots == 0u || n <= tail) return pos;
+    const uint32_t head = n - (uint32_t)tail, rows = ZXC_DEV_ORDER_MIX_ROWS;
+    if (pos >= head) return pos;
+    const uint32_t c_long = (head + rows - 1u) / rows, q = head - rows * (c_long - 1u); /* 1 <= q <= rows */
+    uint32_t r, c;
+    if (pos < q * c_long) { r = pos / c_long; c = pos % c_long; }
+    else { const uint32_t p = pos - q * c_long; r = q + p / (c_long - 1u); c = p % (c_long - 1u); } /* (q < rows: c_long >= 2) */
+    return c * rows + r;
+}
+
 /* Decode launch plans. TWO_PASS (no dictionary, no strict capacity): the lean kernel over every block beside the full kernel over
  * the blocks only it decodes, on helper streams; TWO_PASS_PRE: also the section kernels and the lean kernel's second entry. With
  * the checksums apart (ck_apart), a block whose checksum fails is still decoded into its own output slot: those bytes are

@@ -39,7 +39,7 @@ struct Ord {
 };
 static struct {
     Pool pool[ZXC_POOLS];
-    int cus, wg_per_cu;
+    int cus, wg_per_cu, lean_wg_per_cu;
     Ord ord[ZXC_ORDER_STREAMS];
 } g_dev[ZXC_MAX_DEVICES];
 static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER;
@@ -189,6 +189,10 @@ static int setup_pool(int dev, uint32_t block_size, Pool** pool_out, uint32_t* m
                              d.wg_per_cu <= 0 || d.wg_per_cu > 32))
         d.wg_per_cu = 32;
     *max_slots = (uint32_t)d.cus * (uint32_t)d.wg_per_cu;  // <= 8192
+    // the lean kernel's residency, which the launch order is mixed for (zxc_dev_order_mix)
+    if (d.lean_wg_per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.lean_wg_per_cu, zxc_decode_blocks_lean_kernel, 64, 0) != hipSuccess ||
+                                  d.lean_wg_per_cu <= 0 || d.lean_wg_per_cu > 32))
+        d.lean_wg_per_cu = 24;
     Pool& pool = *(*pool_out = &d.pool[__builtin_ctz(block_size) - 12]);
     if (pool.scratch) return ZXC_OK;
     const uint32_t stride = ZXC_DEV_SLOT_STRIDE(block_size);
@@ -253,7 +257,7 @@ static bool grow(void** p, size_t* cap, size_t bytes) {
 // What the kernels of one decode launch take. The pointers into the launch-order buffer are NULL where the plan has no use for them.
 struct Launch {
     const uint8_t* comp; const zxc_dev_job_t* jobs; uint32_t n; uint8_t* out; int32_t* status; uint32_t bs, cap_override;
-    zxc_dev_plan_t plan; hipStream_t s0; const Pool* pool; uint32_t max_slots, cus; Ord* o;
+    zxc_dev_plan_t plan; hipStream_t s0; const Pool* pool; uint32_t max_slots, cus, mix_slots; Ord* o;
     uint32_t *order, *list, *ctl, *pre_entries; zxc_dev_sec_t* secs; zxc_dev_pre_t* pre;
     uint8_t *ck_bad, *pscratch, *rscratch; uint32_t pscratch_cap16, rscratch_cap16;
 };
@@ -265,7 +269,7 @@ static void order_pass(const Launch& L) {
     hipLaunchKernelGGL(zxc_order_hist_kernel, dim3(g), dim3(256), 0, L.s0, L.comp, L.jobs, L.n, L.bs, L.o->buf);
     hipLaunchKernelGGL(zxc_order_scatter_kernel, dim3(g), dim3(256), 0, L.s0, L.comp, L.jobs, L.n, L.bs, L.o->buf, L.order, L.list,
                        L.plan.trailer_bytes & ~ZXC_DEV_TRAILER_ELSEWHERE, L.pre, L.ctl, L.pre_entries, L.secs, L.pscratch_cap16,
-                       L.cap_override ? L.cap_override : L.bs + 2112u, L.rscratch_cap16);
+                       L.cap_override ? L.cap_override : L.bs + 2112u, L.rscratch_cap16, L.mix_slots);
     if (L.ctl && L.o->hint) {  // (pinned: a stream-ordered copy, read by the next launch without waiting)
         (void)hipMemcpyAsync(L.o->hint, L.ctl + ZXC_DEV_CTL_WANTED, 4, hipMemcpyDeviceToHost, L.s0);
         (void)hipMemcpyAsync(L.o->hint + 1, L.ctl + ZXC_DEV_CTL_RLE_WANTED, 4, hipMemcpyDeviceToHost, L.s0);
@@ -313,7 +317,7 @@ static int enqueue_two_pass(const Launch& L) {
     launch_full(L, aux ? o.aux : s0, L.n < L.max_slots ? L.n : L.max_slots);
     const bool aux2 = L.plan.ck_apart && aux && fork_to(o, o.aux2);
     if (L.plan.ck_apart)
-        hipLaunchKernelGGL(zxc_block_checksum_kernel, dim3((L.n + 8u) / 9u), dim3(64), 0, aux2 ? o.aux2 : s0, L.comp, L.jobs, L.n, L.order, L.ck_bad);
+        hipLaunchKernelGGL(zxc_block_checksum_kernel, dim3((L.n + 8u) / 9u), dim3(64), 0, aux2 ? o.aux2 : s0, L.comp, L.jobs, L.n, L.order, L.ck_bad, L.mix_slots);
     launch_rle(L, s0);
     hipLaunchKernelGGL(zxc_decode_blocks_lean_kernel, dim3(L.n), dim3(64), 0, s0, L.comp, L.jobs, L.n, L.out, L.status, L.bs, L.order,
                        L.cap_override, L.plan.trailer_bytes, L.pre, L.rscratch);
@@ -380,7 +384,10 @@ static int decode_launch(const void* d_comp, const zxc_dev_job_t* d_jobs, uint32
                           hipMemsetAsync(o->buf + at.ctl, 0, ZXC_DEV_CTL_WORDS * 4u, s0) != hipSuccess;
     plan = zxc_dev_plan_choose(&in);  // settle
     Launch L = {(const uint8_t*)d_comp, d_jobs, n_jobs, (uint8_t*)d_out, d_status, block_size, cap_override, plan, s0, pool,
-                in.max_slots, (uint32_t)g_dev[dev].cus, o};
+                in.max_slots, (uint32_t)g_dev[dev].cus, (uint32_t)g_dev[dev].cus * (uint32_t)g_dev[dev].lean_wg_per_cu, o};
+#ifdef ZXC_EXPERIMENT  // (tools/ordermix.py: 0 = sorted, 0xFFFFFFFF = file order, else the residency the order is mixed for)
+    if (const char* e = getenv("ZXC_EXP_ORDER_SLOTS")) L.mix_slots = (uint32_t)strtoul(e, NULL, 0);
+#endif
     if (plan.ordered) L.order = o->buf + at.order;
     if (plan.kind >= ZXC_DEV_PLAN_TWO_PASS) {
         L.list = o->buf + at.list; L.ctl = o->buf + at.ctl; L.pre_entries = o->buf + at.pre_ent;

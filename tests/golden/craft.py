@@ -14,10 +14,11 @@ def _varint(v):
     return bytes([0xC0 | (v & 0x1F), (v >> 5) & 0xFF, v >> 13])
 
 
-def glo_block(oracle, seqs, literals, off8=False):
+def glo_block(oracle, seqs, literals, off8=False, ext=None):
     """One GLO block (type 1) with raw sections. seqs: [(ll, ml, off)], ml >= 5, off >= 1; literals: all literal bytes
-    (those the sequences consume, then the trailing ones)."""
-    tok = bytearray(); offs = bytearray(); ext = bytearray()
+    (those the sequences consume, then the trailing ones). ext: the extras section's bytes instead of the varints the
+    sequences ask for (damaged or truncated varints)."""
+    tok = bytearray(); offs = bytearray(); ext_given = ext; ext = bytearray()
     for ll, ml, off in seqs:
         m = ml - 5
         tok.append((min(ll, 15) << 4) | min(m, 15))
@@ -26,6 +27,8 @@ def glo_block(oracle, seqs, literals, off8=False):
             ext += _varint(ll - 15)
         if m >= 15:
             ext += _varint(m - 15)
+    if ext_given is not None:
+        ext = bytearray(ext_given)
     body = bytes(literals) + bytes(tok) + bytes(offs) + bytes(ext)
     pad = max(0, 32 - (len(tok) + len(offs) + len(ext)))   # FORMAT: at least 32 bytes behind the literal section
     payload = struct.pack("<IIBBBB", len(seqs), len(literals), 0, 0, 0, 1 if off8 else 0) + body + bytes(pad)
@@ -37,25 +40,47 @@ def glo_block(oracle, seqs, literals, off8=False):
     return bytes(hdr) + payload
 
 
-def frame(oracle, blocks, block_size_log2, total):
-    """File header + blocks + EOF block + footer (no checksums, no seek table)."""
+def with_trailer(oracle, blk):
+    """The block followed by its checksum trailer (docs/FORMAT.md §9: zxo_checksum32 over the payload behind the 8-byte block header)."""
+    oracle.lib.zxo_checksum32.restype = C.c_uint32
+    oracle.lib.zxo_checksum32.argtypes = [C.c_char_p, C.c_size_t]
+    payload = bytes(blk[8:])
+    return bytes(blk) + int(oracle.lib.zxo_checksum32(payload, len(payload))).to_bytes(4, "little")
+
+
+def frame(oracle, blocks, block_size_log2, total, checksum=False, seekable=False):
+    """File header + blocks + EOF block + footer. checksum: the blocks carry trailers (with_trailer) and the footer the rotated
+    xor of them; seekable: a seek table (block
+    type 254: every block's stored size) between the EOF block and the footer."""
     hdr = bytearray(16)
     hdr[0:4] = (0x9CB02EF5).to_bytes(4, "little")
     hdr[4] = 8
     hdr[5] = block_size_log2
+    hdr[6] = 0x80 if checksum else 0
     oracle.lib.zxo_hash16.argtypes = [C.c_char_p]
     oracle.lib.zxo_hash8.argtypes = [C.c_char_p]
     hdr[14:16] = int(oracle.lib.zxo_hash16(bytes(hdr))).to_bytes(2, "little")
     eof = bytearray(8)
     eof[0] = 255
     eof[7] = oracle.lib.zxo_hash8(bytes(eof))
-    return bytes(hdr) + b"".join(blocks) + bytes(eof) + int(total).to_bytes(8, "little") + (0).to_bytes(4, "little")
+    gh = 0
+    if checksum:
+        for b in blocks:
+            gh = (((gh << 1) | (gh >> 31)) & 0xFFFFFFFF) ^ int.from_bytes(b[-4:], "little")
+    sek = b""
+    if seekable and blocks:
+        sh = bytearray(8)
+        sh[0] = 254
+        sh[3:7] = struct.pack("<I", 4 * len(blocks))
+        sh[7] = oracle.lib.zxo_hash8(bytes(sh))
+        sek = bytes(sh) + b"".join(struct.pack("<I", len(b)) for b in blocks)
+    return bytes(hdr) + b"".join(blocks) + bytes(eof) + sek + int(total).to_bytes(8, "little") + gh.to_bytes(4, "little")
 
 
-def ghi_block(oracle, seqs, literals):
+def ghi_block(oracle, seqs, literals, ext=None):
     """One GHI block (type 2). seqs: [(ll, ml, off)], ml >= 5, 1 <= off <= 65536 (docs/FORMAT.md §5.3: 32-bit sequence words
-    LL << 24 | (ML - 5) << 16 | (off - 1), 255 = varint-extended)."""
-    words = bytearray(); ext = bytearray()
+    LL << 24 | (ML - 5) << 16 | (off - 1), 255 = varint-extended). ext: as for glo_block."""
+    words = bytearray(); ext_given = ext; ext = bytearray()
     for ll, ml, off in seqs:
         m = ml - 5
         words += struct.pack("<I", (min(ll, 255) << 24) | (min(m, 255) << 16) | (off - 1))
@@ -63,6 +88,8 @@ def ghi_block(oracle, seqs, literals):
             ext += _varint(ll - 255)
         if m >= 255:
             ext += _varint(m - 255)
+    if ext_given is not None:
+        ext = bytearray(ext_given)
     body = bytes(literals) + bytes(words) + bytes(ext)
     pad = max(0, 32 - (len(words) + len(ext)))
     payload = struct.pack("<IIBBBB", len(seqs), len(literals), 0, 0, 0, 0) + body + bytes(pad)

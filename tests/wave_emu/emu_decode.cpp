@@ -19,6 +19,13 @@ static size_t emu_rscratch_bytes = (size_t)4 << 20;  // scratch for the expanded
 extern "C" __attribute__((visibility("default"))) void emu_set_rscratch_bytes(size_t n) { emu_rscratch_bytes = n; }
 extern "C" __attribute__((visibility("default"))) uint32_t emu_last_section_count(int size_class) { return emu_last_secs[size_class]; }
 
+// path markers (ZXC_PATH, zxc_lds.h): lanes that passed each marker since the last reset
+extern "C" __attribute__((visibility("default"))) void emu_path_reset(void) { memset(emu::path_count, 0, sizeof(emu::path_count)); }
+extern "C" __attribute__((visibility("default"))) uint32_t emu_path_read(uint64_t* out, uint32_t n) {
+    for (uint32_t i = 0; i < n && i < (uint32_t)ZXC_PATH_COUNT; i++) out[i] = emu::path_count[i];
+    return (uint32_t)ZXC_PATH_COUNT;
+}
+
 // per-block checksums: 1 = by zxc_block_checksum_kernel beside the decode, merged into the statuses; 0 = inside the decode kernels
 static int emu_ck_apart = 1;
 extern "C" __attribute__((visibility("default"))) void emu_set_ck_apart(int on) { emu_ck_apart = on; }

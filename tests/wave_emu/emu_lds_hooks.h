@@ -14,6 +14,9 @@ void lds_read_unaligned(const void* p, void* out, unsigned size);
 template <typename T> inline T lds_ld(const void* p) { T v; lds_read(p, &v, sizeof(T)); return v; }
 template <typename T> inline void lds_st(void* p, T v) { lds_write(p, &v, sizeof(T), false); }
 }
+// path markers (zxc_lds.h): one counter per id, bumped by every lane that passes the marker
+namespace emu { extern uint64_t path_count[256]; }
+#define ZXC_PATH(id) ((void)++emu::path_count[(unsigned)(id)])
 typedef uint32_t emu_v4u __attribute__((ext_vector_type(4)));
 #define LDS_LD8(p) ((uint32_t)emu::lds_ld<uint8_t>((const void*)(p)))
 #define LDS_LD32(p) (emu::lds_ld<uint32_t>((const void*)(p)))

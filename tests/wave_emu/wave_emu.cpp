@@ -107,6 +107,7 @@ void trampoline() {
 }
 }  // namespace
 
+uint64_t path_count[256];  // ZXC_PATH counters (emu_lds_hooks.h): every library built over this file has them
 void lds_write(void* p, const void* data, unsigned size, bool is_or) {
     WLog w;
     w.addr = (uintptr_t)p;

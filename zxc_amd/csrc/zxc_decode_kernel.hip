@@ -212,10 +212,14 @@ __device__ void coop_copy(RingLds& L, const Out& O, uint32_t dpos, uint32_t spos
         if (lit) v = ld128(lit + o);
         else if (DICT && (int32_t)s < 0) {  // (partly) inside the dictionary: byte gather (rare)
             uint32_t w[4] = {0, 0, 0, 0};
+            ZXC_PATH(C_COPY_DICT_GATHER);
             for (uint32_t k = 0; k < 16u; k++) w[k >> 2] |= src_rd8<DICT>(L, O, s + k, ring_lo) << (8u * (k & 3u));
             v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
         } else if (s >= ring_lo) v = ring_rd128(L, s);
-        else v = far_rd128(O, s);
+        else {
+            ZXC_PATH(C_COPY_FAR);
+            v = far_rd128(O, s);
+        }
         ring_wr128_aligned(L, dpos + o, v);
     }
     const uint32_t tl = (n - h) & 15u;
@@ -249,7 +253,10 @@ __device__ void coop_match(RingLds& L, Out& O, uint32_t M, uint32_t ml, uint32_t
             flush_to(L, O, d + n, lane);
             __builtin_amdgcn_s_waitcnt(0);  // the next piece may read these bytes back from memory (distance > ring - piece)
         }
-        if (n == dist && dist < TILE_MAX) dist <<= 1;
+        if (n == dist && dist < TILE_MAX) {
+            if (lane == 0) ZXC_PATH(C_MATCH_DOUBLE);
+            dist <<= 1;
+        }
     }
 }
 
@@ -281,6 +288,7 @@ __device__ __forceinline__ uint32_t parse_varints(const uint8_t* ext, uint32_t e
     } else {
         lo8 = 0;
         hi4 = 0;
+        if (base < ext_size) ZXC_PATH(C_VARINT_TAIL);  // (a lane whose window holds the stream's last bytes)
         for (uint32_t k = 0; k < 11u; k++) {
             const uint32_t b = (base + k < ext_size) ? ld8(ext + base + k) : 0xFFu;
             if (k < 8u) lo8 |= (uint64_t)b << (8u * k);
@@ -333,6 +341,7 @@ __device__ __forceinline__ uint32_t parse_varints(const uint8_t* ext, uint32_t e
                 uint32_t val = (b0 < 0x80u) ? b0 : (b0 < 0xC0u) ? ((b0 & 0x3Fu) | (b1 << 6))
                                                                   : ((b0 & 0x1Fu) | (b1 << 5) | (b2 << 13));
                 if (badbits & (1u << j)) {
+                    ZXC_PATH(C_VARINT_BAD);
                     val = 0;
                     minbad = k < minbad ? k : minbad;
                 }
@@ -420,6 +429,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
     O.dict_size = S.dict_size;
     uint32_t p = 0, lp = 0, cur = 0, dead = 0, seq_base = 0;
     uint32_t z_end = RING_BYTES;
+    if (lane == 0) ZXC_PATH(GHI ? X_FULL_GHI : X_FULL);
 #ifdef EXP_PHASES
     uint32_t ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t ph_last = __builtin_readcyclecounter();
@@ -485,9 +495,11 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                 fast_vi = __ballot(!small) == 0ull;
             }
             if (fast_vi) {
+                if (lane == 0) ZXC_PATH(F_VARINT_FAST);
                 ll += b0;
                 ml += b1;
             } else {
+                if (lane == 0) ZXC_PATH(F_VARINT_GENERAL);
                 kbad = parse_varints(S.ext, S.ext_size, cur, nv, L, lane);
                 if (escL && r < kbad) ll += L.vval[r];
                 if (escM && r2 < kbad) ml += L.vval[r2];
@@ -542,8 +554,12 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
         k = k ? k - 1u : 64u;
         if (em) {
             const uint32_t e = (uint32_t)__ffsll((unsigned long long)em) - 1u;
-            if (e <= k) return __shfl(err, (int)e);  // first failing sequence in stream order
+            if (e <= k) {
+                if (lane == 0) ZXC_PATH(F_ERR);
+                return __shfl(err, (int)e);  // first failing sequence in stream order
+            }
         }
+        if ((uint32_t)lane == k && k != 0u && valid && !cut4 && err == 0) ZXC_PATH(F_TILE_CUT);  // (the first sequence beyond the tile; k == 0 is a giant)
 
         PH(9);
         // the next batch starts at sequence seq_base + max(k, 1): request its tokens and offsets now
@@ -555,8 +571,11 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const uint64_t km = (kk >= 64u) ? ~0ull : ((1ull << kk) - 1ull);
             const uint32_t used = __popcll(mL & km) + __popcll(mM & km);
             if (fast_vi) cur += used;
-            else if (kbad < used) { dead = 1; cur = S.ext_size; }
-            else cur = uni(L.vpos[used]);
+            else if (kbad < used) {
+                if (lane == 0) ZXC_PATH(F_DEAD);
+                dead = 1;
+                cur = S.ext_size;
+            } else cur = uni(L.vpos[used]);
         }
         const int32_t xi0 = (int32_t)(cur + (uint32_t)lane), xi1 = xi0 + 64;
         const uint32_t nxw0 = ld8(S.ext + (xi0 < ext_last ? xi0 : ext_last));
@@ -564,16 +583,19 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
         PH(10);
         if (k == 0u) {
             // ---- one giant sequence (> TILE_MAX bytes): the whole wave walks it in pieces (plain stores)
+            if (lane == 0) ZXC_PATH(F_GIANT);
             __builtin_amdgcn_s_waitcnt(0);  // (nothing stays on the compiler's scoreboard across the loop edge: see the flush below)
             const uint32_t gll = uni(ll), gml = uni(ml), goff = uni(off);
             uint32_t donel = 0;
             while (donel < gll) {
                 const uint32_t n = (gll - donel < TILE_MAX) ? gll - donel : TILE_MAX;
+                if (lane == 0) ZXC_PATH(F_GIANT_LIT_PIECE);
                 coop_copy<DICT>(L, O, p + donel, 0, S.lit + lp + donel, n, 0, lane);
                 donel += n;
                 flush_to(L, O, p + donel, lane);
             }
             if (gml) {
+                if (lane == 0) ZXC_PATH(F_GIANT_MATCH);
                 __builtin_amdgcn_s_waitcnt(0);  // earlier flush stores must have left before reading them back
                 coop_match<DICT>(L, O, p + gll, gml, goff, 0, true, lane);
             }
@@ -606,6 +628,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const uint8_t* lsrc = S.lit + (int32_t)(lst - la);
             v4u lv0 = {0, 0, 0, 0}, lv1 = {0, 0, 0, 0}, lv2 = {0, 0, 0, 0};
             if (lshort) {
+                ZXC_PATH(F_LIT_GROUP);
                 lv0 = ld128(lsrc);
                 if (le > 16u) lv1 = ld128(lsrc + 16u);
                 if (le > 32u) lv2 = ld128(lsrc + 32u);
@@ -619,6 +642,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             const uint32_t qb = fromdict ? ((off - M < ml) ? ((ml - (off - M) < M) ? ml - (off - M) : M) : 0u)
                                          : ((qa + ml < M) ? qa + ml : M);
             bool pending = mine && ml != 0u;
+            if (pending && fromdict) ZXC_PATH(F_FROM_DICT);
             uint64_t need = 0;
             uint32_t qsrc = qa;  // where the copy reads from (qa unless redirected)
             // A match lands on ITS destination's dword grid like a literal run: group g = 16 bytes at
@@ -646,6 +670,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     const uint32_t jq = __shfl(qsrc, jl);
                     const uint32_t nq = jq + (qa - jM);
                     if (simple && need != 0ull && jready && (int32_t)nq >= 0) {  // not into the dictionary prefix
+                        ZXC_PATH(pass == 0 ? F_REDIRECT0 : F_REDIRECT1);
                         qsrc = nq;
                         need = 0;
                     }
@@ -669,6 +694,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
             PH(13);
             __builtin_amdgcn_s_waitcnt(0);  // also: the flush stores of earlier batches have landed (every far read below relies on it)
             if (pf) {
+                ZXC_PATH(F_FAR_PREFETCH);
                 fr0 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + sg));
                 if (me > 16u) fr1 = __builtin_nontemporal_load((const v4u_unaligned*)(O.dst + sg + 16u));
             }
@@ -708,6 +734,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     const int j = __ffsll((unsigned long long)lm) - 1;
                     lm &= lm - 1ull;
                     const uint32_t jl = __shfl(ll, j), je = __shfl(est, j), js = __shfl(lst, j);
+                    if (lane == 0) ZXC_PATH(F_LIT_LONG);
                     coop_copy<DICT>(L, O, je, 0, S.lit + js, jl, 0, lane);
                 }
                 wave_lds_fence();
@@ -720,6 +747,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                 const bool can = pending && ((dm & need) == need);
                 // lane-per-sequence copy, one 16-byte grid group per step (up to MATCH_MED bytes)
                 const bool sa = can && stepable;
+                if (sa) ZXC_PATH(F_STEPABLE);
                 if (__ballot(sa)) {
 #pragma unroll 1
                     for (uint32_t go = 0; go < MATCH_MED + 4u; go += 16u) {
@@ -731,6 +759,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                         v4u d = {0, 0, 0, 0};
                         if (usepf) d = go == 0u ? fr0 : fr1;
                         if (__ballot(isfar)) {
+                            if (isfar) ZXC_PATH(F_FAR_GROUP);
                             if (isfar) d = far_rd128(O, q);
                         }
                         if (act && !isfar && !usepf) d = ring_rd128(L, q);
@@ -743,6 +772,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                 PH(3);
                 // short period (off < 16, off < ml <= 32): byte loop over the period [M-off, M)
                 const bool sb = can && bytewise;
+                if (sb) ZXC_PATH(F_BYTEWISE);
                 if (__ballot(sb)) {
                     uint32_t r = 0;
 #pragma unroll 1
@@ -763,6 +793,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                     const int j = __ffsll((unsigned long long)lm) - 1;
                     lm &= lm - 1ull;
                     const uint32_t jM = __shfl(M, j), jml = __shfl(ml, j), joff = __shfl(off, j);
+                    if (lane == 0) ZXC_PATH(F_LONG);
                     coop_match<DICT>(L, O, jM, jml, joff, ring_lo, false, lane);
                 }
                 if (can) pending = false;
@@ -776,6 +807,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                 uint64_t pm = __ballot(pending);
                 if (pm != 0ull && __popcll(pm) <= SPARSE_MAX) {
                     const uint64_t longm = __ballot(is_long);
+                    if (lane == 0) ZXC_PATH(F_SPARSE);
                     while (pm) {
                         const int j = __ffsll((unsigned long long)pm) - 1;
                         pm &= pm - 1ull;
@@ -784,10 +816,12 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                                        joff = (uint32_t)__builtin_amdgcn_readlane((int)off, j);
                         const uint32_t jq = jM - joff;
                         if (((longm >> j) & 1ull) || jq < ring_lo) {
+                            if (lane == 0) ZXC_PATH(F_SPARSE_COOP);
                             coop_match<DICT>(L, O, jM, jml, joff, ring_lo, false, lane);
                             continue;
                         }
                         const bool ovl = joff < jml;  // period joff: byte t comes from the first period, t mod joff
+                        if (lane == 0) ZXC_PATH(ovl ? F_SPARSE_OVL : F_SPARSE_PLAIN);
                         const float rcp = __builtin_amdgcn_rcpf((float)joff);
                         for (uint32_t t0 = 0; t0 < jml; t0 += 64u) {
                             const uint32_t t = t0 + (uint32_t)lane;
@@ -824,6 +858,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
                 const uint32_t ge = (uint32_t)__builtin_amdgcn_readlane((int)est, (int)(g - seq_base)),
                                gl = (uint32_t)__builtin_amdgcn_readlane((int)lst, (int)(g - seq_base));
                 carry4x = ge + RD < cap && n_lit > RLM && gl < n_lit - RLM;
+                if (lane == 0) ZXC_PATH(F_CARRY4X);
             }
         }
         seq_base += k;
@@ -846,6 +881,7 @@ __device__ __forceinline__ int run_sequences(const LzStreams& S, uint8_t* __rest
 #endif
     // the last chunk may be partial: it only lives in the ring so far
     if ((p & 15u) != 0u && lane == 0) {
+        ZXC_PATH(F_PARTIAL_CHUNK);
         const uint32_t cs = p & ~15u;
         for (uint32_t kk = 0; cs + kk < p && cs + kk < out_len; kk++) dst[cs + kk] = (uint8_t)ring_rd8(L, cs + kk);
     }

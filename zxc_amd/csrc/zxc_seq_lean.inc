@@ -60,6 +60,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
     uint32_t p = 0, lp = 0, cur = 0, dead = 0, seq_base = 0;
     uint32_t z_end = RING_BYTES;
     const bool far_en = O.out_pad >= 32u;  // (idle lanes of the unconditional far loads read the block's first 16 bytes)
+    if (lane == 0) ZXC_PATH(GHI ? X_LEAN_GHI : X_LEAN);
 
     for (uint32_t i = (uint32_t)lane; i < 68u; i += 64u) {
         const int v = (int)(i >> 2) - 4 * (int)(i & 3u);
@@ -115,6 +116,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 const int f = __ffsll((unsigned long long)late) - 1;  // (>= 30: sixty varints come from at least thirty lanes)
                 vm = (1ull << f) - 1ull;
                 valid = valid && lane < f;
+                if (lane == 0) ZXC_PATH(L_VARINT_CUT);
             }
             const uint32_t nv = __popcll(mL & vm) + __popcll(mM & vm);
             uint32_t bL = 0, bM = 0;
@@ -128,9 +130,11 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 fast_vi = __ballot(big) == 0ull;
             }
             if (fast_vi) {
+                if (lane == 0) ZXC_PATH(L_VARINT_FAST);
                 ll += escL ? bL : 0u;
                 ml += escM ? bM : 0u;
             } else {
+                if (lane == 0) ZXC_PATH(L_VARINT_GENERAL);
                 kbad = parse_varints(S.ext, S.ext_size, cur, nv, L, lane);
                 if (valid && escL && r < kbad) ll += L.vval[r];
                 if (valid && escM && r2 < kbad) ml += L.vval[r2];
@@ -155,6 +159,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint32_t E63 = p + (uint32_t)__builtin_amdgcn_readlane((int)Ei, 63);
             const uint32_t L63 = lp + (uint32_t)__builtin_amdgcn_readlane((int)Li, 63);
             if (seq_base + 64u >= n_total || E63 + trig_d > cap || L63 + trig_l > n_lit || __ballot(bad_off) != 0ull) {
+                if (lane == 0) ZXC_PATH(L_EXACT);
                 const bool pseudo = valid & !real;  // whatever literals are left
                 const bool lit_over = lst > n_lit;
                 const uint32_t lit_left = n_lit - lst;
@@ -193,10 +198,14 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint64_t em = __ballot(err != 0);
             if (em) {
                 const uint32_t e = (uint32_t)__ffsll((unsigned long long)em) - 1u;
-                if (e <= k) return __shfl(err, (int)e);  // first failing sequence in stream order
+                if (e <= k) {
+                    if (lane == 0) ZXC_PATH(L_ERR);
+                    return __shfl(err, (int)e);  // first failing sequence in stream order
+                }
             }
         }
 
+        if ((uint32_t)lane == k && k != 0u && valid && err == 0) ZXC_PATH(L_TILE_CUT);  // (the first sequence beyond the tile; k == 0 is a giant)
         PHM(3);
         // the next batch starts at sequence seq_base + max(k, 1): request its tokens and offsets now
         uint32_t nraw_t, nraw_o;
@@ -206,7 +215,11 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint64_t km = (kk >= 64u) ? ~0ull : ((1ull << kk) - 1ull);
             const uint32_t used = __popcll(mL & km) + __popcll(mM & km);
             if (fast_vi) cur += used;
-            else if (kbad < used) { dead = 1; cur = S.ext_size; }
+            else if (kbad < used) {
+                if (lane == 0) ZXC_PATH(L_DEAD);
+                dead = 1;
+                cur = S.ext_size;
+            }
             else cur = uni(L.vpos[used]);
         }
         const int32_t xi0 = (int32_t)(cur + (uint32_t)lane);
@@ -215,17 +228,20 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
         PHM(4);
         if (k == 0u) {
             // ---- one giant sequence (> LEAN_TILE_MAX bytes): the whole wave walks it in pieces (plain stores)
+            if (lane == 0) ZXC_PATH(L_GIANT);
             __builtin_amdgcn_s_waitcnt(0);
             flush_to(L, O, p, lane);  // (everything finished so far: the pieces below fill the ring)
             const uint32_t gll = uni(ll), gml = uni(ml), goff = uni(off);
             uint32_t donel = 0;
             while (donel < gll) {
                 const uint32_t n = (gll - donel < TILE_MAX) ? gll - donel : TILE_MAX;
+                if (lane == 0) ZXC_PATH(L_GIANT_LIT_PIECE);
                 coop_copy<false>(L, O, p + donel, 0, S.lit + lp + donel, n, 0, lane);
                 donel += n;
                 flush_to(L, O, p + donel, lane);
             }
             if (gml) {
+                if (lane == 0) ZXC_PATH(L_GIANT_MATCH);
                 __builtin_amdgcn_s_waitcnt(0);  // earlier flush stores must have left before reading them back
                 coop_match<false>(L, O, p + gll, gml, goff, 0, true, lane);
             }
@@ -257,8 +273,11 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint32_t lob = lo + 4u + lit_ph;           // offset from lit_al = (S.lit - 8) rounded down to a dword
             const uint32_t ldl = lob & 3u;
             const v4u lv0 = ld128(lit_al + (lshort ? (lob & ~3u) : 8u));
-            const uint32_t lv0e = ld32(lit_al + ((lshort && ldl != 0u && le > 12u) ? (lob & ~3u) + 16u : 8u));
+            const bool lv5 = lshort && ldl != 0u && le > 12u;  // the run's last bytes of group 0 sit in a fifth aligned dword
+            const uint32_t lv0e = ld32(lit_al + (lv5 ? (lob & ~3u) + 16u : 8u));
             const v4u lv1 = ld128(litm4 + (lshort && le > 16u ? lo + 16u : 4u - lit_ph));
+            if (lshort) ZXC_PATH(L_LIT_GROUP);
+            if (lv5) ZXC_PATH(L_LIT_5TH);
             const v4u lv2 = ld128(litm4 + (lshort && le > 32u ? lo + 32u : 4u - lit_ph));
 
             // Match: group g = 16 bytes at (M & ~3) + 16 g, from source position qsrc - (M & 3) + 16 g.
@@ -276,13 +295,25 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             //  has been flushed; a source that straddles the flushed mark, ~3 % of them, takes the near path's whole-wave copy)
             const bool far_ok = far_en && pending && qa < ring_lo && ml <= MATCH_MED && qa >= 4u && qa + ml <= O.flushed &&
                                 (qa - ma) + ((me + 15u) & ~15u) + 4u <= O.out_pad;
+            // (The NO_* markers restate far_ok's clauses: naming the clauses once changes the kernel's register allocation. Only
+            // L_FAR_GROUP observes far_ok itself, so every case that asks for a NO_* marker also pins L_FAR_GROUP's exact count.)
+            if (pending && qa < ring_lo) {  // a source behind the ring: the group path, or which guard sends it to the near paths
+                if (far_ok) ZXC_PATH(L_FAR_GROUP);
+                if (!far_en) ZXC_PATH(L_FAR_OFF);
+                if (ml > MATCH_MED) ZXC_PATH(L_FAR_NO_ML);
+                if (qa < 4u) ZXC_PATH(L_FAR_NO_QA4);
+                if (qa + ml > O.flushed) ZXC_PATH(L_FAR_NO_FLUSHED);
+                if ((qa - ma) + ((me + 15u) & ~15u) + 4u > O.out_pad) ZXC_PATH(L_FAR_NO_EDGE);
+            }
             const uint32_t sgf = qa - ma;
             const uint32_t fdl = sgf & 3u;  // (the block's slot is 16-byte aligned: the source's phase against the destination grid)
             v4u fr0 = {0, 0, 0, 0}, fr1 = {0, 0, 0, 0};
             uint32_t fr0e = 0;
             if (far_en) {  // wave-uniform. Group 0 dword-aligned like the literals'; group 1 is wanted by few lanes.
                 fr0 = ld128(dst + (far_ok ? (sgf & ~3u) : 0u));
-                fr0e = ld32(dst + ((far_ok && fdl != 0u && me > 12u) ? (sgf & ~3u) + 16u : 0u));
+                const bool fr5 = far_ok && fdl != 0u && me > 12u;
+                fr0e = ld32(dst + (fr5 ? (sgf & ~3u) + 16u : 0u));
+                if (fr5) ZXC_PATH(L_FAR_5TH);
                 fr1 = ld128(dst + (far_ok && me > 16u ? sgf + 16u : 0u));
             }
 
@@ -311,6 +342,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 const bool o2 = o1 && ja + 2u < 64u && (k2 >> 16) < xb;
                 uint32_t jb = ja + (o0 ? 1u : 0u) + (o1 ? 1u : 0u);
                 if (o2) jb = (uint32_t)lane;  // a source over more than two earlier matches: wait for everything in front
+                if (inb && o2) ZXC_PATH(L_WAIT_ALL);
                 if (inb && jb > ja) need = ((jb >= 64u) ? ~0ull : ((1ull << jb) - 1ull)) & ~((1ull << ja) - 1ull);
                 // Redirect: when my whole source sits inside ONE earlier match j of this batch (within its first period) and
                 // j has no pending dependency itself, my bytes equal j's source bytes at the same displacement: read those
@@ -323,7 +355,10 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     const uint64_t rm = __ballot(need == 0ull);
                     const uint32_t jq = __shfl(qsrc, (int)(ja & 63u));
                     const uint32_t nq = jq + (qa - jM);
+                    // (restates the condition below, for the same reason: the case pins L_REDIRECT0's exact count beside it)
+                    if (simple && need != 0ull && ((rm >> (ja & 63u)) & 1ull) && !(nq >= ring_lo && (int32_t)nq >= 0)) ZXC_PATH(L_REDIRECT_NO_RING);
                     if (simple && need != 0ull && ((rm >> (ja & 63u)) & 1ull) && nq >= ring_lo && (int32_t)nq >= 0) {
+                        ZXC_PATH(pass == 0 ? L_REDIRECT0 : L_REDIRECT1);
                         qsrc = nq;
                         need = 0;
                     }
@@ -378,6 +413,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     lm &= lm - 1ull;
                     const uint32_t jl = (uint32_t)__builtin_amdgcn_readlane((int)ll, j), je = (uint32_t)__builtin_amdgcn_readlane((int)est, j),
                                    js = (uint32_t)__builtin_amdgcn_readlane((int)lst, j);
+                    if (lane == 0) ZXC_PATH(L_LIT_LONG);
                     coop_copy<false>(L, O, je, 0, S.lit + js, jl, 0, lane);
                 }
             }
@@ -423,6 +459,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 if (round > 70u) return ZXC_DEV_E_INTERNAL;  // cannot happen: the lowest pending lane is always ready
                 const bool can = pending && ((dm & need) == need);
                 const bool sa = can && stepable;
+                if (sa) ZXC_PATH(L_STEPABLE);
                 if (__ballot(sa)) {
 #pragma unroll 1
                     for (uint32_t go = 0; go < MATCH_MED + 4u; go += 16u) {
@@ -438,6 +475,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 PHM(11);
                 // short period (off < 16, off < ml <= 32): byte loop over the period [M-off, M)
                 const bool sb = can && bytewise;
+                if (sb) ZXC_PATH(L_BYTEWISE);
                 if (__ballot(sb)) {
                     uint32_t r = 0;
 #pragma unroll 1
@@ -459,6 +497,8 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     const uint32_t jM = (uint32_t)__builtin_amdgcn_readlane((int)M, j), jml = (uint32_t)__builtin_amdgcn_readlane((int)ml, j),
                                    joff = (uint32_t)__builtin_amdgcn_readlane((int)off, j);
                     if (jM - joff < ring_lo && !far_waited) { __builtin_amdgcn_s_waitcnt(0); far_waited = true; }
+                    if (lane == 0) ZXC_PATH(L_LONG);
+                    if (lane == 0 && jM - joff < ring_lo) ZXC_PATH(L_LONG_FAR);
                     coop_match<false>(L, O, jM, jml, joff, ring_lo, false, lane);
                 }
                 if (can) pending = false;
@@ -468,6 +508,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 uint64_t pm = __ballot(pending);
                 if (pm != 0ull && __popcll(pm) <= SPARSE_MAX) {
                     const uint64_t longm = __ballot(is_long);
+                    if (lane == 0) ZXC_PATH(L_SPARSE);
                     while (pm) {
                         const int j = __ffsll((unsigned long long)pm) - 1;
                         pm &= pm - 1ull;
@@ -477,10 +518,12 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                         const uint32_t jq = jM - joff;
                         if (((longm >> j) & 1ull) || jq < ring_lo) {
                             if (jq < ring_lo && !far_waited) { __builtin_amdgcn_s_waitcnt(0); far_waited = true; }
+                            if (lane == 0) ZXC_PATH(L_SPARSE_COOP);
                             coop_match<false>(L, O, jM, jml, joff, ring_lo, false, lane);
                             continue;
                         }
                         const bool ovl = joff < jml;  // period joff: byte t comes from the first period, t mod joff
+                        if (lane == 0) ZXC_PATH(ovl ? L_SPARSE_OVL : L_SPARSE_PLAIN);
                         const float rcp = __builtin_amdgcn_rcpf((float)joff);
                         for (uint32_t t0 = 0; t0 < jml; t0 += 64u) {
                             const uint32_t t = t0 + (uint32_t)lane;
@@ -515,6 +558,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 const uint32_t ge = (uint32_t)__builtin_amdgcn_readlane((int)est, (int)(g - seq_base)),
                                gl = (uint32_t)__builtin_amdgcn_readlane((int)lst, (int)(g - seq_base));
                 carry4x = ge + RD < cap && n_lit > RLM && gl < n_lit - RLM;
+                if (lane == 0) ZXC_PATH(L_CARRY4X);
             }
         }
         seq_base += k;
@@ -526,6 +570,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
     flush_to(L, O, p, lane);  // what is left of the last KiB
     // the last chunk may be partial: it only lives in the ring so far
     if ((p & 15u) != 0u && lane == 0) {
+        ZXC_PATH(L_PARTIAL_CHUNK);
         const uint32_t cs = p & ~15u;
         for (uint32_t kk = 0; cs + kk < p && cs + kk < out_len; kk++) dst[cs + kk] = (uint8_t)ring_rd8(L, cs + kk);
     }
@@ -563,6 +608,7 @@ __device__ __forceinline__ int decode_lz_block_lean(const uint8_t* data, uint32_
     // GLO: ONE call site of the executor for the three ways a block's streams are found (the executor is inlined: every call
     // site is another copy of it, and the register allocation of the kernel is that of all copies together).
     if (!pd && rle_ok) {
+        if (lane == 0) ZXC_PATH(X_SETUP_RLE);
         // RLE-coded literals, raw tokens, header checked (rle_block_for_lean): zxc_rle_expand_kernel has expanded the literals
         // into the launch's RLE scratch (rle_lit; unused when n_lit == 0)
         const uint32_t lit_comp = uni(ld32(data + 12));
@@ -580,6 +626,7 @@ __device__ __forceinline__ int decode_lz_block_lean(const uint8_t* data, uint32_
         if ((int16_t)(rcs & 0xFFFFu) != 0) return (int)(int16_t)(rcs & 0xFFFFu);
         if ((int16_t)(rcs >> 16) != 0) return (int)(int16_t)(rcs >> 16);
         const uint32_t desc = (enc_lit != 0u ? 4u : 0u) + (enc_tok == 2u ? 4u : 0u);
+        if (lane == 0) ZXC_PATH(X_SETUP_PRE);
         uint32_t lit_comp = S.n_lit, tok_comp = S.n_seq;
         const uint8_t* d = data + 12;
         if (enc_lit != 0u) { lit_comp = uni(ld32(d)); d += 4; }
@@ -602,6 +649,7 @@ __device__ __forceinline__ int decode_lz_block_lean(const uint8_t* data, uint32_
         S.off8 = enc_off;
         S.ext = S.offs + sz_off;
         S.ext_size = avail - (uint32_t)consumed;
+        if (lane == 0) ZXC_PATH(X_SETUP_RAW);
     }
     return run_sequences_lean<false>(S, dst, out_len, cap, L, lane, strict);
 }

@@ -500,8 +500,7 @@ ZXC_EXPORT uint64_t zxc_mi355x_compress_append_device_work_size(uint64_t max_tot
  * is exactly zxc_mi355x_compress_device's size > dst_capacity. Both errors stay and end reports them. Nothing is written at or
  * past d_dst + dst_capacity; d_dst may have any alignment; after an error its bytes are undefined.
  * Options are read like zxc_mi355x_compress_device reads them (opts may be NULL: level 3, 512 KiB blocks). opts->dict != NULL is
- * ZXC_ERROR_GPU_UNSUPPORTED, and there is no sibling that takes a zxc_dev_dict_t yet: a session with a dictionary in device
- * memory is left for later.
+ * ZXC_ERROR_GPU_UNSUPPORTED: a dictionary in device memory goes through zxc_mi355x_compress_begin_dict_device below.
  * Synchronous errors, before any device is touched, in this order. begin: NULL cs / d_dst / d_work -> ZXC_ERROR_NULL_INPUT;
  * opts->dict -> ZXC_ERROR_GPU_UNSUPPORTED; block_size not a power of two in [4 KiB, 2 MiB], max_piece < block_size, more than
  * 2^31 - 1 blocks in max_total (or jobs in a piece) -> ZXC_ERROR_BAD_BLOCK_SIZE; work_size too small -> ZXC_ERROR_MEMORY;
@@ -516,6 +515,34 @@ ZXC_EXPORT int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_d
                                                 void* stream);
 ZXC_EXPORT int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, uint64_t n, void* stream);
 ZXC_EXPORT int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream);
+
+/* The session with a dictionary in device memory: begin with a zxc_dev_dict_t, then zxc_mi355x_compress_append_device and
+ * zxc_mi355x_compress_end_device as above, which serve both kinds of session. After begin, any number of appends and end, d_dst
+ * holds byte for byte the archive zxc_mi355x_compress_dict_device (and zxc_compress of this library with opts->dict) writes for
+ * the concatenation of the appended bytes with the same level, block_size, checksum_enabled, seekable and dictionary, however the
+ * source was cut. The file header carries the dictionary flag and *d_id, which is read on the device when end writes the header;
+ * as in zxc_compress the encoder is given the content only, d_huf enters the id alone. *d_result is written once, last, by end:
+ * the archive size, or the error zxc_mi355x_compress_dict_device would store for that source and capacity, with the one departure
+ * of the session above (ZXC_ERROR_DST_TOO_SMALL is stored where that call refuses a capacity synchronously). What dict points to
+ * must stay valid and unchanged until *d_result is written; the struct itself is read by begin and not kept.
+ * Every block is encoded from a [dict | block] image, as in zxc_mi355x_compress_dict_device: a piece's jobs go through the
+ * encoder in chunks of C = max(4096, 256 MiB / (block_size + dict_size)) jobs, and one image area of min(J, C) images is reused
+ * from chunk to chunk in stream order. The work size is the sibling's plus that area: at most
+ * J x (S + 28) + 16 x ceil(J / 1024) + 3 x (block_size + 64) + 4 x NB (seekable only) + 4096
+ *   + min(J, C) x (block_size + dict_size) + 320,
+ * exactly zxc_mi355x_compress_append_device_work_size with dict_size == 0, and 0 for dict_size > 65535 and for whatever the
+ * sibling refuses. An append still reads exactly d_src[0, n): an image is a copy with padding behind it, so no block is staged
+ * (the stage area goes unused) and the head of an append that completes the waiting block goes from d_src straight into that
+ * block's image, behind the waiting bytes, without passing through the carry area. The trailing partial block is carried as above.
+ * A NULL dict, or one with size == 0, makes begin behave exactly as zxc_mi355x_compress_begin_device: same work size, same bytes.
+ * Synchronous errors of begin: the sibling's, in its order, with two additions directly behind the opts->dict check:
+ * dict->size > 65535 -> ZXC_ERROR_DICT_TOO_LARGE; NULL d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT. opts->dict != NULL
+ * stays ZXC_ERROR_GPU_UNSUPPORTED. A refused begin leaves the struct alone. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_append_dict_device_work_size(uint64_t max_total, uint64_t max_piece,
+                                                                    const zxc_compress_opts_t* opts, uint32_t dict_size);
+ZXC_EXPORT int zxc_mi355x_compress_begin_dict_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total,
+                                                     uint64_t max_piece, const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict,
+                                                     void* d_work, uint64_t work_size, void* stream);
 
 /* ---- one archive into many pieces, device to device (zxc_amd/csrc/zxc_take_device.hip, rules in zxc_amd/csrc/zxc_take.h) ----
  * zxc_mi355x_decompress_device wants one contiguous, 16-byte aligned destination of the whole decoded size: whoever wrote an

@@ -544,6 +544,11 @@ def _bind_compress_append_device(L):
     L.zxc_mi355x_compress_append_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_void_p]
     L.zxc_mi355x_compress_end_device.restype = C.c_int
     L.zxc_mi355x_compress_end_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_compress_append_dict_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_append_dict_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
+    L.zxc_mi355x_compress_begin_dict_device.restype = C.c_int
+    L.zxc_mi355x_compress_begin_dict_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                        C.POINTER(_CompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64, C.c_void_p]
     return L
 
 
@@ -585,6 +590,29 @@ def compress_begin_device(d_dst, dst_capacity, max_total, max_piece, d_work, wor
         C.c_void_p(stream or None))
     if rc < 0:
         raise ZxcError(rc, "zxc_mi355x_compress_begin_device")
+    return CompressAppendSession(cs)
+
+
+def compress_append_dict_device_work_size(max_total, max_piece, dict_size, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_append_dict_device_work_size(): bytes of device scratch a session with a dictionary of dict_size bytes
+    needs (0 for refused arguments; dict_size 0 gives compress_append_device_work_size)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_append_dict_device_work_size(max_total, max_piece, C.byref(o),
+                                                                                                    dict_size))
+
+
+def compress_begin_dict_device(d_dst, dst_capacity, max_total, max_piece, dict_, d_work, work_size, level=3, block_size=0,
+                               seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_begin_dict_device(): compress_begin_device with a dictionary in device memory (dict_ as in
+    compress_dict_device, or None for no dictionary) -> a CompressAppendSession; the work size is
+    compress_append_dict_device_work_size(max_total, max_piece, dict_size, ...)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    cs = _DevCappend()
+    rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_begin_dict_device(
+        C.byref(cs), C.c_void_p(d_dst or None), dst_capacity, max_total, max_piece, C.byref(o), _dev_dict(dict_),
+        C.c_void_p(d_work or None), work_size, C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_begin_dict_device")
     return CompressAppendSession(cs)
 
 

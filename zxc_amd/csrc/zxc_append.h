@@ -13,7 +13,14 @@
  * areas that take turns, one stage area), and with a seek table 4 bytes per block of max_total. In closed form, with
  * J = max_piece / block_size + 2 jobs and NB = ceil(max_total / block_size), the size is at most
  *     J x (S + 28) + 16 x ceil(J / 1024) + 3 x (block_size + 64) + 4 x NB (seekable only) + 4096
- *                                                                          (ZAP_JOB_BYTES, ZAP_TILE_BYTES, ZAP_AREAS, ZAP_WORK_FIXED) */
+ *                                                                          (ZAP_JOB_BYTES, ZAP_TILE_BYTES, ZAP_AREAS, ZAP_WORK_FIXED)
+ *
+ * A session with a dictionary of D bytes (zxc_mi355x_compress_begin_dict_device) encodes every block from a [dict | block] image,
+ * as zxc_mi355x_compress_dict_device does: the rules with `images` in their names. An image is a copy with padding behind it, so
+ * nothing is staged and the head of a piece is not copied into the carry area first: the carried block's image takes its bytes
+ * from two places. The image area lies behind the layout above: min(J, C) images of block_size + D bytes, C =
+ * zc_image_chunk(block_size, D), which the chunks of a piece reuse in stream order, and ZC_IMAGE_PAD; the size is at most the
+ * closed form above + min(J, C) x (block_size + D) + 320                                                    (ZAP_IMAGE_FIXED) */
 #ifndef ZXC_APPEND_H
 #define ZXC_APPEND_H
 #include "zxc_container.h"
@@ -25,6 +32,7 @@
 #define ZAP_TILE_BYTES 16u  /* work area per tile: sum, hash, bad flag */
 #define ZAP_AREAS 3u        /* areas of block_size + ZAP_PAD bytes: two carry areas, one stage area */
 #define ZAP_WORK_FIXED 4096u /* the state, the alignment of the twelve parts and of the caller's pointer */
+#define ZAP_IMAGE_FIXED 320u /* the dictionary session's image area: its ZC_IMAGE_PAD and its alignment */
 
 /* where bytes lie: in the piece's source, or in one of the three areas */
 enum { ZAP_SRC = 0, ZAP_CARRY = 1, ZAP_NEXT = 2, ZAP_STAGE = 3 };
@@ -67,6 +75,33 @@ ZC_FN uint64_t zap_work_bound(uint64_t max_total, uint64_t max_piece, uint32_t b
     const uint64_t J = max_piece / block_size + 2u, nb = max_total / block_size + (max_total % block_size != 0);
     return J * ((uint64_t)slot_stride + ZAP_JOB_BYTES) + ZAP_TILE_BYTES * ((J + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS) +
            ZAP_AREAS * ((uint64_t)block_size + ZAP_PAD) + (seekable ? 4u * nb : 0u) + ZAP_WORK_FIXED;
+}
+/* The dictionary session's shape: the sibling's layout, and behind it the image area of chunk_jobs = min(J, C) images of
+ * image = block_size + dict_size bytes with ZC_IMAGE_PAD behind the last. dict_size == 0: no image area, bytes is the sibling's.
+ * -> 0, or what zap_shape answers. */
+typedef struct zap_shape_images {
+    zap_shape_t s;
+    uint32_t chunk_jobs, image; /* jobs per encode launch (0 without a dictionary); bytes per image */
+    uint64_t o_images, bytes;
+} zap_shape_images_t;
+ZC_FN int zap_shape_images(uint64_t max_total, uint64_t max_piece, uint32_t block_size, uint32_t slot_stride, int seekable,
+                           uint32_t dict_size, zap_shape_images_t* s) {
+    const int rc = zap_shape(max_total, max_piece, block_size, slot_stride, seekable, &s->s);
+    if (rc != 0) return rc;
+    s->chunk_jobs = 0; s->image = block_size + dict_size; s->o_images = s->s.bytes - 256u; s->bytes = s->s.bytes;
+    if (dict_size) {
+        const uint64_t chunk = zc_image_chunk(block_size, dict_size);
+        s->chunk_jobs = s->s.J < chunk ? s->s.J : (uint32_t)chunk;
+        s->bytes = zc_round_up(s->o_images + (uint64_t)s->chunk_jobs * s->image + ZC_IMAGE_PAD, 256u) + 256u;
+    }
+    return 0;
+}
+/* ... and its closed form */
+ZC_FN uint64_t zap_work_bound_images(uint64_t max_total, uint64_t max_piece, uint32_t block_size, uint32_t slot_stride, int seekable,
+                                     uint32_t dict_size) {
+    const uint64_t J = max_piece / block_size + 2u, chunk = zc_image_chunk(block_size, dict_size);
+    return zap_work_bound(max_total, max_piece, block_size, slot_stride, seekable) +
+           (dict_size ? (J < chunk ? J : chunk) * ((uint64_t)block_size + dict_size) + ZAP_IMAGE_FIXED : 0u);
 }
 
 /* ---- the plan of one piece */
@@ -142,6 +177,38 @@ ZC_FN zap_src_t zap_job(const zap_piece_t* p, uint32_t j) {
     return r;
 }
 
+/* The same piece when every job is encoded from an image (the dictionary session). An image is a copy already, with padding
+ * behind it for the encoder's over-read: every whole block is direct whatever lies behind it, nothing is staged, and the head of
+ * the piece is not copied into the carry area, it is delivered to job 0's image straight from the source (zap_job_images). What
+ * is left to copy is the tail, into the other carry area; a piece that completes no block joins the carry as above. nb, tail,
+ * first and swap are zap_plan_piece's. Every source byte is read by one job segment or by the tail copy. The plan of `end` is
+ * zap_plan_end. */
+ZC_FN void zap_plan_piece_images(uint32_t carry, uint64_t n, uint32_t block_size, zap_piece_t* p) {
+    const zap_copy_t none = {ZAP_SRC, 0u, 0u, 0u, 0u};
+    zap_plan_piece(carry, n, block_size, p);
+    if (p->nb == 0) return;
+    p->n_direct = p->nb - (carry ? 1u : 0u);
+    p->n_staged = 0;
+    p->cp[0] = p->cp[1] = none;
+}
+/* job j < nb of such a piece: the one or two places its bytes lie, in order (seg[1].len == 0: one). The carried block is the
+ * `carry` bytes waiting in the current carry area and then the first block_size - carry bytes of the piece; at `end` it is the
+ * carry alone. */
+typedef struct zap_src2 {
+    zap_src_t seg[2];
+} zap_src2_t;
+ZC_FN zap_src2_t zap_job_images(const zap_piece_t* p, uint32_t j) {
+    const uint32_t len = j + 1u == p->nb ? p->last_len : p->block_size;
+    zap_src2_t r = {{{ZAP_SRC, len, 0u}, {ZAP_SRC, 0u, 0u}}};
+    if (p->carry && j == 0) {
+        r.seg[0].area = ZAP_CARRY; r.seg[0].len = p->carry;
+        r.seg[1].len = len - p->carry;
+        return r;
+    }
+    r.seg[0].off = p->first + (uint64_t)(j - (p->carry ? 1u : 0u)) * p->block_size;
+    return r;
+}
+
 /* ---- the session's state in device memory */
 typedef struct zap_ctl {
     int64_t status;   /* 0 while the archive fits, or the sticky negative zxc_error_t; behind `end` the archive size */
@@ -192,19 +259,25 @@ ZC_FN int zap_advance(zap_ctl_t* c, uint32_t nb_piece, uint64_t sum, uint32_t pi
     return 1;
 }
 
-/* ---- finish: the archive around its blocks. total = the bytes appended. Writes the file header, the EOF block, with `seekable`
- * and blocks the SEK header, and the footer with total and the global hash; the seek-table entries are zap_put_seek_entry's.
- * c->status becomes the archive size. Nothing is written for a session whose status is an error. */
-ZC_FN void zap_finish(zap_ctl_t* c, uint8_t* dst, uint64_t dst_capacity, uint64_t total, uint32_t block_size, int checksum, int seekable) {
+/* ---- finish: the archive around its blocks. total = the bytes appended. Writes the file header (with has_dict it carries the
+ * dictionary flag and dict_id: the dictionary session), the EOF block, with `seekable` and blocks the SEK header, and the footer
+ * with total and the global hash; the seek-table entries are zap_put_seek_entry's. c->status becomes the archive size. Nothing is
+ * written for a session whose status is an error. */
+ZC_FN void zap_finish_dict(zap_ctl_t* c, uint8_t* dst, uint64_t dst_capacity, uint64_t total, uint32_t block_size, int checksum,
+                           int seekable, int has_dict, uint32_t dict_id) {
     if (c->status < 0) return;
     const uint64_t eof_at = c->off, size = zap_size_if_ended(c->off, c->nb, seekable);
     if (size > dst_capacity) { c->status = ZXC_ERROR_DST_TOO_SMALL; return; } /* (begin and every piece saw to that) */
-    zc_put_file_header(dst, zc_block_size_lg(block_size), checksum, 0, 0u);
+    zc_put_file_header(dst, zc_block_size_lg(block_size), checksum, has_dict, dict_id);
     zc_st_le(dst + eof_at, zc_blk_hdr(ZC_BLK_EOF, 0u), 8);
     if (seekable && c->nb) zc_st_le(dst + eof_at + ZC_BLK_HDR, zc_blk_hdr(ZC_BLK_SEK, (uint32_t)c->nb * 4u), 8);
     c->seek_at = eof_at + 2u * ZC_BLK_HDR;
     zc_put_footer(dst + size - ZC_FOOTER, total, checksum ? c->hash : 0u);
     c->status = (int64_t)size;
+}
+/* ... of the session without a dictionary */
+ZC_FN void zap_finish(zap_ctl_t* c, uint8_t* dst, uint64_t dst_capacity, uint64_t total, uint32_t block_size, int checksum, int seekable) {
+    zap_finish_dict(c, dst, dst_capacity, total, block_size, checksum, seekable, 0, 0u);
 }
 /* entry b of the seek table: block b's size, from the array in the work area to its unaligned place in the archive */
 ZC_FN void zap_put_seek_entry(const zap_ctl_t* c, uint8_t* dst, const uint32_t* seek, uint64_t b) {

@@ -21,11 +21,27 @@
 //   seek     the entries from the work area to their unaligned place, 4 byte stores each
 //   result   *d_result = archive size or the error, written once, after everything above
 //
+// A session with a dictionary in device memory (zxc_mi355x_compress_begin_dict_device) replaces "prep, encode" by a loop over
+// chunks of at most C = zc_image_chunk(block_size, dict_size) jobs, which reuse one image area in stream order:
+//
+//   images   zxc_append_images_kernel, one workgroup per job of the chunk: [dict | the job's bytes] into the image area and the
+//            job-table entry that points at it; the carried block's bytes come from the carry area and then from the head of the
+//            source, which is not copied anywhere else; in the first chunk one more workgroup copies the tail into the other carry
+//            area. Nothing is staged: an image is a copy with the next image, or ZC_IMAGE_PAD, behind it
+//   encode   the job-table entry of the level over the chunk's images, into the chunk's slots and sizes
+//
+// with tiles, advance, scatter and gather once over the whole piece as above, and the dictionary flag and *d_id in the file header
+// that finish writes. A piece that completes no block is prep's, as it is.
+//
 // No workgroup waits for another: every dependency is the stream order between launches.
 #include <string.h>
 
 #include "zxc_device_util.h"  // the tile passes, copy_bytes (zxc_wave.h), zxc_frame_tiles_kernel, the host-side plumbing
 #include "zxc_append.h"
+
+#ifndef ZAP_IMAGE_THREADS
+#define ZAP_IMAGE_THREADS 256  // threads per image of zxc_append_images_kernel (64 is the other value measured)
+#endif
 
 static_assert(sizeof(zxc_enc_job_t) + 4 + 8 == ZAP_JOB_BYTES && 8 + 4 + 4 == ZAP_TILE_BYTES, "the documented work size");
 static_assert(sizeof(zap_ctl_t) <= 256, "the state's place at the start of the work area");
@@ -34,6 +50,8 @@ static_assert(sizeof(zap_ctl_t) <= 256, "the state's place at the start of the w
 extern "C" int zxc_hip_encode_jobs(const void* d_base, zxc_enc_job_t* d_jobs, uint32_t n_jobs, uint32_t block_size, int level,
                                    int with_checksum, const void* d_dict, uint32_t dict_size, void* d_images, void* d_slots,
                                    uint32_t* d_sizes, void* stream);
+extern "C" int zxc_hip_encode_job_images(const void* d_images, const zxc_enc_job_t* d_jobs, uint32_t n_jobs, uint32_t block_size, int level,
+                                         int with_checksum, uint32_t dict_size, void* d_slots, uint32_t* d_sizes, void* stream);
 
 // ---------------------------------------------------------------- kernels
 extern "C" __global__ void zxc_append_begin_kernel(zap_ctl_t* __restrict__ ctl) {
@@ -59,6 +77,44 @@ zxc_append_prep_kernel(const uint8_t* __restrict__ src, zap_piece_t p, uint8_t* 
         const uint8_t* at = (s.area == ZAP_SRC ? src : s.area == ZAP_CARRY ? (const uint8_t*)carry : (const uint8_t*)stage) + s.off;
         zxc_enc_job_t job = {(uint64_t)(uintptr_t)at, s.len, 0u};
         jobs[j] = job;
+    }
+}
+
+// The dictionary session's prep, for the chunk [j0, j0 + n) of the piece's jobs: workgroup w < n builds the image of job j0 + w,
+// [dict | the job's bytes], at images + w x (block_size + dict_size), from the one or two places zap_job_images names (the carried
+// block: the waiting bytes of the carry area, then the head of the source), and writes the job's table entry: the image's offset
+// from `images`, which the encode launch is given as its base. Workgroup n, which only the piece's first chunk has (j0 == 0),
+// copies the tail into the other carry area with ZAP_PAD zero bytes behind it, as prep does. Reads exactly the source bytes the
+// plan names, at any alignment of source, carry and image (dict_size is odd in general); the image area holds n images and
+// ZC_IMAGE_PAD bytes that are left as they are.
+extern "C" __global__ void __launch_bounds__(ZAP_IMAGE_THREADS)
+zxc_append_images_kernel(const uint8_t* __restrict__ src, zap_piece_t p, uint32_t j0, uint32_t n, const uint8_t* __restrict__ dict,
+                         uint32_t dict_size, const uint8_t* __restrict__ carry, uint8_t* __restrict__ next,
+                         uint8_t* __restrict__ images, zxc_enc_job_t* __restrict__ jobs) {
+    const uint32_t w = blockIdx.x, t = threadIdx.x, threads = blockDim.x;
+    if (w >= n) {
+        const zap_copy_t cp = p.cp[2];
+        if (w == n && j0 == 0 && cp.area == ZAP_NEXT) {
+            uint8_t* d = next + cp.at;
+            copy_bytes(d, src + cp.from, cp.len, t, threads);
+            if (t < ZAP_PAD) d[cp.len + t] = 0u;
+        }
+        return;
+    }
+    const zap_src2_t s = zap_job_images(&p, j0 + w);
+    const uint64_t at = (uint64_t)w * ((uint64_t)p.block_size + dict_size);
+    uint8_t* d = images + at;
+    copy_bytes(d, dict, dict_size, t, threads);
+    d += dict_size;
+#pragma unroll
+    for (uint32_t k = 0; k < 2u; k++) {
+        const zap_src_t g = s.seg[k];
+        copy_bytes(d, (g.area == ZAP_CARRY ? carry : src) + g.off, g.len, t, threads);
+        d += g.len;
+    }
+    if (t == 0) {
+        zxc_enc_job_t job = {at, s.seg[0].len + s.seg[1].len, 0u};
+        jobs[j0 + w] = job;
     }
 }
 
@@ -114,9 +170,12 @@ zxc_append_gather_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride
     }
 }
 
+// dict_id != NULL (the dictionary session): the file header carries the flag and *dict_id, a word in device memory read here.
 extern "C" __global__ void zxc_append_finish_kernel(zap_ctl_t* __restrict__ ctl, uint8_t* __restrict__ dst, uint64_t dst_capacity,
-                                                    uint64_t total, uint32_t block_size, uint32_t checksum, uint32_t seekable) {
-    if (threadIdx.x == 0) zap_finish(ctl, dst, dst_capacity, total, block_size, (int)checksum, (int)seekable);
+                                                    uint64_t total, uint32_t block_size, uint32_t checksum, uint32_t seekable,
+                                                    const uint32_t* __restrict__ dict_id) {
+    if (threadIdx.x == 0)
+        zap_finish_dict(ctl, dst, dst_capacity, total, block_size, (int)checksum, (int)seekable, dict_id != NULL, dict_id ? *dict_id : 0u);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -143,7 +202,9 @@ struct Sess {
     uint64_t total;
     uint32_t block_size, level, checksum, seekable;
     uint32_t cur;   // which of the two carry areas holds the waiting bytes
-    uint32_t rsv;
+    uint32_t dict_size;         // 0: a session without a dictionary, the two pointers below NULL
+    const uint8_t* dict;        // the dictionary's d_content
+    const uint32_t* dict_id;    // ... and its d_id
 };
 static_assert(sizeof(Sess) <= sizeof(zxc_dev_cappend_t), "the session fits the caller's struct");
 
@@ -160,12 +221,14 @@ int ap_opts(const zxc_compress_opts_t* opts, Sess* s) {
     s->seekable = (opts && opts->seekable) ? 1u : 0u;
     return ZXC_OK;
 }
-int ap_shape(const Sess& s, zap_shape_t* sh) {
-    return zap_shape(s.max_total, s.max_piece, s.block_size, zxc_mi355x_encode_slot_stride(s.block_size), (int)s.seekable, sh);
+int ap_shape(const Sess& s, zap_shape_images_t* sh) {
+    return zap_shape_images(s.max_total, s.max_piece, s.block_size, zxc_mi355x_encode_slot_stride(s.block_size), (int)s.seekable,
+                            s.dict_size, sh);
 }
 
 // One piece behind its plan: src is the piece's first byte (not read when the plan has no copy and no direct job).
-int ap_piece(const Sess& s, const zap_shape_t& sh, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+    const zap_shape_t& sh = shi.s;
     uint8_t* base = s.base;
     zap_ctl_t* ctl = (zap_ctl_t*)base;
     uint64_t* tile_sum = (uint64_t*)(base + sh.o_tile_sum);
@@ -176,15 +239,31 @@ int ap_piece(const Sess& s, const zap_shape_t& sh, const uint8_t* src, const zap
     uint64_t* offsets = (uint64_t*)(base + sh.o_offsets);
     uint32_t* seek = (uint32_t*)(base + sh.o_seek);
     uint8_t* slots = base + sh.o_slots;
+    uint8_t* carry = base + sh.o_carry[s.cur];
+    uint8_t* next = base + sh.o_carry[s.cur ^ 1u];
 
-    const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
-    const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
-    hipLaunchKernelGGL(zxc_append_prep_kernel, dim3(groups), dim3(256), 0, st, src, p, base + sh.o_carry[s.cur], base + sh.o_carry[s.cur ^ 1u],
-                       base + sh.o_stage, jobs);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    if (!p.nb) return ZXC_OK;
-    const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
-    if (rc != ZXC_OK) return rc;
+    if (s.dict_size && p.nb) {
+        // Blocks are independent, so chunk by chunk gives the bytes of one launch over all of them. A chunk's images are built and
+        // consumed in stream order before the next chunk overwrites them (frame_enqueue of zxc_frame_device.hip).
+        uint8_t* images = base + shi.o_images;
+        for (uint32_t j0 = 0; j0 < p.nb; j0 += shi.chunk_jobs) {
+            const uint32_t n = p.nb - j0 < shi.chunk_jobs ? p.nb - j0 : shi.chunk_jobs;
+            hipLaunchKernelGGL(zxc_append_images_kernel, dim3(n + (j0 == 0 ? 1u : 0u)), dim3(ZAP_IMAGE_THREADS), 0, st, src, p, j0, n, s.dict,
+                               s.dict_size, (const uint8_t*)carry, next, images, jobs);
+            if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+            const int rc = zxc_hip_encode_job_images(images, jobs + j0, n, s.block_size, (int)s.level, (int)s.checksum, s.dict_size,
+                                                     slots + (uint64_t)j0 * sh.slot_stride, sizes + j0, (void*)st);
+            if (rc != ZXC_OK) return rc;
+        }
+    } else {
+        const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
+        const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
+        hipLaunchKernelGGL(zxc_append_prep_kernel, dim3(groups), dim3(256), 0, st, src, p, carry, next, base + sh.o_stage, jobs);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        if (!p.nb) return ZXC_OK;
+        const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
+        if (rc != ZXC_OK) return rc;
+    }
     const uint32_t n_tiles = (p.nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS;
     hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint8_t*)slots, sh.slot_stride,
                        (const uint32_t*)sizes, p.nb, s.block_size, s.checksum, tile_sum, tile_hash, tile_bad);
@@ -201,27 +280,20 @@ int ap_piece(const Sess& s, const zap_shape_t& sh, const uint8_t* src, const zap
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
-}  // namespace
-
-extern "C" {
-
-uint64_t zxc_mi355x_compress_append_device_work_size(uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts) {
-    Sess s;
-    zap_shape_t sh;
-    if (ap_opts(opts, &s) != ZXC_OK) return 0u;
-    s.max_total = max_total; s.max_piece = max_piece;
-    return ap_shape(s, &sh) == 0 ? sh.bytes : 0u;
-}
-
-int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total, uint64_t max_piece,
-                                     const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size, void* stream) {
+// Both kinds of begin behind their names. dict == NULL: the session without a dictionary.
+int ap_begin(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts,
+             const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, void* stream) {
     if (!cs || !d_dst || !d_work) return ZXC_ERROR_NULL_INPUT;
     Sess s = {};
+    if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    const int drc = dict_arg(&dict);
+    if (drc != ZXC_OK) return drc;
     const int orc = ap_opts(opts, &s);
     if (orc != ZXC_OK) return orc;
     s.dst = (uint8_t*)d_dst; s.dst_capacity = dst_capacity; s.max_total = max_total; s.max_piece = max_piece;
     s.base = zd_work_base(d_work);
-    zap_shape_t sh;
+    if (dict) { s.dict = (const uint8_t*)dict->d_content; s.dict_id = dict->d_id; s.dict_size = dict->size; }
+    zap_shape_images_t sh;
     const int src = ap_shape(s, &sh);
     if (src != 0) return src;
     if (work_size < sh.bytes) return ZXC_ERROR_MEMORY;
@@ -235,6 +307,34 @@ int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_
     return ZXC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+uint64_t zxc_mi355x_compress_append_dict_device_work_size(uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts,
+                                                          uint32_t dict_size) {
+    Sess s = {};
+    zap_shape_images_t sh;
+    if (ap_opts(opts, &s) != ZXC_OK || dict_size > ZC_DICT_MAX) return 0u;
+    s.max_total = max_total; s.max_piece = max_piece; s.dict_size = dict_size;
+    return ap_shape(s, &sh) == 0 ? sh.bytes : 0u;
+}
+
+uint64_t zxc_mi355x_compress_append_device_work_size(uint64_t max_total, uint64_t max_piece, const zxc_compress_opts_t* opts) {
+    return zxc_mi355x_compress_append_dict_device_work_size(max_total, max_piece, opts, 0u);
+}
+
+int zxc_mi355x_compress_begin_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total, uint64_t max_piece,
+                                     const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size, void* stream) {
+    return ap_begin(cs, d_dst, dst_capacity, max_total, max_piece, opts, NULL, d_work, work_size, stream);
+}
+
+int zxc_mi355x_compress_begin_dict_device(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t max_total,
+                                          uint64_t max_piece, const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
+                                          uint64_t work_size, void* stream) {
+    return ap_begin(cs, d_dst, dst_capacity, max_total, max_piece, opts, dict, d_work, work_size, stream);
+}
+
 int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, uint64_t n, void* stream) {
     if (!cs || (n > 0 && !d_src)) return ZXC_ERROR_NULL_INPUT;
     Sess s;
@@ -242,7 +342,7 @@ int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, 
     if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
     if (n > s.max_total - s.total) return ZXC_ERROR_OVERFLOW;
     if (n == 0) return ZXC_OK;
-    zap_shape_t sh;
+    zap_shape_images_t sh;
     if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
     // Pieces are independent but for the state, so piece by piece gives the archive of one piece over all the bytes. A piece's
     // areas, jobs and slots are written and consumed in stream order before the next piece overwrites them. Every piece but the
@@ -254,7 +354,8 @@ int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, 
         const uint32_t carry = (uint32_t)(s.total % s.block_size);
         const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
         zap_piece_t p;
-        zap_plan_piece(carry, m, s.block_size, &p);
+        if (s.dict_size) zap_plan_piece_images(carry, m, s.block_size, &p);
+        else zap_plan_piece(carry, m, s.block_size, &p);
         rc = ap_piece(s, sh, src, p, (hipStream_t)stream);
         if (p.swap) s.cur ^= 1u;
         s.total += m; src += m; left -= m;
@@ -270,7 +371,7 @@ int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, voi
     memcpy(&s, cs, sizeof s);
     if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
     memset(cs, 0, sizeof *cs);  // spent, whatever happens below
-    zap_shape_t sh;
+    zap_shape_images_t sh;
     if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;
     const hipStream_t st = (hipStream_t)stream;
     zap_ctl_t* ctl = (zap_ctl_t*)s.base;
@@ -280,13 +381,14 @@ int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, voi
         const int rc = ap_piece(s, sh, NULL, p, st);
         if (rc != ZXC_OK) return rc;
     }
-    hipLaunchKernelGGL(zxc_append_finish_kernel, dim3(1), dim3(64), 0, st, ctl, s.dst, s.dst_capacity, s.total, s.block_size, s.checksum, s.seekable);
+    hipLaunchKernelGGL(zxc_append_finish_kernel, dim3(1), dim3(64), 0, st, ctl, s.dst, s.dst_capacity, s.total, s.block_size, s.checksum, s.seekable,
+                       s.dict_size ? s.dict_id : (const uint32_t*)NULL);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     const uint64_t nb = s.total / s.block_size + (s.total % s.block_size != 0);  // <= 2^31 - 1 (begin)
     if (s.seekable && nb) {
         const uint32_t groups = (nb + 255u) / 256u < 4096u ? (uint32_t)((nb + 255u) / 256u) : 4096u;
         hipLaunchKernelGGL(zxc_append_seek_kernel, dim3(groups), dim3(256), 0, st, (const zap_ctl_t*)ctl, s.dst,
-                           (const uint32_t*)(s.base + sh.o_seek), (uint32_t)nb);
+                           (const uint32_t*)(s.base + sh.s.o_seek), (uint32_t)nb);
         if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     }
     hipLaunchKernelGGL(zxc_append_result_kernel, dim3(1), dim3(64), 0, st, (const zap_ctl_t*)ctl, d_result);

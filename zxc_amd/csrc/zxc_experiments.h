@@ -15,7 +15,8 @@
 #define ZXC_EXPERIMENTS_H
 #ifndef ZXC_EXPERIMENT
 #if defined(ASM_MARKERS) || defined(EXP_ENC_CLOCKS) || defined(EXP_NO_PRE) || defined(EXP_PHASES) || defined(EXP_PIV_PROF) || defined(EXP_TIMES) || \
-    defined(EXP_ORDER_MIX_ROWS) /* (another row count for zxc_dev_order_mix, zxc_dev.h) */
+    defined(EXP_ORDER_MIX_ROWS) /* (another row count for zxc_dev_order_mix, zxc_dev.h) */ || \
+    defined(ZAP_IMAGE_THREADS)  /* (another workgroup size for zxc_append_images_kernel, zxc_append_device.hip) */
 #error "an experiment switch is defined without -DZXC_EXPERIMENT: this is not the product configuration (zxc_experiments.h)"
 #endif
 #endif

@@ -472,6 +472,28 @@ static int encode_launch(const void* d_src, uint64_t src_size, uint32_t block_si
     return lerr == hipSuccess ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
+/* The encode launch over a job table whose inputs are in place: workgroup i encodes d_jobs[i].len bytes at in + d_jobs[i].src_off
+ * (behind dict_size dictionary bytes when there is a dictionary) into slot i and writes d_sizes[i]. Entry and effort come from the
+ * level table as in encode_launch. */
+static int encode_jobs_launch(const uint8_t* in, const zxc_enc_job_t* d_jobs, uint32_t n_jobs, uint32_t block_size, int level,
+                              int with_checksum, uint32_t dict_size, void* d_slots, uint32_t* d_sizes, void* stream) {
+    zxc_enc_level_t lp = zxc_enc_level_bs(level, block_size);
+    uint8_t* huf_scratch = NULL;
+    if (lp.huf) {  // levels 6-7: the PivCo encoder's scratch per job, stream-ordered as in encode_launch
+        const size_t need = (size_t)n_jobs * 4u * ((size_t)block_size + 64u);
+        if (hipMallocAsync((void**)&huf_scratch, need, (hipStream_t)stream) != hipSuccess || !huf_scratch) return ZXC_ERROR_MEMORY;
+    }
+    auto kern = lp.entry == 0 ? zxc_encode_jobs_kernel_l1 : lp.entry == 1 ? zxc_encode_jobs_kernel_l2
+              : lp.entry == 2 ? zxc_encode_jobs_kernel_l3 : lp.entry == 3 ? zxc_encode_jobs_kernel_l4
+              : lp.entry == 4 ? zxc_encode_jobs_kernel_l57 : zxc_encode_jobs_kernel_l67;
+    hipLaunchKernelGGL(kern, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, in, d_jobs, block_size,
+                       (uint8_t*)d_slots, zxc_mi355x_encode_slot_stride(block_size), d_sizes, n_jobs, with_checksum ? 1u : 0u,
+                       lp.depth, lp.sufficient, lp.lazy, dict_size, huf_scratch, lp.huf);
+    const hipError_t lerr = hipGetLastError();
+    if (huf_scratch) (void)hipFreeAsync(huf_scratch, (hipStream_t)stream);
+    return lerr == hipSuccess ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
 /* internal to the library (hidden): the encode launch over a job table in device memory (zxc_cbatch_device.hip): workgroup i
  * encodes d_jobs[i].len bytes at d_base + d_jobs[i].src_off into slot i and writes d_sizes[i]; a job of len 0 is unused and its
  * d_sizes[i] stays. Entry and effort come from the level table as in encode_launch. With dict_size != 0 the jobs point at
@@ -487,21 +509,16 @@ int zxc_hip_encode_jobs(const void* d_base, zxc_enc_job_t* d_jobs, uint32_t n_jo
         if (hipGetLastError() != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
         in = (const uint8_t*)d_images;
     }
-    zxc_enc_level_t lp = zxc_enc_level_bs(level, block_size);
-    uint8_t* huf_scratch = NULL;
-    if (lp.huf) {  // levels 6-7: the PivCo encoder's scratch per job, stream-ordered as in encode_launch
-        const size_t need = (size_t)n_jobs * 4u * ((size_t)block_size + 64u);
-        if (hipMallocAsync((void**)&huf_scratch, need, (hipStream_t)stream) != hipSuccess || !huf_scratch) return ZXC_ERROR_MEMORY;
-    }
-    auto kern = lp.entry == 0 ? zxc_encode_jobs_kernel_l1 : lp.entry == 1 ? zxc_encode_jobs_kernel_l2
-              : lp.entry == 2 ? zxc_encode_jobs_kernel_l3 : lp.entry == 3 ? zxc_encode_jobs_kernel_l4
-              : lp.entry == 4 ? zxc_encode_jobs_kernel_l57 : zxc_encode_jobs_kernel_l67;
-    hipLaunchKernelGGL(kern, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, in, (const zxc_enc_job_t*)d_jobs, block_size,
-                       (uint8_t*)d_slots, zxc_mi355x_encode_slot_stride(block_size), d_sizes, n_jobs, with_checksum ? 1u : 0u,
-                       lp.depth, lp.sufficient, lp.lazy, dict_size, huf_scratch, lp.huf);
-    const hipError_t lerr = hipGetLastError();
-    if (huf_scratch) (void)hipFreeAsync(huf_scratch, (hipStream_t)stream);
-    return lerr == hipSuccess ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return encode_jobs_launch(in, d_jobs, n_jobs, block_size, level, with_checksum, dict_size, d_slots, d_sizes, stream);
+}
+
+/* internal to the library (hidden): the same launch over images the caller has built (zxc_append_device.hip): job i's src_off is
+ * the offset of its [dict | len bytes] image from d_images, behind the last of which ZC_IMAGE_PAD bytes are readable. dict_size
+ * != 0. Nothing is written to the jobs or the images. */
+int zxc_hip_encode_job_images(const void* d_images, const zxc_enc_job_t* d_jobs, uint32_t n_jobs, uint32_t block_size, int level,
+                              int with_checksum, uint32_t dict_size, void* d_slots, uint32_t* d_sizes, void* stream) {
+    if (n_jobs == 0) return ZXC_OK;
+    return encode_jobs_launch((const uint8_t*)d_images, d_jobs, n_jobs, block_size, level, with_checksum, dict_size, d_slots, d_sizes, stream);
 }
 
 int zxc_mi355x_encode_blocks_device(const void* d_src, uint64_t src_size, uint32_t block_size, int level,

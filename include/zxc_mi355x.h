@@ -544,6 +544,52 @@ ZXC_EXPORT int zxc_mi355x_compress_begin_dict_device(zxc_dev_cappend_t* cs, void
                                                      uint64_t max_piece, const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict,
                                                      void* d_work, uint64_t work_size, void* stream);
 
+/* Append a table of buffers: the writev of the session (rules in zxc_amd/csrc/zxc_appendv.h). One append per tensor of a state
+ * dict is about six launches per tensor, and the encode launch of a small tensor holds a handful of blocks, one wavefront each;
+ * concatenating the tensors first is the second copy of everything the session exists to avoid. Here one call takes a table of
+ * (base, len) entries that lies in device memory and appends their concatenation X, in table order: the blocks of a chunk of at
+ * most max_piece bytes are cut from X, not from the entries, so one encode launch carries max_piece / block_size blocks however
+ * small the entries are. The call is exactly zxc_mi355x_compress_append_device(cs, X, total, stream): after end the archive and
+ * *d_result are byte for byte what the session gives for X. append and appendv mix freely in one session, in any order, with a
+ * carry across every boundary.
+ * The table: d_iov lies in device memory and is read on the stream (a kernel or copy enqueued before the call may write it, a
+ * replayed graph may see other pointers). The host knows only n_iov and total, the caller's promise of the sum of the lengths:
+ * that gives it what it knows in append (carry, chunk cuts, grids), so nothing about the launch shape is decided on the device.
+ * Entries of length 0 are legal anywhere and their base is not looked at; an entry may have any alignment; entries may overlap
+ * each other; entries that overlap d_dst, the work area or d_scratch are the caller's error. The call reads exactly
+ * [base, base + len) of every entry: nothing is promised readable behind an entry.
+ * Stream order: once per call a scan (exclusive prefix sums of the lengths into the scratch, and the table check, in three tile
+ * passes), then per chunk prep, encode, tiles, advance, scatter, gather as in append. Prep runs one workgroup per job: the head
+ * that completes the waiting block and the tail are gathered into the session's carry areas; a whole block that lies inside one
+ * entry with its 32-byte over-read inside that same entry is encoded in place; every other whole block is gathered into an image
+ * in the scratch with 64 zero bytes behind it. The gather is destination-driven (a thread owns 16-byte units of the image, finds
+ * the entry of its first byte by a search over the start offsets, and takes the unit with one 16-byte load when it lies inside
+ * one entry, else byte by byte from consecutive entries), so its cost does not depend on how small the entries are.
+ * Scratch: d_scratch (any alignment) is the call's own until the work this call enqueued has run; a later appendv on the same
+ * stream may reuse it. It is not part of the session's work area. With J = max_piece / block_size + 2 its size is at most
+ * 8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + J x (block_size + 256) + 4096: the entries' start offsets, the words of the scan per
+ * tile of 1024 entries, one image per job of a chunk, alignment. The size function returns 0 for options or a max_piece that begin
+ * would refuse; max_piece is the session's.
+ * Table errors are found on the device and become the session's sticky status, which end reports: an error the session already
+ * has stays; else an entry with len > 0 and base == 0 -> ZXC_ERROR_NULL_INPUT; else an entry longer than total, or a sum above
+ * total (compared without overflow) -> ZXC_ERROR_OVERFLOW; else a sum below total -> ZXC_ERROR_SRC_TOO_SMALL. After any of these
+ * no byte of any entry of that call is read and none of its blocks is encoded or gathered; the host's byte count has moved on by
+ * total, as it cannot know.
+ * Synchronous errors, before anything is enqueued and with the session as it was, in this order: NULL cs, NULL d_scratch, NULL
+ * d_iov with n_iov > 0 -> ZXC_ERROR_NULL_INPUT; a session never begun or ended -> ZXC_ERROR_NULL_INPUT; a session begun with a
+ * dictionary -> ZXC_ERROR_GPU_UNSUPPORTED; n_iov == 0 with total > 0 -> ZXC_ERROR_SRC_TOO_SMALL; bytes so far + total > max_total
+ * -> ZXC_ERROR_OVERFLOW; scratch_size too small -> ZXC_ERROR_MEMORY. n_iov == 0 with total == 0 is ZXC_OK and enqueues nothing.
+ * A launch failure leaves the session spent, as in append. Asynchronous on `stream` and capturable like append: no host
+ * synchronisation, no device allocation beyond the encoder's stream-ordered scratch at levels 6-7. */
+
+/* One entry of a source table (16 bytes, device-visible layout): len bytes at the device address base. */
+typedef struct zxc_dev_iov { uint64_t base; uint64_t len; } zxc_dev_iov_t;
+
+ZXC_EXPORT uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_iov, uint64_t max_piece,
+                                                                    const zxc_compress_opts_t* opts);
+ZXC_EXPORT int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov,
+                                                  uint64_t total, void* d_scratch, uint64_t scratch_size, void* stream);
+
 /* ---- one archive into many pieces, device to device (zxc_amd/csrc/zxc_take_device.hip, rules in zxc_amd/csrc/zxc_take.h) ----
  * zxc_mi355x_decompress_device wants one contiguous, 16-byte aligned destination of the whole decoded size: whoever wrote an
  * archive from a list of tensors with the session above needs a second copy of everything in HBM to read it back, and a device

@@ -15,6 +15,7 @@ JOB_DTYPE = np.dtype([("comp_off", "<u8"), ("out_off", "<u8"), ("comp_size", "<u
 RANGE_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("dst_off", "<u8")])
 # zxc_dev_item_t (include/zxc_mi355x.h)
 ITEM_DTYPE = np.dtype([("src_off", "<u8"), ("src_size", "<u8"), ("dst_off", "<u8"), ("dst_capacity", "<u8")])
+IOV_DTYPE = np.dtype([("base", "<u8"), ("len", "<u8")])  # zxc_dev_iov_t
 
 
 class ZxcError(RuntimeError):
@@ -549,6 +550,11 @@ def _bind_compress_append_device(L):
     L.zxc_mi355x_compress_begin_dict_device.restype = C.c_int
     L.zxc_mi355x_compress_begin_dict_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                         C.POINTER(_CompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zxc_mi355x_compress_appendv_device_scratch_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_appendv_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
+    L.zxc_mi355x_compress_appendv_device.restype = C.c_int
+    L.zxc_mi355x_compress_appendv_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p]
     return L
 
 
@@ -558,10 +564,18 @@ def compress_append_device_work_size(max_total, max_piece, level=3, block_size=0
     return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_append_device_work_size(max_total, max_piece, C.byref(o)))
 
 
+def compress_appendv_device_scratch_size(n_iov, max_piece, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_appendv_device_scratch_size(): bytes of device scratch one appendv of n_iov entries needs in a session
+    of that max_piece (0 for refused arguments)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_device_scratch_size(n_iov, max_piece, C.byref(o)))
+
+
 class CompressAppendSession:
-    """A session of zxc_mi355x_compress_begin_device(): .append(d_src, n) any number of times, then .end(d_result) once. Raw device
-    pointers (ints), asynchronous on `stream`; the calls of one session must be in stream order with each other. The archive
-    size or a negative zxc_error_t lands in the int64 at d_result; a synchronous failure raises ZxcError."""
+    """A session of zxc_mi355x_compress_begin_device(): .append(d_src, n) and .appendv(d_iov, n_iov, total, d_scratch,
+    scratch_size) any number of times, then .end(d_result) once. Raw device pointers (ints), asynchronous on `stream`; the calls of
+    one session must be in stream order with each other. The archive size or a negative zxc_error_t lands in the int64 at d_result;
+    a synchronous failure raises ZxcError."""
 
     def __init__(self, cs):
         self._cs = cs
@@ -571,6 +585,15 @@ class CompressAppendSession:
                                                                                    C.c_void_p(stream or None))
         if rc < 0:
             raise ZxcError(rc, "zxc_mi355x_compress_append_device")
+
+    def appendv(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
+        """zxc_mi355x_compress_appendv_device(): appends the concatenation of the n_iov x IOV_DTYPE entries at d_iov (device
+        memory), `total` bytes in all; the scratch size is compress_appendv_device_scratch_size(n_iov, max_piece, ...)."""
+        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_device(
+            C.byref(self._cs), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
+            C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_compress_appendv_device")
 
     def end(self, d_result, stream=0):
         rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_end_device(C.byref(self._cs), C.c_void_p(d_result or None),

@@ -33,11 +33,24 @@
 // with tiles, advance, scatter and gather once over the whole piece as above, and the dictionary flag and *d_id in the file header
 // that finish writes. A piece that completes no block is prep's, as it is.
 //
+// zxc_mi355x_compress_appendv_device appends a table of (base, len) entries in device memory, the concatenation of which is the
+// source (zxc_appendv.h): once per call
+//
+//   scan     three tile passes over the table: start offsets of the entries into the call's scratch, the table check and its
+//            verdict, which becomes the session's status unless that holds an error
+//
+// then per chunk of at most max_piece bytes of the concatenation the piece above, with
+//
+//   prep     zxc_appendv_prep_kernel, one workgroup per job and one for the tail: head and tail gathered into the carry areas, a
+//            whole block left in place (inside one entry, over-read included) or gathered into its image in the scratch
+//   advance  zxc_appendv_advance_kernel: the advance above, not run after a table error
+//
 // No workgroup waits for another: every dependency is the stream order between launches.
 #include <string.h>
 
 #include "zxc_device_util.h"  // the tile passes, copy_bytes (zxc_wave.h), zxc_frame_tiles_kernel, the host-side plumbing
 #include "zxc_append.h"
+#include "zxc_appendv.h"
 
 #ifndef ZAP_IMAGE_THREADS
 #define ZAP_IMAGE_THREADS 256  // threads per image of zxc_append_images_kernel (64 is the other value measured)
@@ -188,6 +201,132 @@ extern "C" __global__ void zxc_append_result_kernel(const zap_ctl_t* __restrict_
     if (threadIdx.x == 0) *result = ctl->status;
 }
 
+// ---------------------------------------------------------------- appendv: a table of sources (zxc_appendv.h)
+// The scan of a call, three tile passes of 256 threads over tiles of 1024 entries, like the passes of zxc_device_util.h but over
+// 64-bit lengths that add up saturating (zav_sat_add), so that a table whose sum passes 2^64 is still seen as above `total`.
+
+// Exclusive saturating scan of one value per thread over the workgroup of 256: -> the sum of all lower threads' values; *all gets
+// the workgroup's sum. One barrier; called by all threads outside divergent control flow, once per kernel.
+__device__ __forceinline__ uint64_t zav_wg_scan(uint64_t mine, uint64_t* all) {
+    __shared__ uint64_t w_tot[4];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(incl, (unsigned)d);
+        if ((int)lane >= d) incl = zav_sat_add(o, incl);
+    }
+    uint64_t excl = __shfl_up(incl, 1u);
+    if (lane == 0) excl = 0;
+    if (lane == 63) w_tot[wave] = incl;
+    __syncthreads();
+    uint64_t run = 0, tot = 0;
+    for (uint32_t w = 0; w < 4u; w++) {
+        if (w < wave) run = zav_sat_add(run, w_tot[w]);
+        tot = zav_sat_add(tot, w_tot[w]);
+    }
+    *all = tot;
+    return zav_sat_add(run, excl);
+}
+
+// The flags of the check ored over the workgroup (__syncthreads_or answers only whether any thread's value is non-zero). Two barriers.
+__device__ __forceinline__ uint32_t zav_wg_flags(uint32_t flags) {
+    const uint32_t null = __syncthreads_or((int)(flags & ZAV_NULL)) ? ZAV_NULL : 0u;
+    const uint32_t big = __syncthreads_or((int)(flags & ZAV_BIG)) ? ZAV_BIG : 0u;
+    return null | big;
+}
+
+// Reduce, per tile: the sum of the tile's lengths and the flags of its entries.
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
+zxc_appendv_reduce_kernel(const zxc_dev_iov_t* __restrict__ iov, uint32_t n_iov, uint64_t total, uint64_t* __restrict__ tile_sum,
+                          uint32_t* __restrict__ tile_flags) {
+    const uint64_t r0 = (uint64_t)blockIdx.x * ZC_TILE_BLOCKS + threadIdx.x * ZD_PER_THREAD;
+    uint64_t sum = 0;
+    uint32_t flags = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
+        if (r0 + j >= n_iov) break;
+        const zxc_dev_iov_t e = iov[r0 + j];
+        flags |= zav_entry_flags(e.base, e.len, total);
+        sum = zav_sat_add(sum, e.len);
+    }
+    uint64_t all;
+    (void)zav_wg_scan(sum, &all);
+    flags = zav_wg_flags(flags);
+    if (threadIdx.x == 0) { tile_sum[blockIdx.x] = all; tile_flags[blockIdx.x] = flags; }
+}
+
+// One workgroup: tile_sum[t] becomes the virtual offset of tile t's first entry; the table's verdict goes to the call's control
+// word, which every later kernel of the call reads, and into the session's status unless that holds an error already.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_appendv_scan_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_flags, uint32_t n_tiles, uint64_t total,
+                        uint64_t* __restrict__ starts, uint32_t n_iov, zav_ctl_t* __restrict__ vctl, zap_ctl_t* __restrict__ ctl) {
+    const uint32_t t = threadIdx.x, per = (n_tiles + 255u) / 256u;
+    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    uint64_t mine = 0;
+    uint32_t flags = 0;
+    for (uint32_t i = lo; i < hi; i++) { mine = zav_sat_add(mine, tile_sum[i]); flags |= tile_flags[i]; }
+    uint64_t all;
+    uint64_t run = zav_wg_scan(mine, &all);
+    flags = zav_wg_flags(flags);
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint64_t s = tile_sum[i];
+        tile_sum[i] = run;
+        run = zav_sat_add(run, s);
+    }
+    if (t == 0) {
+        const int status = zav_table_status(flags, all, total);
+        vctl->status = status; vctl->rsv = 0; vctl->sum = all;
+        starts[n_iov] = all;
+        zav_fold_status(ctl, status);
+    }
+}
+
+// Scatter, per tile: starts[r] = the virtual offset of entry r.
+extern "C" __global__ void __launch_bounds__(ZD_TILE_THREADS)
+zxc_appendv_starts_kernel(const zxc_dev_iov_t* __restrict__ iov, uint32_t n_iov, const uint64_t* __restrict__ tile_off,
+                          uint64_t* __restrict__ starts) {
+    const uint64_t r0 = (uint64_t)blockIdx.x * ZC_TILE_BLOCKS + threadIdx.x * ZD_PER_THREAD;
+    uint64_t len[ZD_PER_THREAD], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
+        len[j] = r0 + j < n_iov ? iov[r0 + j].len : 0u;
+        sum = zav_sat_add(sum, len[j]);
+    }
+    uint64_t all;
+    uint64_t run = zav_sat_add(tile_off[blockIdx.x], zav_wg_scan(sum, &all));
+#pragma unroll
+    for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
+        if (r0 + j >= n_iov) break;
+        starts[r0 + j] = run;
+        run = zav_sat_add(run, len[j]);
+    }
+}
+
+// Prep of one chunk: workgroup w runs task w of the chunk's plan (zav_prep: the gather into the carry areas and the images, the
+// in-place jobs, the job table), the new hot path: a chunk made of small entries passes through it whole.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_appendv_prep_kernel(const zxc_dev_iov_t* __restrict__ iov, const uint64_t* __restrict__ starts, uint32_t n_iov,
+                        const zav_ctl_t* __restrict__ vctl, zav_chunk_t c, uint8_t* __restrict__ carry, uint8_t* __restrict__ next,
+                        uint8_t* __restrict__ images, uint32_t image, zxc_enc_job_t* __restrict__ jobs) {
+    zav_prep(iov, starts, n_iov, vctl->status, &c, blockIdx.x, threadIdx.x, blockDim.x, carry, next, images, image, jobs);
+}
+
+// zxc_append_advance_kernel for a chunk of an appendv: after a table error the chunk's blocks were never encoded, their sizes are
+// whatever the slots' last user left, and the session's state stays as the scan left it.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_appendv_advance_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
+                           uint32_t n_tiles, uint32_t nb_piece, uint64_t dst_capacity, uint32_t checksum, uint32_t seekable,
+                           zap_ctl_t* __restrict__ ctl, const zav_ctl_t* __restrict__ vctl) {
+    if (vctl->status < 0) return;
+    const uint64_t base = ctl->off;
+    const zd_totals all = zd_scan_tiles(
+        n_tiles, base,
+        [=](uint32_t i, uint32_t& hash, uint32_t& bad) { const uint64_t s = tile_sum[i]; hash ^= tile_hash[i]; bad |= tile_bad[i]; return s; },
+        [=](uint32_t i, uint64_t off) { tile_sum[i] = off; });
+    if (threadIdx.x == 0) zap_advance(ctl, nb_piece, all.sum, all.hash, all.bad, dst_capacity, (int)checksum, (int)seekable);
+}
+
 // ---------------------------------------------------------------- host side
 namespace {
 
@@ -226,8 +365,21 @@ int ap_shape(const Sess& s, zap_shape_images_t* sh) {
                             s.dict_size, sh);
 }
 
-// One piece behind its plan: src is the piece's first byte (not read when the plan has no copy and no direct job).
-int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+// The virtual source of an appendv (zxc_appendv.h): the table, what the call's scan left in its scratch, and the offset in the
+// concatenation of the chunk at hand.
+struct Vsrc {
+    const zxc_dev_iov_t* iov;
+    uint32_t n_iov, image;
+    const uint64_t* starts;
+    const zav_ctl_t* vctl;
+    uint8_t* images;
+    uint64_t v;
+};
+
+// One piece behind its plan: src is the piece's first byte (not read when the plan has no copy and no direct job). With vs (a
+// session without a dictionary) the piece is a chunk of an appendv: src is not looked at, prep is zxc_appendv_prep_kernel and the
+// advance is predicated on the table's verdict.
+int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, const zap_piece_t& p, hipStream_t st, const Vsrc* vs = NULL) {
     const zap_shape_t& sh = shi.s;
     uint8_t* base = s.base;
     zap_ctl_t* ctl = (zap_ctl_t*)base;
@@ -255,6 +407,15 @@ int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, c
                                                      slots + (uint64_t)j0 * sh.slot_stride, sizes + j0, (void*)st);
             if (rc != ZXC_OK) return rc;
         }
+    } else if (vs) {
+        zav_chunk_t c;
+        c.p = p; c.v = vs->v;
+        hipLaunchKernelGGL(zxc_appendv_prep_kernel, dim3(zav_groups(&c)), dim3(256), 0, st, vs->iov, vs->starts, vs->n_iov, vs->vctl, c, carry, next,
+                           vs->images, vs->image, jobs);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        if (!p.nb) return ZXC_OK;
+        const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
+        if (rc != ZXC_OK) return rc;
     } else {
         const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
         const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
@@ -268,8 +429,12 @@ int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, c
     hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint8_t*)slots, sh.slot_stride,
                        (const uint32_t*)sizes, p.nb, s.block_size, s.checksum, tile_sum, tile_hash, tile_bad);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    hipLaunchKernelGGL(zxc_append_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
-                       n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl);
+    if (vs)
+        hipLaunchKernelGGL(zxc_appendv_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
+                           n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl, vs->vctl);
+    else
+        hipLaunchKernelGGL(zxc_append_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
+                           n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     hipLaunchKernelGGL(zxc_append_scatter_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,
                        (const uint64_t*)tile_sum, offsets, seek, s.seekable, (const zap_ctl_t*)ctl);
@@ -361,6 +526,63 @@ int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, 
         s.total += m; src += m; left -= m;
     }
     if (rc != ZXC_OK) s.magic = 0;  // part of the append may be enqueued: the session cannot go on
+    memcpy(cs, &s, sizeof s);
+    return rc;
+}
+
+uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_iov, uint64_t max_piece, const zxc_compress_opts_t* opts) {
+    Sess s = {};
+    zav_shape_t sh;
+    if (ap_opts(opts, &s) != ZXC_OK) return 0u;
+    return zav_shape(n_iov, max_piece, s.block_size, &sh) == 0 ? sh.bytes : 0u;
+}
+
+int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total, void* d_scratch,
+                                       uint64_t scratch_size, void* stream) {
+    if (!cs || !d_scratch || (n_iov > 0 && !d_iov)) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, cs, sizeof s);
+    if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (s.dict_size) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (n_iov == 0 && total > 0) return ZXC_ERROR_SRC_TOO_SMALL;
+    if (total > s.max_total - s.total) return ZXC_ERROR_OVERFLOW;
+    zap_shape_images_t sh;
+    zav_shape_t vsh;
+    if (ap_shape(s, &sh) != 0 || zav_shape(n_iov, s.max_piece, s.block_size, &vsh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    if (scratch_size < vsh.bytes) return ZXC_ERROR_MEMORY;
+    if (n_iov == 0) return ZXC_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* sb = zd_work_base(d_scratch);
+    zav_ctl_t* vctl = (zav_ctl_t*)sb;
+    uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
+    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
+    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
+    // The scan, once per call: the chunks below read starts and the verdict in stream order.
+    int rc = ZXC_OK;
+    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
+    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
+                           n_iov, vctl, (zap_ctl_t*)s.base);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    // The chunks, cut like the pieces of an append of `total` bytes: every chunk but the last ends on a block boundary of the archive.
+    Vsrc vs = {d_iov, n_iov, vsh.image, starts, vctl, sb + vsh.o_images, 0u};
+    uint64_t left = total;
+    while (left && rc == ZXC_OK) {
+        const uint32_t carry = (uint32_t)(s.total % s.block_size);
+        const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
+        zap_piece_t p;
+        zap_plan_piece(carry, m, s.block_size, &p);
+        rc = ap_piece(s, sh, NULL, p, st, &vs);
+        if (p.swap) s.cur ^= 1u;
+        s.total += m; vs.v += m; left -= m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;  // part of the call may be enqueued: the session cannot go on
     memcpy(cs, &s, sizeof s);
     return rc;
 }

@@ -37,7 +37,7 @@ static void rpd_free(rpd_session_t* s) {
     rp_free(&s->r);
 }
 
-/* one piece of the images-mode plan: src = exactly the piece's p->n bytes (NULL for the plan of `end`) */
+/* one piece of the images-mode plan, the images front end: src = exactly the piece's p->n bytes (NULL for the plan of `end`) */
 static void rpd_piece(rpd_session_t* d, const uint8_t* src, const zap_piece_t* p) {
     rp_session_t* s = &d->r;
     if (!p->nb) { rp_piece(s, src, p); return; } /* joins the carry: the prep kernel as it is */
@@ -70,41 +70,24 @@ static void rpd_piece(rpd_session_t* d, const uint8_t* src, const zap_piece_t* p
             const uint64_t k = first_block + j0 + w;
             if (job.src_off + d->dict_size + job.len + ZAP_OVERREAD > (uint64_t)n * image + ZC_IMAGE_PAD) s->bad = 1; /* the over-read */
             if (job.len == 0 || job.len > s->bs || (j0 + w + 1u < p->nb && job.len != s->bs)) s->bad = 1;
-            if (k >= s->n_blocks || memcmp(in, d->dict, d->dict_size) != 0 || memcmp(in + d->dict_size, s->src + k * s->bs, job.len) != 0) {
+            if (memcmp(in, d->dict, d->dict_size) != 0 || !rp_encode_job(s, j0 + w, k, in + d->dict_size, job.len)) {
                 s->bad = 1;
                 s->sizes[j0 + w] = 0;
-                continue;
             }
-            memcpy(s->slots + (size_t)(j0 + w) * s->stride, s->blocks + s->blk_at[k], s->blk_size[k] <= s->stride ? s->blk_size[k] : s->stride);
-            s->sizes[j0 + w] = s->blk_size[k];
         }
     }
-    uint64_t sum = 0;
-    uint32_t hash = 0, bad = 0;
-    zap_piece_totals(s->sizes, s->slots, s->stride, p->nb, s->bs, s->checksum, &sum, &hash, &bad); /* the tiles pass */
-    const uint64_t base = s->ctl.off;
-    if (!zap_advance(&s->ctl, p->nb, sum, hash, bad, s->cap, s->checksum, s->seekable)) return;
-    uint64_t run = base;
-    for (uint32_t b = 0; b < p->nb; b++) { /* scatter and gather */
-        s->offsets[b] = run;
-        run += s->sizes[b];
-        if (s->seekable) s->seek[s->ctl.first + b] = s->sizes[b];
-        memcpy(s->dst + s->offsets[b], s->slots + (size_t)b * s->stride, s->sizes[b]);
-    }
+    rp_back(s, p->nb);
 }
 
 /* the loop of zxc_mi355x_compress_append_device in a dictionary session: the next n bytes of the source */
 static void rpd_append(rpd_session_t* d, uint64_t n) {
     rp_session_t* s = &d->r;
-    uint64_t left = n, at = s->total;
-    while (left) {
-        const uint32_t carry = (uint32_t)(s->total % s->bs);
-        const uint64_t m = zap_piece_len(carry, left, s->max_piece, s->bs);
-        if (m == 0 || m > left || m > s->max_piece || (m < left && (carry + m) % s->bs != 0)) { s->bad = 1; break; }
+    uint64_t left = n, at = s->total, m;
+    while (left && rp_next_piece(s, left, &m)) {
         uint8_t* piece = malloc(m); /* exactly the piece's bytes */
         memcpy(piece, s->src + at, m);
         zap_piece_t p;
-        zap_plan_piece_images(carry, m, s->bs, &p);
+        zap_plan_piece_images((uint32_t)(s->total % s->bs), m, s->bs, &p);
         rpd_piece(d, piece, &p);
         free(piece);
         s->total += m;
@@ -270,7 +253,7 @@ static int64_t rpd_check_archive(const uint8_t* comp, uint64_t comp_size, const 
     return result;
 }
 
-/* Archives of stored blocks (the stand-in encoder of append_san_main.c), built serially with a dictionary header, of several
+/* Archives of stored blocks (rp_stored_archive, the stand-in encoder of append_san_main.c) with a dictionary header, of several
  * blocks: both block sizes, checksum, seekable, dictionaries of 1 and 4099 bytes. -> the number of cut sets, or minus a line. */
 static int64_t rpd_selftest(void) {
     const uint32_t bss[2] = {4096u, 65536u}, dsz[2] = {1u, 4099u};
@@ -285,37 +268,13 @@ static int64_t rpd_selftest(void) {
             for (uint32_t i = 0; i < D; i++) dict[i] = (uint8_t)(i * 7u + 3u);
             for (int t = 0; t < 5; t++) {
                 const uint64_t total = totals[t];
-                const uint32_t nb = (uint32_t)((total + bs - 1u) / bs), id = 0xD1C70000u + (uint32_t)t + 16u * (uint32_t)flags;
+                const uint32_t id = 0xD1C70000u + (uint32_t)t + 16u * (uint32_t)flags;
                 uint8_t* data = malloc(total ? total : 1u);
                 for (uint64_t i = 0; i < total; i++) { r = r * 1664525u + 1013904223u; data[i] = (uint8_t)(r >> 13); }
-                const uint64_t size = zc_known_size(nb, checksum, seekable) + total;
-                uint8_t* comp = malloc(size);
-                zc_put_file_header(comp, zc_block_size_lg(bs), checksum, 1, id);
-                uint64_t o = ZC_FILE_HDR;
-                uint32_t hash = 0;
-                for (uint32_t k = 0; k < nb; k++) {
-                    const uint32_t n = total - (uint64_t)k * bs < bs ? (uint32_t)(total - (uint64_t)k * bs) : bs;
-                    zc_st_le(comp + o, zc_blk_hdr(0u, n), 8);
-                    memcpy(comp + o + 8, data + (uint64_t)k * bs, n);
-                    o += 8u + n;
-                    if (checksum) {
-                        const uint32_t tr = 0x9E3779B9u * (k + 1u) ^ data[(uint64_t)k * bs];
-                        zc_st_le(comp + o, tr, 4);
-                        hash = zc_hash_fold(hash, tr);
-                        o += 4;
-                    }
-                }
-                zc_st_le(comp + o, zc_blk_hdr(ZC_BLK_EOF, 0u), 8); o += 8;
-                if (seekable && nb) {
-                    zc_st_le(comp + o, zc_blk_hdr(ZC_BLK_SEK, nb * 4u), 8); o += 8;
-                    for (uint32_t k = 0; k < nb; k++) {
-                        const uint32_t n = total - (uint64_t)k * bs < bs ? (uint32_t)(total - (uint64_t)k * bs) : bs;
-                        zc_st_le(comp + o, 8u + n + (checksum ? 4u : 0u), 4); o += 4;
-                    }
-                }
-                zc_put_footer(comp + o, total, checksum ? hash : 0u);
-                int64_t rc = o + ZC_FOOTER == size ? rpd_check_archive(comp, size, data, total, dict, D, 7u + (uint32_t)t, 0) : -__LINE__;
-                free(comp); free(data);
+                rp_archive_t a;
+                const int built = rp_stored_archive(data, total, bs, checksum, seekable, 1, id, &a);
+                int64_t rc = built ? rpd_check_archive(a.comp, a.size, data, total, dict, D, 7u + (uint32_t)t, 0) : -__LINE__;
+                rp_archive_free(&a); free(data);
                 if (rc < 0) { free(dict); return rc; }
                 sets += rc;
             }

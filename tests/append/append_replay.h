@@ -56,7 +56,38 @@ static uint8_t* rp_area(rp_session_t* s, uint32_t area) {
     return area == ZAP_CARRY ? s->area[s->cur] : area == ZAP_NEXT ? s->area[s->cur ^ 1u] : s->area[2];
 }
 
-/* one piece: src = exactly the piece's p->n bytes (NULL for the plan of `end`) */
+/* The stand-in encoder on job j of a piece, the archive's block k: its input is `len` bytes at `in`, which must be the source's
+ * bytes of block k; block k's bytes go to slot j and its size to sizes[j]. -> 0 (and `bad`) when the input is not block k's. */
+static int rp_encode_job(rp_session_t* s, uint32_t j, uint64_t k, const uint8_t* in, uint32_t len) {
+    if (k >= s->n_blocks || memcmp(in, s->src + k * s->bs, len) != 0) { s->bad = 1; return 0; }
+    memcpy(s->slots + (size_t)j * s->stride, s->blocks + s->blk_at[k], s->blk_size[k] <= s->stride ? s->blk_size[k] : s->stride);
+    s->sizes[j] = s->blk_size[k];
+    return 1;
+}
+/* the back half of a piece of nb > 0 blocks (ap_back): the tiles pass, the advance, scatter and gather */
+static void rp_back(rp_session_t* s, uint32_t nb) {
+    uint64_t sum = 0;
+    uint32_t hash = 0, bad = 0;
+    zap_piece_totals(s->sizes, s->slots, s->stride, nb, s->bs, s->checksum, &sum, &hash, &bad);
+    uint64_t run = s->ctl.off;
+    if (!zap_advance(&s->ctl, nb, sum, hash, bad, s->cap, s->checksum, s->seekable)) return;
+    for (uint32_t b = 0; b < nb; b++) {
+        s->offsets[b] = run;
+        run += s->sizes[b];
+        if (s->seekable) s->seek[s->ctl.first + b] = s->sizes[b];
+        memcpy(s->dst + s->offsets[b], s->slots + (size_t)b * s->stride, s->sizes[b]);
+    }
+}
+/* the cut of ap_pieces: *m = the bytes of the next piece of a call with `left` bytes to go. -> 0 (and `bad`) when the cut breaks a
+ * promise: some bytes, no more than are left or max_piece, and every piece but a call's last ends on a block boundary */
+static int rp_next_piece(rp_session_t* s, uint64_t left, uint64_t* m) {
+    const uint32_t carry = (uint32_t)(s->total % s->bs);
+    *m = zap_piece_len(carry, left, s->max_piece, s->bs);
+    if (*m == 0 || *m > left || *m > s->max_piece || (*m < left && (carry + *m) % s->bs != 0)) { s->bad = 1; return 0; }
+    return 1;
+}
+
+/* one piece, the plain front end: src = exactly the piece's p->n bytes (NULL for the plan of `end`) */
 static void rp_piece(rp_session_t* s, const uint8_t* src, const zap_piece_t* p) {
     for (int c = 0; c < 3; c++) { /* the prep kernel */
         const zap_copy_t cp = p->cp[c];
@@ -74,24 +105,9 @@ static void rp_piece(rp_session_t* s, const uint8_t* src, const zap_piece_t* p) 
         if (js.area != ZAP_SRC) { /* ... and in an area it meets the padding */
             for (uint32_t k = 0; k < ZAP_OVERREAD; k++) if (in[js.len + k] != 0) s->bad = 1;
         }
-        const uint64_t k = first_block + j;
-        if (k >= s->n_blocks || memcmp(in, s->src + k * s->bs, js.len) != 0) { s->bad = 1; continue; }
-        memcpy(s->slots + (size_t)j * s->stride, s->blocks + s->blk_at[k], s->blk_size[k] <= s->stride ? s->blk_size[k] : s->stride);
-        s->sizes[j] = s->blk_size[k];
+        rp_encode_job(s, j, first_block + j, in, js.len);
     }
-    if (!p->nb) return;
-    uint64_t sum = 0;
-    uint32_t hash = 0, bad = 0;
-    zap_piece_totals(s->sizes, s->slots, s->stride, p->nb, s->bs, s->checksum, &sum, &hash, &bad); /* the tiles pass */
-    const uint64_t base = s->ctl.off;
-    if (!zap_advance(&s->ctl, p->nb, sum, hash, bad, s->cap, s->checksum, s->seekable)) return;
-    uint64_t run = base;
-    for (uint32_t b = 0; b < p->nb; b++) { /* scatter and gather */
-        s->offsets[b] = run;
-        run += s->sizes[b];
-        if (s->seekable) s->seek[s->ctl.first + b] = s->sizes[b];
-        memcpy(s->dst + s->offsets[b], s->slots + (size_t)b * s->stride, s->sizes[b]);
-    }
+    if (p->nb) rp_back(s, p->nb);
 }
 
 /* the loop of zxc_mi355x_compress_append_device: the next n bytes of the source */
@@ -99,15 +115,12 @@ static void rp_append(rp_session_t* s, uint64_t n) {
     uint8_t* mine = malloc(n ? n : 1u); /* exactly the append's bytes */
     memcpy(mine, s->src + s->total, n);
     const uint8_t* src = mine;
-    uint64_t left = n;
-    while (left) {
-        const uint32_t carry = (uint32_t)(s->total % s->bs);
-        const uint64_t m = zap_piece_len(carry, left, s->max_piece, s->bs);
-        if (m == 0 || m > left || m > s->max_piece || (m < left && (carry + m) % s->bs != 0)) { s->bad = 1; break; }
+    uint64_t left = n, m;
+    while (left && rp_next_piece(s, left, &m)) {
         uint8_t* piece = malloc(m); /* ... and exactly the piece's */
         memcpy(piece, src, m);
         zap_piece_t p;
-        zap_plan_piece(carry, m, s->bs, &p);
+        zap_plan_piece((uint32_t)(s->total % s->bs), m, s->bs, &p);
         rp_piece(s, piece, &p);
         free(piece);
         s->total += m; /* (rp_piece counted the blocks in front of the piece from the old total) */
@@ -128,7 +141,7 @@ static int64_t rp_end(rp_session_t* s) {
 }
 
 /* A whole session: begin, the appends of lens[0 .. n_lens) (their sum is total), end. dst: cap bytes. */
-static int64_t rp_session(const uint8_t* src, uint64_t total, const uint8_t* blocks, const uint64_t* blk_at, const uint32_t* blk_size,
+static inline int64_t rp_session(const uint8_t* src, uint64_t total, const uint8_t* blocks, const uint64_t* blk_at, const uint32_t* blk_size,
                           uint32_t n_blocks, uint32_t bs, int checksum, int seekable, const uint64_t* lens, uint32_t n_lens,
                           uint64_t max_piece, uint8_t* dst, uint64_t cap) {
     rp_session_t s;
@@ -143,7 +156,7 @@ static int64_t rp_session(const uint8_t* src, uint64_t total, const uint8_t* blo
 }
 
 /* The promises of one plan, for a piece of n > 0 bytes behind `carry`: -> 0, or the number of the promise it breaks. */
-static int rp_plan_check(uint32_t carry, uint64_t n, uint32_t bs) {
+static inline int rp_plan_check(uint32_t carry, uint64_t n, uint32_t bs) {
     zap_piece_t p;
     zap_plan_piece(carry, n, bs, &p);
     if (p.nb != (carry + n) / bs || p.tail != (carry + n) % bs) return 1;
@@ -181,4 +194,47 @@ static int rp_plan_check(uint32_t carry, uint64_t n, uint32_t bs) {
     if (p.nb && !(p.swap && p.cp[2].area == ZAP_NEXT && p.cp[2].at == 0 && p.cp[2].len == p.tail)) return 12;
     return 0;
 }
+/* ---- the archive the stand-in encoder must give: every block a stored block of the source's bytes, with a trailer when checksums
+ * are on, and the container around them (zxc_container.h), built serially */
+typedef struct rp_archive {
+    uint8_t *blocks, *comp; /* the blocks back to back; the finished archive, `size` bytes */
+    uint64_t *blk_at, size; /* where block b starts in `blocks` */
+    uint32_t *blk_size, nb;
+} rp_archive_t;
+/* -> 1 when the archive came out at the size zc_known_size promises */
+static inline int rp_stored_archive(const uint8_t* src, uint64_t total, uint32_t bs, int checksum, int seekable, int has_dict,
+                                    uint32_t dict_id, rp_archive_t* a) {
+    const uint32_t nb = a->nb = (uint32_t)((total + bs - 1) / bs);
+    a->size = zc_known_size(nb, checksum, seekable) + total;
+    a->comp = malloc(a->size);
+    a->blocks = malloc((size_t)nb * (bs + 12u) + 1u);
+    a->blk_at = malloc((nb + 1u) * 8u);
+    a->blk_size = malloc((nb + 1u) * 4u);
+    uint64_t at = 0;
+    uint32_t hash = 0;
+    for (uint32_t b = 0; b < nb; b++) {
+        const uint32_t n = total - (uint64_t)b * bs < bs ? (uint32_t)(total - (uint64_t)b * bs) : bs;
+        a->blk_at[b] = at;
+        zc_st_le(a->blocks + at, zc_blk_hdr(0u, n), 8);
+        memcpy(a->blocks + at + 8, src + (uint64_t)b * bs, n);
+        if (checksum) {
+            const uint32_t t = 0x9E3779B9u * (b + 1u) ^ src[(uint64_t)b * bs];
+            zc_st_le(a->blocks + at + 8 + n, t, 4);
+            hash = zc_hash_fold(hash, t);
+        }
+        a->blk_size[b] = 8u + n + (checksum ? 4u : 0u);
+        at += a->blk_size[b];
+    }
+    zc_put_file_header(a->comp, zc_block_size_lg(bs), checksum, has_dict, dict_id);
+    memcpy(a->comp + ZC_FILE_HDR, a->blocks, at);
+    uint64_t o = ZC_FILE_HDR + at;
+    zc_st_le(a->comp + o, zc_blk_hdr(ZC_BLK_EOF, 0u), 8); o += 8;
+    if (seekable && nb) {
+        zc_st_le(a->comp + o, zc_blk_hdr(ZC_BLK_SEK, nb * 4u), 8); o += 8;
+        for (uint32_t b = 0; b < nb; b++) { zc_st_le(a->comp + o, a->blk_size[b], 4); o += 4; }
+    }
+    zc_put_footer(a->comp + o, total, checksum ? hash : 0u);
+    return o + ZC_FOOTER == a->size;
+}
+static inline void rp_archive_free(rp_archive_t* a) { free(a->comp); free(a->blocks); free(a->blk_at); free(a->blk_size); }
 #endif

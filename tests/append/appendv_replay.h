@@ -22,9 +22,6 @@ typedef struct rpv_stats {
     uint64_t bytes_read;                /* by the stand-in encoder, over-reads included */
 } rpv_stats_t;
 
-/* (what append_replay.h defines and not every includer of this file calls) */
-static inline void rpv_also_uses(void) { (void)rp_session; (void)rp_plan_check; }
-
 static volatile uint8_t rpv_sink;
 /* the encoder may read these bytes: touch every one (a sanitizer sees an over-read) */
 static void rpv_touch(const uint8_t* p, uint64_t n, rpv_stats_t* st) {
@@ -34,7 +31,7 @@ static void rpv_touch(const uint8_t* p, uint64_t n, rpv_stats_t* st) {
     st->bytes_read += n;
 }
 
-/* One chunk behind its plan (ap_piece with a virtual source). status: the table's verdict. */
+/* One chunk behind its plan, the appendv front end (ap_piece with a virtual source). status: the table's verdict. */
 static void rpv_chunk(rp_session_t* s, const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov, int status, const zav_chunk_t* c,
                       uint8_t* images, uint32_t image, rpv_stats_t* st) {
     const zap_piece_t* p = &c->p;
@@ -60,24 +57,9 @@ static void rpv_chunk(rp_session_t* s, const zxc_dev_iov_t* iov, const uint64_t*
             rpv_touch(in, (uint64_t)job.len + ZAP_OVERREAD, st); /* inside one entry, or the sanitizer reports it */
             st->in_place++;
         }
-        const uint64_t k = first_block + j;
-        if (k >= s->n_blocks || memcmp(in, s->src + k * s->bs, job.len) != 0) { s->bad = 1; continue; }
-        memcpy(s->slots + (size_t)j * s->stride, s->blocks + s->blk_at[k], s->blk_size[k] <= s->stride ? s->blk_size[k] : s->stride);
-        s->sizes[j] = s->blk_size[k];
+        rp_encode_job(s, j, first_block + j, in, job.len);
     }
-    if (status < 0) return; /* zxc_appendv_advance_kernel; scatter and gather see the session's error */
-    uint64_t sum = 0;
-    uint32_t hash = 0, bad = 0;
-    zap_piece_totals(s->sizes, s->slots, s->stride, p->nb, s->bs, s->checksum, &sum, &hash, &bad);
-    const uint64_t base = s->ctl.off;
-    if (!zap_advance(&s->ctl, p->nb, sum, hash, bad, s->cap, s->checksum, s->seekable)) return;
-    uint64_t run = base;
-    for (uint32_t b = 0; b < p->nb; b++) {
-        s->offsets[b] = run;
-        run += s->sizes[b];
-        if (s->seekable) s->seek[s->ctl.first + b] = s->sizes[b];
-        memcpy(s->dst + s->offsets[b], s->slots + (size_t)b * s->stride, s->sizes[b]);
-    }
+    if (status >= 0) rp_back(s, p->nb); /* the advance is not run after a table error; scatter and gather see the session's error */
 }
 
 /* zxc_mi355x_compress_appendv_device behind its synchronous checks: the table iov[0 .. n_iov) (host addresses) and the caller's
@@ -94,13 +76,10 @@ static int rpv_appendv_table(rp_session_t* s, const zxc_dev_iov_t* iov, uint32_t
     vctl->status = zav_scan_serial(iov, n_iov, total, starts); /* the three scan kernels */
     vctl->sum = starts[n_iov];
     zav_fold_status(&s->ctl, vctl->status);
-    uint64_t left = total, v = 0;
-    while (left) {
-        const uint32_t carry = (uint32_t)(s->total % s->bs);
-        const uint64_t m = zap_piece_len(carry, left, s->max_piece, s->bs);
-        if (m == 0 || m > left || m > s->max_piece || (m < left && (carry + m) % s->bs != 0)) { s->bad = 1; break; }
+    uint64_t left = total, v = 0, m;
+    while (left && rp_next_piece(s, left, &m)) {
         zav_chunk_t c;
-        zav_plan_chunk(carry, m, s->bs, v, &c);
+        zav_plan_chunk((uint32_t)(s->total % s->bs), m, s->bs, v, &c);
         rpv_chunk(s, iov, starts, n_iov, vctl->status, &c, sb + vsh.o_images, vsh.image, st);
         s->total += m;
         if (c.p.swap) s->cur ^= 1u;

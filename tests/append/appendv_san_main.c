@@ -3,7 +3,7 @@
  * over heap buffers of exactly the sizes a call is promised: every entry of a table is a malloc of exactly its length, so an
  * over-read of one byte behind an entry is a report. The encoder is a stand-in (every block a stored block of the source's bytes,
  * with a trailer when checksums are on) that reads len + 32 bytes of every in-place job and len + 64 of every image; the archive
- * it must give is built serially here with zxc_container.h. Tables: one entry, random entries with empty ones anywhere, runs of
+ * it must give is rp_stored_archive's. Tables: one entry, random entries with empty ones anywhere, runs of
  * 1-7-byte entries that span several blocks, entries that end 31 / 32 / 33 bytes behind a block boundary, calls that alternate
  * with plain appends and leave a carry each, chunk loops with max_piece of one and two blocks; tables that break each rule.
  * Built by tests/test_compress_appendv_device_cpu.py with -fsanitize=address,undefined. Prints "APPENDV OK <sessions>", exits 0. */
@@ -67,41 +67,13 @@ static void calls(int pattern, uint64_t total, uint32_t bs, uint64_t* lens, uint
     *n_lens = nl; *n_calls = nc;
 }
 
-/* one source: its stored blocks, the archive they make, and sessions over the patterns */
+/* one source: its stored blocks and the archive they make (rp_stored_archive), and sessions over the patterns */
 static void run(uint32_t bs, uint64_t total, int checksum, int seekable) {
-    const uint32_t nb = (uint32_t)((total + bs - 1) / bs);
     uint8_t* src = malloc(total ? total : 1);
     for (uint64_t i = 0; i < total; i++) src[i] = (uint8_t)(rnd() >> 5);
-    uint8_t* blocks = malloc((size_t)nb * (bs + 12u) + 1u);
-    uint64_t* blk_at = malloc((nb + 1u) * 8u);
-    uint32_t* blk_size = malloc((nb + 1u) * 4u);
-    uint64_t at = 0;
-    uint32_t hash = 0;
-    for (uint32_t b = 0; b < nb; b++) {
-        const uint32_t n = total - (uint64_t)b * bs < bs ? (uint32_t)(total - (uint64_t)b * bs) : bs;
-        blk_at[b] = at;
-        zc_st_le(blocks + at, zc_blk_hdr(0u, n), 8);
-        memcpy(blocks + at + 8, src + (uint64_t)b * bs, n);
-        if (checksum) {
-            const uint32_t t = 0x9E3779B9u * (b + 1u) ^ src[(uint64_t)b * bs];
-            zc_st_le(blocks + at + 8 + n, t, 4);
-            hash = zc_hash_fold(hash, t);
-        }
-        blk_size[b] = 8u + n + (checksum ? 4u : 0u);
-        at += blk_size[b];
-    }
-    const uint64_t size = zc_known_size(nb, checksum, seekable) + total;
-    uint8_t* want = malloc(size);
-    zc_put_file_header(want, zc_block_size_lg(bs), checksum, 0, 0u);
-    memcpy(want + ZC_FILE_HDR, blocks, at);
-    uint64_t o = ZC_FILE_HDR + at;
-    zc_st_le(want + o, zc_blk_hdr(ZC_BLK_EOF, 0u), 8); o += 8;
-    if (seekable && nb) {
-        zc_st_le(want + o, zc_blk_hdr(ZC_BLK_SEK, nb * 4u), 8); o += 8;
-        for (uint32_t b = 0; b < nb; b++) { zc_st_le(want + o, blk_size[b], 4); o += 4; }
-    }
-    zc_put_footer(want + o, total, checksum ? hash : 0u);
-    CHECK(o + ZC_FOOTER == size);
+    rp_archive_t a;
+    CHECK(rp_stored_archive(src, total, bs, checksum, seekable, 0, 0u, &a));
+    const uint64_t size = a.size;
 
     uint64_t* lens = malloc((total + 4096u) * 8u);
     uint32_t* counts = malloc((total + 4096u) * 4u);
@@ -114,16 +86,16 @@ static void run(uint32_t bs, uint64_t total, int checksum, int seekable) {
             uint8_t* dst = malloc(cap); /* exactly the capacity */
             memset(dst, CANARY, cap);
             rpv_stats_t st;
-            const int64_t rc = rpv_session(src, total, blocks, blk_at, blk_size, nb, bs, checksum, seekable, lens, counts, n_calls, max_piece, dst,
+            const int64_t rc = rpv_session(src, total, a.blocks, a.blk_at, a.blk_size, a.nb, bs, checksum, seekable, lens, counts, n_calls, max_piece, dst,
                                            cap, &st);
-            if (short_by == 0) CHECK(rc == (int64_t)size && memcmp(dst, want, size) == 0);
+            if (short_by == 0) CHECK(rc == (int64_t)size && memcmp(dst, a.comp, size) == 0);
             else CHECK(rc == ZXC_ERROR_DST_TOO_SMALL);
             in_place += st.in_place; images += st.images;
             free(dst);
             sessions++;
         }
     }
-    free(counts); free(lens); free(want); free(blk_size); free(blk_at); free(blocks); free(src);
+    free(counts); free(lens); rp_archive_free(&a); free(src);
 }
 
 /* tables that break a rule: the verdict, its precedence, the sticky status, and that nothing is read, encoded or written */

@@ -248,6 +248,39 @@ def test_table_errors_become_the_sessions_status_and_stay(gpu, case):
         assert rc == ERR[want], (case, before, rc)
 
 
+def test_a_table_error_behind_a_chunked_appendv_keeps_what_was_gathered(gpu):
+    """max_piece of two blocks: an appendv of 3 blocks + 5 bytes in tiny entries succeeds over two chunks, each through the advance;
+    the table of the next appendv sums one byte short of its promise, and the advance of its chunk must leave the state alone. `end`
+    reports the table's error, the three blocks gathered so far are the one-shot archive's and nothing lies behind them; a fresh
+    session on the same work area and scratch gives the one-shot archive."""
+    n, more = 3 * BS + 5, 2 * BS
+    rng = np.random.default_rng(23)
+    tiny = [int(x) for x in rng.integers(1, 8, n)]
+    tiny = tiny[: int(np.searchsorted(np.cumsum(tiny), n))]
+    tiny.append(n - sum(tiny))
+    data = A._payload(n + more, 22)
+    cap = A._bound(gpu, n + more)
+    want_rc, want = A._baseline(gpu, data[:n], cap, 3, BS, 1, 1)
+    assert want_rc > 0
+    s = VSession(gpu, cap, n + more, 2 * BS, 3, BS, 1, 1)
+    sc = s.appendv(_cut(data[:n], tiny))
+    s.appendv(_cut(data[n: n + more - 1], [BS, 7, BS - 8]), total=more, scratch=sc)
+    s.end()
+    rc, _ = s.result()
+    assert rc == ERR["SRC_TOO_SMALL"], rc
+    dst, whole = s.dst.cpu().numpy(), A._pattern(cap + A.CANARY)
+    sizes = np.frombuffer(want[-12 - 4 * 4: -12], dtype="<u4")  # the seek table of the one-shot archive: four blocks
+    end = 16 + int(sizes[:3].sum())
+    assert bytes(dst[16: end]) == want[16: end], "the blocks gathered before the error"
+    assert (dst[:16] == whole[:16]).all() and (dst[end:] == whole[end:]).all(), "bytes outside the gathered blocks changed"
+    s2 = VSession(gpu, cap, n + more, 2 * BS, 3, BS, 1, 1)
+    s2.s = gpu.compress_begin_device(s2.dst.data_ptr(), cap, n + more, 2 * BS, s.work.data_ptr() + 1, s.work.numel() - 1, 3, BS, 1, 1,
+                                     s2.stream.cuda_stream)  # ... on the first session's work area (its own goes unused)
+    s2.appendv(_cut(data[:n], tiny), scratch=sc)
+    s2.end()
+    assert s2.result() == (want_rc, want)
+
+
 def test_refusals_leave_the_session_usable(gpu):
     import torch
     n = 3 * BS + 10

@@ -41,7 +41,8 @@ def timed(fn, runs, warmup, stream):
         b.record(stream)
         b.synchronize()
         ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms)
+    ms.sort()
+    return statistics.median(ms), ms[0], ms[round(0.1 * (len(ms) - 1))], ms[round(0.9 * (len(ms) - 1))]
 
 
 def main():
@@ -82,7 +83,7 @@ def main():
                                                    stream.cuda_stream)
             assert rc == 0, rc
 
-        enc_ms, enc_min = timed(encode, a.runs, a.warmup, stream)
+        enc_ms, enc_min, _, _ = timed(encode, a.runs, a.warmup, stream)
         del slots, sizes
         ws = zxc_amd.compress_device_work_size(n, a.level, bs, seekable, checksum)
         cap = int(L.zxc_compress_bound(n))
@@ -94,14 +95,15 @@ def main():
             zxc_amd.compress_device(src.data_ptr(), n, dst.data_ptr(), cap, work.data_ptr(), ws, res.data_ptr(), a.level, bs,
                                     seekable, checksum, stream.cuda_stream)
 
-        cd_ms, cd_min = timed(whole, a.runs, a.warmup, stream)
+        cd_ms, cd_min, cd_p10, cd_p90 = timed(whole, a.runs, a.warmup, stream)
         size = int(res.item())
         assert size > 0, size
         line = {"block_size": bs, "level": a.level, "src_bytes": n, "archive_bytes": size, "ratio": round(n / size, 3),
                 "runs": a.runs, "encode_ms": round(enc_ms, 3), "encode_gbps": round(n / enc_ms / 1e6, 2),
                 "compress_device_ms": round(cd_ms, 3), "compress_device_gbps": round(n / cd_ms / 1e6, 2),
                 "after_encode_share": round((cd_ms - enc_ms) / enc_ms, 4), "encode_min_ms": round(enc_min, 3),
-                "compress_device_min_ms": round(cd_min, 3)}
+                "compress_device_min_ms": round(cd_min, 3), "compress_device_ms_p10": round(cd_p10, 3),
+                "compress_device_ms_p90": round(cd_p90, 3)}
         if a.check:
             want = zxc_amd.compress(data, a.level, bs, seekable, checksum)
             line["matches_zxc_compress"] = bytes(dst[:size].cpu().numpy()) == want

@@ -1,49 +1,50 @@
-// zxc_append_device.hip — zxc_mi355x_compress_begin_device / _append_device / _end_device: one v8 archive in device memory from a
-// source that arrives in pieces, each in device memory. The device counterpart of zxc_cstream_* (zxc_stream_host.c).
+// zxc_append_device.hip — zxc_mi355x_compress_begin_device / _begin_dict_device / _append_device / _appendv_device / _end_device:
+// one v8 archive in device memory from a source that arrives in pieces, each in device memory. The device counterpart of
+// zxc_cstream_* (zxc_stream_host.c).
 //
 // zxc_mi355x_compress_device (zxc_frame_device.hip) wants the whole source in one buffer and a slot per block of it. Here a session
 // keeps the archive's running state (offset, blocks, global hash, status) in its work area between calls, and a set of J slots
 // that every piece reuses in stream order, so the work area does not grow with the source. The host knows every n, so it knows the
-// carry and each piece's exact grid: the plan of a piece, its advance and the finish are the inline C of zxc_append.h, which the
-// CPU tests run as well. The stream order of one piece (an append of at most max_piece bytes; a longer one is a loop of these):
+// carry and each piece's exact grid: the plan of a piece, its advance and the finish are the inline C of zxc_append.h and
+// zxc_appendv.h, which the CPU tests run as well.
 //
-//   prep     head of the source -> carry area (completes the waiting block), last whole block -> stage area when its over-read
-//            would leave the source, tail -> the other carry area; zero padding behind each; the job table
-//   encode   the job-table entry of the level over the piece's blocks, in archive order (a piece that completes no block ends at prep)
+// One pipeline. A piece is at most max_piece bytes of one call; a longer call is a loop of pieces (ap_pieces). A piece is a front
+// end, which fills the job table and launches the encoder over it, and one back half (ap_back); a piece that completes no block
+// ends behind its prep. The three front ends:
+//
+//   plain    (append; any session's piece that completes no block)
+//            prep     zxc_append_prep_kernel: head of the source -> carry area (completes the waiting block), last whole block ->
+//                     stage area when its over-read would leave the source, tail -> the other carry area; zero padding behind
+//                     each; the job table
+//            encode   the job-table entry of the level over the piece's blocks, in archive order
+//   images   (append and `end` in a session with a dictionary, zxc_mi355x_compress_begin_dict_device) a loop over chunks of at
+//            most C = zc_image_chunk(block_size, dict_size) jobs, which reuse one image area in stream order:
+//            images   zxc_append_images_kernel, one workgroup per job of the chunk: [dict | the job's bytes] into the image area
+//                     and the job-table entry that points at it; the carried block's bytes come from the carry area and then from
+//                     the head of the source, which is not copied anywhere else; in the first chunk one more workgroup copies the
+//                     tail into the other carry area. Nothing is staged: an image is a copy with the next image, or ZC_IMAGE_PAD,
+//                     behind it
+//            encode   the job-table entry of the level over the chunk's images, into the chunk's slots and sizes
+//   appendv  (a chunk of zxc_mi355x_compress_appendv_device: the source is the concatenation of a table of (base, len) entries in
+//            device memory, zxc_appendv.h) once per call, in front of its chunks,
+//            scan     three tile passes over the table: start offsets of the entries into the call's scratch, the table check and
+//                     its verdict, which becomes the session's status unless that holds an error; then per chunk
+//            prep     zxc_appendv_prep_kernel, one workgroup per job and one for the tail: head and tail gathered into the carry
+//                     areas, a whole block left in place (inside one entry, over-read included) or gathered into its image in the
+//                     scratch; nothing is read after a table error
+//            encode   as plain's (the two share the launch, ap_encode)
+//
+// and the back half, once over the whole piece:
 //   tiles    zxc_frame_tiles_kernel: per tile the sum of the sizes, the size check, the piece's part of the global hash
-//   advance  one workgroup: tile offsets from the running offset; status, offset, block count and hash move on (zap_advance)
+//   advance  one workgroup: tile offsets from the running offset; status, offset, block count and hash move on (zap_advance); not
+//            run for a chunk of an appendv whose table is in error
 //   scatter  per tile: block offsets, seek-table entries into the array in the work area  (only while the status is no error)
 //   gather   one wave per block: slot -> archive                                           (idem)
 //
-// and of `end`: the piece above for what waits in the carry area, as the short last block; then
-//
-//   finish   file header, EOF block, SEK header, footer (zap_finish)
+// `end` is the piece above for what waits in the carry area, as the short last block (plain's or images' front end, no source); then
+//   finish   file header (with a dictionary: its flag and *d_id), EOF block, SEK header, footer (zap_finish_dict)
 //   seek     the entries from the work area to their unaligned place, 4 byte stores each
 //   result   *d_result = archive size or the error, written once, after everything above
-//
-// A session with a dictionary in device memory (zxc_mi355x_compress_begin_dict_device) replaces "prep, encode" by a loop over
-// chunks of at most C = zc_image_chunk(block_size, dict_size) jobs, which reuse one image area in stream order:
-//
-//   images   zxc_append_images_kernel, one workgroup per job of the chunk: [dict | the job's bytes] into the image area and the
-//            job-table entry that points at it; the carried block's bytes come from the carry area and then from the head of the
-//            source, which is not copied anywhere else; in the first chunk one more workgroup copies the tail into the other carry
-//            area. Nothing is staged: an image is a copy with the next image, or ZC_IMAGE_PAD, behind it
-//   encode   the job-table entry of the level over the chunk's images, into the chunk's slots and sizes
-//
-// with tiles, advance, scatter and gather once over the whole piece as above, and the dictionary flag and *d_id in the file header
-// that finish writes. A piece that completes no block is prep's, as it is.
-//
-// zxc_mi355x_compress_appendv_device appends a table of (base, len) entries in device memory, the concatenation of which is the
-// source (zxc_appendv.h): once per call
-//
-//   scan     three tile passes over the table: start offsets of the entries into the call's scratch, the table check and its
-//            verdict, which becomes the session's status unless that holds an error
-//
-// then per chunk of at most max_piece bytes of the concatenation the piece above, with
-//
-//   prep     zxc_appendv_prep_kernel, one workgroup per job and one for the tail: head and tail gathered into the carry areas, a
-//            whole block left in place (inside one entry, over-read included) or gathered into its image in the scratch
-//   advance  zxc_appendv_advance_kernel: the advance above, not run after a table error
 //
 // No workgroup waits for another: every dependency is the stream order between launches.
 #include <string.h>
@@ -133,11 +134,14 @@ zxc_append_images_kernel(const uint8_t* __restrict__ src, zap_piece_t p, uint32_
 
 // One workgroup. tile_sum[t] becomes the archive offset of tile t's first block (exclusive prefix + the running offset, in place);
 // then the session's state moves on. Every thread reads the running offset in front of the barrier of zd_scan_tiles, thread 0
-// writes the state behind it.
+// writes the state behind it. vctl != NULL: the piece is a chunk of an appendv. After a table error its blocks were never encoded,
+// their sizes are whatever the slots' last user left, and the session's state stays as the scan left it: the whole workgroup
+// returns in front of the barrier.
 extern "C" __global__ void __launch_bounds__(256)
 zxc_append_advance_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
                           uint32_t n_tiles, uint32_t nb_piece, uint64_t dst_capacity, uint32_t checksum, uint32_t seekable,
-                          zap_ctl_t* __restrict__ ctl) {
+                          zap_ctl_t* __restrict__ ctl, const zav_ctl_t* __restrict__ vctl) {
+    if (vctl && vctl->status < 0) return;
     const uint64_t base = ctl->off;
     const zd_totals all = zd_scan_tiles(
         n_tiles, base,
@@ -177,10 +181,7 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_append_gather_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride, const uint32_t* __restrict__ sizes,
                          const uint64_t* __restrict__ offsets, uint8_t* __restrict__ dst, uint32_t nb_piece, const zap_ctl_t* __restrict__ ctl) {
     if (ctl->status < 0) return;
-    const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
-    for (uint64_t b = (uint64_t)blockIdx.x * waves + (threadIdx.x >> 6); b < nb_piece; b += (uint64_t)gridDim.x * waves) {
-        copy_bytes(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
-    }
+    zd_gather_blocks(slots, slot_stride, sizes, offsets, dst, nb_piece);
 }
 
 // dict_id != NULL (the dictionary session): the file header carries the flag and *dict_id, a word in device memory read here.
@@ -312,21 +313,6 @@ zxc_appendv_prep_kernel(const zxc_dev_iov_t* __restrict__ iov, const uint64_t* _
     zav_prep(iov, starts, n_iov, vctl->status, &c, blockIdx.x, threadIdx.x, blockDim.x, carry, next, images, image, jobs);
 }
 
-// zxc_append_advance_kernel for a chunk of an appendv: after a table error the chunk's blocks were never encoded, their sizes are
-// whatever the slots' last user left, and the session's state stays as the scan left it.
-extern "C" __global__ void __launch_bounds__(256)
-zxc_appendv_advance_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restrict__ tile_hash, const uint32_t* __restrict__ tile_bad,
-                           uint32_t n_tiles, uint32_t nb_piece, uint64_t dst_capacity, uint32_t checksum, uint32_t seekable,
-                           zap_ctl_t* __restrict__ ctl, const zav_ctl_t* __restrict__ vctl) {
-    if (vctl->status < 0) return;
-    const uint64_t base = ctl->off;
-    const zd_totals all = zd_scan_tiles(
-        n_tiles, base,
-        [=](uint32_t i, uint32_t& hash, uint32_t& bad) { const uint64_t s = tile_sum[i]; hash ^= tile_hash[i]; bad |= tile_bad[i]; return s; },
-        [=](uint32_t i, uint64_t off) { tile_sum[i] = off; });
-    if (threadIdx.x == 0) zap_advance(ctl, nb_piece, all.sum, all.hash, all.bad, dst_capacity, (int)checksum, (int)seekable);
-}
-
 // ---------------------------------------------------------------- host side
 namespace {
 
@@ -347,22 +333,41 @@ struct Sess {
 };
 static_assert(sizeof(Sess) <= sizeof(zxc_dev_cappend_t), "the session fits the caller's struct");
 
-// Options as zxc_mi355x_compress_device reads them (frame_plan of zxc_frame_device.hip), in its order.
+// The options of a session (zd_compress_opts), refused in the order of zxc_mi355x_compress_device.
 int ap_opts(const zxc_compress_opts_t* opts, Sess* s) {
     if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
-    int level = (opts && opts->level > 0) ? opts->level : 3;
-    if (level > 7) level = 7;
-    const uint64_t bs = (opts && opts->block_size > 0) ? (uint64_t)opts->block_size : 512u * 1024u;
-    if (!zc_block_size_ok(bs)) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    s->block_size = (uint32_t)bs;
-    s->level = (uint32_t)level;
-    s->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
-    s->seekable = (opts && opts->seekable) ? 1u : 0u;
+    zd_copts_t o;
+    const int rc = zd_compress_opts(opts, &o);
+    if (rc != ZXC_OK) return rc;
+    s->block_size = o.block_size; s->level = o.level; s->checksum = o.checksum; s->seekable = o.seekable;
     return ZXC_OK;
 }
 int ap_shape(const Sess& s, zap_shape_images_t* sh) {
     return zap_shape_images(s.max_total, s.max_piece, s.block_size, zxc_mi355x_encode_slot_stride(s.block_size), (int)s.seekable,
                             s.dict_size, sh);
+}
+
+// The parts of a session's work area. The carry area that holds the waiting bytes is carry[s.cur].
+struct Work {
+    zap_ctl_t* ctl;
+    uint64_t *tile_sum, *offsets;
+    uint32_t *tile_hash, *tile_bad, *sizes, *seek;
+    zxc_enc_job_t* jobs;
+    uint8_t *slots, *stage, *images, *carry[2];
+    uint32_t slot_stride, chunk_jobs;
+};
+Work ap_work(const Sess& s, const zap_shape_images_t& shi) {
+    const zap_shape_t& sh = shi.s;
+    uint8_t* base = s.base;
+    Work w;
+    w.ctl = (zap_ctl_t*)base; w.jobs = (zxc_enc_job_t*)(base + sh.o_jobs);
+    w.tile_sum = (uint64_t*)(base + sh.o_tile_sum); w.offsets = (uint64_t*)(base + sh.o_offsets);
+    w.tile_hash = (uint32_t*)(base + sh.o_tile_hash); w.tile_bad = (uint32_t*)(base + sh.o_tile_bad);
+    w.sizes = (uint32_t*)(base + sh.o_sizes); w.seek = (uint32_t*)(base + sh.o_seek);
+    w.slots = base + sh.o_slots; w.stage = base + sh.o_stage; w.images = base + shi.o_images;
+    w.carry[0] = base + sh.o_carry[0]; w.carry[1] = base + sh.o_carry[1];
+    w.slot_stride = sh.slot_stride; w.chunk_jobs = shi.chunk_jobs;
+    return w;
 }
 
 // The virtual source of an appendv (zxc_appendv.h): the table, what the call's scan left in its scratch, and the offset in the
@@ -376,73 +381,92 @@ struct Vsrc {
     uint64_t v;
 };
 
-// One piece behind its plan: src is the piece's first byte (not read when the plan has no copy and no direct job). With vs (a
-// session without a dictionary) the piece is a chunk of an appendv: src is not looked at, prep is zxc_appendv_prep_kernel and the
-// advance is predicated on the table's verdict.
-int ap_piece(const Sess& s, const zap_shape_images_t& shi, const uint8_t* src, const zap_piece_t& p, hipStream_t st, const Vsrc* vs = NULL) {
-    const zap_shape_t& sh = shi.s;
-    uint8_t* base = s.base;
-    zap_ctl_t* ctl = (zap_ctl_t*)base;
-    uint64_t* tile_sum = (uint64_t*)(base + sh.o_tile_sum);
-    uint32_t* tile_hash = (uint32_t*)(base + sh.o_tile_hash);
-    uint32_t* tile_bad = (uint32_t*)(base + sh.o_tile_bad);
-    zxc_enc_job_t* jobs = (zxc_enc_job_t*)(base + sh.o_jobs);
-    uint32_t* sizes = (uint32_t*)(base + sh.o_sizes);
-    uint64_t* offsets = (uint64_t*)(base + sh.o_offsets);
-    uint32_t* seek = (uint32_t*)(base + sh.o_seek);
-    uint8_t* slots = base + sh.o_slots;
-    uint8_t* carry = base + sh.o_carry[s.cur];
-    uint8_t* next = base + sh.o_carry[s.cur ^ 1u];
-
-    if (s.dict_size && p.nb) {
-        // Blocks are independent, so chunk by chunk gives the bytes of one launch over all of them. A chunk's images are built and
-        // consumed in stream order before the next chunk overwrites them (frame_enqueue of zxc_frame_device.hip).
-        uint8_t* images = base + shi.o_images;
-        for (uint32_t j0 = 0; j0 < p.nb; j0 += shi.chunk_jobs) {
-            const uint32_t n = p.nb - j0 < shi.chunk_jobs ? p.nb - j0 : shi.chunk_jobs;
-            hipLaunchKernelGGL(zxc_append_images_kernel, dim3(n + (j0 == 0 ? 1u : 0u)), dim3(ZAP_IMAGE_THREADS), 0, st, src, p, j0, n, s.dict,
-                               s.dict_size, (const uint8_t*)carry, next, images, jobs);
-            if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-            const int rc = zxc_hip_encode_job_images(images, jobs + j0, n, s.block_size, (int)s.level, (int)s.checksum, s.dict_size,
-                                                     slots + (uint64_t)j0 * sh.slot_stride, sizes + j0, (void*)st);
-            if (rc != ZXC_OK) return rc;
-        }
-    } else if (vs) {
-        zav_chunk_t c;
-        c.p = p; c.v = vs->v;
-        hipLaunchKernelGGL(zxc_appendv_prep_kernel, dim3(zav_groups(&c)), dim3(256), 0, st, vs->iov, vs->starts, vs->n_iov, vs->vctl, c, carry, next,
-                           vs->images, vs->image, jobs);
+// ---- the front ends of a piece: the job table and the encode launch over it
+// the encode launch of the two front ends without a dictionary: job j's src_off is an address
+int ap_encode(const Sess& s, const Work& w, uint32_t nb, hipStream_t st) {
+    return zxc_hip_encode_jobs(NULL, w.jobs, nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, w.slots, w.sizes, (void*)st);
+}
+// src is the piece's first byte (not read when the plan has no copy and no direct job)
+int ap_front_plain(const Sess& s, const Work& w, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+    const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
+    const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
+    hipLaunchKernelGGL(zxc_append_prep_kernel, dim3(groups), dim3(256), 0, st, src, p, w.carry[s.cur], w.carry[s.cur ^ 1u], w.stage, w.jobs);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    return p.nb ? ap_encode(s, w, p.nb, st) : ZXC_OK;
+}
+// Blocks are independent, so chunk by chunk gives the bytes of one launch over all of them. A chunk's images are built and
+// consumed in stream order before the next chunk overwrites them (frame_enqueue of zxc_frame_device.hip). p.nb > 0.
+int ap_front_images(const Sess& s, const Work& w, const uint8_t* src, const zap_piece_t& p, hipStream_t st) {
+    for (uint32_t j0 = 0; j0 < p.nb; j0 += w.chunk_jobs) {
+        const uint32_t n = p.nb - j0 < w.chunk_jobs ? p.nb - j0 : w.chunk_jobs;
+        hipLaunchKernelGGL(zxc_append_images_kernel, dim3(n + (j0 == 0 ? 1u : 0u)), dim3(ZAP_IMAGE_THREADS), 0, st, src, p, j0, n, s.dict,
+                           s.dict_size, (const uint8_t*)w.carry[s.cur], w.carry[s.cur ^ 1u], w.images, w.jobs);
         if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-        if (!p.nb) return ZXC_OK;
-        const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
-        if (rc != ZXC_OK) return rc;
-    } else {
-        const uint64_t units = ((uint64_t)p.cp[0].len + p.cp[1].len + p.cp[2].len) / 16u + p.nb;  // a thread moves 16 bytes or writes a job
-        const uint32_t groups = units < 256u ? 1u : units / 256u < 1024u ? (uint32_t)(units / 256u) : 1024u;
-        hipLaunchKernelGGL(zxc_append_prep_kernel, dim3(groups), dim3(256), 0, st, src, p, carry, next, base + sh.o_stage, jobs);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-        if (!p.nb) return ZXC_OK;
-        const int rc = zxc_hip_encode_jobs(NULL, jobs, p.nb, s.block_size, (int)s.level, (int)s.checksum, NULL, 0u, NULL, slots, sizes, (void*)st);
+        const int rc = zxc_hip_encode_job_images(w.images, w.jobs + j0, n, s.block_size, (int)s.level, (int)s.checksum, s.dict_size,
+                                                 w.slots + (uint64_t)j0 * w.slot_stride, w.sizes + j0, (void*)st);
         if (rc != ZXC_OK) return rc;
     }
-    const uint32_t n_tiles = (p.nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS;
-    hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint8_t*)slots, sh.slot_stride,
-                       (const uint32_t*)sizes, p.nb, s.block_size, s.checksum, tile_sum, tile_hash, tile_bad);
+    return ZXC_OK;
+}
+int ap_front_v(const Sess& s, const Work& w, const Vsrc& vs, const zap_piece_t& p, hipStream_t st) {
+    zav_chunk_t c;
+    c.p = p; c.v = vs.v;
+    hipLaunchKernelGGL(zxc_appendv_prep_kernel, dim3(zav_groups(&c)), dim3(256), 0, st, vs.iov, vs.starts, vs.n_iov, vs.vctl, c, w.carry[s.cur],
+                       w.carry[s.cur ^ 1u], vs.images, vs.image, w.jobs);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    if (vs)
-        hipLaunchKernelGGL(zxc_appendv_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
-                           n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl, vs->vctl);
-    else
-        hipLaunchKernelGGL(zxc_append_advance_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
-                           n_tiles, p.nb, s.dst_capacity, s.checksum, s.seekable, ctl);
+    return p.nb ? ap_encode(s, w, p.nb, st) : ZXC_OK;
+}
+
+// The back half of a piece that completes nb > 0 blocks: tiles, advance, scatter, gather. vctl: the verdict of the appendv whose
+// chunk the piece is, or NULL.
+int ap_back(const Sess& s, const Work& w, uint32_t nb, const zav_ctl_t* vctl, hipStream_t st) {
+    const uint32_t n_tiles = (nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS;
+    hipLaunchKernelGGL(zxc_frame_tiles_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint8_t*)w.slots, w.slot_stride,
+                       (const uint32_t*)w.sizes, nb, s.block_size, s.checksum, w.tile_sum, w.tile_hash, w.tile_bad);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    hipLaunchKernelGGL(zxc_append_scatter_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,
-                       (const uint64_t*)tile_sum, offsets, seek, s.seekable, (const zap_ctl_t*)ctl);
+    hipLaunchKernelGGL(zxc_append_advance_kernel, dim3(1), dim3(256), 0, st, w.tile_sum, (const uint32_t*)w.tile_hash, (const uint32_t*)w.tile_bad,
+                       n_tiles, nb, s.dst_capacity, s.checksum, s.seekable, w.ctl, vctl);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const uint32_t waves = (p.nb + 3u) / 4u < 65536u ? (p.nb + 3u) / 4u : 65536u;
-    hipLaunchKernelGGL(zxc_append_gather_kernel, dim3(waves), dim3(256), 0, st, (const uint8_t*)slots, sh.slot_stride, (const uint32_t*)sizes,
-                       (const uint64_t*)offsets, s.dst, p.nb, (const zap_ctl_t*)ctl);
+    hipLaunchKernelGGL(zxc_append_scatter_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)w.sizes, nb,
+                       (const uint64_t*)w.tile_sum, w.offsets, w.seek, s.seekable, (const zap_ctl_t*)w.ctl);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const uint32_t waves = (nb + 3u) / 4u < 65536u ? (nb + 3u) / 4u : 65536u;
+    hipLaunchKernelGGL(zxc_append_gather_kernel, dim3(waves), dim3(256), 0, st, (const uint8_t*)w.slots, w.slot_stride, (const uint32_t*)w.sizes,
+                       (const uint64_t*)w.offsets, s.dst, nb, (const zap_ctl_t*)w.ctl);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+// One piece behind its plan. vs != NULL (a session without a dictionary): a chunk of an appendv, src is not looked at. Else src is
+// the piece's first byte, NULL for the plan of `end`. A piece that completes no block ends behind the plain prep or appendv's.
+int ap_piece(const Sess& s, const Work& w, const uint8_t* src, const Vsrc* vs, const zap_piece_t& p, hipStream_t st) {
+    const int rc = vs ? ap_front_v(s, w, *vs, p, st) : s.dict_size && p.nb ? ap_front_images(s, w, src, p, st) : ap_front_plain(s, w, src, p, st);
+    if (rc != ZXC_OK || !p.nb) return rc;
+    return ap_back(s, w, p.nb, vs ? vs->vctl : NULL, st);
+}
+
+// The next n bytes of the source, at src or (vs != NULL) from vs->v of an appendv's table, and the session back into *cs. rc:
+// what the launches in front of the pieces gave; nothing more is enqueued behind an error.
+// Pieces are independent but for the state, so piece by piece gives the archive of one piece over all the bytes. A piece's areas,
+// jobs and slots are written and consumed in stream order before the next piece overwrites them. Every piece but the last ends on
+// a block boundary of the archive.
+int ap_pieces(zxc_dev_cappend_t* cs, Sess& s, const zap_shape_images_t& sh, const uint8_t* src, Vsrc* vs, uint64_t n, int rc, hipStream_t st) {
+    const Work w = ap_work(s, sh);
+    uint64_t left = n;
+    while (left && rc == ZXC_OK) {
+        const uint32_t carry = (uint32_t)(s.total % s.block_size);
+        const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
+        zap_piece_t p;
+        if (s.dict_size) zap_plan_piece_images(carry, m, s.block_size, &p);
+        else zap_plan_piece(carry, m, s.block_size, &p);
+        rc = ap_piece(s, w, src, vs, p, st);
+        if (p.swap) s.cur ^= 1u;
+        s.total += m; left -= m;
+        if (vs) vs->v += m;
+        else src += m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;  // part of the call may be enqueued: the session cannot go on
+    memcpy(cs, &s, sizeof s);
+    return rc;
 }
 
 // Both kinds of begin behind their names. dict == NULL: the session without a dictionary.
@@ -509,25 +533,7 @@ int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, 
     if (n == 0) return ZXC_OK;
     zap_shape_images_t sh;
     if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
-    // Pieces are independent but for the state, so piece by piece gives the archive of one piece over all the bytes. A piece's
-    // areas, jobs and slots are written and consumed in stream order before the next piece overwrites them. Every piece but the
-    // last ends on a block boundary of the archive.
-    const uint8_t* src = (const uint8_t*)d_src;
-    uint64_t left = n;
-    int rc = ZXC_OK;
-    while (left && rc == ZXC_OK) {
-        const uint32_t carry = (uint32_t)(s.total % s.block_size);
-        const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
-        zap_piece_t p;
-        if (s.dict_size) zap_plan_piece_images(carry, m, s.block_size, &p);
-        else zap_plan_piece(carry, m, s.block_size, &p);
-        rc = ap_piece(s, sh, src, p, (hipStream_t)stream);
-        if (p.swap) s.cur ^= 1u;
-        s.total += m; src += m; left -= m;
-    }
-    if (rc != ZXC_OK) s.magic = 0;  // part of the append may be enqueued: the session cannot go on
-    memcpy(cs, &s, sizeof s);
-    return rc;
+    return ap_pieces(cs, s, sh, (const uint8_t*)d_src, NULL, n, ZXC_OK, (hipStream_t)stream);
 }
 
 uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_iov, uint64_t max_piece, const zxc_compress_opts_t* opts) {
@@ -557,7 +563,7 @@ int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_
     uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
     uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
     uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
-    // The scan, once per call: the chunks below read starts and the verdict in stream order.
+    // The scan, once per call: the chunks read starts and the verdict in stream order.
     int rc = ZXC_OK;
     hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
     if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
@@ -570,21 +576,9 @@ int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_
         hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
         if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
     }
-    // The chunks, cut like the pieces of an append of `total` bytes: every chunk but the last ends on a block boundary of the archive.
+    // The chunks, cut like the pieces of an append of `total` bytes.
     Vsrc vs = {d_iov, n_iov, vsh.image, starts, vctl, sb + vsh.o_images, 0u};
-    uint64_t left = total;
-    while (left && rc == ZXC_OK) {
-        const uint32_t carry = (uint32_t)(s.total % s.block_size);
-        const uint64_t m = zap_piece_len(carry, left, s.max_piece, s.block_size);
-        zap_piece_t p;
-        zap_plan_piece(carry, m, s.block_size, &p);
-        rc = ap_piece(s, sh, NULL, p, st, &vs);
-        if (p.swap) s.cur ^= 1u;
-        s.total += m; vs.v += m; left -= m;
-    }
-    if (rc != ZXC_OK) s.magic = 0;  // part of the call may be enqueued: the session cannot go on
-    memcpy(cs, &s, sizeof s);
-    return rc;
+    return ap_pieces(cs, s, sh, NULL, &vs, total, rc, st);
 }
 
 int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream) {
@@ -596,24 +590,23 @@ int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, voi
     zap_shape_images_t sh;
     if (ap_shape(s, &sh) != 0) return ZXC_ERROR_NULL_INPUT;
     const hipStream_t st = (hipStream_t)stream;
-    zap_ctl_t* ctl = (zap_ctl_t*)s.base;
+    const Work w = ap_work(s, sh);
     zap_piece_t p;
     zap_plan_end((uint32_t)(s.total % s.block_size), s.block_size, &p);
     if (p.nb) {
-        const int rc = ap_piece(s, sh, NULL, p, st);
+        const int rc = ap_piece(s, w, NULL, NULL, p, st);
         if (rc != ZXC_OK) return rc;
     }
-    hipLaunchKernelGGL(zxc_append_finish_kernel, dim3(1), dim3(64), 0, st, ctl, s.dst, s.dst_capacity, s.total, s.block_size, s.checksum, s.seekable,
+    hipLaunchKernelGGL(zxc_append_finish_kernel, dim3(1), dim3(64), 0, st, w.ctl, s.dst, s.dst_capacity, s.total, s.block_size, s.checksum, s.seekable,
                        s.dict_size ? s.dict_id : (const uint32_t*)NULL);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     const uint64_t nb = s.total / s.block_size + (s.total % s.block_size != 0);  // <= 2^31 - 1 (begin)
     if (s.seekable && nb) {
         const uint32_t groups = (nb + 255u) / 256u < 4096u ? (uint32_t)((nb + 255u) / 256u) : 4096u;
-        hipLaunchKernelGGL(zxc_append_seek_kernel, dim3(groups), dim3(256), 0, st, (const zap_ctl_t*)ctl, s.dst,
-                           (const uint32_t*)(s.base + sh.s.o_seek), (uint32_t)nb);
+        hipLaunchKernelGGL(zxc_append_seek_kernel, dim3(groups), dim3(256), 0, st, (const zap_ctl_t*)w.ctl, s.dst, (const uint32_t*)w.seek, (uint32_t)nb);
         if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     }
-    hipLaunchKernelGGL(zxc_append_result_kernel, dim3(1), dim3(64), 0, st, (const zap_ctl_t*)ctl, d_result);
+    hipLaunchKernelGGL(zxc_append_result_kernel, dim3(1), dim3(64), 0, st, (const zap_ctl_t*)w.ctl, d_result);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 

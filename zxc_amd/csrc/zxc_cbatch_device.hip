@@ -80,28 +80,10 @@ zxc_cbatch_results_kernel(const zcb_rec_t* __restrict__ recs, uint32_t n_items, 
 // ---------------------------------------------------------------- host side
 namespace {
 
-struct CbOpts {
-    uint32_t block_size, level, checksum, seekable;
-};
-
-// Options as zxc_mi355x_compress_device reads them (frame_plan of zxc_frame_device.hip). -> ZXC_OK or ZXC_ERROR_BAD_BLOCK_SIZE;
-// opts->dict is the caller's to refuse, behind the block size.
-int cb_opts(const zxc_compress_opts_t* opts, CbOpts* o) {
-    int level = (opts && opts->level > 0) ? opts->level : 3;
-    if (level > 7) level = 7;
-    const uint64_t bs = (opts && opts->block_size > 0) ? (uint64_t)opts->block_size : 512u * 1024u;
-    if (!zc_block_size_ok(bs)) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    o->block_size = (uint32_t)bs;
-    o->level = (uint32_t)level;
-    o->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
-    o->seekable = (opts && opts->seekable) ? 1u : 0u;
-    return ZXC_OK;
-}
-
 uint64_t cb_work_size(uint32_t n_items, uint64_t max_size, const zxc_compress_opts_t* opts, uint32_t dict_size) {
-    CbOpts o;
+    zd_copts_t o;
     zcb_shape_t s;
-    if (cb_opts(opts, &o) != ZXC_OK || (opts && opts->dict) || dict_size > ZC_DICT_MAX) return 0u;
+    if (zd_compress_opts(opts, &o) != ZXC_OK || (opts && opts->dict) || dict_size > ZC_DICT_MAX) return 0u;
     return zcb_shape(n_items, max_size, o.block_size, zxc_mi355x_encode_slot_stride(o.block_size), dict_size, &s) != 0 ? 0u : s.bytes;
 }
 
@@ -110,10 +92,10 @@ int cb_call(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_it
             uint64_t dst_capacity, const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size,
             int64_t* d_results, void* stream) {
     if (!d_src || !d_work || !d_results || (!d_items && n_items > 0) || (!d_dst && dst_capacity > 0)) return ZXC_ERROR_NULL_INPUT;
-    CbOpts o;
-    const int orc = cb_opts(opts, &o);
+    zd_copts_t o;
+    const int orc = zd_compress_opts(opts, &o);
     if (orc != ZXC_OK) return orc;
-    if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;  // (behind the block size, unlike the frame and append calls)
     const int drc = dict_arg(&dict);
     if (drc != ZXC_OK) return drc;
     const uint32_t dict_size = dict ? dict->size : 0u;

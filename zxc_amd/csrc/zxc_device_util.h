@@ -1,6 +1,7 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_take_device.hip, zxc_dict_device.hip): the three tile passes every container stage is made of, the copy out of a staged
-// slot and the host-side plumbing of an entry point.
+// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_take_device.hip, zxc_dict_device.hip): the three tile
+// passes every container stage is made of, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
+// of an entry point: the launch check, the work area's base, the dictionary argument and the one reader of zxc_compress_opts_t.
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //
 // A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
@@ -119,6 +120,16 @@ __device__ __forceinline__ void zd_copy_chunk(uint8_t* __restrict__ d, const uin
     }
 }
 
+// Compaction, one wave per block: block b's sizes[b] bytes at slots + b x slot_stride -> dst + offsets[b], for b < nb. The body of
+// zxc_frame_gather_kernel and zxc_append_gather_kernel, behind their test of the status word.
+__device__ __forceinline__ void zd_gather_blocks(const uint8_t* __restrict__ slots, uint32_t slot_stride, const uint32_t* __restrict__ sizes,
+                                                 const uint64_t* __restrict__ offsets, uint8_t* __restrict__ dst, uint32_t nb) {
+    const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
+    for (uint64_t b = (uint64_t)blockIdx.x * waves + (threadIdx.x >> 6); b < nb; b += (uint64_t)gridDim.x * waves) {
+        copy_bytes(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
+    }
+}
+
 // ---------------------------------------------------------------- a kernel two files launch
 // zxc_frame_device.hip defines it; zxc_append_device.hip launches it per piece. Declared once, here, which both include: a
 // definition that departs from this is a conflicting redeclaration and does not compile (as zxc_kernels.h).
@@ -145,6 +156,21 @@ static inline int dict_arg(const zxc_dev_dict_t** dict) {
     if (d && d->size > ZC_DICT_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
     if (d && d->size > 0 && (!d->d_content || !d->d_id)) return ZXC_ERROR_NULL_INPUT;
     if (d && d->size == 0) *dict = NULL;
+    return ZXC_OK;
+}
+// Options as zxc_compress reads them (zxc_host.c): level 3 unless given, at most 7; blocks of 512 KiB unless given. -> ZXC_OK or
+// ZXC_ERROR_BAD_BLOCK_SIZE. opts->dict is not looked at: each caller refuses it at its own place in its order of errors.
+struct zd_copts_t {
+    uint32_t block_size, level, checksum, seekable;
+};
+static inline int zd_compress_opts(const zxc_compress_opts_t* opts, zd_copts_t* o) {
+    const int level = (opts && opts->level > 0) ? opts->level : 3;
+    const uint64_t bs = (opts && opts->block_size > 0) ? (uint64_t)opts->block_size : 512u * 1024u;
+    if (!zc_block_size_ok(bs)) return ZXC_ERROR_BAD_BLOCK_SIZE;
+    o->block_size = (uint32_t)bs;
+    o->level = (uint32_t)(level > 7 ? 7 : level);
+    o->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
+    o->seekable = (opts && opts->seekable) ? 1u : 0u;
     return ZXC_OK;
 }
 #endif

@@ -129,10 +129,7 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_frame_gather_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride, const uint32_t* __restrict__ sizes,
                         const uint64_t* __restrict__ offsets, uint8_t* __restrict__ dst, uint32_t nb, const FrameCtl* __restrict__ ctl) {
     if (ctl->status < 0) return;
-    const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
-    for (uint64_t b = (uint64_t)blockIdx.x * waves + (threadIdx.x >> 6); b < nb; b += (uint64_t)gridDim.x * waves) {
-        copy_bytes(dst + offsets[b], slots + b * slot_stride, sizes[b], lane, 64u);
-    }
+    zd_gather_blocks(slots, slot_stride, sizes, offsets, dst, nb);
 }
 
 extern "C" __global__ void zxc_frame_result_kernel(const FrameCtl* __restrict__ ctl, int64_t* __restrict__ result) {
@@ -149,20 +146,16 @@ struct FramePlan {
     uint64_t o_tile_sum, o_tile_hash, o_tile_bad, o_sizes, o_offsets, o_stage, o_slots, o_images, bytes;  // o_images: the dictionary call's image area, behind the rest
 };
 
-// Options as zxc_compress reads them (zxc_host.c). -> ZXC_OK or a negative zxc_error_t.
+// The options (zd_compress_opts) and the call's shape. -> ZXC_OK or a negative zxc_error_t.
 int frame_plan(uint64_t src_size, const zxc_compress_opts_t* opts, FramePlan* p) {
     if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;
-    int level = (opts && opts->level > 0) ? opts->level : 3;
-    if (level > 7) level = 7;
-    const uint64_t bs = (opts && opts->block_size > 0) ? (uint64_t)opts->block_size : 512u * 1024u;
-    if (!zc_block_size_ok(bs)) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    const uint64_t nb = (src_size + bs - 1u) / bs;
+    zd_copts_t co;
+    const int orc = zd_compress_opts(opts, &co);
+    if (orc != ZXC_OK) return orc;
+    const uint64_t bs = co.block_size, nb = (src_size + bs - 1u) / bs;
     if (nb > 0x7FFFFFFFull) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    p->block_size = (uint32_t)bs;
+    p->block_size = co.block_size; p->level = co.level; p->checksum = co.checksum; p->seekable = co.seekable;
     p->lg = zc_block_size_lg(bs);
-    p->level = (uint32_t)level;
-    p->checksum = (opts && opts->checksum_enabled) ? 1u : 0u;
-    p->seekable = (opts && opts->seekable) ? 1u : 0u;
     p->nb = (uint32_t)nb;
     p->n_tiles = (uint32_t)((nb + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS);
     p->stride = zxc_mi355x_encode_slot_stride(p->block_size);

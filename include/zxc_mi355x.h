@@ -671,6 +671,52 @@ ZXC_EXPORT int zxc_mi355x_decompress_begin_dict_device(zxc_dev_dtake_t* ds, cons
 ZXC_EXPORT int zxc_mi355x_decompress_take_device(zxc_dev_dtake_t* ds, void* d_dst, uint64_t n, void* stream);
 ZXC_EXPORT int zxc_mi355x_decompress_end_device(zxc_dev_dtake_t* ds, int64_t* d_result, void* stream);
 
+/* Take into a table of buffers: the readv of the session (rules in zxc_amd/csrc/zxc_takev.h), the mirror of
+ * zxc_mi355x_compress_appendv_device. One take per tensor of a state dict is a plan launch, one or two decode launches and a copy
+ * launch per tensor, and the decode launch of a small tensor holds a handful of blocks, one wavefront each. Here one call delivers
+ * the next `total` decoded bytes into a table of (base, len) entries that lies in device memory: with Y the concatenation of the
+ * entries' destinations in table order, the call is exactly zxc_mi355x_decompress_take_device(ds, Y, total, stream). The blocks
+ * of a chunk of at most max_piece bytes are cut from Y, not from the entries, so one decode launch carries max_piece / block_size
+ * blocks however small the entries are. After end, *d_result is what the session stores for the same archive, capacity, options
+ * and dictionary; on success the entries hold, in table order, the next `total` decoded bytes. take and takev mix freely in one
+ * session, in any order: the block that a call ends inside waits in the carry slot for whichever call comes next. The call serves
+ * sessions begun with and without a dictionary (the decode launch is the session's).
+ * The table: d_iov lies in device memory and is read on the stream (a kernel or copy enqueued before the call may write it, a
+ * replayed graph may see other pointers). The host knows only n_iov and total, the caller's promise of the sum of the lengths:
+ * that gives it what it knows in take (position, chunk cuts, grids), so nothing about the launch shape is decided on the device.
+ * Entries of length 0 are legal anywhere and their base is not looked at; an entry may have any alignment; entries that overlap
+ * each other, d_src, the work area or d_scratch are the caller's error (undefined bytes, no fault). The call writes nothing
+ * outside [base, base + len) of the entries, the session's work area and d_scratch: nothing is promised writable behind an entry.
+ * Stream order: once per call a scan (appendv's three tile passes: exclusive prefix sums of the lengths into the scratch, and the
+ * table check) and a fold of the verdict into the session, then per chunk plan, decode, copy as in take. The plan decides on the
+ * device where each whole block is decoded: where it belongs when that place is 16-byte aligned and the block plus the decoders'
+ * 32 bytes end inside that one entry; else in a slot of the work area. The copy moves a range that lies inside one entry with the
+ * aligned 16-byte stores take uses; a range that meets an entry boundary is scattered (a lane owns 16-byte units of the slot,
+ * finds the entry of its first byte by a search over the start offsets, and stores the unit with one 16-byte store of any
+ * alignment when it lies inside one entry, else byte by byte into consecutive entries), so its cost does not depend on how small
+ * the entries are.
+ * Scratch: d_scratch (any alignment) is the call's own until the work this call enqueued has run; a later takev on the same
+ * stream may reuse it. It is not part of the session's work area. With J = max_piece / block_size + 2 its size is at most
+ * 8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + 16 x J + 4096: a control word, the entries' start offsets, the words of the scan per
+ * tile of 1024 entries, one place record per job of a chunk, alignment. The size function returns 0 for a block_size or max_piece
+ * that begin would refuse; max_piece and block_size are the session's.
+ * Table errors are found on the device and become the session's result, which end stores: a session whose result is already
+ * final (a file-header error, a dictionary error, the empty-frame probe, an earlier table error) keeps it; else an entry with
+ * len > 0 and base == 0 -> ZXC_ERROR_NULL_INPUT; else an entry longer than total, or a sum above total (compared without overflow)
+ * -> ZXC_ERROR_OVERFLOW; else a sum below total -> ZXC_ERROR_DST_TOO_SMALL (fewer destination bytes than promised). After any of
+ * these no byte of any entry of that call is written and none of its blocks is decoded; every later copy of the session moves nothing
+ * (the bytes of later pieces are undefined); the host's position has moved on by total, as it cannot know, and the session is still taken to the capacity and ended as
+ * usual.
+ * Synchronous errors, before anything is enqueued and with the session as it was, in this order: NULL ds, NULL d_scratch, NULL
+ * d_iov with n_iov > 0 -> ZXC_ERROR_NULL_INPUT; a session never begun or ended -> ZXC_ERROR_NULL_INPUT; n_iov == 0 with total > 0
+ * -> ZXC_ERROR_DST_TOO_SMALL; bytes so far + total > dst_capacity (compared without overflow) -> ZXC_ERROR_OVERFLOW; scratch_size
+ * too small -> ZXC_ERROR_MEMORY. n_iov == 0 with total == 0 is ZXC_OK and enqueues nothing; n_iov > 0 with total == 0 enqueues the
+ * scan alone (a non-empty entry is then an error). A launch failure leaves the session spent, as in take. Asynchronous on `stream`
+ * and capturable like take: no host synchronisation, no device allocation of its own. */
+ZXC_EXPORT uint64_t zxc_mi355x_decompress_takev_device_scratch_size(uint32_t n_iov, uint64_t max_piece, uint32_t block_size);
+ZXC_EXPORT int zxc_mi355x_decompress_takev_device(zxc_dev_dtake_t* ds, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total,
+                                                  void* d_scratch, uint64_t scratch_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

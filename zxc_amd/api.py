@@ -661,6 +661,22 @@ def _bind_decompress_take_device(L):
     return L
 
 
+def _bind_decompress_takev_device(L):
+    _bind_decompress_take_device(L)
+    L.zxc_mi355x_decompress_takev_device_scratch_size.restype = C.c_uint64
+    L.zxc_mi355x_decompress_takev_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
+    L.zxc_mi355x_decompress_takev_device.restype = C.c_int
+    L.zxc_mi355x_decompress_takev_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p]
+    return L
+
+
+def decompress_takev_device_scratch_size(n_iov, max_piece, block_size):
+    """zxc_mi355x_decompress_takev_device_scratch_size(): bytes of device scratch one takev of n_iov entries needs in a session
+    of that max_piece and block_size (0 for refused arguments)."""
+    return int(_bind_decompress_takev_device(lib()).zxc_mi355x_decompress_takev_device_scratch_size(n_iov, max_piece, block_size))
+
+
 def decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_size):
     """zxc_mi355x_decompress_take_device_work_size(): bytes of device scratch a session needs (0 for refused arguments)."""
     return int(_bind_decompress_take_device(lib()).zxc_mi355x_decompress_take_device_work_size(src_size, dst_capacity, max_piece,
@@ -668,8 +684,8 @@ def decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_si
 
 
 class DecompressTakeSession:
-    """A session of zxc_mi355x_decompress_begin_device(): .take(d_dst, n) until dst_capacity bytes are taken, then .end(d_result)
-    once. Raw device pointers (ints), asynchronous on `stream`; the calls of one session must be in stream order with each other.
+    """A session of zxc_mi355x_decompress_begin_device(): .take(d_dst, n) and .takev(d_iov, n_iov, total, d_scratch, scratch_size)
+    until dst_capacity bytes are taken, then .end(d_result) once. Raw device pointers (ints), asynchronous on `stream`; the calls of one session must be in stream order with each other.
     The decoded size or the negative zxc_error_t decompress_device would store lands in the int64 at d_result; a synchronous
     failure raises ZxcError."""
 
@@ -681,6 +697,15 @@ class DecompressTakeSession:
                                                                                    C.c_void_p(stream or None))
         if rc < 0:
             raise ZxcError(rc, "zxc_mi355x_decompress_take_device")
+
+    def takev(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
+        """zxc_mi355x_decompress_takev_device(): delivers the next `total` bytes into the n_iov x IOV_DTYPE entries at d_iov (device
+        memory), in table order; the scratch size is decompress_takev_device_scratch_size(n_iov, max_piece, block_size)."""
+        rc = _bind_decompress_takev_device(lib()).zxc_mi355x_decompress_takev_device(
+            C.byref(self._ds), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
+            C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_decompress_takev_device")
 
     def end(self, d_result, stream=0):
         rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_end_device(C.byref(self._ds), C.c_void_p(d_result or None),

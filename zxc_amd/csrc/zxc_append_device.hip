@@ -50,6 +50,7 @@
 #include <string.h>
 
 #include "zxc_device_util.h"  // the tile passes, copy_bytes (zxc_wave.h), zxc_frame_tiles_kernel, the host-side plumbing
+#include "zxc_kernels.h"      // the scan kernels of appendv, which zxc_take_device.hip launches too
 #include "zxc_append.h"
 #include "zxc_appendv.h"
 

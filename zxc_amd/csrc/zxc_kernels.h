@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "zxc_appendv.h"    // zav_ctl_t, zap_ctl_t
 #include "zxc_container.h"  // zc_ctl_t
 #include "zxc_dev.h"
 
@@ -106,6 +107,15 @@ extern "C" __global__ void zxc_unframe_events_kernel(const int32_t* status, uint
                                                      zc_ctl_t* ctl);
 extern "C" __global__ void zxc_unframe_result_kernel(const zc_ctl_t* ctl, const int32_t* status, uint32_t block_size, uint32_t n_jobs,
                                                      int64_t* result);
+
+// ---------------------------------------------------------------- zxc_append_device.hip
+// The scan of a table of (base, len) entries (zxc_appendv.h): zxc_mi355x_compress_appendv_device's, which the take session's takev
+// (zxc_take_device.hip) launches as it is, with a zap_ctl_t of its own that nobody reads.
+extern "C" __global__ void zxc_appendv_reduce_kernel(const zxc_dev_iov_t* iov, uint32_t n_iov, uint64_t total, uint64_t* tile_sum,
+                                                     uint32_t* tile_flags);
+extern "C" __global__ void zxc_appendv_scan_kernel(uint64_t* tile_sum, const uint32_t* tile_flags, uint32_t n_tiles, uint64_t total,
+                                                   uint64_t* starts, uint32_t n_iov, zav_ctl_t* vctl, zap_ctl_t* ctl);
+extern "C" __global__ void zxc_appendv_starts_kernel(const zxc_dev_iov_t* iov, uint32_t n_iov, const uint64_t* tile_off, uint64_t* starts);
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
 extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 #endif

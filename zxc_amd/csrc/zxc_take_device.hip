@@ -1,6 +1,7 @@
-// zxc_take_device.hip — zxc_mi355x_decompress_begin_device / _take_device / _end_device: one v8 archive in device memory decoded
-// into a destination that is handed over in pieces, each in device memory. The device counterpart of pulling from zxc_dstream_*
-// (zxc_pstream_host.c) and the mirror image of the append session (zxc_append_device.hip).
+// zxc_take_device.hip — zxc_mi355x_decompress_begin_device / _take_device / _takev_device / _end_device: one v8 archive in device
+// memory decoded into a destination that is handed over in pieces, each in device memory (takev: a table of them, zxc_takev.h).
+// The device counterpart of pulling from zxc_dstream_* (zxc_pstream_host.c) and the mirror image of the append session
+// (zxc_append_device.hip).
 //
 // zxc_mi355x_decompress_device (zxc_unframe_device.hip) wants one contiguous, 16-byte aligned destination of the whole decoded
 // size. Here a session parses the container once, keeps the block index and one status word per block in its work area, and every
@@ -32,10 +33,13 @@
 #include "zxc_device_util.h"  // zd_copy_chunk, the host-side plumbing
 #include "zxc_kernels.h"      // the container stages of zxc_unframe_device.hip
 #include "zxc_take.h"
+#include "zxc_takev.h"
 
 static_assert(ZT_COPY_CHUNK == ZD_COPY_CHUNK, "the shape counts the chunks zd_copy_chunk moves");
 static_assert(2 * sizeof(zxc_dev_job_t) + 2 * 4 == ZT_BLOCK_BYTES && 2 * sizeof(zxc_dev_job_t) == ZT_JOB_BYTES, "the documented work size");
 static_assert(sizeof(zc_ctl_t) <= 256, "the state's place at the start of the work area");
+static_assert(sizeof(ztv_place_t) == ZTV_PLACE_BYTES && 8 + 4 + 4 == ZTV_TILE_BYTES, "the documented scratch size");
+static_assert(sizeof(zav_ctl_t) <= ZTV_SINK && ZTV_SINK + sizeof(zap_ctl_t) <= 256, "the call's control word and the unread zap_ctl_t");
 
 // ---------------------------------------------------------------- kernels
 // Job j of the chunk is block c.first + j of the index (both tables: the head stage left one of them empty), decoded where the
@@ -79,6 +83,78 @@ zxc_take_copy_kernel(const uint8_t* __restrict__ carry0, const uint8_t* __restri
         if (n == 0 || (uint64_t)ch * ZT_COPY_CHUNK >= ((uintptr_t)d & 15u) + n) continue;
         const uint8_t* s = (cp.kind == ZT_SLOT ? slots + (uint64_t)cp.slot * slot_stride : cp.slot ? carry1 : carry0) + cp.from;
         zd_copy_chunk(d, s, (int64_t)n, ch, lane);
+    }
+}
+
+// ---------------------------------------------------------------- takev: a table of destinations (zxc_takev.h)
+// The stream order of one call: the scan of zxc_mi355x_compress_appendv_device (zxc_appendv_reduce_kernel, _scan_kernel,
+// _starts_kernel as they are: starts[0 .. n_iov] and the table's status in the call's control word), the fold below, then per chunk
+// plan, the decode launch and copy.
+
+// One thread: the table's status becomes the call's verdict and, an error, the session's result unless that is final already.
+extern "C" __global__ void zxc_takev_fold_kernel(zav_ctl_t* __restrict__ vctl, zc_ctl_t* __restrict__ ctl) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int verdict = ztv_verdict(vctl->status);
+    vctl->status = verdict;
+    ztv_fold(ctl, verdict);
+}
+
+// zxc_take_plan_kernel over a virtual destination: job j of the chunk is block c.c.first + j of the index, decoded where
+// ztv_job_place says (inside its entry, into slot j, into the next carry slot); the job's out_off is that address minus the
+// launch's d_out (the work area's base) modulo 2^64, a multiple of 16. Behind a table error, and in a session whose result is
+// final, every job is written empty and neither the table nor an entry is read.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_takev_plan_kernel(const zxc_dev_job_t* __restrict__ index, uint32_t n_jobs, uint32_t tables, ztv_chunk_t c,
+                      const zxc_dev_iov_t* __restrict__ iov, const uint64_t* __restrict__ starts, uint32_t n_iov,
+                      const zav_ctl_t* __restrict__ vctl, const zc_ctl_t* __restrict__ ctl, uint64_t out_base, uint64_t carry0, uint64_t carry1,
+                      uint64_t slots, uint32_t slot_stride, uint32_t J, zxc_dev_job_t* __restrict__ cjobs, ztv_place_t* __restrict__ places) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= c.c.nb || j >= J || c.c.first + j >= n_jobs) return;
+    if (vctl->status < 0 || ctl->final) {
+        const zxc_dev_job_t empty = {0u, slots + (uint64_t)j * slot_stride - out_base, 0u, c.c.block_size};  // (its wave leaves at once)
+        const ztv_place_t none = {ZT_NONE, 0u, 0u};
+        for (uint32_t tb = 0; tb < tables; tb++) cjobs[(uint64_t)tb * J + j] = empty;
+        places[j] = none;
+        return;
+    }
+    uint64_t addr;
+    places[j] = ztv_job_place(&c, j, iov, starts, n_iov, carry0, carry1, slots, slot_stride, &addr);
+    for (uint32_t tb = 0; tb < tables; tb++) {
+        zxc_dev_job_t job = index[(uint64_t)tb * n_jobs + c.c.first + j];
+        job.out_off = addr - out_base;
+        cjobs[(uint64_t)tb * J + j] = job;
+    }
+}
+
+// zxc_take_copy_kernel over a virtual destination, one wavefront per (copy, 8 KiB): a copy whose bytes lie inside one entry is
+// zd_copy_chunk to its place there, 8 KiB of destination per wavefront; one that meets an entry boundary is the scatter, 8 KiB of
+// the slot per wavefront, a lane owning 16-byte units of the slot. A block decoded in its entry has no copy.
+extern "C" __global__ void __launch_bounds__(256)
+zxc_takev_copy_kernel(const uint8_t* __restrict__ carry0, const uint8_t* __restrict__ carry1, const uint8_t* __restrict__ slots,
+                      uint32_t slot_stride, ztv_chunk_t c, const int32_t* __restrict__ status, uint32_t n_jobs,
+                      const zc_ctl_t* __restrict__ ctl, const zav_ctl_t* __restrict__ vctl, uint32_t chunks,
+                      const zxc_dev_iov_t* __restrict__ iov, const uint64_t* __restrict__ starts, uint32_t n_iov,
+                      const ztv_place_t* __restrict__ places) {
+    if (vctl->status < 0 || ctl->final) return;
+    const uint32_t lane = threadIdx.x & 63u, found = ctl->found;
+    const int32_t* st = status + (uint64_t)ctl->sel * n_jobs;
+    const uint64_t units = ((uint64_t)c.c.nb + 1u) * chunks, waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t it = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); it < units; it += waves) {
+        const uint32_t k = (uint32_t)(it / chunks), ch = (uint32_t)(it - (uint64_t)k * chunks);
+        const zt_copy_t cp = zt_copy(&c.c, k);
+        if (cp.kind == ZT_NONE || cp.block >= found) continue;
+        const ztv_place_t* rec = k ? places + (k - 1u) : NULL;
+        if (rec && rec->kind != cp.kind) continue;  // decoded in its entry
+        const uint32_t n = zt_copy_bytes(&cp, st[cp.block], c.c.block_size);
+        if (n == 0 || (uint64_t)ch * ZT_COPY_CHUNK >= (uint64_t)n + 15u) continue;
+        const ztv_copy_t o = ztv_copy_place(&c, &cp, n, rec, iov, starts, n_iov);
+        const uint8_t* s = (cp.kind == ZT_SLOT ? slots + (uint64_t)cp.slot * slot_stride : cp.slot ? carry1 : carry0) + cp.from;
+        if (o.one) {
+            uint8_t* d = (uint8_t*)(uintptr_t)o.d;
+            if ((uint64_t)ch * ZT_COPY_CHUNK < ((uintptr_t)d & 15u) + n) zd_copy_chunk(d, s, (int64_t)n, ch, lane);
+            continue;
+        }
+        ztv_scatter_lane(s, n, o.y, ch, lane, iov, starts, o.e_lo, n_iov);
     }
 }
 
@@ -136,6 +212,44 @@ int tk_chunk(const Sess& s, const zt_shape_t& sh, uint8_t* d, const zt_chunk_t& 
     hipLaunchKernelGGL(zxc_take_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
                        (const uint8_t*)(base + sh.o_carry[0]), (const uint8_t*)(base + sh.o_carry[1]), (const uint8_t*)(base + sh.o_slots),
                        sh.slot_stride, c, (const int32_t*)(base + sh.o_status), sh.n_jobs, (const zc_ctl_t*)base, sh.copy_chunks, d);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+// The virtual destination of a takev (zxc_takev.h): the table, what the call's scan left in its scratch.
+struct Vdst {
+    const zxc_dev_iov_t* iov;
+    uint32_t n_iov;
+    const uint64_t* starts;
+    const zav_ctl_t* vctl;
+    ztv_place_t* places;
+};
+
+// One chunk of a takev behind its plan: plan, decode, copy. The decode launch's d_out is the work area's 256-byte aligned base;
+// a job's out_off is its address minus that base modulo 2^64 (the entries may lie above or below the work area), which the decode
+// kernels only ever add to d_out in 64 bits. Slots, carry slots and the places of blocks decoded in their entries are 16-byte
+// aligned, so every out_off is a multiple of 16.
+int tkv_chunk(const Sess& s, const zt_shape_t& sh, const Vdst& vd, const ztv_chunk_t& c, hipStream_t st) {
+    uint8_t* base = s.base;
+    const zc_ctl_t* ctl = (const zc_ctl_t*)base;
+    int32_t* status = (int32_t*)(base + sh.o_status);
+    if (c.c.nb) {
+        zxc_dev_job_t* cjobs = (zxc_dev_job_t*)(base + sh.o_cjobs);
+        hipLaunchKernelGGL(zxc_takev_plan_kernel, dim3((c.c.nb + 255u) / 256u), dim3(256), 0, st, (const zxc_dev_job_t*)(base + sh.o_jobs), sh.n_jobs,
+                           s.tables, c, vd.iov, vd.starts, vd.n_iov, vd.vctl, ctl, (uint64_t)(uintptr_t)base,
+                           (uint64_t)(uintptr_t)(base + sh.o_carry[0]), (uint64_t)(uintptr_t)(base + sh.o_carry[1]),
+                           (uint64_t)(uintptr_t)(base + sh.o_slots), sh.slot_stride, sh.J, cjobs, vd.places);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        for (uint32_t tb = 0; tb < s.tables; tb++) {
+            const int rc = zxc_hip_decode_blocks(s.src, cjobs + (uint64_t)tb * sh.J, c.c.nb, base, status + (uint64_t)tb * sh.n_jobs + c.c.first,
+                                                 s.block_size, (int)tb, s.d_dict, s.dict_size, s.d_huf, 0u, (void*)st);
+            if (rc != ZXC_OK) return rc;
+        }
+    }
+    const uint64_t groups = (((uint64_t)c.c.nb + 1u) * sh.copy_chunks + 3u) / 4u;
+    hipLaunchKernelGGL(zxc_takev_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
+                       (const uint8_t*)(base + sh.o_carry[0]), (const uint8_t*)(base + sh.o_carry[1]), (const uint8_t*)(base + sh.o_slots),
+                       sh.slot_stride, c, (const int32_t*)status, sh.n_jobs, ctl, vd.vctl, sh.copy_chunks, vd.iov, vd.starts, vd.n_iov,
+                       (const ztv_place_t*)vd.places);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
@@ -233,6 +347,65 @@ int zxc_mi355x_decompress_take_device(zxc_dev_dtake_t* ds, void* d_dst, uint64_t
         d += m; left -= m;
     }
     if (rc != ZXC_OK) s.magic = 0;  // part of the take may be enqueued: the session cannot go on
+    memcpy(ds, &s, sizeof s);
+    return rc;
+}
+
+uint64_t zxc_mi355x_decompress_takev_device_scratch_size(uint32_t n_iov, uint64_t max_piece, uint32_t block_size) {
+    ztv_shape_t sh;
+    return ztv_shape(n_iov, max_piece, block_size, &sh) == 0 ? sh.bytes : 0u;
+}
+
+int zxc_mi355x_decompress_takev_device(zxc_dev_dtake_t* ds, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total, void* d_scratch,
+                                       uint64_t scratch_size, void* stream) {
+    if (!ds || !d_scratch || (n_iov > 0 && !d_iov)) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, ds, sizeof s);
+    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (n_iov == 0 && total > 0) return ZXC_ERROR_DST_TOO_SMALL;
+    if (total > s.dst_capacity - s.pos) return ZXC_ERROR_OVERFLOW;
+    zt_shape_t sh;
+    ztv_shape_t vsh;
+    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0 || ztv_shape(n_iov, s.max_piece, s.block_size, &vsh) != 0)
+        return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    if (scratch_size < vsh.bytes) return ZXC_ERROR_MEMORY;
+    if (n_iov == 0) return ZXC_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* sb = zd_work_base(d_scratch);
+    zav_ctl_t* vctl = (zav_ctl_t*)sb;
+    uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
+    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
+    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
+    // The scan, once per call (appendv's kernels as they are; their fold goes to a zap_ctl_t in the scratch that nobody reads), and
+    // the fold of the verdict into the session: the chunks read starts and the verdict in stream order.
+    int rc = ZXC_OK;
+    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
+    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
+                           n_iov, vctl, (zap_ctl_t*)(sb + ZTV_SINK));
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_takev_fold_kernel, dim3(1), dim3(64), 0, st, vctl, (zc_ctl_t*)s.base);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    // The chunks, cut like those of a take of `total` bytes; v is the chunk's offset in the concatenation of the entries.
+    const Vdst vd = {d_iov, n_iov, starts, vctl, (ztv_place_t*)(sb + vsh.o_places)};
+    uint64_t left = total, v = 0;
+    while (left && rc == ZXC_OK) {
+        const uint64_t m = zt_chunk_len(s.pos, left, s.max_piece, s.block_size);
+        ztv_chunk_t c;
+        ztv_plan_chunk(s.pos, m, s.block_size, s.cur, v, &c);
+        rc = tkv_chunk(s, sh, vd, c, st);
+        zt_advance(&c.c, &s.pos, &s.cur);
+        v += m; left -= m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;  // part of the call may be enqueued: the session cannot go on
     memcpy(ds, &s, sizeof s);
     return rc;
 }

@@ -421,7 +421,8 @@ ZXC_EXPORT uint64_t zxc_mi355x_compress_batch_device_work_size(uint32_t n_items,
  * graph may see other items each time. All items' blocks are encoded by one launch of the level's encoder over a job table (one
  * wavefront per job; the unused ones of an item's J exit at once); one thread per item then writes the container around them,
  * serially over the item's blocks, so this call is for items of few blocks: a source of many blocks belongs in
- * zxc_mi355x_compress_device. The archives are not packed back to back: each goes where its item says.
+ * zxc_mi355x_compress_device. The archives are not packed back to back: each goes where its item says
+ * (zxc_mi355x_compress_pack_device below packs them).
  * Options are read like zxc_mi355x_compress_device reads them (opts may be NULL: level 3, 512 KiB blocks); n_threads, progress_cb
  * and user_data are ignored.
  * Synchronous errors, in this order, before any device is touched: NULL d_src / d_work / d_results, NULL d_items with
@@ -454,6 +455,69 @@ ZXC_EXPORT int zxc_mi355x_compress_batch_dict_device(const void* d_src, uint64_t
                                                      uint32_t n_items, uint64_t max_size, void* d_dst, uint64_t dst_capacity,
                                                      const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict, void* d_work,
                                                      uint64_t work_size, int64_t* d_results, void* stream);
+
+/* ---- many buffers per call, packed back to back (zxc_amd/csrc/zxc_cbatch_device.hip, rules in zxc_amd/csrc/zxc_cpack.h) ----
+ * zxc_mi355x_compress_batch_device wants a destination of zxc_compress_bound per item, because nobody knows an archive's size
+ * before the call, and leaves the archives with gaps of unknown size between them. This call takes no destination per item: it
+ * lays the archives out itself, one behind the other in table order, and writes the table with which
+ * zxc_mi355x_decompress_batch_device finds them again. No size or offset is ever known to the host. */
+
+/* Bytes of device scratch the call below needs; 0 for whatever zxc_mi355x_compress_batch_device_work_size answers 0. The size is
+ * that call's plus the words of the layout's scan, one 64-bit sum per tile of 1024 items and the end word: at most
+ * n_items x J x (S + 28) + 64 x n_items + 1536 + 8 x ceil(n_items / 1024) + 256. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_pack_device_work_size(uint32_t n_items, uint64_t max_size, const zxc_compress_opts_t* opts);
+
+/* zxc_mi355x_compress_batch_device with the archives packed. Of d_items[r] only src_off and src_size are read (dst_off and
+ * dst_capacity are not looked at: the table of a zxc_mi355x_compress_batch_device call can be passed as it is); the table is
+ * device data read on the stream, as there.
+ * Layout: an item is SIZED when its source lies inside d_src[0, src_capacity), src_size_r <= max_size and the encoder left legal
+ * block sizes for it; its archive size size_r is the one zxc_compress gives for those bytes and options. The sized items are laid
+ * out in table order: at_r = the end of the sized item in front of it rounded up to `align`, the first at 0. Items that are not
+ * sized take no room. The layout does not depend on dst_capacity. *d_total (device memory) receives the end at_r + size_r of the
+ * last sized item, 0 when there is none, whether or not everything fits: it is the dst_capacity with which everything fits, so a
+ * caller whose capacity was too small learns the right one from one word. *d_total is never an error word.
+ * Per item, decided on the device in this order: src_off_r + src_size_r > src_capacity (compared without overflow) ->
+ * ZXC_ERROR_SRC_TOO_SMALL; src_size_r > max_size -> ZXC_ERROR_OVERFLOW (after either, nothing of the item is read and no block of
+ * it is encoded); behind the encoder, a block size outside [8 (+4), block_size + 64] -> ZXC_ERROR_CORRUPT_DATA; at_r + size_r >
+ * dst_capacity -> ZXC_ERROR_DST_TOO_SMALL, and nothing of the item is written; else the archive is written at d_dst + at_r and
+ * d_results[r] = size_r. The archive is byte for byte the one zxc_mi355x_compress_batch_device and zxc_compress of this library
+ * write for that buffer and those options. Offsets only grow and every archive has at least 36 bytes, so the items that fit are a
+ * prefix of the sized ones.
+ * d_packed[r] (n_items entries, device memory) is the item of zxc_mi355x_decompress_batch_device that restores buffer r. For an
+ * item that was written: src_off = at_r, src_size = size_r, dst_off = d_items[r].src_off, dst_capacity = d_items[r].src_size. For
+ * every other item src_off = 0 and src_size = 0, which that call answers with ZXC_ERROR_SRC_TOO_SMALL without reading anything
+ * (dst_off and dst_capacity are the item's all the same). d_packed may be d_items itself: the plan keeps what it needs in the
+ * item's record, and the packed table is written by the last stage. Any other overlap is the caller's error.
+ * Synchronous errors, in this order, before any device is touched: NULL d_src / d_work / d_results / d_packed / d_total, NULL
+ * d_items with n_items > 0, NULL d_dst with dst_capacity > 0 -> ZXC_ERROR_NULL_INPUT; block_size not a power of two in [4 KiB,
+ * 2 MiB] -> ZXC_ERROR_BAD_BLOCK_SIZE; opts->dict != NULL -> ZXC_ERROR_GPU_UNSUPPORTED; align not a power of two in [1, 4096] ->
+ * ZXC_ERROR_GPU_UNSUPPORTED; n_items x J above 2^31 - 2, or work_size too small -> ZXC_ERROR_MEMORY; n_items == 0 is ZXC_OK here,
+ * enqueues nothing and does not write *d_total; then, without a device, ZXC_ERROR_GPU_UNAVAILABLE. dst_capacity == 0 with a NULL
+ * d_dst is legal, the sizing run: every sized item gets ZXC_ERROR_DST_TOO_SMALL, and *d_total holds the need.
+ * Guarantees: nothing is written outside [at_r, at_r + size_r) of the written items, d_work, d_packed, d_results and d_total; the
+ * alignment gaps between archives, and everything at and past *d_total or dst_capacity, are left as they were. d_dst may have
+ * any alignment (at_r is aligned relative to d_dst). d_src must be READABLE up to src_capacity + 64 and is never written, as in
+ * the sibling. No host synchronisation and no device allocation (beyond the encoder's stream-ordered scratch at levels 6-7).
+ * d_work: any alignment, owned by the call until the last result is written; the result words, the packed table and *d_total are
+ * written once, behind the last archive byte. Calls on different streams with different work areas may overlap. */
+ZXC_EXPORT int zxc_mi355x_compress_pack_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                               uint32_t n_items, uint64_t max_size, void* d_dst, uint64_t dst_capacity, uint32_t align,
+                                               const zxc_compress_opts_t* opts, void* d_work, uint64_t work_size,
+                                               zxc_dev_item_t* d_packed, int64_t* d_results, uint64_t* d_total, void* stream);
+
+/* The call above with a dictionary in device memory that the whole batch shares, as zxc_mi355x_compress_batch_dict_device: every
+ * header carries the dictionary flag and *d_id, and the archives go back through zxc_mi355x_decompress_batch_dict_device. The work
+ * size is at most the sibling's plus min(n_items x J, C) x (block_size + dict_size) + 320 (0 also for dict_size > 65535); a NULL
+ * dict, or one of size 0, is the call without one. Synchronous errors: the sibling's, with dict->size > 65535 ->
+ * ZXC_ERROR_DICT_TOO_LARGE and NULL d_content or d_id with size > 0 -> ZXC_ERROR_NULL_INPUT behind the opts->dict check and in
+ * front of the one of align. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_pack_dict_device_work_size(uint32_t n_items, uint64_t max_size,
+                                                                  const zxc_compress_opts_t* opts, uint32_t dict_size);
+ZXC_EXPORT int zxc_mi355x_compress_pack_dict_device(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_items,
+                                                    uint32_t n_items, uint64_t max_size, void* d_dst, uint64_t dst_capacity,
+                                                    uint32_t align, const zxc_compress_opts_t* opts, const zxc_dev_dict_t* dict,
+                                                    void* d_work, uint64_t work_size, zxc_dev_item_t* d_packed, int64_t* d_results,
+                                                    uint64_t* d_total, void* stream);
 
 /* ---- one archive from many pieces, device to device (zxc_amd/csrc/zxc_append_device.hip, rules in zxc_amd/csrc/zxc_append.h) ----
  * zxc_mi355x_compress_device wants the whole source in one device buffer, a work area of about twice the source and a destination

@@ -530,6 +530,59 @@ def compress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_size, 
         raise ZxcError(rc, "zxc_mi355x_compress_batch_dict_device")
 
 
+# ---- many buffers per call, the archives packed back to back (d_packed: the item table of decompress_batch_device)
+def _bind_compress_pack_device(L):
+    L.zxc_mi355x_compress_pack_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_pack_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
+    L.zxc_mi355x_compress_pack_dict_device_work_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_pack_dict_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
+    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_CompressOpts)]
+    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zxc_mi355x_compress_pack_device.restype = C.c_int
+    L.zxc_mi355x_compress_pack_device.argtypes = head + tail
+    L.zxc_mi355x_compress_pack_dict_device.restype = C.c_int
+    L.zxc_mi355x_compress_pack_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
+    return L
+
+
+def compress_pack_device_work_size(n_items, max_size, level=3, block_size=0, seekable=False, checksum=False, dict_size=0):
+    """zxc_mi355x_compress_pack_device_work_size(), or with dict_size the _dict call's: bytes of device scratch the call needs
+    (0 for refused arguments)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    L = _bind_compress_pack_device(lib())
+    if dict_size:
+        return int(L.zxc_mi355x_compress_pack_dict_device_work_size(n_items, max_size, C.byref(o), dict_size))
+    return int(L.zxc_mi355x_compress_pack_device_work_size(n_items, max_size, C.byref(o)))
+
+
+def compress_pack_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align, d_work, work_size, d_packed,
+                         d_results, d_total, level=3, block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_pack_device(): compress_batch_device with the archives laid back to back, each at a multiple of `align`.
+    Raw device pointers (ints); of d_items (n_items x ITEM_DTYPE) only src_off / src_size are read; d_packed (n_items x ITEM_DTYPE,
+    may be d_items) receives the item table of decompress_batch_device, d_results n_items x int64, d_total one uint64: the end of
+    the last archive, whatever dst_capacity was. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = _bind_compress_pack_device(lib()).zxc_mi355x_compress_pack_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
+        align, C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_packed or None), C.c_void_p(d_results or None),
+        C.c_void_p(d_total or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_pack_device")
+
+
+def compress_pack_dict_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align, dict_, d_work, work_size,
+                              d_packed, d_results, d_total, level=3, block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_pack_dict_device(): compress_pack_device with one dictionary in device memory for the whole batch
+    (dict_ as in compress_dict_device); the work size is compress_pack_device_work_size(..., dict_size=size)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    rc = _bind_compress_pack_device(lib()).zxc_mi355x_compress_pack_dict_device(
+        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
+        align, C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_packed or None),
+        C.c_void_p(d_results or None), C.c_void_p(d_total or None), C.c_void_p(stream or None))
+    if rc < 0:
+        raise ZxcError(rc, "zxc_mi355x_compress_pack_dict_device")
+
+
 # ---- one archive from many pieces: a session (zxc_dev_cappend_t is a host struct of 16 words, caller-owned)
 class _DevCappend(C.Structure):  # zxc_dev_cappend_t
     _fields_ = [("opaque", C.c_uint64 * 16)]

@@ -205,31 +205,8 @@ extern "C" __global__ void zxc_append_result_kernel(const zap_ctl_t* __restrict_
 
 // ---------------------------------------------------------------- appendv: a table of sources (zxc_appendv.h)
 // The scan of a call, three tile passes of 256 threads over tiles of 1024 entries, like the passes of zxc_device_util.h but over
-// 64-bit lengths that add up saturating (zav_sat_add), so that a table whose sum passes 2^64 is still seen as above `total`.
-
-// Exclusive saturating scan of one value per thread over the workgroup of 256: -> the sum of all lower threads' values; *all gets
-// the workgroup's sum. One barrier; called by all threads outside divergent control flow, once per kernel.
-__device__ __forceinline__ uint64_t zav_wg_scan(uint64_t mine, uint64_t* all) {
-    __shared__ uint64_t w_tot[4];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    uint64_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(incl, (unsigned)d);
-        if ((int)lane >= d) incl = zav_sat_add(o, incl);
-    }
-    uint64_t excl = __shfl_up(incl, 1u);
-    if (lane == 0) excl = 0;
-    if (lane == 63) w_tot[wave] = incl;
-    __syncthreads();
-    uint64_t run = 0, tot = 0;
-    for (uint32_t w = 0; w < 4u; w++) {
-        if (w < wave) run = zav_sat_add(run, w_tot[w]);
-        tot = zav_sat_add(tot, w_tot[w]);
-    }
-    *all = tot;
-    return zav_sat_add(run, excl);
-}
+// 64-bit lengths that add up saturating (zav_sat_add), so that a table whose sum passes 2^64 is still seen as above `total`. The
+// workgroup scan itself is zd_wg_scan64 of zxc_device_util.h (same adds), which the pack call's passes use as well.
 
 // The flags of the check ored over the workgroup (__syncthreads_or answers only whether any thread's value is non-zero). Two barriers.
 __device__ __forceinline__ uint32_t zav_wg_flags(uint32_t flags) {
@@ -253,7 +230,7 @@ zxc_appendv_reduce_kernel(const zxc_dev_iov_t* __restrict__ iov, uint32_t n_iov,
         sum = zav_sat_add(sum, e.len);
     }
     uint64_t all;
-    (void)zav_wg_scan(sum, &all);
+    (void)zd_wg_scan64(sum, &all);
     flags = zav_wg_flags(flags);
     if (threadIdx.x == 0) { tile_sum[blockIdx.x] = all; tile_flags[blockIdx.x] = flags; }
 }
@@ -269,7 +246,7 @@ zxc_appendv_scan_kernel(uint64_t* __restrict__ tile_sum, const uint32_t* __restr
     uint32_t flags = 0;
     for (uint32_t i = lo; i < hi; i++) { mine = zav_sat_add(mine, tile_sum[i]); flags |= tile_flags[i]; }
     uint64_t all;
-    uint64_t run = zav_wg_scan(mine, &all);
+    uint64_t run = zd_wg_scan64(mine, &all);
     flags = zav_wg_flags(flags);
     for (uint32_t i = lo; i < hi; i++) {
         const uint64_t s = tile_sum[i];
@@ -296,7 +273,7 @@ zxc_appendv_starts_kernel(const zxc_dev_iov_t* __restrict__ iov, uint32_t n_iov,
         sum = zav_sat_add(sum, len[j]);
     }
     uint64_t all;
-    uint64_t run = zav_sat_add(tile_off[blockIdx.x], zav_wg_scan(sum, &all));
+    uint64_t run = zav_sat_add(tile_off[blockIdx.x], zd_wg_scan64(sum, &all));
 #pragma unroll
     for (uint32_t j = 0; j < ZD_PER_THREAD; j++) {
         if (r0 + j >= n_iov) break;

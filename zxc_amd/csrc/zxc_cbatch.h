@@ -109,19 +109,29 @@ ZC_FN uint32_t zcb_chunk_len(const zcb_shape_t* s, uint32_t c0) { return s->n_jo
  * item is written. Else offsets[b] = block b's offset in the archive, and the file header (with a dictionary: its flag and id), the
  * EOF block, with `seekable` and nb > 0 the SEK header and entries, and the footer are written at dst + dst_off: the footer's
  * global hash is rotl(h, 1) ^ t_b folded from 0 over the trailers in order, which is what zxc_frame_tiles_kernel computes in
- * parallel as XOR_b rotl(t_b, (nb - 1 - b) mod 32). rec->result becomes the archive size; the blocks themselves are the gather's. */
+ * parallel as XOR_b rotl(t_b, (nb - 1 - b) mod 32). rec->result becomes the archive size; the blocks themselves are the gather's.
+ * zcb_archive_size is its first half, the size check and the archive size, and writes nothing (zxc_cpack.h sizes every item with
+ * it before it knows where one goes): -> the size of the archive around nb blocks of these sizes, or 0 when one of them is outside
+ * the legal range; *eof_at = where its EOF block lies, *seek_bytes = its seek table's bytes (0: none). */
+ZC_FN uint64_t zcb_archive_size(uint32_t nb, const uint32_t* sizes, uint32_t block_size, int checksum, int seekable, uint64_t* eof_at,
+                                uint64_t* seek_bytes) {
+    const uint32_t min_size = ZC_BLK_HDR + (checksum ? 4u : 0u), max_size = block_size + 64u;
+    uint64_t sum = 0;
+    for (uint32_t b = 0; b < nb; b++) {
+        if (sizes[b] < min_size || sizes[b] > max_size) return 0;
+        sum += sizes[b];
+    }
+    *eof_at = ZC_FILE_HDR + sum;
+    *seek_bytes = (seekable && nb) ? ZC_BLK_HDR + 4ull * nb : 0ull;
+    return *eof_at + ZC_BLK_HDR + *seek_bytes + ZC_FOOTER;
+}
 ZC_FN void zcb_finish_item(zcb_rec_t* rec, const uint32_t* sizes, uint64_t* offsets, const uint8_t* slots, uint32_t slot_stride,
                            uint8_t* dst, uint32_t block_size, int checksum, int seekable, int has_dict, uint32_t dict_id) {
     if (rec->result < 0) return;
-    const uint32_t nb = rec->nb, min_size = ZC_BLK_HDR + (checksum ? 4u : 0u), max_size = block_size + 64u;
-    uint64_t sum = 0;
-    for (uint32_t b = 0; b < nb; b++) {
-        if (sizes[b] < min_size || sizes[b] > max_size) { rec->result = ZXC_ERROR_CORRUPT_DATA; return; }
-        sum += sizes[b];
-    }
-    const uint64_t eof_at = ZC_FILE_HDR + sum;
-    const uint64_t seek_bytes = (seekable && nb) ? ZC_BLK_HDR + 4ull * nb : 0ull;
-    const uint64_t size = eof_at + ZC_BLK_HDR + seek_bytes + ZC_FOOTER;
+    const uint32_t nb = rec->nb;
+    uint64_t eof_at = 0, seek_bytes = 0;
+    const uint64_t size = zcb_archive_size(nb, sizes, block_size, checksum, seekable, &eof_at, &seek_bytes);
+    if (size == 0) { rec->result = ZXC_ERROR_CORRUPT_DATA; return; }
     if (size > rec->cap) { rec->result = ZXC_ERROR_DST_TOO_SMALL; return; }
     uint8_t* arc = dst + rec->dst_off;
     uint8_t* seek = arc + eof_at + 2u * ZC_BLK_HDR;

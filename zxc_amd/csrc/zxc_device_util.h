@@ -1,6 +1,6 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
-// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_append_device.hip, zxc_take_device.hip, zxc_dict_device.hip): the three tile
-// passes every container stage is made of, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
+// zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_cpack_device.hip, zxc_append_device.hip, zxc_take_device.hip,
+// zxc_dict_device.hip): the three tile passes every container stage is made of, the 64-bit workgroup scan, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
 // of an entry point: the launch check, the work area's base, the dictionary argument and the one reader of zxc_compress_opts_t.
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //
@@ -96,6 +96,37 @@ __device__ __forceinline__ zd_totals zd_scan_tiles(uint32_t n_tiles, uint64_t ba
         run += s;
     }
     return r;
+}
+
+// Exclusive scan of one 64-bit value per thread over the workgroup of 256, adding up saturating at 2^64 - 1 (min(a + b, 2^64 - 1)
+// is associative, so the grouping does not show): -> the sum of all lower threads' values; *all gets the workgroup's sum. The
+// scan of appendv's table of lengths (zxc_append_device.hip), which may say anything, and of the pack call's extents
+// (zxc_cpack_device.hip), which never saturate. zd_sat_add is zav_sat_add of zxc_appendv.h, which the plain C rules keep. One
+// barrier; called by all threads outside divergent control flow, once per kernel.
+__device__ __forceinline__ uint64_t zd_sat_add(uint64_t a, uint64_t b) {
+    const uint64_t s = a + b;
+    return s < a ? ~0ull : s;
+}
+__device__ __forceinline__ uint64_t zd_wg_scan64(uint64_t mine, uint64_t* all) {
+    __shared__ uint64_t w_tot[4];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(incl, (unsigned)d);
+        if ((int)lane >= d) incl = zd_sat_add(o, incl);
+    }
+    uint64_t excl = __shfl_up(incl, 1u);
+    if (lane == 0) excl = 0;
+    if (lane == 63) w_tot[wave] = incl;
+    __syncthreads();
+    uint64_t run = 0, tot = 0;
+    for (uint32_t w = 0; w < 4u; w++) {
+        if (w < wave) run = zd_sat_add(run, w_tot[w]);
+        tot = zd_sat_add(tot, w_tot[w]);
+    }
+    *all = tot;
+    return zd_sat_add(run, excl);
 }
 
 // ---------------------------------------------------------------- staged slot -> destination

@@ -91,6 +91,35 @@ __device__ __forceinline__ T* uni_ptr(T* p) {
     return (T*)(((uint64_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a));
 }
 
+// A lane's unsigned 32-bit byte offset from a wave-uniform pointer, kept a 32-bit value up to the load: the global
+// instructions take "scalar base + 32-bit lane offset" as it is, but the compiler widens an offset it can see through (a
+// select of masked values) to 64 bits first and then forms the address per load with a v_mov of the zero high half and a
+// 64-bit vector add. No instruction; the CPU emulator build sees the plain value.
+__device__ __forceinline__ uint32_t lane_off(uint32_t o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(o));
+#endif
+    return o;
+}
+// The first t (0..16) bytes of group go / 16 of a run whose end on its grid is e, with e == 0 for the lanes that take no
+// part (so that "is this lane active here" and "how many bytes" are one compare and one saturating subtract of ONE register
+// instead of a lane mask carried beside the length).
+__device__ __forceinline__ uint32_t group_take(uint32_t e, uint32_t go) {
+    const uint32_t r = e > go ? e - go : 0u;
+    return r < 16u ? r : 16u;
+}
+
+// The lanes with a > b, by ONE compare that writes the lane mask. (__ballot of a bool that was computed in an earlier basic
+// block goes mask -> v_cndmask 0 / 1 -> v_cmp -> mask; with group_take's encoding every "any lane left?" of the group loops
+// is a compare of one register.)
+__device__ __forceinline__ uint64_t lanes_gt(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_uicmp(a, b, 34);  // (llvm ICMP_UGT)
+#else
+    return __ballot(a > b);
+#endif
+}
+
 // LDS traffic between lanes of the one wave. One wave's DS instructions execute in program order, so a read issued
 // after another lane's write sees it: only the COMPILER must keep the order (wavefront-scope fence: no instruction,
 // where a workgroup-scope one drains the LDS queue with s_waitcnt lgkmcnt(0), ~10 times per batch).
@@ -401,7 +430,7 @@ __device__ __forceinline__ void load_seq_raw(const LzStreams& S, uint32_t s, uin
     if (GHI) raw_t = ld32(S.tok + 4ull * c);
     else {
         raw_t = ld8(S.tok + c);
-        raw_o = S.off8 ? ld8(S.offs + c) : ld16(S.offs + 2ull * c);
+        raw_o = S.off8 ? ld8(S.offs + lane_off(c)) : ld16(S.offs + lane_off(2u * c));  // (the offsets lie inside the block: 2 c < 2^32)
     }
 }
 

@@ -76,8 +76,10 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
     const uint8_t* const lit_al = S.lit - 8 - lit_ph;  // (at least 20 header bytes sit in front of the literals)
     uint32_t raw_t, raw_o;
     load_seq_raw<GHI>(S, (uint32_t)lane, raw_t, raw_o);
-    const int32_t ext_last = (int32_t)S.ext_size - 1;
-    uint32_t xw = ld8(S.ext + (lane < ext_last ? lane : ext_last));
+    // extras byte cur + lane, clamped to the stream's last byte (an empty stream: the byte in front of it), as an unsigned
+    // offset from ext - 1
+    const uint8_t* const extm1 = S.ext - 1;
+    uint32_t xw = ld8(extm1 + lane_off((uint32_t)lane + 1u < S.ext_size ? (uint32_t)lane + 1u : S.ext_size));
     __builtin_amdgcn_s_waitcnt(0);
 
     while (seq_base < n_total) {
@@ -135,7 +137,8 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 ml += escM ? bM : 0u;
             } else {
                 if (lane == 0) ZXC_PATH(L_VARINT_GENERAL);
-                kbad = parse_varints(S.ext, S.ext_size, cur, nv, L, lane);
+                // (the same in every lane; said so, it and the cursor and the dead flag behind it are scalars, not lane registers)
+                kbad = uni(parse_varints(S.ext, S.ext_size, cur, nv, L, lane));
                 if (valid && escL && r < kbad) ll += L.vval[r];
                 if (valid && escM && r2 < kbad) ml += L.vval[r2];
             }
@@ -222,8 +225,8 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             }
             else cur = uni(L.vpos[used]);
         }
-        const int32_t xi0 = (int32_t)(cur + (uint32_t)lane);
-        const uint32_t nxw = ld8(S.ext + (xi0 < ext_last ? xi0 : ext_last));
+        const uint32_t xi1 = cur + 1u + (uint32_t)lane;  // (cur ends at most one varint window behind a block's section: no wrap)
+        const uint32_t nxw = ld8(extm1 + lane_off(xi1 < S.ext_size ? xi1 : S.ext_size));
 
         PHM(4);
         if (k == 0u) {
@@ -265,20 +268,24 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             // lst - (est & 3) + 16 g (loads take any alignment: the bytes arrive on the destination's dword grid).
             const uint32_t la = est & 3u;
             const uint32_t le = la + ll;  // end of the run on its grid
-            const bool lshort = mine && ll != 0u && ll <= LIT_MED;
+            const bool lshort = mine & (ll - 1u < LIT_MED);  // (0 < ll <= LIT_MED)
+            // Lane predicates are straight-line code: & and | on values in registers, one unsigned compare for a range. And the
+            // literal passes carry no mask beside the run: les is its end for the lanes of the group path and 0 for everybody
+            // else (le >= 1 there), so every later "lshort && le > x" is ONE compare of it.
+            const uint32_t les = lshort ? le : 0u;
             const uint32_t lo = lst - la + 4u;  // offset from litm4
             // Group 0 (the one most lanes need) is fetched dword-ALIGNED: an unaligned 16-byte gather costs the CU's address
             // pipeline 4 clocks per active lane, an aligned one 1.3 (profiles/r3_vmem_test.log). Four aligned dwords and a fifth
             // for the lanes whose last bytes sit there; v_alignbyte moves them onto the destination grid.
             const uint32_t lob = lo + 4u + lit_ph;           // offset from lit_al = (S.lit - 8) rounded down to a dword
             const uint32_t ldl = lob & 3u;
-            const v4u lv0 = ld128(lit_al + (lshort ? (lob & ~3u) : 8u));
-            const bool lv5 = lshort && ldl != 0u && le > 12u;  // the run's last bytes of group 0 sit in a fifth aligned dword
-            const uint32_t lv0e = ld32(lit_al + (lv5 ? (lob & ~3u) + 16u : 8u));
-            const v4u lv1 = ld128(litm4 + (lshort && le > 16u ? lo + 16u : 4u - lit_ph));
+            const v4u lv0 = ld128(lit_al + lane_off(lshort ? (lob & ~3u) : 8u));
+            const bool lv5 = (ldl != 0u) & (les > 12u);  // the run's last bytes of group 0 sit in a fifth aligned dword
+            const uint32_t lv0e = ld32(lit_al + lane_off(lv5 ? (lob & ~3u) + 16u : 8u));
+            const v4u lv1 = ld128(litm4 + lane_off(les > 16u ? lo + 16u : 4u - lit_ph));
             if (lshort) ZXC_PATH(L_LIT_GROUP);
             if (lv5) ZXC_PATH(L_LIT_5TH);
-            const v4u lv2 = ld128(litm4 + (lshort && le > 32u ? lo + 32u : 4u - lit_ph));
+            const v4u lv2 = ld128(litm4 + lane_off(les > 32u ? lo + 32u : 4u - lit_ph));
 
             // Match: group g = 16 bytes at (M & ~3) + 16 g, from source position qsrc - (M & 3) + 16 g.
             const uint32_t ma = M & 3u;
@@ -286,15 +293,20 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint32_t mg = M - ma;
             const uint32_t qa = M - off;  // (my lanes: off <= M, checked above)
             const bool overlap = off < ml;
-            bool pending = mine && ml != 0u;
+            bool pending = mine & (ml != 0u);
             // Far: the source starts behind the ring. It ends at least 350 bytes before the batch (ring_lo <= p - 497,
             // ml <= MATCH_MED), all of it was flushed by earlier batches (a wave's stores and loads reach L2 in program
             // order), it cannot overlap its destination and depends on nothing in this batch: every group comes from the
             // block's own output in memory, the first two are requested here.
             // (round 5: output leaves the ring in whole KiB — see the flush at the batch's end — so the source must also END inside what
             //  has been flushed; a source that straddles the flushed mark, ~3 % of them, takes the near path's whole-wave copy)
-            const bool far_ok = far_en && pending && qa < ring_lo && ml <= MATCH_MED && qa >= 4u && qa + ml <= O.flushed &&
-                                (qa - ma) + ((me + 15u) & ~15u) + 4u <= O.out_pad;
+            // (no && here: every clause is arithmetic on registers, and a short-circuit chain costs this loop two nested exec
+            // regions. 4 <= qa < ring_lo is one unsigned compare against ring_lo - 4, clamped at 0 where the ring still holds all.)
+            const uint32_t sgf = qa - ma;
+            const uint32_t far_hi = ring_lo > 4u ? ring_lo - 4u : 0u;
+            const bool far_ok = far_en & pending & (qa - 4u < far_hi) & (ml <= MATCH_MED) & (qa + ml <= O.flushed) &
+                                (sgf + ((me + 15u) & ~15u) + 4u <= O.out_pad);
+            const uint32_t mef = far_ok ? me : 0u;  // like les: the match's end on its grid on the far lanes (me >= 1), 0 elsewhere
             // (The NO_* markers restate far_ok's clauses: naming the clauses once changes the kernel's register allocation. Only
             // L_FAR_GROUP observes far_ok itself, so every case that asks for a NO_* marker also pins L_FAR_GROUP's exact count.)
             if (pending && qa < ring_lo) {  // a source behind the ring: the group path, or which guard sends it to the near paths
@@ -305,16 +317,16 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 if (qa + ml > O.flushed) ZXC_PATH(L_FAR_NO_FLUSHED);
                 if ((qa - ma) + ((me + 15u) & ~15u) + 4u > O.out_pad) ZXC_PATH(L_FAR_NO_EDGE);
             }
-            const uint32_t sgf = qa - ma;
             const uint32_t fdl = sgf & 3u;  // (the block's slot is 16-byte aligned: the source's phase against the destination grid)
             v4u fr0 = {0, 0, 0, 0}, fr1 = {0, 0, 0, 0};
             uint32_t fr0e = 0;
             if (far_en) {  // wave-uniform. Group 0 dword-aligned like the literals'; group 1 is wanted by few lanes.
-                fr0 = ld128(dst + (far_ok ? (sgf & ~3u) : 0u));
-                const bool fr5 = far_ok && fdl != 0u && me > 12u;
-                fr0e = ld32(dst + (fr5 ? (sgf & ~3u) + 16u : 0u));
+                // (uniform base + 32-bit lane offset, like the literal loads)
+                fr0 = ld128(dst + lane_off(far_ok ? (sgf & ~3u) : 0u));
+                const bool fr5 = (fdl != 0u) & (mef > 12u);
+                fr0e = ld32(dst + lane_off(fr5 ? (sgf & ~3u) + 16u : 0u));
                 if (fr5) ZXC_PATH(L_FAR_5TH);
-                fr1 = ld128(dst + (far_ok && me > 16u ? sgf + 16u : 0u));
+                fr1 = ld128(dst + lane_off(mef > 16u ? sgf + 16u : 0u));
             }
 
             // ---- dependencies. Sequence i may only copy once every earlier match of this batch that overlaps its
@@ -322,7 +334,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             const uint32_t qb = (qa + ml < M) ? qa + ml : M;
             uint64_t need = 0;
             uint32_t qsrc = qa;
-            const bool inb = pending && !far_ok && qb > p;  // the source reaches into this batch
+            const bool inb = pending & !far_ok & (qb > p);  // the source reaches into this batch
             if (__ballot(inb)) {
                 // positions relative to the batch: 12 bits each (a tile spans at most TILE_MAX < 4096 bytes)
                 const uint32_t key = mine ? ((E - p) | ((M - p) << 16)) : 0xFFFFFFFFu;
@@ -338,18 +350,18 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                                k2 = __shfl(key, (int)((ja + 2u) & 63u));
                 const uint32_t xb = qb - p;
                 const bool o0 = (k0 >> 16) < xb;
-                const bool o1 = o0 && ja + 1u < 64u && (k1 >> 16) < xb;
-                const bool o2 = o1 && ja + 2u < 64u && (k2 >> 16) < xb;
+                const bool o1 = o0 & (ja + 1u < 64u) & ((k1 >> 16) < xb);
+                const bool o2 = o1 & (ja + 2u < 64u) & ((k2 >> 16) < xb);
                 uint32_t jb = ja + (o0 ? 1u : 0u) + (o1 ? 1u : 0u);
                 if (o2) jb = (uint32_t)lane;  // a source over more than two earlier matches: wait for everything in front
                 if (inb && o2) ZXC_PATH(L_WAIT_ALL);
-                if (inb && jb > ja) need = ((jb >= 64u) ? ~0ull : ((1ull << jb) - 1ull)) & ~((1ull << ja) - 1ull);
+                need = (inb & (jb > ja)) ? (((jb >= 64u) ? ~0ull : ((1ull << jb) - 1ull)) & ~((1ull << ja) - 1ull)) : 0ull;
                 // Redirect: when my whole source sits inside ONE earlier match j of this batch (within its first period) and
                 // j has no pending dependency itself, my bytes equal j's source bytes at the same displacement: read those
                 // instead and drop the dependency — unless they are behind the ring (not requested: wait for j instead).
                 const uint32_t jM = p + (k0 >> 16), jE = p + (k0 & 0xFFFFu);
                 const uint32_t jo = __shfl(off, (int)(ja & 63u));
-                const bool simple = need != 0ull && jb == ja + 1u && off >= ml && qa >= jM && qb <= jE && qb - jM <= jo;
+                const bool simple = (need != 0ull) & (jb == ja + 1u) & (off >= ml) & (qa >= jM) & (qb <= jE) & (qb - jM <= jo);
 #pragma unroll
                 for (int pass = 0; pass < REDIRECT_PASSES; pass++) {
                     const uint64_t rm = __ballot(need == 0ull);
@@ -357,20 +369,20 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     const uint32_t nq = jq + (qa - jM);
                     // (restates the condition below, for the same reason: the case pins L_REDIRECT0's exact count beside it)
                     if (simple && need != 0ull && ((rm >> (ja & 63u)) & 1ull) && !(nq >= ring_lo && (int32_t)nq >= 0)) ZXC_PATH(L_REDIRECT_NO_RING);
-                    if (simple && need != 0ull && ((rm >> (ja & 63u)) & 1ull) && nq >= ring_lo && (int32_t)nq >= 0) {
-                        ZXC_PATH(pass == 0 ? L_REDIRECT0 : L_REDIRECT1);
-                        qsrc = nq;
-                        need = 0;
-                    }
+                    const bool redir = simple & (need != 0ull) & (((rm >> (ja & 63u)) & 1ull) != 0ull) & (nq >= ring_lo) & ((int32_t)nq >= 0);
+                    if (redir) ZXC_PATH(pass == 0 ? L_REDIRECT0 : L_REDIRECT1);
+                    qsrc = redir ? nq : qsrc;
+                    need = redir ? 0ull : need;
                 }
             }
             PHM(7);
             const uint32_t sg = qsrc - ma;  // the match's source on the destination's dword grid
-            const bool nearl = pending && !far_ok;
-            const bool farsrc = qsrc < ring_lo;  // (near lanes: far but too long / too close to the block's edges for the group path)
-            const bool stepable = nearl && !farsrc && ml <= MATCH_MED && (!overlap || off >= 16u);
-            const bool bytewise = nearl && !farsrc && overlap && off < 16u && ml <= BYTEWISE_MAX;
-            const bool is_long = nearl && !stepable && !bytewise;
+            const bool nearl = pending & !far_ok;
+            const bool inring = nearl & (qsrc >= ring_lo);  // (the others: far but too long / too close to the block's edges for the group path)
+            const bool shortp = overlap & (off < 16u);      // a period shorter than a group
+            const bool stepable = inring & (ml <= MATCH_MED) & !shortp;
+            const bool bytewise = inring & shortp & (ml <= BYTEWISE_MAX);
+            const bool is_long = nearl & !stepable & !bytewise;
             bool far_waited = false;
 
             PHM(8);
@@ -378,7 +390,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
             {
                 const uint32_t lg = est - la;
                 {
-                    const uint32_t t = lshort ? (le < 16u ? le : 16u) : 0u;
+                    const uint32_t t = group_take(les, 0u);
                     v4u d;
                     d.x = __builtin_amdgcn_alignbyte(lv0.y, lv0.x, ldl);
                     d.y = __builtin_amdgcn_alignbyte(lv0.z, lv0.y, ldl);
@@ -388,26 +400,18 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     d.x &= head_mask(la);
                     ring_or_group(L, lg, d);
                 }
-                if (__ballot(lshort && le > 16u)) {
-                    const uint32_t t = (lshort && le > 16u) ? (le - 16u < 16u ? le - 16u : 16u) : 0u;
-                    ring_or_group(L, lg + 16u, group_keep_first(L, lv1, t));
-                }
-                if (__ballot(lshort && le > 32u)) {
-                    const uint32_t t = (lshort && le > 32u) ? (le - 32u < 16u ? le - 32u : 16u) : 0u;
-                    ring_or_group(L, lg + 32u, group_keep_first(L, lv2, t));
-                }
+                if (lanes_gt(les, 16u)) ring_or_group(L, lg + 16u, group_keep_first(L, lv1, group_take(les, 16u)));
+                if (lanes_gt(les, 32u)) ring_or_group(L, lg + 32u, group_keep_first(L, lv2, group_take(les, 32u)));
 #pragma unroll 1
                 for (uint32_t go = 48u; go < LIT_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
-                    const bool actA = lshort && le > go, actB = lshort && le > go + 16u;
-                    if (__ballot(actA) == 0ull) break;
-                    const v4u lvA = ld128(litm4 + (actA ? lo + go : 4u - lit_ph));
-                    const v4u lvB = ld128(litm4 + (actB ? lo + go + 16u : 4u - lit_ph));
-                    const uint32_t tA = actA ? (le - go < 16u ? le - go : 16u) : 0u;
-                    const uint32_t tB = actB ? (le - go - 16u < 16u ? le - go - 16u : 16u) : 0u;
-                    ring_or_group(L, lg + go, group_keep_first(L, lvA, tA));
-                    ring_or_group(L, lg + go + 16u, group_keep_first(L, lvB, tB));
+                    const bool actA = les > go, actB = les > go + 16u;
+                    if (lanes_gt(les, go) == 0ull) break;
+                    const v4u lvA = ld128(litm4 + lane_off(actA ? lo + go : 4u - lit_ph));
+                    const v4u lvB = ld128(litm4 + lane_off(actB ? lo + go + 16u : 4u - lit_ph));
+                    ring_or_group(L, lg + go, group_keep_first(L, lvA, group_take(les, go)));
+                    ring_or_group(L, lg + go + 16u, group_keep_first(L, lvB, group_take(les, go + 16u)));
                 }
-                uint64_t lm = __ballot(mine && ll > LIT_MED);
+                uint64_t lm = __ballot(mine & (ll > LIT_MED));
                 while (lm) {
                     const int j = __ffsll((unsigned long long)lm) - 1;
                     lm &= lm - 1ull;
@@ -420,9 +424,9 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
 
             PHM(9);
             // ---- far matches: their own pass (nothing in this batch can be their source)
-            if (__ballot(far_ok)) {
+            if (lanes_gt(mef, 0u)) {
                 {
-                    const uint32_t t = far_ok ? (me < 16u ? me : 16u) : 0u;
+                    const uint32_t t = group_take(mef, 0u);
                     v4u d;
                     d.x = __builtin_amdgcn_alignbyte(fr0.y, fr0.x, fdl);
                     d.y = __builtin_amdgcn_alignbyte(fr0.z, fr0.y, fdl);
@@ -432,23 +436,18 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     d.x &= head_mask(ma);
                     ring_or_group(L, mg, d);
                 }
-                if (__ballot(far_ok && me > 16u)) {
-                    const uint32_t t = (far_ok && me > 16u) ? (me - 16u < 16u ? me - 16u : 16u) : 0u;
-                    ring_or_group(L, mg + 16u, group_keep_first(L, fr1, t));
-                }
+                if (lanes_gt(mef, 16u)) ring_or_group(L, mg + 16u, group_keep_first(L, fr1, group_take(mef, 16u)));
 #pragma unroll 1
                 for (uint32_t go = 32u; go < MATCH_MED + 4u; go += 32u) {  // two groups per step, both requested by every lane
-                    const bool actA = far_ok && me > go, actB = far_ok && me > go + 16u;
-                    if (__ballot(actA) == 0ull) break;
-                    const v4u fA = ld128(dst + (actA ? sgf + go : 0u));
-                    const v4u fB = ld128(dst + (actB ? sgf + go + 16u : 0u));
-                    const uint32_t tA = actA ? (me - go < 16u ? me - go : 16u) : 0u;
-                    const uint32_t tB = actB ? (me - go - 16u < 16u ? me - go - 16u : 16u) : 0u;
-                    ring_or_group(L, mg + go, group_keep_first(L, fA, tA));
-                    ring_or_group(L, mg + go + 16u, group_keep_first(L, fB, tB));
+                    const bool actA = mef > go, actB = mef > go + 16u;
+                    if (lanes_gt(mef, go) == 0ull) break;
+                    const v4u fA = ld128(dst + lane_off(actA ? sgf + go : 0u));
+                    const v4u fB = ld128(dst + lane_off(actB ? sgf + go + 16u : 0u));
+                    ring_or_group(L, mg + go, group_keep_first(L, fA, group_take(mef, go)));
+                    ring_or_group(L, mg + go + 16u, group_keep_first(L, fB, group_take(mef, go + 16u)));
                 }
-                if (far_ok) pending = false;
             }
+            pending = nearl;  // (the far lanes are done)
             wave_lds_fence();
 
             PHM(10);
@@ -457,31 +456,32 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                 const uint64_t dm = __ballot(!pending);
                 if (dm == ~0ull) break;
                 if (round > 70u) return ZXC_DEV_E_INTERNAL;  // cannot happen: the lowest pending lane is always ready
-                const bool can = pending && ((dm & need) == need);
-                const bool sa = can && stepable;
+                const bool can = pending & ((dm & need) == need);
+                const bool sa = can & stepable;
                 if (sa) ZXC_PATH(L_STEPABLE);
-                if (__ballot(sa)) {
+                const uint32_t mes = sa ? me : 0u;  // (like les and mef: the lanes that step this round)
+                if (lanes_gt(mes, 0u)) {
 #pragma unroll 1
                     for (uint32_t go = 0; go < MATCH_MED + 4u; go += 16u) {
-                        const bool act = sa && me > go;
-                        if (__ballot(act) == 0ull) break;
+                        const bool act = mes > go;
+                        if (lanes_gt(mes, go) == 0ull) break;
                         v4u d = ring_rd128(L, act ? sg + go : 0u);
-                        const uint32_t t = act ? (me - go < 16u ? me - go : 16u) : 0u;
-                        d = group_keep_first(L, d, t);
+                        d = group_keep_first(L, d, group_take(mes, go));
                         if (go == 0u) d.x &= head_mask(ma);
                         ring_or_group(L, mg + go, d);
                     }
                 }
                 PHM(11);
                 // short period (off < 16, off < ml <= 32): byte loop over the period [M-off, M)
-                const bool sb = can && bytewise;
+                const bool sb = can & bytewise;
                 if (sb) ZXC_PATH(L_BYTEWISE);
-                if (__ballot(sb)) {
+                const uint32_t mlb = sb ? ml : 0u;
+                if (lanes_gt(mlb, 0u)) {
                     uint32_t r = 0;
 #pragma unroll 1
                     for (uint32_t t = 0; t < BYTEWISE_MAX; t++) {
-                        const bool act = sb && t < ml;
-                        if (__ballot(act) == 0ull) break;
+                        const bool act = t < mlb;  // (the byte stores stay masked: an idle lane has no harmless byte to store)
+                        if (lanes_gt(mlb, t) == 0ull) break;
                         if (act) {
                             ring_wr8(L, M + t, ring_rd8(L, qa + r));
                             r = (r + 1u == off) ? 0u : r + 1u;
@@ -489,7 +489,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     }
                 }
                 // long: the whole wave copies one match at a time
-                uint64_t lm = __ballot(can && is_long);
+                uint64_t lm = __ballot(can & is_long);
                 if (lm) wave_lds_fence();
                 while (lm) {
                     const int j = __ffsll((unsigned long long)lm) - 1;
@@ -501,7 +501,7 @@ __device__ __forceinline__ int run_sequences_lean(const LzStreams& S, uint8_t* _
                     if (lane == 0 && jM - joff < ring_lo) ZXC_PATH(L_LONG_FAR);
                     coop_match<false>(L, O, jM, jml, joff, ring_lo, false, lane);
                 }
-                if (can) pending = false;
+                pending = pending & !can;
                 wave_lds_fence();
                 PHM(12);
                 // few sequences left: finish them one by one, in stream order, with the whole wave (a byte per lane)

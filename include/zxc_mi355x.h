@@ -641,7 +641,7 @@ ZXC_EXPORT int zxc_mi355x_compress_begin_dict_device(zxc_dev_cappend_t* cs, void
  * total, as it cannot know.
  * Synchronous errors, before anything is enqueued and with the session as it was, in this order: NULL cs, NULL d_scratch, NULL
  * d_iov with n_iov > 0 -> ZXC_ERROR_NULL_INPUT; a session never begun or ended -> ZXC_ERROR_NULL_INPUT; a session begun with a
- * dictionary -> ZXC_ERROR_GPU_UNSUPPORTED; n_iov == 0 with total > 0 -> ZXC_ERROR_SRC_TOO_SMALL; bytes so far + total > max_total
+ * dictionary -> ZXC_ERROR_GPU_UNSUPPORTED (zxc_mi355x_compress_appendv_dict_device below serves it); n_iov == 0 with total > 0 -> ZXC_ERROR_SRC_TOO_SMALL; bytes so far + total > max_total
  * -> ZXC_ERROR_OVERFLOW; scratch_size too small -> ZXC_ERROR_MEMORY. n_iov == 0 with total == 0 is ZXC_OK and enqueues nothing.
  * A launch failure leaves the session spent, as in append. Asynchronous on `stream` and capturable like append: no host
  * synchronisation, no device allocation beyond the encoder's stream-ordered scratch at levels 6-7. */
@@ -653,6 +653,38 @@ ZXC_EXPORT uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_i
                                                                     const zxc_compress_opts_t* opts);
 ZXC_EXPORT int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov,
                                                   uint64_t total, void* d_scratch, uint64_t scratch_size, void* stream);
+
+/* The same call for a session begun with a dictionary (zxc_mi355x_compress_begin_dict_device): with X the concatenation of the
+ * entries in table order it is exactly zxc_mi355x_compress_append_device(cs, X, total, stream) on that session, so after end the
+ * archive and *d_result are byte for byte what zxc_mi355x_compress_dict_device writes for the concatenation of everything
+ * appended, with the same options, dictionary and capacity, however the bytes were cut into calls and entries. append and
+ * appendv_dict mix freely in one dictionary session, with a carry across every boundary.
+ * The table, its rules, the table errors with their precedence and the sticky status are those of
+ * zxc_mi355x_compress_appendv_device above, word for word: device data read on the stream; entries of length 0 legal anywhere,
+ * their base not looked at; any alignment; exactly [base, base + len) of each entry is read; after a table error no entry of that
+ * call is read and no block of it is encoded or gathered, and the host's byte count has moved on by total.
+ * Stream order: once per call the scan, then per chunk of at most max_piece bytes the loop of a dictionary session's append over
+ * at most C = min(J, zc_image_chunk(block_size, dict_size)) jobs: one launch gathers every job's [dict | block] image straight
+ * from the entries into the session's own image area (the carried block takes the waiting bytes of the carry area and then the
+ * head of X, which is copied nowhere else; one more workgroup of a chunk's first launch gathers the tail into the other carry
+ * area), then the encode launch over those images; then tiles, advance, scatter, gather once per chunk. No block is encoded where
+ * it lies: an image is a copy by construction.
+ * Scratch: as above, but it holds no images, since every block is an image in the session's work area: the control word, the
+ * entries' start offsets and the words of the scan, at most 8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + 4096 for dict_size in
+ * [1, 65535]. For dict_size == 0 the size function returns zxc_mi355x_compress_appendv_device_scratch_size's value; it returns 0
+ * for dict_size > 65535 and for options or a max_piece that begin would refuse. The call requires the size that belongs to the
+ * session's own dict_size. A session begun without a dictionary (NULL dict or size 0) is served exactly as
+ * zxc_mi355x_compress_appendv_device serves it: same launches, same bytes, same scratch need.
+ * Synchronous errors, before anything is enqueued and with the session as it was, in this order: NULL cs, NULL d_scratch, NULL
+ * d_iov with n_iov > 0 -> ZXC_ERROR_NULL_INPUT; a session never begun or ended -> ZXC_ERROR_NULL_INPUT; n_iov == 0 with total > 0
+ * -> ZXC_ERROR_SRC_TOO_SMALL; bytes so far + total > max_total (compared without overflow) -> ZXC_ERROR_OVERFLOW; scratch_size
+ * too small -> ZXC_ERROR_MEMORY. n_iov == 0 with total == 0 is ZXC_OK and enqueues nothing. A launch failure leaves the session
+ * spent, as in append. Asynchronous on `stream` and capturable like append: no host synchronisation, no device allocation beyond
+ * the encoder's stream-ordered scratch at levels 6-7. */
+ZXC_EXPORT uint64_t zxc_mi355x_compress_appendv_dict_device_scratch_size(uint32_t n_iov, uint64_t max_piece,
+                                                                         const zxc_compress_opts_t* opts, uint32_t dict_size);
+ZXC_EXPORT int zxc_mi355x_compress_appendv_dict_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov,
+                                                       uint64_t total, void* d_scratch, uint64_t scratch_size, void* stream);
 
 /* ---- one archive into many pieces, device to device (zxc_amd/csrc/zxc_take_device.hip, rules in zxc_amd/csrc/zxc_take.h) ----
  * zxc_mi355x_decompress_device wants one contiguous, 16-byte aligned destination of the whole decoded size: whoever wrote an

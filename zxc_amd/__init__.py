@@ -13,6 +13,7 @@ from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_siz
                   decompress_batch_device, decompress_batch_dict_device, compress_batch_device_work_size, compress_batch_device,
                   compress_batch_dict_device, compress_pack_device_work_size, compress_pack_device, compress_pack_dict_device,
                   compress_append_device_work_size, compress_begin_device, compress_appendv_device_scratch_size,
+                  compress_appendv_dict_device_scratch_size,
                   compress_append_dict_device_work_size, compress_begin_dict_device, CompressAppendSession, decompress_take_device_work_size, decompress_begin_device,
                   decompress_begin_dict_device, decompress_takev_device_scratch_size, DecompressTakeSession, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, ITEM_DTYPE, IOV_DTYPE,
                   error_name)

@@ -608,6 +608,11 @@ def _bind_compress_append_device(L):
     L.zxc_mi355x_compress_appendv_device.restype = C.c_int
     L.zxc_mi355x_compress_appendv_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
                                                      C.c_void_p]
+    L.zxc_mi355x_compress_appendv_dict_device_scratch_size.restype = C.c_uint64
+    L.zxc_mi355x_compress_appendv_dict_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
+    L.zxc_mi355x_compress_appendv_dict_device.restype = C.c_int
+    L.zxc_mi355x_compress_appendv_dict_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                          C.c_void_p]
     return L
 
 
@@ -624,9 +629,18 @@ def compress_appendv_device_scratch_size(n_iov, max_piece, level=3, block_size=0
     return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_device_scratch_size(n_iov, max_piece, C.byref(o)))
 
 
+def compress_appendv_dict_device_scratch_size(n_iov, max_piece, dict_size, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_appendv_dict_device_scratch_size(): bytes of device scratch one appendv_dict of n_iov entries needs in a
+    session of that max_piece with a dictionary of dict_size bytes (0 for refused arguments; dict_size 0 gives
+    compress_appendv_device_scratch_size)."""
+    o = _compress_device_opts(level, block_size, seekable, checksum)
+    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_dict_device_scratch_size(n_iov, max_piece, C.byref(o),
+                                                                                                        dict_size))
+
+
 class CompressAppendSession:
     """A session of zxc_mi355x_compress_begin_device(): .append(d_src, n) and .appendv(d_iov, n_iov, total, d_scratch,
-    scratch_size) any number of times, then .end(d_result) once. Raw device pointers (ints), asynchronous on `stream`; the calls of
+    scratch_size) (with a dictionary: .appendv_dict) any number of times, then .end(d_result) once. Raw device pointers (ints), asynchronous on `stream`; the calls of
     one session must be in stream order with each other. The archive size or a negative zxc_error_t lands in the int64 at d_result;
     a synchronous failure raises ZxcError."""
 
@@ -647,6 +661,15 @@ class CompressAppendSession:
             C.c_void_p(stream or None))
         if rc < 0:
             raise ZxcError(rc, "zxc_mi355x_compress_appendv_device")
+
+    def appendv_dict(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
+        """zxc_mi355x_compress_appendv_dict_device(): appendv for a session begun with a dictionary (one begun without is served as
+        appendv serves it); the scratch size is compress_appendv_dict_device_scratch_size(n_iov, max_piece, dict_size, ...)."""
+        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_dict_device(
+            C.byref(self._cs), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
+            C.c_void_p(stream or None))
+        if rc < 0:
+            raise ZxcError(rc, "zxc_mi355x_compress_appendv_dict_device")
 
     def end(self, d_result, stream=0):
         rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_end_device(C.byref(self._cs), C.c_void_p(d_result or None),

@@ -1,5 +1,5 @@
-// zxc_append_device.hip — zxc_mi355x_compress_begin_device / _begin_dict_device / _append_device / _appendv_device / _end_device:
-// one v8 archive in device memory from a source that arrives in pieces, each in device memory. The device counterpart of
+// zxc_append_device.hip — zxc_mi355x_compress_begin_device / _begin_dict_device / _append_device / _appendv_device /
+// _appendv_dict_device / _end_device: one v8 archive in device memory from a source that arrives in pieces, each in device memory. The device counterpart of
 // zxc_cstream_* (zxc_stream_host.c).
 //
 // zxc_mi355x_compress_device (zxc_frame_device.hip) wants the whole source in one buffer and a slot per block of it. Here a session
@@ -10,7 +10,7 @@
 //
 // One pipeline. A piece is at most max_piece bytes of one call; a longer call is a loop of pieces (ap_pieces). A piece is a front
 // end, which fills the job table and launches the encoder over it, and one back half (ap_back); a piece that completes no block
-// ends behind its prep. The three front ends:
+// ends behind its prep. The four front ends:
 //
 //   plain    (append; any session's piece that completes no block)
 //            prep     zxc_append_prep_kernel: head of the source -> carry area (completes the waiting block), last whole block ->
@@ -33,6 +33,13 @@
 //                     areas, a whole block left in place (inside one entry, over-read included) or gathered into its image in the
 //                     scratch; nothing is read after a table error
 //            encode   as plain's (the two share the launch, ap_encode)
+//   appendv images  (a chunk of zxc_mi355x_compress_appendv_dict_device in a session with a dictionary that completes a block)
+//            scan     as appendv's, into a scratch that holds no images; then per chunk the loop of `images` over at most C jobs:
+//            images   zxc_appendv_images_kernel, one workgroup per job: [dict | the job's bytes] into the session's image area,
+//                     the bytes gathered straight from the table's entries (the carried block: the carry area, then the head of
+//                     the concatenation); in the first launch one more workgroup gathers the tail into the other carry area;
+//                     nothing is read after a table error, every job is then unused
+//            encode   as images'
 //
 // and the back half, once over the whole piece:
 //   tiles    zxc_frame_tiles_kernel: per tile the sum of the sizes, the size check, the piece's part of the global hash
@@ -291,6 +298,17 @@ zxc_appendv_prep_kernel(const zxc_dev_iov_t* __restrict__ iov, const uint64_t* _
     zav_prep(iov, starts, n_iov, vctl->status, &c, blockIdx.x, threadIdx.x, blockDim.x, carry, next, images, image, jobs);
 }
 
+// The same chunk in a session with a dictionary, for the jobs [j0, j0 + n) of it: workgroup w < n gathers image w of the session's
+// image area, [dict | the job's bytes], from the entries (zav_prep_images); workgroup n, which only the first launch of a chunk
+// has, gathers the tail. The grid is n + (j0 == 0).
+extern "C" __global__ void __launch_bounds__(ZAP_IMAGE_THREADS)
+zxc_appendv_images_kernel(const zxc_dev_iov_t* __restrict__ iov, const uint64_t* __restrict__ starts, uint32_t n_iov,
+                          const zav_ctl_t* __restrict__ vctl, zav_chunk_t c, uint32_t j0, uint32_t n, const uint8_t* __restrict__ dict,
+                          uint32_t dict_size, const uint8_t* __restrict__ carry, uint8_t* __restrict__ next, uint8_t* __restrict__ images,
+                          zxc_enc_job_t* __restrict__ jobs) {
+    zav_prep_images(iov, starts, n_iov, vctl->status, &c, j0, n, blockIdx.x, threadIdx.x, blockDim.x, dict, dict_size, carry, next, images, jobs);
+}
+
 // ---------------------------------------------------------------- host side
 namespace {
 
@@ -394,6 +412,21 @@ int ap_front_v(const Sess& s, const Work& w, const Vsrc& vs, const zap_piece_t& 
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     return p.nb ? ap_encode(s, w, p.nb, st) : ZXC_OK;
 }
+// The chunk loop of ap_front_images over the table's entries. p.nb > 0, s.dict_size != 0.
+int ap_front_v_images(const Sess& s, const Work& w, const Vsrc& vs, const zap_piece_t& p, hipStream_t st) {
+    zav_chunk_t c;
+    c.p = p; c.v = vs.v;
+    for (uint32_t j0 = 0; j0 < p.nb; j0 += w.chunk_jobs) {
+        const uint32_t n = p.nb - j0 < w.chunk_jobs ? p.nb - j0 : w.chunk_jobs;
+        hipLaunchKernelGGL(zxc_appendv_images_kernel, dim3(n + (j0 == 0 ? 1u : 0u)), dim3(ZAP_IMAGE_THREADS), 0, st, vs.iov, vs.starts, vs.n_iov,
+                           vs.vctl, c, j0, n, s.dict, s.dict_size, (const uint8_t*)w.carry[s.cur], w.carry[s.cur ^ 1u], w.images, w.jobs);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        const int rc = zxc_hip_encode_job_images(w.images, w.jobs + j0, n, s.block_size, (int)s.level, (int)s.checksum, s.dict_size,
+                                                 w.slots + (uint64_t)j0 * w.slot_stride, w.sizes + j0, (void*)st);
+        if (rc != ZXC_OK) return rc;
+    }
+    return ZXC_OK;
+}
 
 // The back half of a piece that completes nb > 0 blocks: tiles, advance, scatter, gather. vctl: the verdict of the appendv whose
 // chunk the piece is, or NULL.
@@ -414,10 +447,11 @@ int ap_back(const Sess& s, const Work& w, uint32_t nb, const zav_ctl_t* vctl, hi
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
-// One piece behind its plan. vs != NULL (a session without a dictionary): a chunk of an appendv, src is not looked at. Else src is
-// the piece's first byte, NULL for the plan of `end`. A piece that completes no block ends behind the plain prep or appendv's.
+// One piece behind its plan. vs != NULL: a chunk of an appendv, src is not looked at. Else src is the piece's first byte, NULL for
+// the plan of `end`. A piece that completes no block ends behind the plain prep or appendv's, with a dictionary or without.
 int ap_piece(const Sess& s, const Work& w, const uint8_t* src, const Vsrc* vs, const zap_piece_t& p, hipStream_t st) {
-    const int rc = vs ? ap_front_v(s, w, *vs, p, st) : s.dict_size && p.nb ? ap_front_images(s, w, src, p, st) : ap_front_plain(s, w, src, p, st);
+    const int rc = vs ? (s.dict_size && p.nb ? ap_front_v_images(s, w, *vs, p, st) : ap_front_v(s, w, *vs, p, st))
+                      : s.dict_size && p.nb ? ap_front_images(s, w, src, p, st) : ap_front_plain(s, w, src, p, st);
     if (rc != ZXC_OK || !p.nb) return rc;
     return ap_back(s, w, p.nb, vs ? vs->vctl : NULL, st);
 }
@@ -474,6 +508,45 @@ int ap_begin(zxc_dev_cappend_t* cs, void* d_dst, uint64_t dst_capacity, uint64_t
     return ZXC_OK;
 }
 
+// Both kinds of appendv behind their names. with_dict: the call that serves a session begun with a dictionary; the other refuses it.
+int ap_appendv(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total, void* d_scratch, uint64_t scratch_size,
+               void* stream, bool with_dict) {
+    if (!cs || !d_scratch || (n_iov > 0 && !d_iov)) return ZXC_ERROR_NULL_INPUT;
+    Sess s;
+    memcpy(&s, cs, sizeof s);
+    if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
+    if (s.dict_size && !with_dict) return ZXC_ERROR_GPU_UNSUPPORTED;
+    if (n_iov == 0 && total > 0) return ZXC_ERROR_SRC_TOO_SMALL;
+    if (total > s.max_total - s.total) return ZXC_ERROR_OVERFLOW;
+    zap_shape_images_t sh;
+    zav_shape_t vsh;
+    if (ap_shape(s, &sh) != 0 || zav_shape_dict(n_iov, s.max_piece, s.block_size, s.dict_size, &vsh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    if (scratch_size < vsh.bytes) return ZXC_ERROR_MEMORY;
+    if (n_iov == 0) return ZXC_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* sb = zd_work_base(d_scratch);
+    zav_ctl_t* vctl = (zav_ctl_t*)sb;
+    uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
+    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
+    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
+    // The scan, once per call: the chunks read starts and the verdict in stream order.
+    int rc = ZXC_OK;
+    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
+    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
+                           n_iov, vctl, (zap_ctl_t*)s.base);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    if (rc == ZXC_OK) {
+        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
+        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    // The chunks, cut like the pieces of an append of `total` bytes.
+    Vsrc vs = {d_iov, n_iov, vsh.image, starts, vctl, sb + vsh.o_images, 0u};
+    return ap_pieces(cs, s, sh, NULL, &vs, total, rc, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -514,49 +587,26 @@ int zxc_mi355x_compress_append_device(zxc_dev_cappend_t* cs, const void* d_src, 
     return ap_pieces(cs, s, sh, (const uint8_t*)d_src, NULL, n, ZXC_OK, (hipStream_t)stream);
 }
 
-uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_iov, uint64_t max_piece, const zxc_compress_opts_t* opts) {
+uint64_t zxc_mi355x_compress_appendv_dict_device_scratch_size(uint32_t n_iov, uint64_t max_piece, const zxc_compress_opts_t* opts,
+                                                              uint32_t dict_size) {
     Sess s = {};
     zav_shape_t sh;
-    if (ap_opts(opts, &s) != ZXC_OK) return 0u;
-    return zav_shape(n_iov, max_piece, s.block_size, &sh) == 0 ? sh.bytes : 0u;
+    if (ap_opts(opts, &s) != ZXC_OK || dict_size > ZC_DICT_MAX) return 0u;
+    return zav_shape_dict(n_iov, max_piece, s.block_size, dict_size, &sh) == 0 ? sh.bytes : 0u;
+}
+
+uint64_t zxc_mi355x_compress_appendv_device_scratch_size(uint32_t n_iov, uint64_t max_piece, const zxc_compress_opts_t* opts) {
+    return zxc_mi355x_compress_appendv_dict_device_scratch_size(n_iov, max_piece, opts, 0u);
 }
 
 int zxc_mi355x_compress_appendv_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total, void* d_scratch,
                                        uint64_t scratch_size, void* stream) {
-    if (!cs || !d_scratch || (n_iov > 0 && !d_iov)) return ZXC_ERROR_NULL_INPUT;
-    Sess s;
-    memcpy(&s, cs, sizeof s);
-    if (s.magic != SESS_LIVE) return ZXC_ERROR_NULL_INPUT;
-    if (s.dict_size) return ZXC_ERROR_GPU_UNSUPPORTED;
-    if (n_iov == 0 && total > 0) return ZXC_ERROR_SRC_TOO_SMALL;
-    if (total > s.max_total - s.total) return ZXC_ERROR_OVERFLOW;
-    zap_shape_images_t sh;
-    zav_shape_t vsh;
-    if (ap_shape(s, &sh) != 0 || zav_shape(n_iov, s.max_piece, s.block_size, &vsh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
-    if (scratch_size < vsh.bytes) return ZXC_ERROR_MEMORY;
-    if (n_iov == 0) return ZXC_OK;
-    const hipStream_t st = (hipStream_t)stream;
-    uint8_t* sb = zd_work_base(d_scratch);
-    zav_ctl_t* vctl = (zav_ctl_t*)sb;
-    uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
-    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
-    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
-    // The scan, once per call: the chunks read starts and the verdict in stream order.
-    int rc = ZXC_OK;
-    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
-    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
-                           n_iov, vctl, (zap_ctl_t*)s.base);
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    // The chunks, cut like the pieces of an append of `total` bytes.
-    Vsrc vs = {d_iov, n_iov, vsh.image, starts, vctl, sb + vsh.o_images, 0u};
-    return ap_pieces(cs, s, sh, NULL, &vs, total, rc, st);
+    return ap_appendv(cs, d_iov, n_iov, total, d_scratch, scratch_size, stream, false);
+}
+
+int zxc_mi355x_compress_appendv_dict_device(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov, uint64_t total,
+                                            void* d_scratch, uint64_t scratch_size, void* stream) {
+    return ap_appendv(cs, d_iov, n_iov, total, d_scratch, scratch_size, stream, true);
 }
 
 int zxc_mi355x_compress_end_device(zxc_dev_cappend_t* cs, int64_t* d_result, void* stream) {

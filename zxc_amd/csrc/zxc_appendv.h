@@ -14,7 +14,10 @@
  *
  * Scratch, from its 256-byte aligned base: the call's control word, starts[0 .. n_iov], per tile of 1024 entries a sum and the
  * flags of the check, and J = max_piece / block_size + 2 images of block_size + 256 bytes. In closed form the size is at most
- *     8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + J x (block_size + 256) + 4096          (ZAV_TILE_BYTES, ZAV_IMAGE_SLACK, ZAV_FIXED) */
+ *     8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + J x (block_size + 256) + 4096          (ZAV_TILE_BYTES, ZAV_IMAGE_SLACK, ZAV_FIXED)
+ *
+ * The rules of zxc_mi355x_compress_appendv_dict_device, the same call in a session begun with a dictionary, stand at the end: the
+ * scratch without images (zav_shape_dict) and the gather of [dict | block] images from the entries (zav_prep_images). */
 #ifndef ZXC_APPENDV_H
 #define ZXC_APPENDV_H
 #include "zxc_append.h"
@@ -220,5 +223,88 @@ ZC_FN void zav_prep(const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n
     }
     if (t < ZAP_PAD) d[k.len + t] = 0u;
     if (t == 0 && k.job != ZAV_NO_JOB) jobs[k.job] = job;
+}
+
+/* ---- the same call in a session with a dictionary of dict_size bytes (zxc_mi355x_compress_appendv_dict_device). Every block of
+ * such a session is encoded from a [dict | block] image in the session's own image area (zxc_append.h), so the call's scratch
+ * holds no images: the control word, starts[0 .. n_iov] and the tile words, at most
+ *     8 x (n_iov + 1) + 16 x ceil(n_iov / 1024) + 4096                                              (ZAV_TILE_BYTES, ZAV_FIXED)
+ * dict_size == 0 (a session without a dictionary through that call): the shape and the bound above. */
+ZC_FN int zav_shape_dict(uint32_t n_iov, uint64_t max_piece, uint32_t block_size, uint32_t dict_size, zav_shape_t* s) {
+    const int rc = zav_shape(n_iov, max_piece, block_size, s);
+    if (rc != 0 || dict_size == 0) return rc;
+    s->image = 0;
+    s->bytes = s->o_images + 256u;
+    return 0;
+}
+ZC_FN uint64_t zav_scratch_bound_dict(uint32_t n_iov, uint64_t max_piece, uint32_t block_size, uint32_t dict_size) {
+    if (dict_size == 0) return zav_scratch_bound(n_iov, max_piece, block_size);
+    return 8ull * ((uint64_t)n_iov + 1u) + ZAV_TILE_BYTES * (((uint64_t)n_iov + ZC_TILE_BLOCKS - 1u) / ZC_TILE_BLOCKS) + ZAV_FIXED;
+}
+
+/* d[0, n) = s[0, n), both of any alignment: thread t of `threads` moves the 16 bytes at 16 t, 16 (t + threads), ... */
+ZC_FN void zav_copy(uint8_t* d, const uint8_t* s, uint32_t n, uint32_t t, uint32_t threads) {
+    for (uint32_t o = 16u * t; o < n; o += 16u * threads) {
+        if (o + 16u <= n) {
+            zav_u128_t v;
+            __builtin_memcpy(&v, s + o, 16);
+            __builtin_memcpy(d + o, &v, 16);
+        } else {
+            for (uint32_t k = o; k < n; k++) d[k] = s[k];
+        }
+    }
+}
+/* d[0, n) = X[vlo, vlo + n), d of any alignment: the workgroup's share of thread t. The search is narrowed once to the entries
+ * [e_lo, e_hi] that meet the range; the thread owns units t, t + threads, ... (zav_gather_unit). Reads exactly those bytes. */
+ZC_FN void zav_gather(uint8_t* d, uint64_t n, uint64_t vlo, const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov, uint32_t t,
+                      uint32_t threads) {
+    if (!n) return;
+    const uint32_t e_lo = zav_find(starts, 0u, n_iov - 1u, vlo), e_hi = zav_find(starts, e_lo, n_iov - 1u, vlo + n - 1u);
+    const uint64_t units = zav_units(d, n);
+    zav_cursor_t cur = {0u, 0u, 0u, 0u, 0u};
+    for (uint64_t u = t; u < units; u += threads) zav_gather_unit(d, n, vlo, u, iov, starts, e_lo, e_hi, &cur);
+}
+
+/* Prep of the jobs [j0, j0 + n) of a chunk that completes blocks (c->p is zap_plan_piece_images', nb > 0), which the encoder takes
+ * in one launch over the session's image area: what thread t of the `threads` (>= ZAP_PAD) of workgroup w does. Workgroup w < n
+ * builds image w at images + w x (block_size + dict_size): the dictionary, then the bytes of job j0 + w from the one or two places
+ * zap_job_images names, its ZAP_SRC segment being X[c->v + off, + len) gathered straight into the image (the carried block: the
+ * waiting bytes of `carry`, then the head of X, which is copied nowhere else); thread 0 writes the job's table entry, the image's
+ * offset from `images`. Workgroup n, which only the first launch of a chunk has (j0 == 0), gathers the tail into the other carry
+ * area with ZAP_PAD zero bytes behind it. No block is encoded where it lies: an image is a copy by construction, and its over-read
+ * is served by the next image or by ZC_IMAGE_PAD. After a table error (status < 0) every job is unused and nothing else is read
+ * or written: not the table, not an entry, not starts. */
+ZC_FN void zav_prep_images(const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov, int status, const zav_chunk_t* c, uint32_t j0,
+                           uint32_t n, uint32_t w, uint32_t t, uint32_t threads, const uint8_t* dict, uint32_t dict_size,
+                           const uint8_t* carry, uint8_t* next, uint8_t* images, zxc_enc_job_t* jobs) {
+    const zap_piece_t* p = &c->p;
+    if (status < 0) {
+        const zxc_enc_job_t unused = {0u, 0u, 0u};
+        if (t == 0 && w < n) jobs[j0 + w] = unused;
+        return;
+    }
+    if (w >= n) {
+        if (w == n && j0 == 0 && p->cp[2].area == ZAP_NEXT) {
+            uint8_t* d = next + p->cp[2].at;
+            zav_gather(d, p->tail, c->v + p->n - p->tail, iov, starts, n_iov, t, threads);
+            if (t < ZAP_PAD) d[p->tail + t] = 0u;
+        }
+        return;
+    }
+    const zap_src2_t s = zap_job_images(p, j0 + w);
+    const uint64_t at = (uint64_t)w * ((uint64_t)p->block_size + dict_size);
+    uint8_t* d = images + at;
+    zav_copy(d, dict, dict_size, t, threads);
+    d += dict_size;
+    for (uint32_t k = 0; k < 2u; k++) {
+        const zap_src_t g = s.seg[k];
+        if (g.area == ZAP_CARRY) zav_copy(d, carry + g.off, g.len, t, threads);
+        else zav_gather(d, g.len, c->v + g.off, iov, starts, n_iov, t, threads);
+        d += g.len;
+    }
+    if (t == 0) {
+        const zxc_enc_job_t job = {at, s.seg[0].len + s.seg[1].len, 0u};
+        jobs[j0 + w] = job;
+    }
 }
 #endif

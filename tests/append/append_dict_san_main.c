@@ -5,11 +5,9 @@
  * every triple of arguments <archive> <decoded bytes> <dictionary content> that archive cut near the ends of its first block at
  * every byte, between them at every 97th (the test runs every byte boundary outside this program), and at random. Built by tests/test_compress_append_dict_device_cpu.py with -fsanitize=address,undefined.
  * Prints "APPEND DICT OK <cut sets>" and exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
 
 #include "append_dict_replay.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 
 static uint8_t* slurp(const char* path, uint64_t* n) {
     FILE* f = fopen(path, "rb");

@@ -6,15 +6,11 @@
  * several blocks + 5 and 70 blocks (the hash rotation wraps); cuts at block boundaries, inside blocks, zero-length appends, many
  * sub-block appends in a row, random cuts, pieces shorter than the appends; a capacity of exactly the archive and one byte less.
  * Built by tests/test_compress_append_device_cpu.py with -fsanitize=address,undefined. Prints "APPEND OK <sessions>" and exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
 
 #include "append_replay.h"
 
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 #define CANARY 0xC3u
-
-static uint32_t rnd_state = 4321u;
-static uint32_t rnd(void) { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
 
 static int sessions = 0;
 
@@ -58,6 +54,7 @@ static void run(uint32_t bs, uint64_t total, int checksum, int seekable) {
 }
 
 int main(void) {
+    rnd_state = 4321u;
     const uint32_t bss[] = {4096u, 65536u};
     for (int b = 0; b < 2; b++)
         for (int checksum = 0; checksum < 2; checksum++)

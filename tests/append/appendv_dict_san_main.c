@@ -8,11 +8,9 @@
  * for every triple of arguments <archive> <decoded bytes> <dictionary content> that archive under the same cut sets.
  * Built by tests/test_compress_appendv_dict_device_cpu.py with -fsanitize=address,undefined.
  * Prints "APPENDV DICT OK <sessions>" and exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
 
 #include "appendv_dict_replay.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 
 static uint8_t* slurp(const char* path, uint64_t* n) {
     FILE* f = fopen(path, "rb");

@@ -7,16 +7,12 @@
  * 1-7-byte entries that span several blocks, entries that end 31 / 32 / 33 bytes behind a block boundary, calls that alternate
  * with plain appends and leave a carry each, chunk loops with max_piece of one and two blocks; tables that break each rule.
  * Built by tests/test_compress_appendv_device_cpu.py with -fsanitize=address,undefined. Prints "APPENDV OK <sessions>", exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
 
 #include "appendv_replay.h"
 
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 #define CANARY 0xC3u
 #define PATTERNS 8
-
-static uint32_t rnd_state = 8765u;
-static uint32_t rnd(void) { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
 
 static int sessions = 0;
 static uint64_t in_place = 0, images = 0;
@@ -141,6 +137,7 @@ static void bad_tables(void) {
 }
 
 int main(void) {
+    rnd_state = 8765u;
     const uint32_t bss[] = {4096u, 65536u};
     for (int b = 0; b < 2; b++)
         for (int checksum = 0; checksum < 2; checksum++)

@@ -5,17 +5,13 @@
  * dictionary flag, items of 0, 1, a block, a block + 1 and several blocks at odd offsets, and the refused items. Every archive is
  * walked back with zxc_container.h (file header, block chain, seek table, footer, global hash) and compared with its source.
  * Built by tests/test_compress_batch_device_cpu.py with -fsanitize=address,undefined. Prints "CBATCH OK <archives>" and exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
 #include <stdlib.h>
 #include <string.h>
 
 #include "../../zxc_amd/csrc/zxc_cbatch.h"
 
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 #define CANARY 0xC3u
-
-static uint32_t rnd_state = 12345u;
-static uint32_t rnd(void) { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
 
 /* a stored block of n bytes in a slot: header, bytes, trailer (any word will do: the rules only fold it) -> its size */
 static uint32_t fake_encode(uint8_t* slot, const uint8_t* in, uint32_t n, int checksum) {
@@ -119,6 +115,7 @@ static int run(uint32_t bs, int checksum, int seekable, int has_dict, uint32_t d
 }
 
 int main(void) {
+    rnd_state = 12345u;
     int archives = 0;
     const uint32_t bss[] = {4096u, 65536u};
     for (int b = 0; b < 2; b++)

@@ -8,18 +8,14 @@
  * with items without a size at the tile edges; the capacity cut one byte short of every archive's end, at it, at 0 and at the
  * total; the packed table written over the item table. Every written archive is walked back with zxc_container.h and compared
  * with its source. Built by tests/test_compress_pack_device_cpu.py with -fsanitize=address,undefined. Prints "CPACK OK <archives>". */
-#include <stdio.h>
+#include "../container/san_util.h"
 #include <stdlib.h>
 #include <string.h>
 
 #include "cpack_shim.c"
 
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 #define CANARY 0xC3u
 #define WHOLE (~0ull) /* capacity: exactly the total */
-
-static uint32_t rnd_state = 4321u;
-static uint32_t rnd(void) { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
 
 /* a stored block of n bytes in a slot: header, bytes, trailer (any word will do: the rules only fold it) -> its size */
 static uint32_t fake_encode(uint8_t* slot, const uint8_t* in, uint32_t n, int checksum) {
@@ -163,6 +159,7 @@ static uint64_t run(uint32_t n, int small, uint32_t bs, int checksum, int seekab
 }
 
 int main(void) {
+    rnd_state = 4321u;
     int archives = 0;
     const uint32_t bss[] = {4096u, 65536u}, aligns[] = {1u, 16u, 256u, 4096u}, counts[] = {0u, 1u, 1023u, 1024u, 1025u, 2049u};
     /* the rules over every kind of archive */

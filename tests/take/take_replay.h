@@ -10,7 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../zxc_amd/csrc/zxc_take.h"
+#include "../../zxc_amd/csrc/zxc_takev.h" /* zxc_take.h, and the chunk of a takev for the shared loop */
 
 #define TR_BAD_PLAN (-1000) /* the replay's own verdict: a plan that breaks one of its promises */
 #define TR_SCRIBBLE 0xEEu
@@ -120,20 +120,31 @@ static void tr_chunk_copy(tr_session_t* s, uint8_t* d, const zt_chunk_t* c) {
     }
 }
 
-/* the loop of zxc_mi355x_decompress_take_device: the next n bytes to d[0, n) -> ZXC_OK or the synchronous error */
-static int tr_take(tr_session_t* s, uint8_t* d, uint64_t n) {
-    if (n > s->cap - s->pos) return ZXC_ERROR_OVERFLOW;
-    uint64_t left = n;
+/* The chunk loop of tk_chunks (zxc_take_device.hip): the next n bytes, to d or (vchunk != NULL) into the table of a takev, whose
+ * front end (plan, decode, copy of one chunk over the virtual destination vd) is takev_replay.h's. */
+typedef void (*tr_vchunk_fn)(tr_session_t* s, const ztv_chunk_t* c, const void* vd);
+static void tr_chunks(tr_session_t* s, uint8_t* d, tr_vchunk_fn vchunk, const void* vd, uint64_t n) {
+    uint64_t left = n, v = 0;
     while (left) {
         const uint64_t m = zt_chunk_len(s->pos, left, s->max_piece, s->bs);
         if (m == 0 || m > left || m > s->max_piece || (m < left && (s->pos + m) % s->bs != 0)) { s->bad = 1; break; }
-        zt_chunk_t c;
-        zt_plan_chunk(s->pos, m, left, (uint32_t)((uintptr_t)d & 15u), s->bs, s->cur, &c);
-        tr_chunk_decode(s, d, &c, left);
-        tr_chunk_copy(s, d, &c);
-        zt_advance(&c, &s->pos, &s->cur);
-        d += m; left -= m;
+        ztv_chunk_t c;
+        if (vchunk) {
+            ztv_plan_chunk(s->pos, m, s->bs, s->cur, v, &c);
+            vchunk(s, &c, vd);
+        } else {
+            zt_plan_chunk(s->pos, m, left, (uint32_t)((uintptr_t)(d + v) & 15u), s->bs, s->cur, &c.c);
+            tr_chunk_decode(s, d + v, &c.c, left);
+            tr_chunk_copy(s, d + v, &c.c);
+        }
+        zt_advance(&c.c, &s->pos, &s->cur);
+        v += m; left -= m;
     }
+}
+/* zxc_mi355x_decompress_take_device: the next n bytes to d[0, n) -> ZXC_OK or the synchronous error */
+static int tr_take(tr_session_t* s, uint8_t* d, uint64_t n) {
+    if (n > s->cap - s->pos) return ZXC_ERROR_OVERFLOW;
+    tr_chunks(s, d, NULL, NULL, n);
     return ZXC_OK;
 }
 /* zxc_mi355x_decompress_end_device -> the result word (TR_BAD_PLAN when the replay met a broken promise) */
@@ -158,6 +169,20 @@ static int64_t tr_end(tr_session_t* s) {
     return s->bad ? TR_BAD_PLAN : r;
 }
 
+/* A heap buffer for n bytes with at least TR_GUARD canary bytes in front and behind, its first byte at an address that is
+ * `align` mod 16 -> that byte; *raw is what to free. And whether a canary around d[0, n) changed. */
+static uint8_t* tr_guarded(uint64_t n, uint32_t align, uint8_t** raw) {
+    *raw = malloc(TR_GUARD + 16u + n + TR_GUARD + 16u);
+    memset(*raw, TR_CANARY, TR_GUARD + 16u + n + TR_GUARD + 16u);
+    return (uint8_t*)(((uintptr_t)*raw + TR_GUARD + 15u) & ~(uintptr_t)15u) + (align & 15u);
+}
+static int tr_guards_changed(const uint8_t* raw, const uint8_t* d, uint64_t n) {
+    int bad = 0;
+    for (const uint8_t* p = raw; p < d; p++) if (*p != TR_CANARY) bad = 1;
+    for (const uint8_t* p = d + n; p < raw + TR_GUARD + 16u + n + TR_GUARD + 16u; p++) if (*p != TR_CANARY) bad = 1;
+    return bad;
+}
+
 /* A whole session: begin, the takes of lens[0 .. n_lens) (their sum is cap), end. Every piece is a heap buffer of its own with
  * at least TR_GUARD canary bytes in front and behind, its first byte at an address that is `align` mod 16 (the sanitizer program
  * also hands tr_take buffers of exactly n bytes). out[0, cap) receives the pieces' bytes concatenated. -> the result word, or
@@ -174,12 +199,10 @@ static int64_t tr_session(const uint8_t* src, uint64_t src_size, uint64_t cap, u
     int canary_bad = 0;
     for (uint32_t i = 0; i < n_lens; i++) {
         const uint64_t n = lens[i];
-        uint8_t* raw = malloc(TR_GUARD + 16u + n + TR_GUARD + 16u);
-        uint8_t* d = (uint8_t*)(((uintptr_t)raw + TR_GUARD + 15u) & ~(uintptr_t)15u) + (align & 15u);
-        memset(raw, TR_CANARY, TR_GUARD + 16u + n + TR_GUARD + 16u);
+        uint8_t* raw;
+        uint8_t* d = tr_guarded(n, align, &raw);
         if (tr_take(&s, d, n) != ZXC_OK) s.bad = 1;
-        for (uint8_t* p = raw; p < d; p++) if (*p != TR_CANARY) canary_bad = 1;
-        for (uint8_t* p = d + n; p < raw + TR_GUARD + 16u + n + TR_GUARD + 16u; p++) if (*p != TR_CANARY) canary_bad = 1;
+        canary_bad |= tr_guards_changed(raw, d, n);
         if (at + n <= cap) memcpy(out + at, d, n);
         at += n;
         free(raw);

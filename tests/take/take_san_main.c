@@ -1,20 +1,16 @@
 /* Stand-alone program (its own main, not loaded into anything) that replays sessions of zxc_amd/csrc/zxc_take.h the way the entry
  * points and kernels of zxc_take_device.hip run them (take_replay.h), over heap buffers of exactly the sizes a session is promised,
- * so that AddressSanitizer and UBSan see any read or write outside them. The archives are built here with zxc_container.h (every
+ * so that AddressSanitizer and UBSan see any read or write outside them. The archives are tests/container/stored_archive.h's (every
  * block a stored block, with a trailer when checksums are on) and parsed by the real container stages; the decoder is the replay's
  * stand-in, which scribbles 32 bytes behind every block. Every combination of block size, checksum, seek table and verification;
  * sizes of 0, 1, a block - 1, a block, a block + 1, several blocks + 5 and 70 blocks; takes at block boundaries, inside blocks,
  * zero-length takes, many takes inside one block, random cuts, chunks shorter than the takes; pieces at aligned and odd addresses;
  * a capacity of exactly the size, one byte less and a block and 3 bytes more.
  * Built by tests/test_decompress_take_device_cpu.py with -fsanitize=address,undefined. Prints "TAKE OK <sessions>" and exits 0. */
-#include <stdio.h>
+#include "../container/san_util.h"
+#include "../container/stored_archive.h"
 
 #include "take_replay.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
-
-static uint32_t rnd_state = 4321u;
-static uint32_t rnd(void) { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
 
 static int sessions = 0;
 
@@ -43,37 +39,16 @@ static int64_t session_exact(const uint8_t* arc, uint64_t size, uint64_t cap, ui
 }
 
 static void run(uint32_t bs, uint64_t total, int checksum, int seekable) {
-    const uint32_t nb = (uint32_t)((total + bs - 1) / bs);
     uint8_t* data = malloc(total ? total : 1);
     for (uint64_t i = 0; i < total; i++) data[i] = (uint8_t)(rnd() >> 5);
-    const uint64_t size = zc_known_size(nb, checksum, seekable) + total;
-    uint8_t* arc = malloc(size);
-    uint64_t* blk_at = malloc((nb + 1u) * 8u);
-    int32_t* blk_status = malloc((nb + 1u) * 4u);
-    uint64_t o = ZC_FILE_HDR;
-    uint32_t hash = 0;
-    zc_put_file_header(arc, zc_block_size_lg(bs), checksum, 0, 0u);
-    for (uint32_t b = 0; b < nb; b++) {
-        const uint32_t n = total - (uint64_t)b * bs < bs ? (uint32_t)(total - (uint64_t)b * bs) : bs;
-        blk_at[b] = (uint64_t)b * bs;
-        blk_status[b] = (int32_t)n;
-        zc_st_le(arc + o, zc_blk_hdr(0u, n), 8);
-        memcpy(arc + o + 8, data + (uint64_t)b * bs, n);
-        o += 8u + n;
-        if (checksum) {
-            const uint32_t t = 0x9E3779B9u * (b + 1u) ^ data[(uint64_t)b * bs];
-            zc_st_le(arc + o, t, 4);
-            o += 4;
-            hash = zc_hash_fold(hash, t);
-        }
-    }
-    zc_st_le(arc + o, zc_blk_hdr(ZC_BLK_EOF, 0u), 8); o += 8;
-    if (seekable && nb) {
-        zc_st_le(arc + o, zc_blk_hdr(ZC_BLK_SEK, nb * 4u), 8); o += 8;
-        for (uint32_t b = 0; b < nb; b++) { zc_st_le(arc + o, 8u + (uint32_t)blk_status[b] + (checksum ? 4u : 0u), 4); o += 4; }
-    }
-    zc_put_footer(arc + o, total, checksum ? hash : 0u);
-    CHECK(o + ZC_FOOTER == size);
+    rp_archive_t a;
+    CHECK(rp_stored_archive(data, total, bs, checksum, seekable, 0, 0u, &a));
+    const uint8_t* arc = a.comp;
+    const uint64_t size = a.size;
+    const uint32_t nb = a.nb;
+    uint64_t* blk_at;
+    int32_t* blk_status;
+    rp_stored_decoded(&a, bs, checksum, &blk_at, &blk_status);
 
     const uint64_t caps[3] = {total, total ? total - 1u : 0u, total + bs + 3u};
     uint64_t* lens = malloc(((total + bs + 3u) / 111u + 64u) * 8u);
@@ -112,10 +87,11 @@ static void run(uint32_t bs, uint64_t total, int checksum, int seekable) {
             }
         }
     }
-    free(out); free(lens); free(blk_status); free(blk_at); free(arc); free(data);
+    free(out); free(lens); free(blk_status); free(blk_at); rp_archive_free(&a); free(data);
 }
 
 int main(void) {
+    rnd_state = 4321u;
     const uint32_t bss[] = {4096u, 65536u};
     for (int b = 0; b < 2; b++)
         for (int checksum = 0; checksum < 2; checksum++)

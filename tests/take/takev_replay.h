@@ -10,8 +10,6 @@
 #define TAKEV_REPLAY_H
 #include "take_replay.h"
 
-#include "../../zxc_amd/csrc/zxc_takev.h"
-
 /* plan kernel and decode launches of one chunk */
 static void tvr_chunk_decode(tr_session_t* s, const ztv_chunk_t* c, const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov,
                              int verdict, ztv_place_t* places) {
@@ -84,6 +82,20 @@ static void tvr_chunk_copy(tr_session_t* s, const ztv_chunk_t* c, const zxc_dev_
             }
 }
 
+/* The front end tr_chunks calls per chunk of a takev: the table, what the call's scan left, the verdict, the place records. */
+typedef struct tvr_dst {
+    const zxc_dev_iov_t* iov;
+    const uint64_t* starts;
+    uint32_t n_iov;
+    int verdict;
+    ztv_place_t* places;
+} tvr_dst_t;
+static void tvr_chunk(tr_session_t* s, const ztv_chunk_t* c, const void* dst) {
+    const tvr_dst_t* vd = dst;
+    tvr_chunk_decode(s, c, vd->iov, vd->starts, vd->n_iov, vd->verdict, vd->places);
+    tvr_chunk_copy(s, c, vd->iov, vd->starts, vd->n_iov, vd->verdict, vd->places);
+}
+
 /* zxc_mi355x_decompress_takev_device behind its pointer checks: the next `total` bytes into the table -> ZXC_OK or the
  * synchronous error. The table lies in host memory here; starts and the place records are heap buffers of exactly the sizes the
  * scratch gives them. */
@@ -95,19 +107,9 @@ static int tvr_takev(tr_session_t* s, const zxc_dev_iov_t* iov, uint32_t n_iov, 
     if (n_iov == 0) return ZXC_OK;
     uint64_t* starts = malloc(((size_t)n_iov + 1u) * 8u);
     ztv_place_t* places = malloc((size_t)vsh.J * sizeof *places);
-    const int verdict = ztv_scan_serial(iov, n_iov, total, starts);
-    ztv_fold(&s->ctl, verdict);
-    uint64_t left = total, v = 0;
-    while (left) {
-        const uint64_t m = zt_chunk_len(s->pos, left, s->max_piece, s->bs);
-        if (m == 0 || m > left || m > s->max_piece || (m < left && (s->pos + m) % s->bs != 0)) { s->bad = 1; break; }
-        ztv_chunk_t c;
-        ztv_plan_chunk(s->pos, m, s->bs, s->cur, v, &c);
-        tvr_chunk_decode(s, &c, iov, starts, n_iov, verdict, places);
-        tvr_chunk_copy(s, &c, iov, starts, n_iov, verdict, places);
-        zt_advance(&c.c, &s->pos, &s->cur);
-        v += m; left -= m;
-    }
+    const tvr_dst_t vd = {iov, starts, n_iov, ztv_scan_serial(iov, n_iov, total, starts), places};
+    ztv_fold(&s->ctl, vd.verdict);
+    tr_chunks(s, NULL, tvr_chunk, &vd, total);
     free(places); free(starts);
     return ZXC_OK;
 }
@@ -137,9 +139,7 @@ static int64_t tvr_session(const uint8_t* src, uint64_t src_size, uint64_t cap, 
         for (uint32_t r = 0; r < cnt; r++) {
             const uint64_t n = lens[e + r];
             const uint32_t a = align >= 16u ? ((e + r) * 7u) & 15u : align;
-            raw[r] = malloc(TR_GUARD + 16u + n + TR_GUARD + 16u);
-            memset(raw[r], TR_CANARY, TR_GUARD + 16u + n + TR_GUARD + 16u);
-            iov[r].base = (((uint64_t)(uintptr_t)raw[r] + TR_GUARD + 15u) & ~(uint64_t)15u) + a;
+            iov[r].base = (uint64_t)(uintptr_t)tr_guarded(n, a, &raw[r]);
             iov[r].len = n;
             total += n;
         }
@@ -148,8 +148,7 @@ static int64_t tvr_session(const uint8_t* src, uint64_t src_size, uint64_t cap, 
         for (uint32_t r = 0; r < cnt; r++) {
             uint8_t* d = (uint8_t*)(uintptr_t)iov[r].base;
             const uint64_t n = iov[r].len;
-            for (uint8_t* p = raw[r]; p < d; p++) if (*p != TR_CANARY) canary_bad = 1;
-            for (uint8_t* p = d + n; p < raw[r] + TR_GUARD + 16u + n + TR_GUARD + 16u; p++) if (*p != TR_CANARY) canary_bad = 1;
+            canary_bad |= tr_guards_changed(raw[r], d, n);
             if (at + n <= cap) memcpy(out + at, d, n);
             at += n;
             free(raw[r]);

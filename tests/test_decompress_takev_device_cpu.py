@@ -96,6 +96,22 @@ def test_valid_arguments_without_a_device(product, L):
         assert _takev(L, ds) == ERR["NULL_INPUT"]
 
 
+def test_a_launch_error_ends_the_chunk_loop_and_spends_the_session(product, L):
+    """4 KiB blocks, max_piece two blocks, a call of five blocks and 7 bytes (three chunks), on a machine without a device only. A
+    take's first launch belongs to its first chunk: the loop ends behind that chunk (the position is two blocks, not the call's
+    bytes) and the session is spent. A takev's first launch is its scan, in front of the loop: no chunk is planned."""
+    if product.lib().zxc_mi355x_device_count() == 0:
+        product.api._bind_decompress_take_device(L)
+        n = 5 * 4096 + 7
+        ds = _live(mp=8192)
+        assert L.zxc_mi355x_decompress_take_device(C.byref(ds), T.FAKE_DST, n, None) == ERR["GPU_UNAVAILABLE"]
+        assert ds.opaque[0] == 0 and ds.opaque[6] == 8192
+        assert L.zxc_mi355x_decompress_take_device(C.byref(ds), T.FAKE_DST, 1, None) == ERR["NULL_INPUT"]
+        ds = _live(mp=8192)
+        assert _takev(L, ds, total=n) == ERR["GPU_UNAVAILABLE"] and ds.opaque[0] == 0 and ds.opaque[6] == 0
+        assert L.zxc_mi355x_decompress_end_device(C.byref(ds), T.FAKE_RES, None) == ERR["NULL_INPUT"]
+
+
 def test_python_binding_raises(product):
     s = product.api.DecompressTakeSession(product.api._DevDtake())  # never begun
     with pytest.raises(product.ZxcError) as e:

@@ -39,7 +39,7 @@ def once(fn, stream):
 
 
 def alternating(fns, runs, warmup, stream):
-    """-> per function (median wall ms, median event ms); run i times every function once, in turn"""
+    """-> per function (median wall ms, median event ms, p10 and p90 of the wall ms); run i times every function once, in turn"""
     for _ in range(warmup):
         for fn in fns:
             fn()
@@ -48,7 +48,11 @@ def alternating(fns, runs, warmup, stream):
     for _ in range(runs):
         for k, fn in enumerate(fns):
             ms[k].append(once(fn, stream))
-    return [(statistics.median(w for w, _ in m), statistics.median(e for _, e in m)) for m in ms]
+    def pct(m, p):
+        w = sorted(w for w, _ in m)
+        return w[min(len(w) - 1, max(0, round(p * (len(w) - 1))))]
+
+    return [(statistics.median(w for w, _ in m), statistics.median(e for _, e in m), pct(m, 0.1), pct(m, 0.9)) for m in ms]
 
 
 def case(item, n, content, a, stream):
@@ -110,12 +114,12 @@ def case(item, n, content, a, stream):
         stream.synchronize()
         assert int(res.min().item()) == item == int(res.max().item()), (fn.__name__, int(res.min().item()))
         assert torch.equal(out.view(n, stride)[:, :item], want), fn.__name__
-    (b_wall, b_ev), (l_wall, l_ev) = alternating((batch, loop), a.runs, a.warmup, stream)
+    (b_wall, b_ev, b_p10, b_p90), (l_wall, l_ev, l_p10, l_p90) = alternating((batch, loop), a.runs, a.warmup, stream)
     total = item * n
     return {"corpus": "silesia mix, level 3", "item_bytes": item, "items": n, "block_size": bs, "dict_bytes": len(content) if content else 0,
             "source_bytes": total, "archive_bytes": sum(sizes), "runs": a.runs, "batch_work_bytes": ws_b,
-            "batch_wall_ms": round(b_wall, 3), "batch_event_ms": round(b_ev, 3), "batch_gbps": round(total / b_wall / 1e6, 2),
-            "loop_wall_ms": round(l_wall, 3), "loop_event_ms": round(l_ev, 3), "loop_gbps": round(total / l_wall / 1e6, 2),
+            "batch_wall_ms": round(b_wall, 3), "batch_wall_ms_p10": round(b_p10, 3), "batch_wall_ms_p90": round(b_p90, 3), "batch_event_ms": round(b_ev, 3), "batch_gbps": round(total / b_wall / 1e6, 2),
+            "loop_wall_ms": round(l_wall, 3), "loop_wall_ms_p10": round(l_p10, 3), "loop_wall_ms_p90": round(l_p90, 3), "loop_event_ms": round(l_ev, 3), "loop_gbps": round(total / l_wall / 1e6, 2),
             "speedup_wall": round(l_wall / b_wall, 2)}
 
 

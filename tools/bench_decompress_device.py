@@ -130,14 +130,15 @@ def main():
         check("before")
         base_ms, whole_ms, walk_ms = alternating((baseline, whole, walk), a.runs, a.warmup, stream)
         check("after")
-        q = statistics.quantiles(base_ms, n=10)
+        q, qd = statistics.quantiles(base_ms, n=10), statistics.quantiles(whole_ms, n=10)
         b_med, d_med, w_med = statistics.median(base_ms), statistics.median(whole_ms), statistics.median(walk_ms)
         line = {"block_size": bs, "level": a.level, "blocks": nb, "decoded_bytes": n, "archive_bytes": size, "runs": a.runs,
                 "checksum": bool(a.checksum),
                 "decode_blocks_ms": round(b_med, 4), "decode_blocks_gbps": round(n / b_med / 1e6, 1),
                 "decode_blocks_p10_ms": round(q[0], 4), "decode_blocks_p90_ms": round(q[-1], 4),
                 "decode_blocks_spread": round((q[-1] - q[0]) / b_med, 4),
-                "decompress_device_ms": round(d_med, 4), "decompress_device_gbps": round(n / d_med / 1e6, 1),
+                "decompress_device_ms": round(d_med, 4), "decompress_device_p10_ms": round(qd[0], 4), "decompress_device_p90_ms": round(qd[-1], 4),
+                "decompress_device_gbps": round(n / d_med / 1e6, 1),
                 "ratio_to_decode_blocks": round(d_med / b_med, 4),
                 "walk_call_ms": round(w_med, 4), "walk_call_gbps": round(n / w_med / 1e6, 1),
                 "walk_ns_per_block": round((w_med - d_med) * 1e6 / nb, 1),

@@ -527,21 +527,9 @@ int ap_appendv(zxc_dev_cappend_t* cs, const zxc_dev_iov_t* d_iov, uint32_t n_iov
     uint8_t* sb = zd_work_base(d_scratch);
     zav_ctl_t* vctl = (zav_ctl_t*)sb;
     uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
-    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
-    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
     // The scan, once per call: the chunks read starts and the verdict in stream order.
-    int rc = ZXC_OK;
-    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
-    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
-                           n_iov, vctl, (zap_ctl_t*)s.base);
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
+    const int rc = zd_iov_scan(d_iov, n_iov, total, vsh.n_tiles, (uint64_t*)(sb + vsh.o_tile_sum), (uint32_t*)(sb + vsh.o_tile_flags), starts, vctl,
+                               (zap_ctl_t*)s.base, st);
     // The chunks, cut like the pieces of an append of `total` bytes.
     Vsrc vs = {d_iov, n_iov, vsh.image, starts, vctl, sb + vsh.o_images, 0u};
     return ap_pieces(cs, s, sh, NULL, &vs, total, rc, st);

@@ -103,28 +103,18 @@ static int batch_call(const void* d_src, uint64_t src_capacity, const zxc_dev_it
     zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
     int32_t* status = (int32_t*)(base + s.o_status);
     uint8_t* stage = base + s.o_stage;
-    // One decode launch for both areas: job offsets are 64-bit and counted from d_out, so d_out is the lower of the two (both are
-    // 16-byte aligned, which keeps the out_off of every slot and of every block decoded straight a multiple of 16).
-    uint8_t* out = (d_dst && (uint8_t*)d_dst < stage) ? (uint8_t*)d_dst : stage;
-    const uint64_t dst_rel = d_dst ? (uint64_t)((uint8_t*)d_dst - out) : 0u, stage_rel = (uint64_t)(stage - out);
-    const void* d_dict = dict ? dict->d_content : NULL;
-    const void* d_huf = dict ? dict->d_huf : NULL;
-    const uint32_t dict_size = dict ? dict->size : 0u;
+    uint64_t dst_rel, stage_rel;
+    uint8_t* out = zd_out_base(d_dst, stage, &dst_rel, &stage_rel);
+    const zd_dict_t dc = zd_dict_of(dict);
 
     if (hipMemsetAsync(jobs, 0, 2u * (size_t)s.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
     hipLaunchKernelGGL(zxc_batch_plan_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, st, (const uint8_t*)d_src, src_capacity, d_items,
-                       n_items, s.J, s.n_jobs, max_capacity, dst_capacity, block_size, want_verify, dst_rel, stage_rel, recs, jobs,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
+                       n_items, s.J, s.n_jobs, max_capacity, dst_capacity, block_size, want_verify, dst_rel, stage_rel, recs, jobs, dc.id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    for (uint32_t tb = 0; tb < tables; tb++) {
-        const int rc = zxc_hip_decode_blocks(d_src, jobs + (uint64_t)tb * s.n_jobs, s.n_jobs, out, status + (uint64_t)tb * s.n_jobs, block_size,
-                                             (int)tb, d_dict, dict_size, d_huf, 0u, stream);
-        if (rc != ZXC_OK) return rc;
-    }
-    const uint64_t groups = ((uint64_t)s.n_jobs * s.copy_chunks + 3u) / 4u;
-    hipLaunchKernelGGL(zxc_batch_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
-                       (const uint8_t*)stage, s.slot_stride, (const zb_rec_t*)recs, (const int32_t*)status, s.J, s.n_jobs, s.copy_chunks,
-                       block_size, (uint8_t*)d_dst);
+    const int rc = zd_decode_tables(d_src, jobs, s.n_jobs, s.n_jobs, out, status, s.n_jobs, block_size, tables, dc, stream);
+    if (rc != ZXC_OK) return rc;
+    hipLaunchKernelGGL(zxc_batch_copy_kernel, zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), dim3(256), 0, st, (const uint8_t*)stage,
+                       s.slot_stride, (const zb_rec_t*)recs, (const int32_t*)status, s.J, s.n_jobs, s.copy_chunks, block_size, (uint8_t*)d_dst);
     hipLaunchKernelGGL(zxc_batch_verdict_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, st, (const zb_rec_t*)recs, n_items, s.J,
                        s.n_jobs, (const int32_t*)status, block_size, d_results);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;

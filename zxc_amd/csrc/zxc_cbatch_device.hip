@@ -212,7 +212,7 @@ int cb_call(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_it
     if (opts && opts->dict) return ZXC_ERROR_GPU_UNSUPPORTED;  // (behind the block size, unlike the frame and append calls)
     const int drc = dict_arg(&dict);
     if (drc != ZXC_OK) return drc;
-    const uint32_t dict_size = dict ? dict->size : 0u;
+    const uint32_t dict_size = zd_dict_of(dict).size;
     zcb_shape_t s;
     if (zcb_shape(n_items, max_size, o.block_size, zxc_mi355x_encode_slot_stride(o.block_size), dict_size, &s) != 0 || work_size < s.bytes)
         return ZXC_ERROR_MEMORY;
@@ -238,7 +238,7 @@ int cb_call(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_it
     if (erc != ZXC_OK) return erc;
     hipLaunchKernelGGL(zxc_cbatch_finish_kernel, per_item, dim3(256), 0, st, recs, n_items, s.J, (const uint32_t*)sizes, offsets,
                        (const uint8_t*)slots, s.slot_stride, (uint8_t*)d_dst, o.block_size, o.checksum, o.seekable,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
+                       zd_dict_of(dict).id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     const uint32_t groups = (s.n_jobs + 3u) / 4u < 65536u ? (s.n_jobs + 3u) / 4u : 65536u;
     hipLaunchKernelGGL(zxc_cbatch_gather_kernel, dim3(groups), dim3(256), 0, st, (const zcb_rec_t*)recs, s.J, s.n_jobs, (const uint32_t*)sizes,
@@ -269,7 +269,7 @@ int cp_call(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_it
     if (drc != ZXC_OK) return drc;
     if (!zcp_align_ok(align)) return ZXC_ERROR_GPU_UNSUPPORTED;
     zcp_shape_t p;
-    if (zcp_shape(n_items, max_size, o.block_size, zxc_mi355x_encode_slot_stride(o.block_size), dict ? dict->size : 0u, &p) != 0 ||
+    if (zcp_shape(n_items, max_size, o.block_size, zxc_mi355x_encode_slot_stride(o.block_size), zd_dict_of(dict).size, &p) != 0 ||
         work_size < p.bytes)
         return ZXC_ERROR_MEMORY;
     if (n_items == 0) return ZXC_OK;
@@ -304,7 +304,7 @@ int cp_call(const void* d_src, uint64_t src_capacity, const zxc_dev_item_t* d_it
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     hipLaunchKernelGGL(zxc_cbatch_finish_kernel, per_item, dim3(256), 0, st, recs, n_items, s.J, (const uint32_t*)sizes, offsets,
                        (const uint8_t*)slots, s.slot_stride, (uint8_t*)d_dst, o.block_size, o.checksum, o.seekable,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
+                       zd_dict_of(dict).id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     const uint32_t groups = (s.n_jobs + 3u) / 4u < 65536u ? (s.n_jobs + 3u) / 4u : 65536u;
     hipLaunchKernelGGL(zxc_cbatch_gather_kernel, dim3(groups), dim3(256), 0, st, (const zcb_rec_t*)recs, s.J, s.n_jobs, (const uint32_t*)sizes,

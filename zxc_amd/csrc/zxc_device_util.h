@@ -1,7 +1,8 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
 // zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_cpack_device.hip, zxc_append_device.hip, zxc_take_device.hip,
 // zxc_dict_device.hip): the three tile passes every container stage is made of, the 64-bit workgroup scan, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
-// of an entry point: the launch check, the work area's base, the dictionary argument and the one reader of zxc_compress_opts_t.
+// of an entry point: the launch check, the work area's base, the dictionary argument, the one reader of zxc_compress_opts_t, and
+// the launches the decode-side calls share: the verification tables, the copy grid, the container and the verdict stages.
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //
 // A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
@@ -13,6 +14,7 @@
 #include <stdint.h>
 
 #include "zxc_container.h"
+#include "zxc_kernels.h"  // the container stages that zd_container_stages and zd_verdict_stages launch
 #include "zxc_wave.h"
 
 #define ZD_TILE_THREADS 256u
@@ -188,6 +190,85 @@ static inline int dict_arg(const zxc_dev_dict_t** dict) {
     if (d && d->size > 0 && (!d->d_content || !d->d_id)) return ZXC_ERROR_NULL_INPUT;
     if (d && d->size == 0) *dict = NULL;
     return ZXC_OK;
+}
+// The dictionary as a call's launches take it, behind dict_arg: everything NULL or 0 when there is none.
+struct zd_dict_t {
+    const void *content, *huf;
+    const uint32_t* id;
+    uint32_t size;
+};
+static inline zd_dict_t zd_dict_of(const zxc_dev_dict_t* d) { return d ? zd_dict_t{d->d_content, d->d_huf, d->d_id, d->size} : zd_dict_t{NULL, NULL, NULL, 0u}; }
+// ---- the launches the decode-side calls share
+// A call that may verify decodes table tb < tables with verify_trailer = tb (whether the blocks carry trailers is known on the
+// device only): its n jobs at jobs + tb x job_stride, their statuses at status + tb x status_stride. -> the first rc != ZXC_OK.
+static inline int zd_decode_tables(const void* d_src, const zxc_dev_job_t* jobs, uint64_t job_stride, uint32_t n, void* d_out, int32_t* status,
+                                   uint64_t status_stride, uint32_t block_size, uint32_t tables, const zd_dict_t& dict, void* stream) {
+    int rc = ZXC_OK;
+    for (uint32_t tb = 0; tb < tables && rc == ZXC_OK; tb++)
+        rc = zxc_hip_decode_blocks(d_src, jobs + tb * job_stride, n, d_out, status + tb * status_stride, block_size, (int)tb, dict.content,
+                                   dict.size, dict.huf, 0u, stream);
+    return rc;
+}
+// One decode launch for a call's destination and the staged slots of its work area: job offsets are 64-bit and counted from d_out,
+// so d_out is the lower of the two (both are 16-byte aligned, which keeps the out_off of every slot and of every block decoded
+// straight a multiple of 16). -> d_out; *dst_rel, *stage_rel: the two areas counted from it (d_dst == NULL: no destination).
+static inline uint8_t* zd_out_base(void* d_dst, uint8_t* stage, uint64_t* dst_rel, uint64_t* stage_rel) {
+    uint8_t *dst = (uint8_t*)d_dst, *out = (dst && dst < stage) ? dst : stage;
+    *dst_rel = dst ? (uint64_t)(dst - out) : 0u;
+    *stage_rel = (uint64_t)(stage - out);
+    return out;
+}
+// The grid of a copy launch over `units` (copy, 8 KiB) pairs: a wavefront each, four to a workgroup; past 2^20 workgroups the kernels stride.
+static inline dim3 zd_copy_grid(uint64_t units) { return dim3((uint32_t)((units + 3u) / 4u < (1u << 20) ? (units + 3u) / 4u : (1u << 20))); }
+// The container's parts of a work area, from a zc_shape_t or from a zt_shape_t, which keeps zc_shape's offsets up to o_status.
+struct zd_cwork_t {
+    zc_ctl_t* ctl;
+    uint64_t* tile_sum;
+    uint32_t *tile_hash, *tile_bad, n_jobs, n_tiles;
+    zxc_dev_job_t* jobs;
+    int32_t* status;
+};
+template <class Shape>
+static inline zd_cwork_t zd_cwork(uint8_t* base, const Shape& s) {
+    return zd_cwork_t{(zc_ctl_t*)base, (uint64_t*)(base + s.o_tile_sum), (uint32_t*)(base + s.o_tile_hash), (uint32_t*)(base + s.o_tile_bad),
+                      s.n_jobs, s.n_tiles, (zxc_dev_job_t*)(base + s.o_jobs), (int32_t*)(base + s.o_status)};
+}
+// The container stages of zxc_unframe_device.hip in stream order: clear, head, tiles, scan, scatter, walk -> the control word and
+// the job table the head stage picks. Jobs below k_direct get their block's place in one destination as out_off.
+static inline int zd_container_stages(const zd_cwork_t& w, const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size,
+                                      uint32_t want_verify, uint32_t k_direct, const uint32_t* dict_id, hipStream_t st) {
+    if (hipMemsetAsync(w.jobs, 0, (size_t)(1u + want_verify) * w.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, dst_capacity, block_size, want_verify, w.n_jobs, w.ctl, dict_id);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    if (dst_capacity == 0) return ZXC_OK;  // (the empty-frame probe is answered by the head stage alone)
+    hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(w.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)w.ctl, w.tile_sum, w.tile_bad);
+    hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, w.tile_sum, (const uint32_t*)w.tile_bad, w.n_tiles, w.ctl);
+    hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(w.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)w.ctl,
+                       (const uint64_t*)w.tile_sum, block_size, k_direct, w.n_jobs, w.jobs, w.tile_hash, w.tile_bad);
+    hipLaunchKernelGGL(zxc_unframe_walk_kernel, dim3(1), dim3(256), 0, st, src, src_size, block_size, k_direct, w.n_jobs,
+                       (const uint32_t*)w.tile_hash, (const uint32_t*)w.tile_bad, w.jobs, w.ctl);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+// ... and the verdict stages behind every decode launch: events over the whole status table, then *d_result, written once.
+static inline int zd_verdict_stages(const zd_cwork_t& w, uint32_t block_size, uint64_t dst_capacity, int64_t* d_result, hipStream_t st) {
+    if (dst_capacity > 0) {
+        hipLaunchKernelGGL(zxc_unframe_events_kernel, dim3(w.n_tiles * 4u < 1024u ? w.n_tiles * 4u : 1024u), dim3(256), 0, st,
+                           (const int32_t*)w.status, block_size, w.n_jobs, dst_capacity, w.ctl);
+        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    }
+    hipLaunchKernelGGL(zxc_unframe_result_kernel, dim3(1), dim3(64), 0, st, (const zc_ctl_t*)w.ctl, (const int32_t*)w.status, block_size, w.n_jobs, d_result);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+// The scan of a table of (base, len) entries (zxc_appendv.h; the kernels of zxc_append_device.hip), in stream order: starts[0 .. n_iov],
+// the table's status in *vctl, and its fold into *fold: the session's control word for appendv, a word nobody reads for takev.
+static inline int zd_iov_scan(const zxc_dev_iov_t* iov, uint32_t n_iov, uint64_t total, uint32_t n_tiles, uint64_t* tile_sum, uint32_t* tile_flags,
+                              uint64_t* starts, zav_ctl_t* vctl, zap_ctl_t* fold, hipStream_t st) {
+    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, iov, n_iov, total, tile_sum, tile_flags);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, n_tiles, total, starts, n_iov, vctl, fold);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(n_tiles), dim3(ZD_TILE_THREADS), 0, st, iov, n_iov, (const uint64_t*)tile_sum, starts);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 // Options as zxc_compress reads them (zxc_host.c): level 3 unless given, at most 7; blocks of 512 KiB unless given. -> ZXC_OK or
 // ZXC_ERROR_BAD_BLOCK_SIZE. opts->dict is not looked at: each caller refuses it at its own place in its order of errors.

@@ -243,7 +243,7 @@ int frame_enqueue(const void* d_src, uint64_t src_size, void* d_dst, uint64_t ds
     if (!dict) zc_file_header_words(p.lg, (int)p.checksum, 0, 0u, &hdr_lo, &hdr_hi);
     hipLaunchKernelGGL(zxc_frame_finish_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_hash, (const uint32_t*)tile_bad,
                        p.n_tiles, p.nb, src_size, dst, dst_capacity, hdr_lo, hdr_hi, zc_blk_hdr(ZC_BLK_EOF, 0u), zc_blk_hdr(ZC_BLK_SEK, p.nb * 4u), p.seekable, p.checksum, ctl,
-                       p.lg, dict ? dict->d_id : (const uint32_t*)NULL);
+                       p.lg, zd_dict_of(dict).id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     if (p.nb) {
         hipLaunchKernelGGL(zxc_frame_scatter_kernel, dim3(p.n_tiles), dim3(ZD_TILE_THREADS), 0, st, (const uint32_t*)sizes, p.nb,

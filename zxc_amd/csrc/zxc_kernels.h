@@ -92,7 +92,7 @@ extern "C" __global__ void zxc_gather_blocks_kernel(const uint8_t* slots, uint32
                                                     const uint64_t* offsets, uint8_t* out, uint32_t n_blocks);
 
 // ---------------------------------------------------------------- zxc_unframe_device.hip
-// The container stages of zxc_mi355x_decompress_device, which the take session (zxc_take_device.hip) launches as they are.
+// The container stages of zxc_mi355x_decompress_device and of the take session: zd_container_stages, zd_verdict_stages (zxc_device_util.h).
 extern "C" __global__ void zxc_unframe_head_kernel(const uint8_t* src, uint64_t src_size, uint64_t dst_capacity, uint32_t block_size,
                                                    uint32_t want_verify, uint32_t n_jobs, zc_ctl_t* ctl, const uint32_t* dict_id);
 extern "C" __global__ void zxc_unframe_tiles_kernel(const uint8_t* src, const zc_ctl_t* ctl, uint64_t* tile_sum, uint32_t* tile_bad);

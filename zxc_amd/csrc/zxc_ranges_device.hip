@@ -205,29 +205,24 @@ static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
 
     const hipStream_t st = (hipStream_t)stream;
-    const uint32_t* d_id = dict ? dict->d_id : NULL;
+    const zd_dict_t dc = zd_dict_of(dict);
     uint8_t* base = zd_work_base(d_work);
     zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
     int32_t* status = (int32_t*)(base + s.o_status);
     zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);
     uint8_t* stage = base + s.o_stage;
-    // One decode launch for both areas: job offsets are 64-bit and counted from d_out, so d_out is the lower of the two (both are
-    // 16-byte aligned, which keeps every out_off a multiple of 16).
-    uint8_t* out = (d_dst && (uint8_t*)d_dst < stage) ? (uint8_t*)d_dst : stage;
-    const uint64_t dst_rel = d_dst ? (uint64_t)((uint8_t*)d_dst - out) : 0u, stage_rel = (uint64_t)(stage - out);
+    uint64_t dst_rel, stage_rel;
+    uint8_t* out = zd_out_base(d_dst, stage, &dst_rel, &stage_rel);
 
     hipLaunchKernelGGL(zxc_ranges_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
-                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies, d_id);
+                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies, dc.id);
     if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, dict ? dict->d_content : NULL, dict ? dict->size : 0u,
-                                         dict ? dict->d_huf : NULL, 0u, stream);
+    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, dc.content, dc.size, dc.huf, 0u, stream);
     if (rc != ZXC_OK) return rc;
-    const uint64_t groups = ((uint64_t)s.n_jobs * s.copy_chunks + 3u) / 4u;
-    hipLaunchKernelGGL(zxc_ranges_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
-                       (const uint8_t*)stage, s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks,
-                       (uint8_t*)d_dst);
+    hipLaunchKernelGGL(zxc_ranges_copy_kernel, zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), dim3(256), 0, st, (const uint8_t*)stage,
+                       s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks, (uint8_t*)d_dst);
     hipLaunchKernelGGL(zxc_ranges_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
-                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results, d_id);
+                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results, dc.id);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 

@@ -28,10 +28,14 @@
 //
 // No workgroup waits for another: every dependency is the stream order between launches, and every stage is predicated on the
 // control word.
+//
+// The host side, as the append session's: tk_load reads the caller's struct for take, takev and end; tk_chunks is the one chunk
+// loop and the one store, over a destination pointer or a Vdst; tk_chunk and tkv_chunk are its two front ends (their plan and copy
+// kernels differ), whose decode step is tk_tables. begin's stages, end's verdict, the tables loop and the scan of a takev's table
+// are zxc_device_util.h's (zd_container_stages, zd_verdict_stages, zd_decode_tables, zd_iov_scan), which other calls launch too.
 #include <string.h>
 
-#include "zxc_device_util.h"  // zd_copy_chunk, the host-side plumbing
-#include "zxc_kernels.h"      // the container stages of zxc_unframe_device.hip
+#include "zxc_device_util.h"  // zd_copy_chunk, the host-side plumbing and shared launches (zxc_kernels.h through it)
 #include "zxc_take.h"
 #include "zxc_takev.h"
 
@@ -176,42 +180,53 @@ struct Sess {
 };
 static_assert(sizeof(Sess) <= sizeof(zxc_dev_dtake_t), "the session fits the caller's struct");
 
-// plan and decode of one chunk: d = where its first byte goes (not touched when no block is decoded straight)
-int tk_decode(const Sess& s, const zt_shape_t& sh, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
-    if (!c.nb) return ZXC_OK;
-    uint8_t* base = s.base;
-    const zxc_dev_job_t* index = (const zxc_dev_job_t*)(base + sh.o_jobs);
-    zxc_dev_job_t* cjobs = (zxc_dev_job_t*)(base + sh.o_cjobs);
-    int32_t* status = (int32_t*)(base + sh.o_status);
-    // One decode launch for the piece and the work area: job offsets are 64-bit and counted from d_out, so d_out is the lower of
-    // the two; the piece's side is rounded down to 16, which keeps d_out and the out_off of every slot and of every block decoded
-    // straight (whose place is 16-byte aligned) multiples of 16.
-    uint8_t* work = base + sh.o_carry[0];
-    uint8_t* lo = (uint8_t*)((uintptr_t)d & ~(uintptr_t)15u);
-    uint8_t* out = (c.n_direct && lo < work) ? lo : work;
-    const uint64_t dst_rel = c.n_direct ? (uint64_t)(d - out) : 0u;
-    hipLaunchKernelGGL(zxc_take_plan_kernel, dim3((c.nb + 255u) / 256u), dim3(256), 0, st, index, sh.n_jobs, s.tables, c, dst_rel,
-                       (uint64_t)(base + sh.o_carry[0] - out), (uint64_t)(base + sh.o_carry[1] - out), (uint64_t)(base + sh.o_slots - out),
-                       sh.slot_stride, sh.J, cjobs);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    for (uint32_t tb = 0; tb < s.tables; tb++) {
-        const int rc = zxc_hip_decode_blocks(s.src, cjobs + (uint64_t)tb * sh.J, c.nb, out, status + (uint64_t)tb * sh.n_jobs + c.first,
-                                             s.block_size, (int)tb, s.d_dict, s.dict_size, s.d_huf, 0u, (void*)st);
-        if (rc != ZXC_OK) return rc;
-    }
-    return ZXC_OK;
+// A live session and its shape out of the caller's struct. -> false: never begun, ended, or spent by an error.
+bool tk_load(const zxc_dev_dtake_t* ds, Sess* s, zt_shape_t* sh) {
+    memcpy(s, ds, sizeof *s);
+    return s->magic == TAKE_LIVE && zt_shape(s->dst_capacity, s->max_piece, s->block_size, sh) == 0;  // (begin accepted these)
 }
 
-// One chunk behind its plan: decode, then the copies.
-int tk_chunk(const Sess& s, const zt_shape_t& sh, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
-    const int rc = tk_decode(s, sh, d, c, st);
+// The parts of a session's work area: the container's, then what a chunk uses.
+struct Work {
+    zd_cwork_t c;
+    zxc_dev_job_t* cjobs;  // the chunk's two tables of J jobs
+    const uint8_t *carry[2], *slots;
+};
+Work tk_work(const Sess& s, const zt_shape_t& sh) {
+    uint8_t* b = s.base;
+    return Work{zd_cwork(b, sh), (zxc_dev_job_t*)(b + sh.o_cjobs), {b + sh.o_carry[0], b + sh.o_carry[1]}, b + sh.o_slots};
+}
+
+// The decode step of both front ends, behind their plan kernels: the chunk's tables into `out`, the statuses to the blocks' words
+// of the session's status table.
+int tk_tables(const Sess& s, const zt_shape_t& sh, const Work& w, const zt_chunk_t& c, const uint8_t* out, hipStream_t st) {
+    const zd_dict_t dc = {s.d_dict, s.d_huf, NULL, s.dict_size};
+    return zd_decode_tables(s.src, w.cjobs, sh.J, c.nb, (void*)out, w.c.status + c.first, sh.n_jobs, s.block_size, s.tables, dc, (void*)st);
+}
+
+// plan and decode of one chunk of a take: d = where its first byte goes (not touched when no block is decoded straight)
+int tk_decode(const Sess& s, const zt_shape_t& sh, const Work& w, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
+    if (!c.nb) return ZXC_OK;
+    // One decode launch for the piece and the work area: job offsets are 64-bit and counted from d_out, so d_out is the lower of
+    // the two; the piece's side is rounded down to 16, which keeps d_out and the out_off of every slot and of every block decoded
+    // straight (whose place is 16-byte aligned) multiples of 16. (Not zd_out_base: the rounding, and a piece no block goes to.)
+    const uint8_t* lo = (const uint8_t*)((uintptr_t)d & ~(uintptr_t)15u);
+    const uint8_t* out = (c.n_direct && lo < w.carry[0]) ? lo : w.carry[0];
+    const uint64_t dst_rel = c.n_direct ? (uint64_t)(d - out) : 0u;
+    hipLaunchKernelGGL(zxc_take_plan_kernel, dim3((c.nb + 255u) / 256u), dim3(256), 0, st, (const zxc_dev_job_t*)w.c.jobs, sh.n_jobs, s.tables, c,
+                       dst_rel, (uint64_t)(w.carry[0] - out), (uint64_t)(w.carry[1] - out), (uint64_t)(w.slots - out), sh.slot_stride, sh.J,
+                       w.cjobs);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    return tk_tables(s, sh, w, c, out, st);
+}
+
+// One chunk of a take behind its plan: decode, then the copies.
+int tk_chunk(const Sess& s, const zt_shape_t& sh, const Work& w, uint8_t* d, const zt_chunk_t& c, hipStream_t st) {
+    const int rc = tk_decode(s, sh, w, d, c, st);
     if (rc != ZXC_OK) return rc;
     if (!c.head && c.nb == c.n_direct) return ZXC_OK;  // every byte lies in a block decoded straight
-    uint8_t* base = s.base;
-    const uint64_t groups = (((uint64_t)c.nb + 1u) * sh.copy_chunks + 3u) / 4u;
-    hipLaunchKernelGGL(zxc_take_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
-                       (const uint8_t*)(base + sh.o_carry[0]), (const uint8_t*)(base + sh.o_carry[1]), (const uint8_t*)(base + sh.o_slots),
-                       sh.slot_stride, c, (const int32_t*)(base + sh.o_status), sh.n_jobs, (const zc_ctl_t*)base, sh.copy_chunks, d);
+    hipLaunchKernelGGL(zxc_take_copy_kernel, zd_copy_grid(((uint64_t)c.nb + 1u) * sh.copy_chunks), dim3(256), 0, st, w.carry[0], w.carry[1],
+                       w.slots, sh.slot_stride, c, (const int32_t*)w.c.status, sh.n_jobs, (const zc_ctl_t*)w.c.ctl, sh.copy_chunks, d);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
 }
 
@@ -228,29 +243,46 @@ struct Vdst {
 // a job's out_off is its address minus that base modulo 2^64 (the entries may lie above or below the work area), which the decode
 // kernels only ever add to d_out in 64 bits. Slots, carry slots and the places of blocks decoded in their entries are 16-byte
 // aligned, so every out_off is a multiple of 16.
-int tkv_chunk(const Sess& s, const zt_shape_t& sh, const Vdst& vd, const ztv_chunk_t& c, hipStream_t st) {
-    uint8_t* base = s.base;
-    const zc_ctl_t* ctl = (const zc_ctl_t*)base;
-    int32_t* status = (int32_t*)(base + sh.o_status);
+int tkv_chunk(const Sess& s, const zt_shape_t& sh, const Work& w, const Vdst& vd, const ztv_chunk_t& c, hipStream_t st) {
+    const zc_ctl_t* ctl = w.c.ctl;
     if (c.c.nb) {
-        zxc_dev_job_t* cjobs = (zxc_dev_job_t*)(base + sh.o_cjobs);
-        hipLaunchKernelGGL(zxc_takev_plan_kernel, dim3((c.c.nb + 255u) / 256u), dim3(256), 0, st, (const zxc_dev_job_t*)(base + sh.o_jobs), sh.n_jobs,
-                           s.tables, c, vd.iov, vd.starts, vd.n_iov, vd.vctl, ctl, (uint64_t)(uintptr_t)base,
-                           (uint64_t)(uintptr_t)(base + sh.o_carry[0]), (uint64_t)(uintptr_t)(base + sh.o_carry[1]),
-                           (uint64_t)(uintptr_t)(base + sh.o_slots), sh.slot_stride, sh.J, cjobs, vd.places);
+        hipLaunchKernelGGL(zxc_takev_plan_kernel, dim3((c.c.nb + 255u) / 256u), dim3(256), 0, st, (const zxc_dev_job_t*)w.c.jobs, sh.n_jobs, s.tables,
+                           c, vd.iov, vd.starts, vd.n_iov, vd.vctl, ctl, (uint64_t)(uintptr_t)s.base, (uint64_t)(uintptr_t)w.carry[0],
+                           (uint64_t)(uintptr_t)w.carry[1], (uint64_t)(uintptr_t)w.slots, sh.slot_stride, sh.J, w.cjobs, vd.places);
         if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-        for (uint32_t tb = 0; tb < s.tables; tb++) {
-            const int rc = zxc_hip_decode_blocks(s.src, cjobs + (uint64_t)tb * sh.J, c.c.nb, base, status + (uint64_t)tb * sh.n_jobs + c.c.first,
-                                                 s.block_size, (int)tb, s.d_dict, s.dict_size, s.d_huf, 0u, (void*)st);
-            if (rc != ZXC_OK) return rc;
-        }
+        const int rc = tk_tables(s, sh, w, c.c, s.base, st);
+        if (rc != ZXC_OK) return rc;
     }
-    const uint64_t groups = (((uint64_t)c.c.nb + 1u) * sh.copy_chunks + 3u) / 4u;
-    hipLaunchKernelGGL(zxc_takev_copy_kernel, dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20))), dim3(256), 0, st,
-                       (const uint8_t*)(base + sh.o_carry[0]), (const uint8_t*)(base + sh.o_carry[1]), (const uint8_t*)(base + sh.o_slots),
-                       sh.slot_stride, c, (const int32_t*)status, sh.n_jobs, ctl, vd.vctl, sh.copy_chunks, vd.iov, vd.starts, vd.n_iov,
+    hipLaunchKernelGGL(zxc_takev_copy_kernel, zd_copy_grid(((uint64_t)c.c.nb + 1u) * sh.copy_chunks), dim3(256), 0, st, w.carry[0], w.carry[1],
+                       w.slots, sh.slot_stride, c, (const int32_t*)w.c.status, sh.n_jobs, ctl, vd.vctl, sh.copy_chunks, vd.iov, vd.starts, vd.n_iov,
                        (const ztv_place_t*)vd.places);
     return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+// The next n bytes, to d or (vd != NULL) into the table of a takev, and the session back into *ds. rc: what the launches in front
+// of the chunks gave; nothing more is enqueued behind an error, which spends the session (part of the call may be enqueued).
+// Chunk by chunk: a chunk's table and slots are written and consumed in stream order before the next chunk overwrites them. Every
+// chunk but the last ends on a block boundary of the archive. The 32 bytes a block decoded straight may store behind itself stay
+// inside the call: a copy of the same or a later chunk fills them. v: the chunk's offset in the piece or in the entries' concatenation.
+int tk_chunks(zxc_dev_dtake_t* ds, Sess& s, const zt_shape_t& sh, uint8_t* d, const Vdst* vd, uint64_t n, int rc, hipStream_t st) {
+    const Work w = tk_work(s, sh);
+    uint64_t left = n, v = 0;
+    while (left && rc == ZXC_OK) {
+        const uint64_t m = zt_chunk_len(s.pos, left, s.max_piece, s.block_size);
+        ztv_chunk_t c;
+        if (vd) {
+            ztv_plan_chunk(s.pos, m, s.block_size, s.cur, v, &c);
+            rc = tkv_chunk(s, sh, w, *vd, c, st);
+        } else {
+            zt_plan_chunk(s.pos, m, left, (uint32_t)((uintptr_t)(d + v) & 15u), s.block_size, s.cur, &c.c);
+            rc = tk_chunk(s, sh, w, d + v, c.c, st);
+        }
+        zt_advance(&c.c, &s.pos, &s.cur);
+        v += m; left -= m;
+    }
+    if (rc != ZXC_OK) s.magic = 0;
+    memcpy(ds, &s, sizeof s);
+    return rc;
 }
 
 // Both begins. dict == NULL: the one that takes no dictionary.
@@ -266,35 +298,18 @@ int tk_begin(zxc_dev_dtake_t* ds, const void* d_src, uint64_t src_size, uint64_t
     if (work_size < sh.bytes) return ZXC_ERROR_MEMORY;
     if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
 
-    const hipStream_t st = (hipStream_t)stream;
     const uint32_t want_verify = (opts && opts->checksum_enabled) ? 1u : 0u;
+    const zd_dict_t dc = zd_dict_of(dict);
     Sess s = {};
     s.src = (const uint8_t*)d_src; s.src_size = src_size; s.dst_capacity = dst_capacity; s.max_piece = max_piece;
     s.base = zd_work_base(d_work);
-    s.d_dict = dict ? dict->d_content : NULL; s.d_huf = dict ? dict->d_huf : NULL; s.dict_size = dict ? dict->size : 0u;
+    s.d_dict = dc.content; s.d_huf = dc.huf; s.dict_size = dc.size;
     s.block_size = block_size; s.tables = 1u + want_verify;
-    uint8_t* base = s.base;
-    zc_ctl_t* ctl = (zc_ctl_t*)base;
-    uint64_t* tile_sum = (uint64_t*)(base + sh.o_tile_sum);
-    uint32_t* tile_hash = (uint32_t*)(base + sh.o_tile_hash);
-    uint32_t* tile_bad = (uint32_t*)(base + sh.o_tile_bad);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + sh.o_jobs);
-
     // The container stages of zxc_mi355x_decompress_device. k_direct = n_jobs: every entry's out_off is its block's place in one
     // destination, which no take reads (the chunk plan writes its own).
-    if (hipMemsetAsync(jobs, 0, (size_t)s.tables * sh.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
-    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, s.src, src_size, dst_capacity, block_size, want_verify, sh.n_jobs, ctl,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    if (dst_capacity > 0) {  // (the empty-frame probe is answered by the head stage alone)
-        hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(sh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, s.src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
-        hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_bad, sh.n_tiles, ctl);
-        hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(sh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, s.src, (const zc_ctl_t*)ctl,
-                           (const uint64_t*)tile_sum, block_size, sh.n_jobs, sh.n_jobs, jobs, tile_hash, tile_bad);
-        hipLaunchKernelGGL(zxc_unframe_walk_kernel, dim3(1), dim3(256), 0, st, s.src, src_size, block_size, sh.n_jobs, sh.n_jobs,
-                           (const uint32_t*)tile_hash, (const uint32_t*)tile_bad, jobs, ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    }
+    const int rc = zd_container_stages(zd_cwork(s.base, sh), s.src, src_size, dst_capacity, block_size, want_verify, sh.n_jobs, dc.id,
+                                       (hipStream_t)stream);
+    if (rc != ZXC_OK) return rc;
     s.magic = TAKE_LIVE;
     memset(ds, 0, sizeof *ds);
     memcpy(ds, &s, sizeof s);
@@ -326,29 +341,11 @@ int zxc_mi355x_decompress_begin_dict_device(zxc_dev_dtake_t* ds, const void* d_s
 int zxc_mi355x_decompress_take_device(zxc_dev_dtake_t* ds, void* d_dst, uint64_t n, void* stream) {
     if (!ds || (n > 0 && !d_dst)) return ZXC_ERROR_NULL_INPUT;
     Sess s;
-    memcpy(&s, ds, sizeof s);
-    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    zt_shape_t sh;
+    if (!tk_load(ds, &s, &sh)) return ZXC_ERROR_NULL_INPUT;
     if (n > s.dst_capacity - s.pos) return ZXC_ERROR_OVERFLOW;
     if (n == 0) return ZXC_OK;
-    zt_shape_t sh;
-    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
-    // Chunk by chunk: a chunk's table and slots are written and consumed in stream order before the next chunk overwrites them.
-    // Every chunk but the last ends on a block boundary of the archive. The 32 bytes a block decoded straight may store behind
-    // itself stay inside the take: a copy of the same chunk or a later chunk fills them afterwards.
-    uint8_t* d = (uint8_t*)d_dst;
-    uint64_t left = n;
-    int rc = ZXC_OK;
-    while (left && rc == ZXC_OK) {
-        const uint64_t m = zt_chunk_len(s.pos, left, s.max_piece, s.block_size);
-        zt_chunk_t c;
-        zt_plan_chunk(s.pos, m, left, (uint32_t)((uintptr_t)d & 15u), s.block_size, s.cur, &c);
-        rc = tk_chunk(s, sh, d, c, (hipStream_t)stream);
-        zt_advance(&c, &s.pos, &s.cur);
-        d += m; left -= m;
-    }
-    if (rc != ZXC_OK) s.magic = 0;  // part of the take may be enqueued: the session cannot go on
-    memcpy(ds, &s, sizeof s);
-    return rc;
+    return tk_chunks(ds, s, sh, (uint8_t*)d_dst, NULL, n, ZXC_OK, (hipStream_t)stream);
 }
 
 uint64_t zxc_mi355x_decompress_takev_device_scratch_size(uint32_t n_iov, uint64_t max_piece, uint32_t block_size) {
@@ -360,79 +357,46 @@ int zxc_mi355x_decompress_takev_device(zxc_dev_dtake_t* ds, const zxc_dev_iov_t*
                                        uint64_t scratch_size, void* stream) {
     if (!ds || !d_scratch || (n_iov > 0 && !d_iov)) return ZXC_ERROR_NULL_INPUT;
     Sess s;
-    memcpy(&s, ds, sizeof s);
-    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    zt_shape_t sh;
+    if (!tk_load(ds, &s, &sh)) return ZXC_ERROR_NULL_INPUT;
     if (n_iov == 0 && total > 0) return ZXC_ERROR_DST_TOO_SMALL;
     if (total > s.dst_capacity - s.pos) return ZXC_ERROR_OVERFLOW;
-    zt_shape_t sh;
     ztv_shape_t vsh;
-    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0 || ztv_shape(n_iov, s.max_piece, s.block_size, &vsh) != 0)
-        return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
+    if (ztv_shape(n_iov, s.max_piece, s.block_size, &vsh) != 0) return ZXC_ERROR_NULL_INPUT;  // (begin accepted these)
     if (scratch_size < vsh.bytes) return ZXC_ERROR_MEMORY;
     if (n_iov == 0) return ZXC_OK;
     const hipStream_t st = (hipStream_t)stream;
     uint8_t* sb = zd_work_base(d_scratch);
     zav_ctl_t* vctl = (zav_ctl_t*)sb;
     uint64_t* starts = (uint64_t*)(sb + vsh.o_starts);
-    uint64_t* tile_sum = (uint64_t*)(sb + vsh.o_tile_sum);
-    uint32_t* tile_flags = (uint32_t*)(sb + vsh.o_tile_flags);
-    // The scan, once per call (appendv's kernels as they are; their fold goes to a zap_ctl_t in the scratch that nobody reads), and
-    // the fold of the verdict into the session: the chunks read starts and the verdict in stream order.
-    int rc = ZXC_OK;
-    hipLaunchKernelGGL(zxc_appendv_reduce_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, total, tile_sum, tile_flags);
-    if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_flags, vsh.n_tiles, total, starts,
-                           n_iov, vctl, (zap_ctl_t*)(sb + ZTV_SINK));
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
-    if (rc == ZXC_OK) {
-        hipLaunchKernelGGL(zxc_appendv_starts_kernel, dim3(vsh.n_tiles), dim3(ZD_TILE_THREADS), 0, st, d_iov, n_iov, (const uint64_t*)tile_sum, starts);
-        if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
-    }
+    // The scan, once per call (appendv's, as it is; its fold goes to a zap_ctl_t in the scratch that nobody reads), and the fold of
+    // the verdict into the session: the chunks read starts and the verdict in stream order.
+    int rc = zd_iov_scan(d_iov, n_iov, total, vsh.n_tiles, (uint64_t*)(sb + vsh.o_tile_sum), (uint32_t*)(sb + vsh.o_tile_flags), starts, vctl,
+                         (zap_ctl_t*)(sb + ZTV_SINK), st);
     if (rc == ZXC_OK) {
         hipLaunchKernelGGL(zxc_takev_fold_kernel, dim3(1), dim3(64), 0, st, vctl, (zc_ctl_t*)s.base);
         if (!launched()) rc = ZXC_ERROR_GPU_UNAVAILABLE;
     }
-    // The chunks, cut like those of a take of `total` bytes; v is the chunk's offset in the concatenation of the entries.
     const Vdst vd = {d_iov, n_iov, starts, vctl, (ztv_place_t*)(sb + vsh.o_places)};
-    uint64_t left = total, v = 0;
-    while (left && rc == ZXC_OK) {
-        const uint64_t m = zt_chunk_len(s.pos, left, s.max_piece, s.block_size);
-        ztv_chunk_t c;
-        ztv_plan_chunk(s.pos, m, s.block_size, s.cur, v, &c);
-        rc = tkv_chunk(s, sh, vd, c, st);
-        zt_advance(&c.c, &s.pos, &s.cur);
-        v += m; left -= m;
-    }
-    if (rc != ZXC_OK) s.magic = 0;  // part of the call may be enqueued: the session cannot go on
-    memcpy(ds, &s, sizeof s);
-    return rc;
+    return tk_chunks(ds, s, sh, NULL, &vd, total, rc, st);
 }
 
 int zxc_mi355x_decompress_end_device(zxc_dev_dtake_t* ds, int64_t* d_result, void* stream) {
     if (!ds || !d_result) return ZXC_ERROR_NULL_INPUT;
     Sess s;
-    memcpy(&s, ds, sizeof s);
-    if (s.magic != TAKE_LIVE) return ZXC_ERROR_NULL_INPUT;
+    zt_shape_t sh;
+    if (!tk_load(ds, &s, &sh)) return ZXC_ERROR_NULL_INPUT;
     if (s.pos < s.dst_capacity) return ZXC_ERROR_DST_TOO_SMALL;  // the verdict needs every block's status: take the rest, end again
     memset(ds, 0, sizeof *ds);  // spent, whatever happens below
-    zt_shape_t sh;
-    if (zt_shape(s.dst_capacity, s.max_piece, s.block_size, &sh) != 0) return ZXC_ERROR_NULL_INPUT;
     const hipStream_t st = (hipStream_t)stream;
-    zc_ctl_t* ctl = (zc_ctl_t*)s.base;
-    const int32_t* status = (const int32_t*)(s.base + sh.o_status);
-    if (s.dst_capacity > 0) {
+    const Work w = tk_work(s, sh);
+    if (s.dst_capacity > 0) {  // the one job behind the capacity, between the session's two halves of zxc_mi355x_decompress_device
         zt_chunk_t c;
         zt_plan_extra(sh.n_jobs - 1u, s.block_size, s.cur, &c);
-        const int rc = tk_decode(s, sh, NULL, c, st);
+        const int rc = tk_decode(s, sh, w, NULL, c, st);
         if (rc != ZXC_OK) return rc;
-        const uint32_t groups = sh.n_tiles * 4u < 1024u ? sh.n_tiles * 4u : 1024u;
-        hipLaunchKernelGGL(zxc_unframe_events_kernel, dim3(groups), dim3(256), 0, st, status, s.block_size, sh.n_jobs, s.dst_capacity, ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
     }
-    hipLaunchKernelGGL(zxc_unframe_result_kernel, dim3(1), dim3(64), 0, st, (const zc_ctl_t*)ctl, status, s.block_size, sh.n_jobs, d_result);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return zd_verdict_stages(w.c, s.block_size, s.dst_capacity, d_result, st);
 }
 
 }  // extern "C"

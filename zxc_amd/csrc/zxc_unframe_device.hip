@@ -26,7 +26,6 @@
 // dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launches get the dictionary (the plan then is
 // the dictionary kernel, one wavefront per block).
 #include "zxc_device_util.h"  // the tile passes, the copy, the host-side plumbing; zxc_container.h: the container rules
-#include "zxc_kernels.h"      // the stages the take session launches as well are declared there
 
 // ---------------------------------------------------------------- kernels
 extern "C" __global__ void __launch_bounds__(64)
@@ -198,47 +197,28 @@ static int unframe_call(const void* d_src, uint64_t src_size, void* d_dst, uint6
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t want_verify = (opts && opts->checksum_enabled) ? 1u : 0u, tables = 1u + want_verify;
     uint8_t* base = zd_work_base(d_work);
-    zc_ctl_t* ctl = (zc_ctl_t*)base;
-    uint64_t* tile_sum = (uint64_t*)(base + s.o_tile_sum);
-    uint32_t* tile_hash = (uint32_t*)(base + s.o_tile_hash);
-    uint32_t* tile_bad = (uint32_t*)(base + s.o_tile_bad);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
-    int32_t* status = (int32_t*)(base + s.o_status);
+    const zd_cwork_t w = zd_cwork(base, s);
+    const zd_dict_t dc = zd_dict_of(dict);
     uint8_t* stage = base + s.o_stage;
-    const uint8_t* src = (const uint8_t*)d_src;
 
-    if (hipMemsetAsync(jobs, 0, (size_t)tables * s.n_jobs * sizeof(zxc_dev_job_t), st) != hipSuccess) return ZXC_ERROR_GPU_UNAVAILABLE;
-    hipLaunchKernelGGL(zxc_unframe_head_kernel, dim3(1), dim3(64), 0, st, src, src_size, dst_capacity, block_size, want_verify, s.n_jobs, ctl,
-                       dict ? dict->d_id : (const uint32_t*)NULL);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const void* d_dict = dict ? dict->d_content : NULL;
-    const void* d_huf = dict ? dict->d_huf : NULL;
-    const uint32_t dict_size = dict ? dict->size : 0u;
-    if (dst_capacity > 0) {  // (the empty-frame probe is answered by the head stage alone)
-        hipLaunchKernelGGL(zxc_unframe_tiles_kernel, dim3(s.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)ctl, tile_sum, tile_bad);
-        hipLaunchKernelGGL(zxc_unframe_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, (const uint32_t*)tile_bad, s.n_tiles, ctl);
-        hipLaunchKernelGGL(zxc_unframe_scatter_kernel, dim3(s.n_tiles), dim3(ZD_TILE_THREADS), 0, st, src, (const zc_ctl_t*)ctl,
-                           (const uint64_t*)tile_sum, block_size, s.k_direct, s.n_jobs, jobs, tile_hash, tile_bad);
-        hipLaunchKernelGGL(zxc_unframe_walk_kernel, dim3(1), dim3(256), 0, st, src, src_size, block_size, s.k_direct, s.n_jobs,
-                           (const uint32_t*)tile_hash, (const uint32_t*)tile_bad, jobs, ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const int crc = zd_container_stages(w, (const uint8_t*)d_src, src_size, dst_capacity, block_size, want_verify, s.k_direct, dc.id, st);
+    if (crc != ZXC_OK) return crc;
+    if (dst_capacity > 0) {
+        // Not zd_decode_tables: per table the direct launch, then the staged one. Two calls of the helper would enqueue both
+        // tables' direct launches in front of the staged ones, another stream order than this call has always had.
         for (uint32_t tb = 0; tb < tables; tb++) {
-            const zxc_dev_job_t* tab = jobs + (uint64_t)tb * s.n_jobs;
-            int32_t* tst = status + (uint64_t)tb * s.n_jobs;
-            int rc = zxc_hip_decode_blocks(d_src, tab, s.k_direct, d_dst, tst, block_size, (int)tb, d_dict, dict_size, d_huf, 0u, stream);
+            const zxc_dev_job_t* tab = w.jobs + (uint64_t)tb * s.n_jobs;
+            int32_t* tst = w.status + (uint64_t)tb * s.n_jobs;
+            int rc = zxc_hip_decode_blocks(d_src, tab, s.k_direct, d_dst, tst, block_size, (int)tb, dc.content, dc.size, dc.huf, 0u, stream);
             if (rc == ZXC_OK)
-                rc = zxc_hip_decode_blocks(d_src, tab + s.k_direct, s.n_jobs - s.k_direct, stage, tst + s.k_direct, block_size, (int)tb, d_dict,
-                                           dict_size, d_huf, 0u, stream);
+                rc = zxc_hip_decode_blocks(d_src, tab + s.k_direct, s.n_jobs - s.k_direct, stage, tst + s.k_direct, block_size, (int)tb, dc.content,
+                                           dc.size, dc.huf, 0u, stream);
             if (rc != ZXC_OK) return rc;
         }
-        hipLaunchKernelGGL(zxc_unframe_tail_kernel, dim3(ZC_STAGED_MAX), dim3(256), 0, st, (const uint8_t*)stage, (const int32_t*)status,
-                           (const zc_ctl_t*)ctl, block_size, s.k_direct, s.n_jobs, (uint8_t*)d_dst, dst_capacity);
-        const uint32_t groups = s.n_tiles * 4u < 1024u ? s.n_tiles * 4u : 1024u;
-        hipLaunchKernelGGL(zxc_unframe_events_kernel, dim3(groups), dim3(256), 0, st, (const int32_t*)status, block_size, s.n_jobs, dst_capacity, ctl);
-        if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+        hipLaunchKernelGGL(zxc_unframe_tail_kernel, dim3(ZC_STAGED_MAX), dim3(256), 0, st, (const uint8_t*)stage, (const int32_t*)w.status,
+                           (const zc_ctl_t*)w.ctl, block_size, s.k_direct, s.n_jobs, (uint8_t*)d_dst, dst_capacity);
     }
-    hipLaunchKernelGGL(zxc_unframe_result_kernel, dim3(1), dim3(64), 0, st, (const zc_ctl_t*)ctl, (const int32_t*)status, block_size, s.n_jobs, d_result);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return zd_verdict_stages(w, block_size, dst_capacity, d_result, st);  // (its first launch check covers the tail stage)
 }
 
 int zxc_mi355x_decompress_device(const void* d_src, uint64_t src_size, void* d_dst, uint64_t dst_capacity, uint32_t block_size,

@@ -9,17 +9,17 @@ and UBSan in a stand-alone program."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-from zxc_amd.api import _CompressOpts, _DevCappend as Cs  # zxc_dev_cappend_t
+import cshim
+from conftest import GOLDEN
+from cshim import opts as _opts, ref as _ref
+from devtest import ERR
+from zxc_amd.api import _DevCappend as Cs  # zxc_dev_cappend_t
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x30000, 0x40000, 0x50000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, CORRUPT_DATA=-8, OVERFLOW=-10, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, GPU_UNAVAILABLE=-100,
-           GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 JOB_BYTES, TILE_BYTES, AREAS, PAD, WORK_FIXED = 28, 16, 3, 64, 4096  # the stated bound: J (S + 28) + 16 ceil(J / 1024) + 3 (bs + 64) + 4 NB + 4096
@@ -30,28 +30,17 @@ def _stride(bs):
     return 2 * bs + 512  # zxc_mi355x_encode_slot_stride, checked against the library below
 
 
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
-
-
 def _host_dict_opts(**kw):
-    o = _opts(**kw)
-    o.dict, o.dict_size = FAKE_SRC, 100
-    return o
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
+    return cshim.host_dict(_opts(**kw))
 
 
 @pytest.fixture(scope="module")
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_begin_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_begin_device"
-    L.zxc_mi355x_encode_slot_stride.restype = C.c_uint32
     for bs in BLOCK_SIZES:
         assert int(L.zxc_mi355x_encode_slot_stride(bs)) == _stride(bs)
-    return product.api._bind_compress_append_device(L)
+    return L
 
 
 def _ws(L, max_total, max_piece, o):
@@ -73,7 +62,8 @@ def test_symbols_and_names_exported(product):
         assert hasattr(L, sym), sym
     for name in ("compress_append_device_work_size", "compress_begin_device"):
         assert hasattr(product, name) and hasattr(product.api, name), name
-    assert hasattr(product.api, "_bind_compress_append_device")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_compress_append_device_work_size", "zxc_mi355x_compress_begin_device",
+                                                          "zxc_mi355x_compress_append_device", "zxc_mi355x_compress_end_device"))
     assert hasattr(product.api.CompressAppendSession, "append") and hasattr(product.api.CompressAppendSession, "end")
 
 
@@ -166,10 +156,7 @@ class Shape(C.Structure):  # zap_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("append") / "libappend_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "append", "append_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "append", "append/append_shim.c")
     for f in ("t_shape_size", "t_ctl_size", "t_piece_size"):
         getattr(S, f).restype = C.c_size_t
     assert S.t_shape_size() == C.sizeof(Shape) and S.t_ctl_size() <= 256
@@ -426,12 +413,5 @@ def test_a_block_size_outside_the_range_is_corrupt_data(shim, ref):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/append/append_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "append_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "append", "append_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "APPEND OK 784" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "append/append_san_main.c")
+    assert "APPEND OK 784" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

@@ -9,39 +9,30 @@ byte for byte, bytes 6..15 of the file header included, with a pattern intact ev
 AddressSanitizer and UBSan in a stand-alone program."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT, load_dict
-from zxc_amd.api import _CompressOpts, _DevCappend as Cs, _DevDict  # zxc_dev_cappend_t, zxc_dev_dict_t
+import cshim
+from conftest import GOLDEN, load_dict
+from cshim import opts as _opts, ref as _ref
+from devtest import ERR
+from zxc_amd.api import _DevCappend as Cs, _DevDict  # zxc_dev_cappend_t, zxc_dev_dict_t
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_DICT, FAKE_ID, FAKE_HUF = 0x10000, 0x30000, 0x40000, 0x60000, 0x70000, 0x80000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, DICT_TOO_LARGE=-17, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 DICT_SIZES = (0, 1, 4097, 65535)
 JOB_BYTES, TILE_BYTES, AREAS, PAD, WORK_FIXED, IMAGE_FIXED = 28, 16, 3, 64, 4096, 320
 # the stated bound: J (S + 28) + 16 ceil(J / 1024) + 3 (bs + 64) + 4 NB (seekable) + 4096 + min(J, C) (bs + D) + 320
 DICTS = (("dict_http.zxc", "dict_http.expected", "dict_http.zxd"), ("dict_seekable_l7.zxc", "dict_seekable_l7.expected", "dict_text.zxd"))
-GCC = ["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function"]
-
-
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
+NO_UNUSED = ["-Wno-unused-function"]  # (the replay headers the C sources include serve other programs too)
 
 
 def _host_dict_opts(**kw):
-    o = _opts(**kw)
-    o.dict, o.dict_size = FAKE_SRC, 100
-    return o
+    return cshim.host_dict(_opts(**kw))
 
 
 def _dict(size=100, content=FAKE_DICT, huf=None, did=FAKE_ID):
     return _DevDict(content, huf, did, size)
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +40,7 @@ def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_begin_dict_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_begin_dict_device"
     assert C.sizeof(_DevDict) == 32
-    return product.api._bind_compress_append_device(L)
+    return L
 
 
 def _ws(L, max_total, max_piece, o, dict_size):
@@ -179,9 +170,7 @@ class ShapeImages(C.Structure):  # zap_shape_images_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("append_dict") / "libappend_dict_shim.so")
-    subprocess.run(GCC + ["-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "append", "append_dict_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "append_dict", "append/append_dict_shim.c", NO_UNUSED)
     S.t_shape_images_size.restype = C.c_size_t
     assert S.t_shape_images_size() == C.sizeof(ShapeImages)
     S.t_shape_images.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(ShapeImages)]
@@ -316,10 +305,6 @@ def test_sessions_put_the_reference_dictionary_archives_together_again(shim, ref
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/append/append_dict_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "append_dict_san")
-    r = subprocess.run(GCC + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                              os.path.join(ROOT, "tests", "append", "append_dict_san_main.c")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
     args, want = [], 0  # (a golden's cut sets: 70 at each end of the first block, and the random ones)
     for k, (arc, comp, data, content) in enumerate(_golden_dicts()):
         p = tmp_path / ("dict%d.bin" % k)
@@ -327,8 +312,6 @@ def test_rules_under_sanitizers(tmp_path):
         d = os.path.join(GOLDEN, "conformance", "valid")
         args += [os.path.join(d, arc), os.path.join(d, arc.replace(".zxc", ".expected")), str(p)]
         want += 140 + 12
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "APPEND DICT OK" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "append/append_dict_san_main.c", args, NO_UNUSED)
+    assert "APPEND DICT OK" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])
     assert int(r.stdout.split()[-1]) > want + 1000  # the goldens' cut sets and the program's own

@@ -10,17 +10,17 @@ import bisect
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-from zxc_amd.api import _CompressOpts, _DevCappend as Cs  # zxc_dev_cappend_t
+import cshim
+from conftest import GOLDEN
+from cshim import opts as _opts, ref as _ref
+from devtest import ERR
+from zxc_amd.api import _DevCappend as Cs  # zxc_dev_cappend_t
 
 FAKE_IOV, FAKE_DST, FAKE_WORK, FAKE_SCRATCH, FAKE_DICT = 0x10000, 0x30000, 0x40000, 0x50000, 0x60000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, CORRUPT_DATA=-8, OVERFLOW=-10, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14,
-           GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 BAD_BLOCK_SIZES = (1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 TILE_BYTES, IMAGE_SLACK, FIXED = 16, 256, 4096  # the stated bound: 8 (n + 1) + 16 ceil(n / 1024) + J (bs + 256) + 4096
@@ -29,19 +29,11 @@ CANARY = 0xC3
 RP_BAD_PLAN = -1000
 
 
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
-
-
 @pytest.fixture(scope="module")
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_appendv_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_appendv_device"
-    return product.api._bind_compress_append_device(L)
+    return L
 
 
 def _live(total=0, max_total=1 << 24, max_piece=1 << 20, bs=65536, dict_size=0):
@@ -75,7 +67,7 @@ def test_symbols_and_names_exported(product):
     assert hasattr(product.api.CompressAppendSession, "appendv")
     d = product.IOV_DTYPE
     assert d.names == ("base", "len") and d.itemsize == 16 and all(d[n] == np.dtype("<u8") for n in d.names)
-    b = product.api._bind_compress_append_device(L)
+    b = product.lib()
     assert b.zxc_mi355x_compress_appendv_device.argtypes is not None and b.zxc_mi355x_compress_appendv_device_scratch_size.restype is C.c_uint64
 
 
@@ -144,10 +136,7 @@ IOV = np.dtype([("base", "<u8"), ("len", "<u8")])
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("appendv") / "libappendv_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "append", "appendv_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "appendv", "append/appendv_shim.c")
     for f in ("t_vshape_size", "t_vctl_size", "t_iov_size"):
         getattr(S, f).restype = C.c_size_t
     assert S.t_vshape_size() == C.sizeof(VShape) and S.t_vctl_size() <= 256 and S.t_iov_size() == 16 == IOV.itemsize
@@ -489,12 +478,5 @@ def test_a_table_error_reads_nothing_and_stays(shim):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/append/appendv_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "appendv_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "append", "appendv_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "APPENDV OK 664" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "append/appendv_san_main.c")
+    assert "APPENDV OK 664" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

@@ -9,39 +9,31 @@ stand-in encoder runs, and the output the archive byte for byte, with a pattern 
 AddressSanitizer and UBSan in a stand-alone program in which every entry is a malloc of exactly its length."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, load_dict
-from zxc_amd.api import _CompressOpts, _DevCappend as Cs  # zxc_dev_cappend_t
+import cshim
+from conftest import GOLDEN, load_dict
+from cshim import opts as _opts, ref as _ref
+from devtest import ERR
+from zxc_amd.api import _DevCappend as Cs  # zxc_dev_cappend_t
 
 FAKE_IOV, FAKE_DST, FAKE_WORK, FAKE_SCRATCH, FAKE_DICT = 0x10000, 0x30000, 0x40000, 0x50000, 0x60000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, CORRUPT_DATA=-8, OVERFLOW=-10, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14,
-           GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 BAD_BLOCK_SIZES = (1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 DICT_SIZES = (1, 100, 65535)
 TILE_BYTES, FIXED = 16, 4096  # the stated bound: 8 (n + 1) + 16 ceil(n / 1024) + 4096
 SESS_LIVE = 0x7A78632D61707064  # a session between begin and end (zxc_append_device.hip)
 DICTS = (("dict_http.zxc", "dict_http.expected", "dict_http.zxd"), ("dict_seekable_l7.zxc", "dict_seekable_l7.expected", "dict_text.zxd"))
-GCC = ["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function"]  # (the replay headers it includes serve other programs too)
-
-
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
+NO_UNUSED = ["-Wno-unused-function"]  # (the replay headers the C sources include serve other programs too)
 
 
 @pytest.fixture(scope="module")
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_appendv_dict_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_appendv_dict_device"
-    return product.api._bind_compress_append_device(L)
+    return L
 
 
 def _live(total=0, max_total=1 << 24, max_piece=1 << 20, bs=65536, dict_size=100):
@@ -77,7 +69,7 @@ def test_symbols_and_names_exported(product):
     name = "compress_appendv_dict_device_scratch_size"
     assert hasattr(product, name) and hasattr(product.api, name), name
     assert hasattr(product.api.CompressAppendSession, "appendv_dict")
-    b = product.api._bind_compress_append_device(L)
+    b = product.lib()
     f, g = b.zxc_mi355x_compress_appendv_dict_device, b.zxc_mi355x_compress_appendv_dict_device_scratch_size
     assert f.argtypes is not None and len(f.argtypes) == 7 and f.restype is C.c_int
     assert g.argtypes is not None and len(g.argtypes) == 4 and g.restype is C.c_uint64
@@ -154,9 +146,7 @@ IOV = np.dtype([("base", "<u8"), ("len", "<u8")])
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("appendv_dict") / "libappendv_dict_shim.so")
-    subprocess.run(GCC + ["-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "append", "appendv_dict_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "appendv_dict", "append/appendv_dict_shim.c", NO_UNUSED)
     for f in ("t_vshape_size", "t_stats_size"):
         getattr(S, f).restype = C.c_size_t
     assert S.t_vshape_size() == C.sizeof(VShape) and S.t_stats_size() == C.sizeof(Stats)
@@ -316,18 +306,12 @@ def test_a_table_error_reads_nothing_and_stays(shim):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/append/appendv_dict_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "appendv_dict_san")
-    r = subprocess.run(GCC + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                              os.path.join(ROOT, "tests", "append", "appendv_dict_san_main.c")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
     args = []
     for k, (arc, comp, data, content) in enumerate(_golden_dicts()):
         p = tmp_path / ("dict%d.bin" % k)
         p.write_bytes(content)
         d = os.path.join(GOLDEN, "conformance", "valid")
         args += [os.path.join(d, arc), os.path.join(d, arc.replace(".zxc", ".expected")), str(p)]
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
+    r = cshim.run_san_program(tmp_path, "append/appendv_dict_san_main.c", args, NO_UNUSED)
     want = 2 * 30 * 17 + len(DICTS) * 17 + 7 * 2 * 5  # the program's own archives twice, the goldens, the bad tables
-    assert r.returncode == 0 and not bad and "APPENDV DICT OK %d" % want in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    assert "APPENDV DICT OK %d" % want in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

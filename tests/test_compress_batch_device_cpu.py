@@ -7,18 +7,16 @@ pattern intact everywhere else. The same rules run under AddressSanitizer and UB
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-from zxc_amd.api import _CompressOpts, _DevDict
+import cshim
+from conftest import GOLDEN
+from cshim import FAKE_DICT, FAKE_HUF, FAKE_ID, dd as _dd, opts as _opts, ref as _ref  # noqa: F401  (the pack call's tests take them from here)
+from devtest import ERR
 
 FAKE_SRC, FAKE_ITEMS, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
-FAKE_DICT, FAKE_HUF, FAKE_ID = 0x70000, 0x80000, 0x90000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, CORRUPT_DATA=-8, OVERFLOW=-10, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14,
-           DICT_TOO_LARGE=-17, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 REC_BYTES, JOB_BYTES, WORK_FIXED, IMAGE_FIXED = 64, 28, 1536, 320  # the stated bound: n J (S + 28) + 64 n + 1536 (+ images + 320)
@@ -30,22 +28,13 @@ def _stride(bs):
     return 2 * bs + 512  # zxc_mi355x_encode_slot_stride, checked against the library below
 
 
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
-
-
 @pytest.fixture(scope="module")
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_batch_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_batch_device"
-    L.zxc_mi355x_encode_slot_stride.restype = C.c_uint32
     for bs in BLOCK_SIZES:
         assert int(L.zxc_mi355x_encode_slot_stride(bs)) == _stride(bs)
-    return product.api._bind_compress_batch_device(L)
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
+    return L
 
 
 def _ws(L, n, max_size, o, dict_size=None):
@@ -66,13 +55,7 @@ def _call(L, n=8, max_size=100000, o="default", src_cap=1 << 20, cap=1 << 20, sr
 
 
 def _host_dict_opts(**kw):
-    o = _opts(**kw)
-    o.dict, o.dict_size = FAKE_SRC, 100
-    return o
-
-
-def _dd(size=1000, content=FAKE_DICT, huf=FAKE_HUF, id_=FAKE_ID):
-    return _DevDict(content, huf, id_, size)
+    return cshim.host_dict(_opts(**kw))
 
 
 def test_symbols_and_names_exported(product):
@@ -82,7 +65,9 @@ def test_symbols_and_names_exported(product):
         assert hasattr(L, sym), sym
     for name in ("compress_batch_device_work_size", "compress_batch_device", "compress_batch_dict_device"):
         assert hasattr(product, name) and hasattr(product.api, name), name
-    assert hasattr(product.api, "_bind_compress_batch_device")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_compress_batch_device_work_size", "zxc_mi355x_compress_batch_device",
+                                                          "zxc_mi355x_compress_batch_dict_device_work_size",
+                                                          "zxc_mi355x_compress_batch_dict_device"))
 
 
 def test_each_synchronous_error_and_their_order(L):
@@ -217,10 +202,7 @@ JOB = np.dtype([("src_off", "<u8"), ("len", "<u4"), ("pad", "<u4")])
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("cbatch") / "libcbatch_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "batch", "cbatch_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "cbatch", "batch/cbatch_shim.c")
     for f in ("t_rec_size", "t_item_size", "t_shape_size", "t_job_size"):
         getattr(S, f).restype = C.c_size_t
     assert (S.t_rec_size(), S.t_item_size(), S.t_shape_size(), S.t_job_size()) == (REC_BYTES, 32, C.sizeof(Shape), JOB.itemsize)
@@ -493,12 +475,5 @@ def test_finish_refuses_sizes_outside_the_legal_range(shim):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/batch/cbatch_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "cbatch_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "batch", "cbatch_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "CBATCH OK 128" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "batch/cbatch_san_main.c")
+    assert "CBATCH OK 128" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

@@ -4,25 +4,15 @@ import ctypes as C
 
 import pytest
 
-from zxc_amd.api import _CompressOpts
+from cshim import opts as _opts
+from devtest import ERR
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x20000, 0x30000, 0x40000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 
 
 @pytest.fixture(scope="module")
 def L(product):
-    L = product.lib()
-    L.zxc_mi355x_compress_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_device.restype = C.c_int
-    L.zxc_mi355x_compress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts),
-                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    return L
-
-
-def _opts(level=3, block_size=65536, seekable=False, checksum=False):
-    return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
+    return product.lib()
 
 
 def _ws(L, n, o):
@@ -68,7 +58,6 @@ def test_work_size_arithmetic(L):
 
 
 def product_stride(L, bs):
-    L.zxc_mi355x_encode_slot_stride.restype = C.c_uint32
     return int(L.zxc_mi355x_encode_slot_stride(bs))
 
 

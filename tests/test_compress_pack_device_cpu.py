@@ -8,12 +8,12 @@ a pattern intact in every gap, behind *d_total and behind the capacity. The same
 a stand-alone program."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+import cshim
+from conftest import GOLDEN
 from test_compress_batch_device_cpu import (BAD_BLOCK_SIZES, BLOCK_SIZES, CANARY, ERR, FAKE_DICT, FAKE_DST, FAKE_HUF, FAKE_ID, FAKE_ITEMS,
                                             FAKE_RES, FAKE_SRC, FAKE_WORK, IMAGE_FIXED, JOB, JOB_BYTES, M64, REC_BYTES, WORK_FIXED, Arc, Item,
                                             Rec, Shape, _dd, _host_dict_opts, _opts, _ref, _ref_arcs, _stride)
@@ -27,8 +27,7 @@ ALIGNS = (1, 16, 256, 4096)
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_compress_pack_device"), "libzxc_mi355x.so does not export zxc_mi355x_compress_pack_device"
-    product.api._bind_compress_batch_device(L)
-    return product.api._bind_compress_pack_device(L)
+    return L
 
 
 def _ws(L, n, max_size, o, dict_size=None):
@@ -62,7 +61,9 @@ def test_symbols_and_names_exported(product):
         assert hasattr(L, sym), sym
     for name in ("compress_pack_device_work_size", "compress_pack_device", "compress_pack_dict_device"):
         assert hasattr(product, name) and hasattr(product.api, name), name
-    assert hasattr(product.api, "_bind_compress_pack_device")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_compress_pack_device_work_size", "zxc_mi355x_compress_pack_device",
+                                                          "zxc_mi355x_compress_pack_dict_device_work_size",
+                                                          "zxc_mi355x_compress_pack_dict_device"))
 
 
 def test_each_synchronous_error_and_their_order(product, L):
@@ -196,10 +197,7 @@ class PShape(C.Structure):  # zcp_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("cpack") / "libcpack_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "batch", "cpack_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "cpack", "batch/cpack_shim.c")
     S.t_pshape_size.restype = C.c_size_t
     assert S.t_pshape_size() == C.sizeof(PShape)
     S.t_pshape.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PShape)]
@@ -415,12 +413,5 @@ def test_in_place(shim, ref):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/batch/cpack_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "cpack_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "batch", "cpack_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "CPACK OK" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "batch/cpack_san_main.c")
+    assert "CPACK OK" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

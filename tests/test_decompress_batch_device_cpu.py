@@ -7,18 +7,17 @@ bytes, capacity and options, with every write inside the item's own destination 
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, load_dict
-from zxc_amd.api import _DecompressOpts, _DevDict
+import cshim
+from conftest import GOLDEN, load_dict
+from cshim import FAKE_DICT, FAKE_ID, dd as _dd, ref as _ref
+from devtest import ERR
+from zxc_amd.api import _DecompressOpts
 
 FAKE_SRC, FAKE_ITEMS, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
-FAKE_DICT, FAKE_HUF, FAKE_ID = 0x70000, 0x80000, 0x90000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, BAD_MAGIC=-4, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15,
-           DICT_MISMATCH=-16, DICT_TOO_LARGE=-17, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (0, 1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 REC_BYTES, JOB_BYTES, WORK_FIXED = 128, 56, 1536  # the stated bound: n J (block_size + 64) + 56 n J + 128 n + 1536
@@ -31,15 +30,11 @@ DST_REL = 1 << 40  # d_dst's distance from the launch's base in the emulation: a
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_decompress_batch_device"), "libzxc_mi355x.so does not export zxc_mi355x_decompress_batch_device"
-    return product.api._bind_decompress_batch_device(L)
+    return L
 
 
 def _ws(L, n, max_cap, bs):
     return int(L.zxc_mi355x_decompress_batch_device_work_size(n, max_cap, bs))
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
 
 
 def _call(L, n=8, max_cap=100000, bs=65536, src_cap=1 << 20, cap=1 << 20, src=FAKE_SRC, items=FAKE_ITEMS, dst=FAKE_DST, work=FAKE_WORK,
@@ -52,13 +47,7 @@ def _call(L, n=8, max_cap=100000, bs=65536, src_cap=1 << 20, cap=1 << 20, src=FA
 
 
 def _host_dict_opts():
-    o = _DecompressOpts()
-    o.dict, o.dict_size = FAKE_SRC, 100
-    return o
-
-
-def _dd(size=1000, content=FAKE_DICT, huf=FAKE_HUF, id_=FAKE_ID):
-    return _DevDict(content, huf, id_, size)
+    return cshim.host_dict(_DecompressOpts())
 
 
 def test_symbols_and_names_exported(product):
@@ -68,7 +57,8 @@ def test_symbols_and_names_exported(product):
         assert hasattr(L, sym), sym
     for name in ("ITEM_DTYPE", "decompress_batch_device_work_size", "decompress_batch_device", "decompress_batch_dict_device"):
         assert hasattr(product, name) and hasattr(product.api, name), name
-    assert hasattr(product.api, "_bind_decompress_batch_device")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_decompress_batch_device_work_size", "zxc_mi355x_decompress_batch_device",
+                                                          "zxc_mi355x_decompress_batch_dict_device"))
     assert product.ITEM_DTYPE.itemsize == 32 and product.ITEM_DTYPE.names == ("src_off", "src_size", "dst_off", "dst_capacity")
 
 
@@ -191,10 +181,7 @@ class Shape(C.Structure):  # zb_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("batch") / "libbatch_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "batch", "batch_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "batch", "batch/batch_shim.c")
     for f in ("t_rec_size", "t_item_size", "t_shape_size", "t_job_size"):
         getattr(S, f).restype = C.c_size_t
     assert (S.t_rec_size(), S.t_item_size(), S.t_shape_size(), S.t_job_size()) == (REC_BYTES, 32, C.sizeof(Shape), 24)

@@ -5,17 +5,16 @@ and the walk give the job table of Seekable.plan() / of a header walk restated b
 decoder's block statuses gives what the oracle's whole-frame decoder (the CPU restatement of zxc_decompress) returns."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+import cshim
+from conftest import GOLDEN
+from devtest import ERR
 from zxc_amd.api import _DecompressOpts
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x20000, 0x30000, 0x40000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, BAD_MAGIC=-4, BAD_HEADER=-6, BAD_CHECKSUM=-7, CORRUPT_DATA=-8, NULL_INPUT=-12,
-           BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 JOB_BYTES = 24
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 # archives written with a dictionary: the call takes none, so the device's answer is the header's dictionary id -> DICT_REQUIRED
@@ -28,7 +27,7 @@ DICT_ARCHIVES = {"conformance/valid/dict_http.zxc", "conformance/valid/dict_seek
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_decompress_device"), "libzxc_mi355x.so does not export zxc_mi355x_decompress_device"
-    return product.api._bind_decompress_device(L)
+    return L
 
 
 def _ws(L, n, cap, bs):
@@ -145,10 +144,7 @@ class Shape(C.Structure):  # zc_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("container") / "libcontainer_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "container", "container_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "container", "container/container_shim.c")
     S.t_ctl_size.restype = S.t_shape_size.restype = C.c_size_t
     assert S.t_ctl_size() == C.sizeof(Ctl) and S.t_shape_size() == C.sizeof(Shape)
     S.t_shape.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(Shape)]

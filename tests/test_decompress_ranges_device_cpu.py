@@ -7,16 +7,15 @@ range result and bytes, with nothing written outside the valid ranges."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+import cshim
+from conftest import GOLDEN
+from devtest import ERR
 
 FAKE_SRC, FAKE_IDX, FAKE_RNG, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, BAD_MAGIC=-4, BAD_HEADER=-6, CORRUPT_DATA=-8, NULL_INPUT=-12,
-           BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (0, 1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 JOB_BYTES, WORK_FIXED = 44, 1536  # the stated bound: n J (block_size + 64) + 44 n J + 1536
@@ -27,7 +26,7 @@ CANARY = 0xC3
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_decompress_ranges_device"), "libzxc_mi355x.so does not export zxc_mi355x_decompress_ranges_device"
-    return product.api._bind_ranges_device(L)
+    return L
 
 
 def _open(L, n=1000, bs=65536, mb=10, src=FAKE_SRC, idx=FAKE_IDX, isz=None):
@@ -176,10 +175,7 @@ class Shape(C.Structure):  # zr_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("ranges") / "libranges_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "ranges", "ranges_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "ranges", "ranges/ranges_shim.c")
     for f in ("t_index_hdr_size", "t_copy_size", "t_shape_size", "t_range_size"):
         getattr(S, f).restype = C.c_size_t
     assert (S.t_index_hdr_size(), S.t_copy_size(), S.t_shape_size(), S.t_range_size()) == (64, 16, C.sizeof(Shape), 24)

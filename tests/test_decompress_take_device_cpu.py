@@ -10,39 +10,32 @@ program."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+import cshim
+from conftest import GOLDEN
+from cshim import ref as _ref
+from devtest import ERR
 from zxc_amd.api import _DecompressOpts, _DevDict, _DevDtake as Ds  # zxc_dev_dtake_t
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x30000, 0x40000, 0x50000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, OVERFLOW=-10, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15,
-           DICT_TOO_LARGE=-17, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (0, 1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 BLOCK_BYTES, TILE_BYTES, JOB_BYTES, PAD, CARRIES, WORK_FIXED = 56, 16, 48, 64, 2, 4096  # the stated bound
 BAD_PLAN = -1000
 
 
-def _ref(x):
-    return C.byref(x) if x is not None else None
-
-
 def _host_dict_opts():
-    o = _DecompressOpts()
-    o.dict, o.dict_size = FAKE_SRC, 100
-    return o
+    return cshim.host_dict(_DecompressOpts())
 
 
 @pytest.fixture(scope="module")
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_decompress_begin_device"), "libzxc_mi355x.so does not export zxc_mi355x_decompress_begin_device"
-    product.api._bind_decompress_device(L)
-    return product.api._bind_decompress_take_device(L)
+    return L
 
 
 def _ws(L, n, cap, mp, bs):
@@ -65,7 +58,9 @@ def test_symbols_and_names_exported(product):
         assert hasattr(L, sym), sym
     for name in ("decompress_take_device_work_size", "decompress_begin_device", "decompress_begin_dict_device", "DecompressTakeSession"):
         assert hasattr(product, name) and hasattr(product.api, name), name
-    assert hasattr(product.api, "_bind_decompress_take_device") and hasattr(product.api, "_DevDtake")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_decompress_take_device_work_size", "zxc_mi355x_decompress_begin_device",
+                                                          "zxc_mi355x_decompress_begin_dict_device", "zxc_mi355x_decompress_take_device",
+                                                          "zxc_mi355x_decompress_end_device")) and hasattr(product.api, "_DevDtake")
     assert hasattr(product.api.DecompressTakeSession, "take") and hasattr(product.api.DecompressTakeSession, "end")
     assert C.sizeof(product.api._DevDtake) == 128
 
@@ -167,10 +162,7 @@ class Shape(C.Structure):  # zt_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("take") / "libtake_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "take", "take_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "take", "take/take_shim.c")
     S.t_shape_size.restype = S.t_chunk_size.restype = C.c_size_t
     assert S.t_shape_size() == C.sizeof(Shape)
     S.t_shape.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Shape)]
@@ -427,12 +419,5 @@ def test_dictionary_rule_of_the_head(shim, oracle):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/take/take_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "take_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "take", "take_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "TAKE OK 2688" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "take/take_san_main.c")
+    assert "TAKE OK 2688" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

@@ -9,16 +9,16 @@ around it. The same replay runs under AddressSanitizer and UBSan in a stand-alon
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import cshim
 import test_decompress_take_device_cpu as T
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from devtest import ERR
 from zxc_amd.api import IOV_DTYPE, _DevDtake as Ds
 
-ERR = T.ERR
 FAKE_IOV, FAKE_SCRATCH = 0x60000, 0x70000
 TAKE_LIVE = 0x7A78632D74616B65
 TAKE = 0xFFFFFFFF
@@ -29,7 +29,7 @@ BAD_PLAN = T.BAD_PLAN
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_decompress_takev_device"), "libzxc_mi355x.so does not export zxc_mi355x_decompress_takev_device"
-    return product.api._bind_decompress_takev_device(L)
+    return L
 
 
 def _ss(L, n_iov, mp, bs):
@@ -54,7 +54,8 @@ def test_symbols_and_names_exported(product):
     for sym in ("zxc_mi355x_decompress_takev_device_scratch_size", "zxc_mi355x_decompress_takev_device"):
         assert hasattr(L, sym), sym
     assert hasattr(product, "decompress_takev_device_scratch_size") and hasattr(product.api, "decompress_takev_device_scratch_size")
-    assert hasattr(product.api, "_bind_decompress_takev_device") and hasattr(product.api.DecompressTakeSession, "takev")
+    assert all(sym in product.api._PROTOTYPES for sym in ("zxc_mi355x_decompress_takev_device_scratch_size", "zxc_mi355x_decompress_takev_device"))
+    assert hasattr(product.api.DecompressTakeSession, "takev")
     assert IOV_DTYPE.itemsize == 16
 
 
@@ -101,7 +102,6 @@ def test_a_launch_error_ends_the_chunk_loop_and_spends_the_session(product, L):
     take's first launch belongs to its first chunk: the loop ends behind that chunk (the position is two blocks, not the call's
     bytes) and the session is spent. A takev's first launch is its scan, in front of the loop: no chunk is planned."""
     if product.lib().zxc_mi355x_device_count() == 0:
-        product.api._bind_decompress_take_device(L)
         n = 5 * 4096 + 7
         ds = _live(mp=8192)
         assert L.zxc_mi355x_decompress_take_device(C.byref(ds), T.FAKE_DST, n, None) == ERR["GPU_UNAVAILABLE"]
@@ -135,10 +135,7 @@ class VShape(C.Structure):  # ztv_shape_t
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("takev") / "libtakev_shim.so")
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "take", "takev_shim.c")], check=True)
-    S = C.CDLL(so)
+    S = cshim.build_shim(tmp_path_factory, "takev", "take/takev_shim.c")
     S.tv_shape_size.restype = S.tv_place_size.restype = C.c_size_t
     assert S.tv_shape_size() == C.sizeof(VShape) and S.tv_place_size() == 16
     S.tv_shape.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(VShape)]
@@ -408,12 +405,5 @@ def test_table_errors_in_a_replayed_session(shim, oracle):
 
 def test_rules_under_sanitizers(tmp_path):
     """the stand-alone program tests/take/takev_san_main.c (its own main; nothing of it is loaded into this process)"""
-    exe = str(tmp_path / "takev_san")
-    r = subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tests", "take", "takev_san_main.c")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    bad = [k for k in ("ERROR: AddressSanitizer", "runtime error:", "LeakSanitizer") if k in r.stderr]
-    assert r.returncode == 0 and not bad and "TAKEV OK 2016" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-3000:])
+    r = cshim.run_san_program(tmp_path, "take/takev_san_main.c")
+    assert "TAKEV OK 2016" in r.stdout, (r.stdout[-300:], r.stderr[-3000:])

@@ -5,17 +5,15 @@ zxc_ranges.h), compiled here with the host C compiler and driven over the golden
 wrong one is DICT_MISMATCH, none is DICT_REQUIRED, and the functions of the calls that take no dictionary answer as before."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from cshim import FAKE_DICT, FAKE_HUF, FAKE_ID, build_shim, dd as _dd, ref as _ref
+from devtest import ERR
 from zxc_amd.api import _CompressOpts, _DecompressOpts, _DevDict
 
 FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES, FAKE_IDX, FAKE_RNG = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000
-FAKE_DICT, FAKE_HUF, FAKE_ID = 0x70000, 0x80000, 0x90000
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, NULL_INPUT=-12, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15, DICT_MISMATCH=-16,
-           DICT_TOO_LARGE=-17, GPU_UNAVAILABLE=-100, GPU_UNSUPPORTED=-101)
 BAD_BLOCK_SIZES = (1000, 4095, 5000, 3 << 12, 1 << 22)
 DICT_SIZES = (1, 4096, 65535)
 IMAGE_BYTES, IMAGE_MIN_BLOCKS, WORK_SLACK = 256 << 20, 4096, 4096  # the documented chunk rule and bound
@@ -25,18 +23,7 @@ IMAGE_BYTES, IMAGE_MIN_BLOCKS, WORK_SLACK = 256 << 20, 4096, 4096  # the documen
 def L(product):
     L = product.lib()
     assert hasattr(L, "zxc_mi355x_dict_prepare_device"), "libzxc_mi355x.so does not export zxc_mi355x_dict_prepare_device"
-    product.api._bind_decompress_device(L)
-    product.api._bind_ranges_device(L)
-    L.zxc_mi355x_compress_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_device.restype = C.c_int
-    L.zxc_mi355x_compress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts), C.c_void_p,
-                                             C.c_uint64, C.c_void_p, C.c_void_p]
-    return product.api._bind_dict_device(L)
-
-
-def _dd(size=1000, content=FAKE_DICT, huf=FAKE_HUF, id_=FAKE_ID):
-    return _DevDict(content, huf, id_, size)
+    return L
 
 
 def _copts(level=3, block_size=65536, seekable=False, checksum=False, host_dict=False):
@@ -51,10 +38,6 @@ def _dopts(host_dict=False):
     if host_dict:
         o.dict, o.dict_size = FAKE_SRC, 100
     return o
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None
 
 
 def test_symbols_and_names_exported(product):
@@ -293,16 +276,9 @@ class Copy(C.Structure):  # zr_copy_t
     _fields_ = [("dst_at", C.c_uint64), ("from_", C.c_uint32), ("n", C.c_uint32)]
 
 
-def _build(tmp, name, src):
-    so = str(tmp / name)
-    subprocess.run(["gcc", "-std=gnu11", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", src)],
-                   check=True)
-    return C.CDLL(so)
-
-
 @pytest.fixture(scope="module")
 def cshim(tmp_path_factory):
-    S = _build(tmp_path_factory.mktemp("container_dict"), "libcontainer_dict_shim.so", "container/container_dict_shim.c")
+    S = build_shim(tmp_path_factory, "container_dict", "container/container_dict_shim.c")
     S.t_ctl_size.restype = C.c_size_t
     assert S.t_ctl_size() == C.sizeof(Ctl)
     S.t_head_dict.restype = None
@@ -316,7 +292,7 @@ def cshim(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def rshim(tmp_path_factory):
-    S = _build(tmp_path_factory.mktemp("ranges_dict"), "libranges_dict_shim.so", "ranges/ranges_dict_shim.c")
+    S = build_shim(tmp_path_factory, "ranges_dict", "ranges/ranges_dict_shim.c")
     S.t_index_size.restype = C.c_uint64
     S.t_index_size.argtypes = [C.c_uint32]
     S.t_open.restype = None

@@ -4,72 +4,17 @@ of the pieces with the same options and capacity (existing code, not the code un
 decoder and decompress_device. The destination starts as a pattern and has a canary area behind dst_capacity; every piece is a
 tensor of its own at an odd offset inside a buffer that ends with the piece (nothing readable is promised behind n). Payloads are
 text-like, and incompressible (stored blocks). Nothing here provokes a fault: every refused input is refused by status."""
-import numpy as np
 import pytest
+
+import devtest
+from devtest import CANARY, ERR, UNSET, bound as _bound, pattern as _pattern, payload as _payload, piece as _piece, split as _split
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-ERR = dict(DST_TOO_SMALL=-2, OVERFLOW=-10)
 BS = 4096
 SIZES = (0, 1, 4095, 4096, 4097, 3 * 4096 + 5)
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "compress_begin_device"), "zxc_amd has no compress_begin_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
-_TEXT = []
-
-
-def _payload(n, seed):
-    """a slice of one generated text, or for an odd seed bytes that do not compress (stored blocks)"""
-    from zxc_amd import corpus
-    if seed % 2:
-        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
-    if not _TEXT:
-        _TEXT.append(corpus.synth_text(6 << 20, seed=17))
-    at = (seed * 100003) % (len(_TEXT[0]) - n + 1)
-    return _TEXT[0][at: at + n]
-
-
-def _bound(gpu, n):
-    import ctypes as C
-    L = gpu.lib()
-    L.zxc_compress_bound.restype = C.c_uint64
-    L.zxc_compress_bound.argtypes = [C.c_size_t]
-    return int(L.zxc_compress_bound(n))
-
-
-def _piece(data: bytes, k):
-    """the piece's bytes at an odd offset of a buffer that ends with them -> (tensor that keeps it alive, pointer)"""
-    import torch
-    off = 1 + 2 * (k % 7)
-    t = torch.full((off + len(data),), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[off:] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t, t.data_ptr() + off
-
-
-def _split(data, lens):
-    assert sum(lens) == len(data)
-    out, at = [], 0
-    for n in lens:
-        out.append(data[at: at + n])
-        at += n
-    return out
-
+gpu = devtest.gpu_fixture("compress_begin_device")
 
 _BASE = {}
 

@@ -5,76 +5,27 @@ with the same options, dictionary and capacity; for round trips the unmodified r
 destination starts as a pattern and has a canary area behind dst_capacity; every piece is a tensor of its own at an odd offset
 inside a buffer that ends with the piece (nothing readable is promised behind n); d_work has an odd address. Payloads are
 text-like, and incompressible (stored blocks). Nothing here provokes a fault: every refused input is refused by status."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict
+from devtest import (CANARY, ERR, UNSET, bound as _bound, pattern as _pattern, payload as _payload, piece as _piece,
+                     ref_decompress as _ref_decompress, split as _split)
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-ERR = dict(DST_TOO_SMALL=-2, OVERFLOW=-10, DICT_REQUIRED=-15, DICT_MISMATCH=-16)
 BS = 4096
 SIZES = (0, 1, 4095, 4096, 4097, 3 * 4096 + 5)
 DICT_SIZES = (1, 100, 4096 + 3, 65535)
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "compress_begin_dict_device"), "zxc_amd has no compress_begin_dict_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
-_TEXT = []
+gpu = devtest.gpu_fixture("compress_begin_dict_device")
 
 
 def _text():
-    from zxc_amd import corpus
-    if not _TEXT:
-        _TEXT.append(corpus.synth_text(6 << 20, seed=17))
-    return _TEXT[0]
-
-
-def _payload(n, seed):
-    """a slice of one generated text, or for an odd seed bytes that do not compress (stored blocks)"""
-    if seed % 2:
-        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
-    at = (seed * 100003) % (len(_text()) - n + 1)
-    return _text()[at: at + n]
-
-
-def _bound(gpu, n):
-    L = gpu.lib()
-    L.zxc_compress_bound.restype = C.c_uint64
-    L.zxc_compress_bound.argtypes = [C.c_size_t]
-    return int(L.zxc_compress_bound(n))
-
-
-class DevDict:
-    """a dictionary in device memory, at an odd address: content, optional table, the prepared id word"""
-
-    def __init__(self, gpu, content, huf=None, stream=None):
-        import torch
-        s = torch.cuda.current_stream() if stream is None else stream
-        self.content, self.huf = content, huf
-        with torch.cuda.stream(s):
-            self.d_content = torch.frombuffer(bytearray(b"\xA5" + content), dtype=torch.uint8).to("cuda")
-            self.d_huf = torch.frombuffer(bytearray(huf), dtype=torch.uint8).to("cuda") if huf else None
-            self.d_id = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-            self.tup = (self.d_content.data_ptr() + 1, len(content), self.d_huf.data_ptr() if huf else 0, self.d_id.data_ptr())
-            gpu.dict_prepare_device(self.tup[0], len(content), self.tup[2], self.tup[3], s.cuda_stream)
+    return devtest.text(6 << 20)  # (the text the payloads are cut from)
 
 
 _DICTS = {}
@@ -86,27 +37,8 @@ def _dict(gpu, size, with_huf=False, seed=0):
     if key not in _DICTS:
         at = (5 << 20) + 70001 * seed
         _, huf = load_dict(os.path.join(GOLDEN, "conformance", "valid", "dict_text.zxd"))
-        _DICTS[key] = DevDict(gpu, _text()[at: at + size], huf if with_huf else None)
+        _DICTS[key] = devtest.DevDict(gpu, _text()[at: at + size], huf if with_huf else None, odd=True)  # at an odd address
     return _DICTS[key]
-
-
-def _piece(data: bytes, k):
-    """the piece's bytes at an odd offset of a buffer that ends with them -> (tensor that keeps it alive, pointer)"""
-    import torch
-    off = 1 + 2 * (k % 7)
-    t = torch.full((off + len(data),), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[off:] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t, t.data_ptr() + off
-
-
-def _split(data, lens):
-    assert sum(lens) == len(data)
-    out, at = [], 0
-    for n in lens:
-        out.append(data[at: at + n])
-        at += n
-    return out
 
 
 _BASE = {}
@@ -325,20 +257,6 @@ def test_a_dropped_session_does_not_disturb_the_next_on_its_work_area(gpu):
     assert s.result() == want
     torch.cuda.synchronize()
     assert int(dropped.res.item()) == UNSET  # nothing was written for the session without an end
-
-
-def _ref_decompress(ref, comp, n, content=None, huf=None, checksum=False):
-    import oracle_py
-    o = oracle_py.DecompressOpts()
-    o.checksum_enabled = int(checksum)
-    keep = None
-    if content:
-        keep = (C.create_string_buffer(content, len(content)), C.create_string_buffer(huf, 128) if huf else None)
-        o.dict, o.dict_size = C.cast(keep[0], C.c_void_p), len(content)
-        o.dict_huf = C.cast(keep[1], C.c_void_p) if huf else None
-    out = C.create_string_buffer(max(n, 1))
-    rc = ref.lib.zxc_decompress(comp, len(comp), out, n, C.byref(o))
-    return rc, out.raw[:max(rc, 0)]
 
 
 def _take(gpu, arc, n, bs, dd, lens, checksum):

@@ -8,25 +8,18 @@ refused by status, and a table that breaks a rule names only buffers that exist.
 import numpy as np
 import pytest
 
+import devtest
 import test_gpu_compress_append_device as A
 import test_gpu_compress_append_dict_device as D
+from devtest import ERR
 
 pytestmark = pytest.mark.gpu
 
 BS = 4096
-ERR = dict(DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, OVERFLOW=-10, NULL_INPUT=-12, GPU_UNSUPPORTED=-101)
 LENS = (0, 1, 3, 31, 32, 33, 4095, 4096, 4097, 4096 + 31, 4096 + 32, 2 * 4096 + 33, 3 * 4096 + 5)
 SCRATCH_CANARY = 256
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product.api.CompressAppendSession, "appendv"), "zxc_amd has no CompressAppendSession.appendv"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture(session_method=("CompressAppendSession", "appendv"))
 
 
 class Table:

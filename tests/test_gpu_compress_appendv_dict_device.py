@@ -9,28 +9,21 @@ refused by status, and a table that breaks a rule names only buffers that exist.
 import numpy as np
 import pytest
 
+import devtest
 import test_gpu_compress_append_device as A
 import test_gpu_compress_append_dict_device as D
 import test_gpu_compress_appendv_device as V
 import test_gpu_decompress_takev_device as T
+from devtest import ERR
 
 pytestmark = pytest.mark.gpu
 
 BS = 4096
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, OVERFLOW=-10, NULL_INPUT=-12, DICT_REQUIRED=-15)
 LENS = V.LENS
 DICT_SIZES = (1, 100, 4099, 65535)
 SCRATCH_CANARY = 256
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product.api.CompressAppendSession, "appendv_dict"), "zxc_amd has no CompressAppendSession.appendv_dict"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture(session_method=("CompressAppendSession", "appendv_dict"))
 
 
 class Scratch:

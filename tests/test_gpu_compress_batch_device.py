@@ -13,60 +13,20 @@ import random
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict
+from devtest import CANARY, ERR, PAD, UNSET, bound as _bound, pattern as _pattern, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-PAD = 64  # d_src must be readable 64 bytes past src_capacity
-ERR = dict(DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, OVERFLOW=-10)
 SIZES_4K = (0, 1, 31, 32, 33, 4095, 4096, 4097, 8192, 3 * 4096 + 5, 16 * 4096)
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "compress_batch_device"), "zxc_amd has no compress_batch_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
-def _to_dev(data: bytes, pad=0):
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-_TEXT = {}
+gpu = devtest.gpu_fixture("compress_batch_device")
 
 
 def _payload(n, seed):
     """a slice of one generated text, or bytes that do not compress (stored blocks) for every fourth seed"""
-    from zxc_amd import corpus
-    if seed % 4 == 3:
-        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
-    size = 1 << 20
-    if size not in _TEXT:
-        _TEXT[size] = corpus.synth_text(size, seed=17)
-    at = (seed * 100003) % (size - n + 1)
-    return _TEXT[size][at: at + n]
-
-
-def _bound(gpu, n):
-    import ctypes as C
-    L = gpu.lib()
-    L.zxc_compress_bound.restype = C.c_uint64
-    L.zxc_compress_bound.argtypes = [C.c_size_t]
-    return int(L.zxc_compress_bound(n))
+    return devtest.payload(n, seed, stored_every=4, text_size=1 << 20)
 
 
 class Area:
@@ -161,30 +121,10 @@ def _verify(gpu, table, datas, got, dst, level, bs, seekable, checksum, dict_=No
 
 def _device_written(gpu, data, level, bs, seekable, checksum):
     """compress_device -> the archive's bytes"""
-    import torch
-    src = _to_dev(data)
-    bound = _bound(gpu, len(data))
-    ws = gpu.compress_device_work_size(len(data), level, bs, seekable, checksum)
-    work = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    arc = torch.empty(bound, dtype=torch.uint8, device="cuda")
-    res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-    gpu.compress_device(src.data_ptr() if data else 0, len(data), arc.data_ptr(), bound, work.data_ptr(), ws, res.data_ptr(), level, bs,
-                        seekable, checksum)
-    n = int(res.item())
-    assert n > 0
-    return bytes(arc[:n].cpu().numpy())
+    return bytes(devtest.device_written(gpu, data, level, bs, seekable, checksum).cpu().numpy())
 
 
-@pytest.fixture(scope="module")
-def area_4k(gpu):
-    """every size of the issue as text and as bytes that do not compress, shuffled in the table"""
-    area = Area(gpu, 21)
-    for k, size in enumerate(SIZES_4K):
-        area.add(_payload(size, 4 * k))      # text
-        area.add(_payload(size, 4 * k + 3))  # incompressible
-    order = list(range(len(area.rows)))
-    random.Random(5).shuffle(order)
-    return area, area.tensor(), area.table(order), [area.datas[k] for k in order]
+area_4k = devtest.area_4k_fixture(Area, SIZES_4K, _payload)
 
 
 @pytest.mark.parametrize("level", [1, 2, 3, 4, 5, 6, 7])

@@ -1,38 +1,20 @@
 """zxc_mi355x_compress_device on the GPU: a whole archive from device memory to device memory, byte for byte the one
 zxc_compress writes, read back by the unmodified reference decoder; capacity edges with a canary behind the capacity; stream
 order on torch streams; the source left untouched."""
-import ctypes as C
 import random
 
-import numpy as np
 import pytest
+
+import devtest
+from devtest import CANARY, UNSET, bound as _bound, canary_ok as _canary_ok, inputs as _inputs
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _bound(gpu, n):
-    L = gpu.lib()
-    L.zxc_compress_bound.restype = C.c_uint64
-    return int(L.zxc_compress_bound(n))
+gpu = devtest.gpu_fixture()
 
 
 def _to_dev(data: bytes):
-    import torch
-    if not data:
-        return torch.empty(0, dtype=torch.uint8, device="cuda")
-    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
+    return devtest.to_dev(data, exact=True)
 
 
 def _dev_compress(gpu, src, n, level, bs, seekable, checksum, cap=None, stream=None):
@@ -50,28 +32,6 @@ def _dev_compress(gpu, src, n, level, bs, seekable, checksum, cap=None, stream=N
                         seekable, checksum, s.cuda_stream)
     s.synchronize()
     return int(res.item()), dst, cap
-
-
-def _canary_ok(dst, cap):
-    import torch
-    want = torch.arange(CANARY, dtype=torch.int32).remainder(251).to(torch.uint8) + 1
-    return torch.equal(dst[cap:].cpu(), want)
-
-
-def _inputs(bs):
-    from zxc_amd import corpus
-    rng = np.random.default_rng(bs)
-    text = corpus.synth_text(3 * bs + 1000, seed=bs & 0xFFFF)
-    return {
-        "empty": b"",
-        "1B": b"Q",
-        "bs-1": text[: bs - 1],
-        "bs": text[bs: 2 * bs],
-        "bs+1": text[7: bs + 8],
-        "text": text,
-        "random": rng.integers(0, 256, 2 * bs + 77, dtype=np.uint8).tobytes(),
-        "zeros": bytes(2 * bs + 5),
-    }
 
 
 @pytest.mark.parametrize("bs", [4096, 65536, 1 << 19, 1 << 21])

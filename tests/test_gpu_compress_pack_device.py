@@ -15,24 +15,17 @@ import random
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict
-from test_gpu_compress_batch_device import CANARY, SIZES_4K, UNSET, Area, _host, _pattern, _payload, _to_dev
+from devtest import CANARY, ERR, UNSET, pattern as _pattern, to_dev as _to_dev
+from test_gpu_compress_batch_device import SIZES_4K, Area, _host, _payload  # (the batch call's areas, payloads and host archives)
 from test_gpu_compress_batch_device import _run as _run_batch
 
 pytestmark = pytest.mark.gpu
 
-ERR = dict(DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, OVERFLOW=-10)
 M64 = (1 << 64) - 1
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "compress_pack_device"), "zxc_amd has no compress_pack_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture("compress_pack_device")
 
 
 def _run(gpu, src, src_cap, table, max_size, dst_cap, align, level, bs, seekable, checksum, dd=False, stream=None, sync=True, d_items=None,
@@ -106,16 +99,7 @@ def _verify(gpu, table, datas, out, dst_cap, align, level, bs, seekable, checksu
     return arcs, at, total
 
 
-@pytest.fixture(scope="module")
-def area_4k(gpu):
-    """every size of the issue as text and as bytes that do not compress, shuffled in the table"""
-    area = Area(gpu, 21)
-    for k, size in enumerate(SIZES_4K):
-        area.add(_payload(size, 4 * k))      # text
-        area.add(_payload(size, 4 * k + 3))  # incompressible
-    order = list(range(len(area.rows)))
-    random.Random(5).shuffle(order)
-    return area, area.tensor(), area.table(order), [area.datas[k] for k in order]
+area_4k = devtest.area_4k_fixture(Area, SIZES_4K, _payload)
 
 
 def _enough(datas):

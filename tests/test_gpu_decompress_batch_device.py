@@ -11,53 +11,22 @@ import random
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict
+from devtest import CANARY, ERR, PAD, UNSET, device_written as _device_written, pattern as _pattern, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-PAD = 64  # d_src must be readable 64 bytes past src_capacity
-ERR = dict(DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, BAD_CHECKSUM=-7, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15, DICT_MISMATCH=-16)
 SIZES_4K = (0, 1, 4095, 4096, 4097, 8192, 3 * 4096 + 5, 16 * 4096)
 LEVELS = (1, 3, 6, 7)
 
 
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "decompress_batch_device"), "zxc_amd has no decompress_batch_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
-def _to_dev(data: bytes, pad=0):
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-_TEXT = {}
+gpu = devtest.gpu_fixture("decompress_batch_device")
 
 
 def _payload(n, seed):
     """a slice of one generated text, or bytes that do not compress (stored blocks) for every fourth seed"""
-    from zxc_amd import corpus
-    if seed % 4 == 3:
-        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
-    size = 1 << 20 if n <= (1 << 19) else 7 << 20
-    if size not in _TEXT:
-        _TEXT[size] = corpus.synth_text(size, seed=17)
-    at = (seed * 100003) % (size - n + 1)
-    return _TEXT[size][at: at + n]
+    return devtest.payload(n, seed, stored_every=4, text_size=lambda n: 1 << 20 if n <= (1 << 19) else 7 << 20)
 
 
 class Entry:
@@ -163,22 +132,6 @@ def _verify(gpu, table, who, got, dst, max_cap, dst_cap, bs, checksum, dict_=Non
     assert sum(seen.values()) == len(table) == len(got)
     assert np.array_equal(dst[~keep], _pattern(len(dst))[~keep])  # gaps, other items, behind the capacity
     return seen
-
-
-def _device_written(gpu, data, level, bs, seekable, checksum):
-    """compress_device -> the archive's bytes (the batch decodes a device copy placed in the area)"""
-    import torch
-    src = _to_dev(data)
-    bound = int(gpu.lib().zxc_compress_bound(len(data)))
-    ws = gpu.compress_device_work_size(len(data), level, bs, seekable, checksum)
-    work = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    arc = torch.empty(bound, dtype=torch.uint8, device="cuda")
-    res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-    gpu.compress_device(src.data_ptr() if data else 0, len(data), arc.data_ptr(), bound, work.data_ptr(), ws, res.data_ptr(), level, bs,
-                        seekable, checksum)
-    n = int(res.item())
-    assert n > 0
-    return arc[:n]
 
 
 def _first_block(comp):

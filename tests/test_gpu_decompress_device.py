@@ -5,41 +5,21 @@ stream order on torch streams; the archive left untouched. Nothing here provokes
 is tested with, and the kernels refuse them by status."""
 import os
 
-import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN
+from devtest import CANARY, ERR, PAD, UNSET, bound as _bound, canary as _canary, canary_ok as _canary_ok, inputs as _inputs
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-PAD = 64  # d_src must be readable 64 bytes past the archive
-ERR = dict(DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, BAD_CHECKSUM=-7, CORRUPT_DATA=-8, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15, GPU_UNSUPPORTED=-101)
 DICT_ARCHIVES = {"conformance/valid/dict_http.zxc", "conformance/valid/dict_seekable_l7.zxc", "conformance/invalid/dict_required.zxc"}
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture()
 
 
 def _to_dev(data: bytes, pad=PAD):
-    """-> uint8 tensor of len(data) + pad bytes (the pad is 0xA5: never used, only readable)"""
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-def _canary():
-    import torch
-    return torch.arange(CANARY, dtype=torch.int32).remainder(251).to(torch.uint8) + 1
+    return devtest.to_dev(data, pad)
 
 
 def _dev_decompress(gpu, arc, n_arc, bs, cap, checksum=False, stream=None, sync=True):
@@ -60,37 +40,12 @@ def _dev_decompress(gpu, arc, n_arc, bs, cap, checksum=False, stream=None, sync=
     return int(res.item()), dst
 
 
-def _canary_ok(dst, cap):
-    import torch
-    return torch.equal(dst[cap:].cpu(), _canary())
-
-
 def _check_round_trip(gpu, arc, n_arc, data, bs, checksum, what):
     for cap in sorted({len(data), len(data) + 1000, len(data) + 3 * bs + 77}):  # exact, and both sides of the k split
         rc, dst = _dev_decompress(gpu, arc, n_arc, bs, cap, checksum)
         assert rc == len(data), (what, cap, rc)
         assert bytes(dst[: len(data)].cpu().numpy()) == data, (what, cap)
         assert _canary_ok(dst, cap), (what, cap)
-
-
-def _inputs(bs):
-    from zxc_amd import corpus
-    rng = np.random.default_rng(bs)
-    text = corpus.synth_text(3 * bs + 1000, seed=bs & 0xFFFF)
-    return {
-        "empty": b"",
-        "1B": b"Q",
-        "bs-1": text[: bs - 1],
-        "bs": text[bs: 2 * bs],
-        "bs+1": text[7: bs + 8],
-        "text": text,
-        "random": rng.integers(0, 256, 2 * bs + 77, dtype=np.uint8).tobytes(),
-        "zeros": bytes(2 * bs + 5),
-    }
-
-
-def _bound(gpu, n):
-    return int(gpu.lib().zxc_compress_bound(n))
 
 
 @pytest.mark.parametrize("bs", [4096, 65536, 1 << 19, 1 << 21])

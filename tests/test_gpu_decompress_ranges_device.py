@@ -10,37 +10,19 @@ import random
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN
+from devtest import CANARY, ERR, PAD, UNSET, pattern as _pattern
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-PAD = 64  # d_src must be readable 64 bytes past the archive
-ERR = dict(MEMORY=-1, DST_TOO_SMALL=-2, SRC_TOO_SMALL=-3, CORRUPT_DATA=-8, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15)
 DICT_ARCHIVES = ("conformance/valid/dict_http.zxc", "conformance/valid/dict_seekable_l7.zxc", "conformance/invalid/dict_required.zxc")
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture()
 
 
 def _to_dev(data: bytes, pad=PAD):
-    """-> uint8 tensor of len(data) + pad bytes (the pad is 0xA5: never used, only readable)"""
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
+    return devtest.to_dev(data, pad)
 
 
 def _open(gpu, arc, n_arc, bs, max_blocks, stream=None):

@@ -5,68 +5,19 @@ for one round trip the unmodified reference decoder. Every piece is a tensor of 
 behind, both checked after every session; a run with every piece 16-byte aligned and every cut a multiple of 16 takes the direct
 path, a run with the pieces at odd addresses sends everything through slots. Payloads are text-like, and incompressible (stored
 blocks). Nothing here provokes a fault: every refused input is refused by status."""
-import numpy as np
 import pytest
+
+import devtest
+from devtest import ERR, PAD, UNSET, DevDict, pattern as _pattern, payload as _payload, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
 FRONT = 256   # pattern bytes in front of a piece (keeps an aligned piece 16-byte aligned)
 CANARY = 256  # ... and behind it
-PAD = 64      # readable bytes behind an archive
-UNSET = -(1 << 62)
-ERR = dict(DST_TOO_SMALL=-2, BAD_HEADER=-6, BAD_CHECKSUM=-7, CORRUPT_DATA=-8, OVERFLOW=-10, BAD_BLOCK_SIZE=-14, DICT_REQUIRED=-15,
-           DICT_MISMATCH=-16)
 BS = 4096
 SIZES = (0, 1, 4095, 4096, 4097, 3 * 4096 + 5)
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "decompress_begin_device"), "zxc_amd has no decompress_begin_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
-
-
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
-_TEXT = []
-
-
-def _payload(n, seed):
-    """a slice of one generated text, or for an odd seed bytes that do not compress (stored blocks)"""
-    from zxc_amd import corpus
-    if seed % 2:
-        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
-    if not _TEXT:
-        _TEXT.append(corpus.synth_text(6 << 20, seed=17))
-    at = (seed * 100003) % (len(_TEXT[0]) - n + 1)
-    return _TEXT[0][at: at + n]
-
-
-def _to_dev(data: bytes, pad=0):
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-class DevDict:
-    """a dictionary in device memory: content, the prepared id word"""
-
-    def __init__(self, gpu, content):
-        import torch
-        self.content = content
-        self.d_content = _to_dev(content)
-        self.d_id = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        gpu.dict_prepare_device(self.d_content.data_ptr(), len(content), 0, self.d_id.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        self.tup = (self.d_content.data_ptr(), len(content), 0, self.d_id.data_ptr())
-
+gpu = devtest.gpu_fixture("decompress_begin_device")
 
 _ONE = {}
 

@@ -8,24 +8,18 @@ refused by status, and a table in error is never dereferenced."""
 import numpy as np
 import pytest
 
+import devtest
 import test_gpu_decompress_take_device as K
-from test_gpu_decompress_take_device import BS, ERR, PAD, UNSET, _archive, _oneshot, _pattern, _payload, _to_dev
+from devtest import ERR, PAD, UNSET, pattern as _pattern, payload as _payload, to_dev as _to_dev
+from test_gpu_decompress_take_device import BS, _archive, _oneshot  # (the take session's archives and one-shot reference)
 
 pytestmark = pytest.mark.gpu
 
 GAP = 64  # canary bytes between two entries
-ERRV = dict(ERR, NULL_INPUT=-12, MEMORY=-1)
+ERRV = ERR
 EDGE_LENS = [0, 1, 15, 16, 17, 31, 32, 33, 4095, 4096, 4097, 4096 + 31, 4096 + 32, 4096 + 33, 2 * 4096 + 32, 3 * 4096 + 5]
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product.api.DecompressTakeSession, "takev"), "DecompressTakeSession has no takev"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture(session_method=("DecompressTakeSession", "takev"))
 
 
 class VSession:

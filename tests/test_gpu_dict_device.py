@@ -11,71 +11,25 @@ import random
 import numpy as np
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict, read
+from devtest import (CANARY, ERR, PAD, UNSET, DevDict, bound as _bound, canary as _canary, canary_ok as _canary_ok, pattern as _pattern,
+                     ref_decompress as _ref_decompress, to_dev as _to_dev)
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 4096
-UNSET = -(1 << 62)
-PAD = 64  # an archive in device memory must be readable 64 bytes past its end
-ERR = dict(DST_TOO_SMALL=-2, DICT_REQUIRED=-15, DICT_MISMATCH=-16)
 ID_LENGTHS = (1, 3, 4, 8, 16, 17, 112, 113, 225, 65535)
 BIG_BLOCKS = 20001  # more than one chunk of the compress call (4096 blocks at 4 KiB under a full dictionary), and >= 16 400
 
 
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    assert hasattr(product, "dict_prepare_device"), "zxc_amd has no dict_prepare_device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    L = product.lib()
+gpu = devtest.gpu_fixture("dict_prepare_device")
+
+
+def _lib(gpu):
+    L = gpu.lib()
     L.zxc_dict_id.restype = C.c_uint32
     L.zxc_dict_id.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
-    L.zxc_compress_bound.restype = C.c_uint64
-    return product
-
-
-def _to_dev(data: bytes, pad=0):
-    import torch
-    t = torch.full((len(data) + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    if data:
-        t[: len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda")
-    return t
-
-
-def _canary():
-    import torch
-    return torch.arange(CANARY, dtype=torch.int32).remainder(251).to(torch.uint8) + 1
-
-
-def _canary_ok(dst, cap):
-    import torch
-    return torch.equal(dst[cap:].cpu(), _canary())
-
-
-class DevDict:
-    """a dictionary in device memory: content, optional table, the prepared id word. The tensors have exactly the dictionary's
-    length, but torch's allocator rounds an allocation up, so these tests could not see a read past `size`: that the calls make
-    none is established by reading the kernels (include/zxc_mi355x.h)."""
-
-    def __init__(self, gpu, content, huf=None, stream=None):
-        import torch
-        s = torch.cuda.current_stream() if stream is None else stream
-        self.content, self.huf = content, huf
-        with torch.cuda.stream(s):
-            self.d_content = _to_dev(content)
-            self.d_huf = _to_dev(huf) if huf else None
-            self.d_id = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-            gpu.dict_prepare_device(self.d_content.data_ptr(), len(content), self.d_huf.data_ptr() if huf else 0, self.d_id.data_ptr(),
-                                    s.cuda_stream)
-        self.tup = (self.d_content.data_ptr(), len(content), self.d_huf.data_ptr() if huf else 0, self.d_id.data_ptr())
-
-    def id(self):
-        import torch
-        torch.cuda.synchronize()
-        return int(self.d_id.cpu().numpy().view(np.uint32)[0])
+    return L
 
 
 def _golden_dict(name):
@@ -89,7 +43,7 @@ def _text_dict(n=5000, seed=77):
 
 # ---------------------------------------------------------------- the id
 def test_id_of_the_golden_dictionaries(gpu):
-    L = gpu.lib()
+    L = _lib(gpu)
     for name in ("dict_http.zxd", "dict_text.zxd"):
         raw = read("conformance/valid/" + name)
         content, huf = _golden_dict(name)
@@ -101,7 +55,7 @@ def test_id_of_the_golden_dictionaries(gpu):
 
 
 def test_id_over_content_lengths(gpu):
-    L = gpu.lib()
+    L = _lib(gpu)
     rng = np.random.default_rng(5)
     _, huf = _golden_dict("dict_http.zxd")
     for n in ID_LENGTHS + (2, 5, 7, 15, 32, 33, 111, 114, 224, 226, 1000, 65534):
@@ -112,10 +66,6 @@ def test_id_over_content_lengths(gpu):
 
 
 # ---------------------------------------------------------------- compress
-def _bound(gpu, n):
-    return int(gpu.lib().zxc_compress_bound(n))
-
-
 def _dev_compress(gpu, src, n, dd, level, bs, seekable, checksum, cap=None, stream=None):
     """-> (result, dst tensor of cap + CANARY bytes, cap); the CANARY bytes behind cap start as a known pattern"""
     import torch
@@ -134,25 +84,10 @@ def _dev_compress(gpu, src, n, dd, level, bs, seekable, checksum, cap=None, stre
     return int(res.item()), dst, cap
 
 
-def _ref_decompress(ref, comp, n, content=None, huf=None, checksum=False):
-    """the unmodified reference's zxc_decompress, options built as in tests/test_gpu_encode.py::test_dictionary_compression"""
-    import oracle_py
-    o = oracle_py.DecompressOpts()
-    o.checksum_enabled = int(checksum)
-    keep = None
-    if content:
-        keep = (C.create_string_buffer(content, len(content)), C.create_string_buffer(huf, 128) if huf else None)
-        o.dict, o.dict_size = C.cast(keep[0], C.c_void_p), len(content)
-        o.dict_huf = C.cast(keep[1], C.c_void_p) if huf else None
-    out = C.create_string_buffer(max(n, 1))
-    rc = ref.lib.zxc_decompress(comp, len(comp), out, n, C.byref(o))
-    return rc, out.raw[:max(rc, 0)]
-
-
 @pytest.mark.parametrize("bs", [4096, 65536, 1 << 19])
 @pytest.mark.parametrize("level", [1, 2, 3, 4, 5, 6, 7])
 def test_byte_identity_with_zxc_compress(gpu, ref, level, bs):
-    from test_gpu_compress_device import _inputs
+    from devtest import inputs as _inputs
     http, huf = _golden_dict("dict_http.zxd")
     text = _text_dict()
     dicts = {(k, h is not None): DevDict(gpu, c, h) for k, c in (("http", http), ("text", text)) for h in (None, huf)}
@@ -333,10 +268,6 @@ def test_mutated_archives_get_the_hosts_verdict(gpu, oracle, bs):
 
 
 # ---------------------------------------------------------------- ranges
-def _pattern(n):
-    return np.tile(np.arange(1, 252, dtype=np.uint8), n // 251 + 1)[:n]
-
-
 def _open(gpu, arc, n_arc, bs, max_blocks):
     import torch
     isz = gpu.seekable_index_size(max_blocks)

@@ -6,16 +6,12 @@ import random
 
 import pytest
 
+import devtest
 from conftest import GOLDEN, load_dict, read
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    return product
+gpu = devtest.gpu_fixture(torch_device=False)
 
 
 def _check(gpu, oracle, ref, data, level=3, block_size=65536, seekable=True, checksum=False):

@@ -21,34 +21,21 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import devtest  # noqa: E402
 import encode_limit_cases as E  # noqa: E402
 import zxc_block_model as M  # noqa: E402
+from devtest import UNSET, bound as _bound  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 4096
-UNSET = -(1 << 62)
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    return product
+gpu = devtest.gpu_fixture()
 
 
 @pytest.fixture(scope="module")
 def digests():
     return json.load(open(os.path.join(ROOT, E.DIGESTS)))
-
-
-def _bound(gpu, n):
-    L = gpu.lib()
-    L.zxc_compress_bound.restype = C.c_uint64
-    L.zxc_compress_bound.argtypes = [C.c_size_t]
-    return int(L.zxc_compress_bound(n))
 
 
 def _guarded(data, fill):

@@ -12,16 +12,12 @@ import threading
 
 import pytest
 
+import devtest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    return product
+gpu = devtest.gpu_fixture(torch_device=False)
 
 
 def _text(rng, n):

@@ -7,6 +7,7 @@ import random
 
 import pytest
 
+import devtest
 import zxc_amd.api as api
 from conftest import push_random_schedule
 
@@ -14,12 +15,7 @@ pytestmark = pytest.mark.gpu
 
 CHUNKINGS = ((1 << 30, 1 << 30), (1 << 20, 1 << 20), (8192, 8192), (13 * 1024, 7 * 1024), (511, 7000), (137, 53))
 
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    return product
+gpu = devtest.gpu_fixture(torch_device=False)
 
 
 def _text(rng, n, vocab=60):

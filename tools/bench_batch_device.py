@@ -13,12 +13,12 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import devbench  # noqa: E402
 import zxc_amd  # noqa: E402
 from zxc_amd import corpus  # noqa: E402
 
@@ -26,33 +26,11 @@ ITEM_BYTES = (4096, 65536, 262144)
 DICT_BYTES = 32768
 
 
-def once(fn, stream):
-    """-> (wall ms from the first enqueue to the end of the stream, hipEvent ms)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream.synchronize()
-    t0 = time.perf_counter()
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return (time.perf_counter() - t0) * 1e3, a.elapsed_time(b)
-
-
 def alternating(fns, runs, warmup, stream):
     """-> per function (median wall ms, median event ms, p10 and p90 of the wall ms); run i times every function once, in turn"""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    stream.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(runs):
-        for k, fn in enumerate(fns):
-            ms[k].append(once(fn, stream))
-    def pct(m, p):
-        w = sorted(w for w, _ in m)
-        return w[min(len(w) - 1, max(0, round(p * (len(w) - 1))))]
-
-    return [(statistics.median(w for w, _ in m), statistics.median(e for _, e in m), pct(m, 0.1), pct(m, 0.9)) for m in ms]
+    ms = devbench.alternating(fns, runs, warmup, stream)
+    walls = [sorted(w for w, _ in m) for m in ms]
+    return [(statistics.median(w), statistics.median(e for _, e in m), devbench.pct(w, 0.1), devbench.pct(w, 0.9)) for m, w in zip(ms, walls)]
 
 
 def case(item, n, content, a, stream):

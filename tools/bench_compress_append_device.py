@@ -13,44 +13,15 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import zxc_amd  # noqa: E402
+from devbench import alternating, pct  # noqa: E402  (per function [(wall ms, event ms) per run])
 from zxc_amd import corpus  # noqa: E402
 
 CORPUS_BYTES = 64 << 20  # generated once; a larger source repeats it
-
-
-def once(fn, stream):
-    """-> (wall ms from the first enqueue to the end of the stream, hipEvent ms)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream.synchronize()
-    t0 = time.perf_counter()
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return (time.perf_counter() - t0) * 1e3, a.elapsed_time(b)
-
-
-def alternating(fns, runs, warmup, stream):
-    """-> per function [(wall ms, event ms) per run]; run i times every function once, in turn"""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    stream.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(runs):
-        for k, fn in enumerate(fns):
-            ms[k].append(once(fn, stream))
-    return ms
-
-
-def pct(sorted_vals, p):
-    return sorted_vals[min(len(sorted_vals) - 1, max(0, round(p * (len(sorted_vals) - 1))))]
 
 
 def case(d_src, total, bs, appends, a, stream):

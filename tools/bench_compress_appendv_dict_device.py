@@ -27,17 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import zxc_amd  # noqa: E402
 from zxc_amd import corpus  # noqa: E402
-from bench_compress_appendv_device import CORPUS_BYTES, alternating, pct  # noqa: E402
-
-
-def lengths(n, total, seed):
-    """n lengths, uniform within +-50 % of total / n, adding up to total"""
-    rng = np.random.default_rng(seed)
-    raw = rng.uniform(0.5, 1.5, n)
-    lens = np.maximum(1, np.floor(raw * (total / raw.sum()))).astype(np.int64)
-    lens[np.argmax(lens)] += total - int(lens.sum())
-    assert lens.min() >= 1 and int(lens.sum()) == total
-    return [int(x) for x in lens]
+from bench_compress_appendv_device import CORPUS_BYTES, alternating  # noqa: E402
+from devbench import lengths_uniform as lengths, pct  # noqa: E402
 
 
 def case(entries, lens, total, bs, dd, a, stream):

@@ -21,6 +21,7 @@ import sys
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import devbench  # noqa: E402
 import zxc_amd  # noqa: E402
 from zxc_amd import corpus  # noqa: E402
 
@@ -32,26 +33,9 @@ def source(n):
     return b"".join(parts)[:n]
 
 
-def once(fn, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
 def alternating(fns, runs, warmup, stream):
-    """-> one list of milliseconds per function; run i times every function once, in turn"""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    stream.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(runs):
-        for k, fn in enumerate(fns):
-            ms[k].append(once(fn, stream))
-    return ms
+    """-> one list of hipEvent milliseconds per function; run i times every function once, in turn"""
+    return devbench.alternating(fns, runs, warmup, stream, "event")
 
 
 def archive_on_device(src, n, level, bs, seekable, checksum, stream):

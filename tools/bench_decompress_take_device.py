@@ -15,31 +15,15 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import zxc_amd  # noqa: E402
+from devbench import once, pct  # noqa: E402  (once: (wall ms, event ms))
 from zxc_amd import corpus  # noqa: E402
 
 CORPUS_BYTES = 64 << 20  # generated once; a larger source repeats it
-
-
-def once(fn, stream):
-    """-> (wall ms from the first enqueue to the end of the stream, hipEvent ms)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream.synchronize()
-    t0 = time.perf_counter()
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return (time.perf_counter() - t0) * 1e3, a.elapsed_time(b)
-
-
-def pct(sorted_vals, p):
-    return sorted_vals[min(len(sorted_vals) - 1, max(0, round(p * (len(sorted_vals) - 1))))]
 
 
 def main():

@@ -20,51 +20,22 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import devbench  # noqa: E402
 import zxc_amd  # noqa: E402
+from devbench import lengths_log as lengths, pct  # noqa: E402
 from zxc_amd import corpus  # noqa: E402
 
 CORPUS_BYTES = 64 << 20  # generated once; a larger source repeats it
 
 
-def once(fn, stream):
-    """-> wall ms from the first enqueue to the end of the stream"""
-    stream.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    stream.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
 def alternating(fns, runs, warmup, stream):
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    stream.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(runs):
-        for k, fn in enumerate(fns):
-            ms[k].append(once(fn, stream))
-    return ms
-
-
-def pct(sorted_vals, p):
-    return sorted_vals[min(len(sorted_vals) - 1, max(0, round(p * (len(sorted_vals) - 1))))]
-
-
-def lengths(n, total, seed):
-    """n lengths, log-uniform from 4 bytes to 64 MiB, scaled to add up to total"""
-    rng = np.random.default_rng(seed)
-    raw = np.exp(rng.uniform(np.log(4.0), np.log(64.0 * (1 << 20)), n))
-    lens = np.maximum(1, np.floor(raw * (total / raw.sum()))).astype(np.int64)
-    lens[np.argmax(lens)] += total - int(lens.sum())
-    assert lens.min() >= 1 and int(lens.sum()) == total
-    return [int(x) for x in lens]
+    """-> per function the wall ms of every run, from the first enqueue to the end of the stream"""
+    return devbench.alternating(fns, runs, warmup, stream, "wall")
 
 
 def case(d_src, lens, total, bs, a, stream):

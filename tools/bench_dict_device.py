@@ -21,6 +21,7 @@ import numpy as np
 import torch  # (first: the library shares torch's HIP runtime)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import devbench  # noqa: E402
 import zxc_amd  # noqa: E402
 
 PATHS = ["/api/v1/users", "/api/v1/orders", "/api/v2/items/search", "/static/js/app.bundle.js", "/healthz", "/api/v1/sessions/refresh",
@@ -46,26 +47,9 @@ def records(n_bytes, seed):
     return b"".join(out)[:n_bytes]
 
 
-def once(fn, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
 def alternating(fns, runs, warmup, stream):
-    """-> the median milliseconds of every function; run i times every function once, in turn"""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    stream.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(runs):
-        for k, fn in enumerate(fns):
-            ms[k].append(once(fn, stream))
-    return [statistics.median(m) for m in ms]
+    """-> the median hipEvent milliseconds of every function; run i times every function once, in turn"""
+    return [statistics.median(m) for m in devbench.alternating(fns, runs, warmup, stream, "event")]
 
 
 def main():

@@ -44,6 +44,161 @@ class _Reader(C.Structure):  # zxc_reader_t, include/zxc_seekable.h
     _fields_ = [("read_at", _READ_AT), ("ctx", C.c_void_p), ("size", C.c_uint64)]
 
 
+class _DevDict(C.Structure):  # zxc_dev_dict_t (include/zxc_mi355x.h): a dictionary in device memory
+    _fields_ = [("d_content", C.c_void_p), ("d_huf", C.c_void_p), ("d_id", C.c_void_p), ("size", C.c_uint32)]
+
+
+class _DevCappend(C.Structure):  # zxc_dev_cappend_t: the append session, a host struct of 16 words, caller-owned
+    _fields_ = [("opaque", C.c_uint64 * 16)]
+
+
+class _DevDtake(C.Structure):  # zxc_dev_dtake_t: the take session, a host struct of 16 words, caller-owned
+    _fields_ = [("opaque", C.c_uint64 * 16)]
+
+
+class _InBuf(C.Structure):  # zxc_inbuf_t (include/zxc_pstream.h)
+    _fields_ = [("src", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
+class _OutBuf(C.Structure):  # zxc_outbuf_t (include/zxc_pstream.h)
+    _fields_ = [("dst", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
+# ---- every prototype this module binds: C name -> (restype, argtypes). tests/test_api_prototypes.py holds the
+# zxc_mi355x_* entries against include/zxc_mi355x.h.
+_I, _I64, _U32, _U64, _SZ, _STR, _P = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_char_p, C.c_void_p
+_CO, _DO, _DD = C.POINTER(_CompressOpts), C.POINTER(_DecompressOpts), C.POINTER(_DevDict)
+_CS, _DS, _IN, _OUT = C.POINTER(_DevCappend), C.POINTER(_DevDtake), C.POINTER(_InBuf), C.POINTER(_OutBuf)
+_TAIL = [_P, _U64, _P, _P]  # d_work, work_size, d_result(s), stream
+_RANGES = [_P, _U64, _P, _P, _U32, _U64, _P, _U64, _U32]  # d_src .. block_size of decompress_ranges_device
+_DBATCH = [_P, _U64, _P, _U32, _U64, _P, _U64, _U32, _DO]  # d_src .. opts of decompress_batch_device
+_CBATCH = [_P, _U64, _P, _U32, _U64, _P, _U64, _CO]  # d_src .. opts of compress_batch_device
+_CPACK = [_P, _U64, _P, _U32, _U64, _P, _U64, _U32, _CO]  # d_src .. align, opts of compress_pack_device
+_PACK_TAIL = [_P, _U64, _P, _P, _P, _P]  # d_work, work_size, d_packed, d_results, d_total, stream
+_CBEGIN = [_CS, _P, _U64, _U64, _U64, _CO]  # cs .. opts of compress_begin_device
+_DBEGIN = [_DS, _P, _U64, _U64, _U64, _U32, _DO]  # ds .. opts of decompress_begin_device
+_IOV = [_P, _U32, _U64, _P, _U64, _P]  # d_iov, n_iov, total, d_scratch, scratch_size, stream
+
+_PROTOTYPES = {
+    # include/zxc_buffer.h, include/zxc_error.h
+    "zxc_error_name": (_STR, [_I]),
+    "zxc_compress_bound": (_U64, [_SZ]),
+    "zxc_compress": (_I64, [_STR, _SZ, _P, _SZ, _CO]),
+    "zxc_decompress": (_I64, [_STR, _SZ, _P, _SZ, _DO]),
+    "zxc_get_decompressed_size": (_U64, [_STR, _SZ]),
+    # include/zxc_seekable.h
+    "zxc_seekable_open": (_P, [_STR, _SZ]),
+    "zxc_seekable_open_reader": (_P, [C.POINTER(_Reader)]),
+    "zxc_seekable_free": (None, [_P]),
+    "zxc_seekable_get_num_blocks": (_U32, [_P]),
+    "zxc_seekable_get_decompressed_size": (_U64, [_P]),
+    "zxc_seekable_get_block_comp_size": (_U32, [_P, _U32]),
+    "zxc_seekable_get_block_decomp_size": (_U32, [_P, _U32]),
+    "zxc_seekable_decompress_range": (_I64, [_P, _P, _SZ, _U64, _SZ]),
+    "zxc_seekable_decompress_range_mt": (_I64, [_P, _P, _SZ, _U64, _SZ, _I]),
+    "zxc_seekable_set_dict": (_I, [_P, _STR, _SZ, _STR]),
+    # include/zxc_mi355x.h: the block-level calls
+    "zxc_mi355x_device_count": (_I, []),
+    "zxc_mi355x_set_device": (_I, [_I]),
+    "zxc_mi355x_plan_seekable": (_I64, [_P, _U32, _U32, _U64, _P]),
+    "zxc_mi355x_decode_blocks_device": (_I, [_P, _P, _U32, _P, _P, _U32, _I, _P]),
+    "zxc_mi355x_encode_slot_stride": (_U32, [_U32]),
+    "zxc_mi355x_encode_blocks_device": (_I, [_P, _U64, _U32, _I, _I, _P, _P, _P]),
+    # whole archives, device to device
+    "zxc_mi355x_compress_device_work_size": (_U64, [_U64, _CO]),
+    "zxc_mi355x_compress_device": (_I, [_P, _U64, _P, _U64, _CO] + _TAIL),
+    "zxc_mi355x_decompress_device_work_size": (_U64, [_U64, _U64, _U32]),
+    "zxc_mi355x_decompress_device": (_I, [_P, _U64, _P, _U64, _U32, _DO] + _TAIL),
+    "zxc_mi355x_frame_info_device": (_I, [_P, _U64, C.POINTER(_U32), C.POINTER(_U64), C.POINTER(_I), _P]),
+    # random access
+    "zxc_mi355x_seekable_index_size": (_U64, [_U32]),
+    "zxc_mi355x_seekable_open_device": (_I, [_P, _U64, _U32, _U32, _P, _U64, _P]),
+    "zxc_mi355x_decompress_ranges_device_work_size": (_U64, [_U32, _U64, _U32]),
+    "zxc_mi355x_decompress_ranges_device": (_I, _RANGES + _TAIL),
+    # with a dictionary in device memory
+    "zxc_mi355x_dict_prepare_device": (_I, [_P, _U32, _P, _P, _P]),
+    "zxc_mi355x_compress_dict_device_work_size": (_U64, [_U64, _CO, _U32]),
+    "zxc_mi355x_compress_dict_device": (_I, [_P, _U64, _P, _U64, _CO, _DD] + _TAIL),
+    "zxc_mi355x_decompress_dict_device": (_I, [_P, _U64, _P, _U64, _U32, _DO, _DD] + _TAIL),
+    "zxc_mi355x_decompress_ranges_dict_device": (_I, _RANGES + [_DD] + _TAIL),
+    # many archives / many buffers per call
+    "zxc_mi355x_decompress_batch_device_work_size": (_U64, [_U32, _U64, _U32]),
+    "zxc_mi355x_decompress_batch_device": (_I, _DBATCH + _TAIL),
+    "zxc_mi355x_decompress_batch_dict_device": (_I, _DBATCH + [_DD] + _TAIL),
+    "zxc_mi355x_compress_batch_device_work_size": (_U64, [_U32, _U64, _CO]),
+    "zxc_mi355x_compress_batch_dict_device_work_size": (_U64, [_U32, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_batch_device": (_I, _CBATCH + _TAIL),
+    "zxc_mi355x_compress_batch_dict_device": (_I, _CBATCH + [_DD] + _TAIL),
+    "zxc_mi355x_compress_pack_device_work_size": (_U64, [_U32, _U64, _CO]),
+    "zxc_mi355x_compress_pack_dict_device_work_size": (_U64, [_U32, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_pack_device": (_I, _CPACK + _PACK_TAIL),
+    "zxc_mi355x_compress_pack_dict_device": (_I, _CPACK + [_DD] + _PACK_TAIL),
+    # one archive from many pieces: the append session
+    "zxc_mi355x_compress_append_device_work_size": (_U64, [_U64, _U64, _CO]),
+    "zxc_mi355x_compress_append_dict_device_work_size": (_U64, [_U64, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_begin_device": (_I, _CBEGIN + [_P, _U64, _P]),
+    "zxc_mi355x_compress_begin_dict_device": (_I, _CBEGIN + [_DD, _P, _U64, _P]),
+    "zxc_mi355x_compress_append_device": (_I, [_CS, _P, _U64, _P]),
+    "zxc_mi355x_compress_end_device": (_I, [_CS, _P, _P]),
+    "zxc_mi355x_compress_appendv_device_scratch_size": (_U64, [_U32, _U64, _CO]),
+    "zxc_mi355x_compress_appendv_dict_device_scratch_size": (_U64, [_U32, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_appendv_device": (_I, [_CS] + _IOV),
+    "zxc_mi355x_compress_appendv_dict_device": (_I, [_CS] + _IOV),
+    # one archive into many pieces: the take session
+    "zxc_mi355x_decompress_take_device_work_size": (_U64, [_U64, _U64, _U64, _U32]),
+    "zxc_mi355x_decompress_begin_device": (_I, _DBEGIN + [_P, _U64, _P]),
+    "zxc_mi355x_decompress_begin_dict_device": (_I, _DBEGIN + [_DD, _P, _U64, _P]),
+    "zxc_mi355x_decompress_take_device": (_I, [_DS, _P, _U64, _P]),
+    "zxc_mi355x_decompress_end_device": (_I, [_DS, _P, _P]),
+    "zxc_mi355x_decompress_takev_device_scratch_size": (_U64, [_U32, _U64, _U32]),
+    "zxc_mi355x_decompress_takev_device": (_I, [_DS] + _IOV),
+    # include/zxc_stream.h (FILE* as void*)
+    "zxc_stream_compress": (_I64, [_P, _P, _CO]),
+    "zxc_stream_decompress": (_I64, [_P, _P, _DO]),
+    "zxc_stream_get_decompressed_size": (_I64, [_P]),
+    "zxc_seekable_open_file": (_P, [_P]),
+    # include/zxc_pstream.h
+    "zxc_cstream_create": (_P, [_CO]),
+    "zxc_cstream_free": (None, [_P]),
+    "zxc_cstream_compress": (_I64, [_P, _OUT, _IN]),
+    "zxc_cstream_end": (_I64, [_P, _OUT]),
+    "zxc_cstream_in_size": (_SZ, [_P]),
+    "zxc_cstream_out_size": (_SZ, [_P]),
+    "zxc_dstream_create": (_P, [_DO]),
+    "zxc_dstream_free": (None, [_P]),
+    "zxc_dstream_decompress": (_I64, [_P, _OUT, _IN]),
+    "zxc_dstream_finished": (_I, [_P]),
+    "zxc_dstream_in_size": (_SZ, [_P]),
+    "zxc_dstream_out_size": (_SZ, [_P]),
+}
+_STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
+_PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
+
+
+def _bind(L, names=_PROTOTYPES):
+    """Set restype and argtypes of those of `names` that L exports (the reference and the mock-device library have no device
+    calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
+    for name in names:
+        f = getattr(L, name, None)
+        if f is not None:
+            f.restype, f.argtypes = _PROTOTYPES[name]
+    return L
+
+
+# The per-call binders of earlier versions keep their names and their contract (a library in, the same library out, bound) for
+# callers that hold a library of their own; each applies the whole table.
+_bind_decompress_device = _bind_ranges_device = _bind_dict_device = _bind_decompress_batch_device = _bind_compress_batch_device = \
+    _bind_compress_pack_device = _bind_compress_append_device = _bind_decompress_take_device = _bind_decompress_takev_device = _bind
+
+
+def _bind_stream(L):
+    return _bind(L, _STREAM)
+
+
+def _bind_pstream(L):
+    return _bind(L, _PSTREAM)
+
+
 def lib_path():
     # The product library, always — unless a development harness under tools/ asks for an A/B build on purpose: both
     # ZXC_TOOLS_AB=1 and ZXC_LIB_VARIANT=<file> must be set (a stray ZXC_LIB_VARIANT alone is ignored: experiment builds may
@@ -60,51 +215,19 @@ def lib():
         p = lib_path()
         if not os.path.exists(p):
             raise ImportError(f"{p} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        L = C.CDLL(p)
-        L.zxc_error_name.restype = C.c_char_p
-        L.zxc_error_name.argtypes = [C.c_int]
-        L.zxc_decompress.restype = C.c_int64
-        L.zxc_decompress.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_DecompressOpts)]
-        L.zxc_compress.restype = C.c_int64
-        L.zxc_compress.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_CompressOpts)]
-        L.zxc_mi355x_encode_slot_stride.restype = C.c_uint32
-        L.zxc_mi355x_encode_slot_stride.argtypes = [C.c_uint32]
-        L.zxc_mi355x_encode_blocks_device.restype = C.c_int
-        L.zxc_mi355x_encode_blocks_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p]
-        L.zxc_get_decompressed_size.restype = C.c_uint64
-        L.zxc_get_decompressed_size.argtypes = [C.c_char_p, C.c_size_t]
-        L.zxc_compress_bound.restype = C.c_uint64
-        L.zxc_compress_bound.argtypes = [C.c_size_t]
-        L.zxc_seekable_open.restype = C.c_void_p
-        L.zxc_seekable_open.argtypes = [C.c_char_p, C.c_size_t]
-        L.zxc_seekable_free.argtypes = [C.c_void_p]
-        L.zxc_seekable_open_reader.restype = C.c_void_p
-        L.zxc_seekable_open_reader.argtypes = [C.POINTER(_Reader)]
-        for f in ("zxc_seekable_get_num_blocks",):
-            getattr(L, f).restype = C.c_uint32
-            getattr(L, f).argtypes = [C.c_void_p]
-        L.zxc_seekable_get_decompressed_size.restype = C.c_uint64
-        L.zxc_seekable_get_decompressed_size.argtypes = [C.c_void_p]
-        for f in ("zxc_seekable_get_block_comp_size", "zxc_seekable_get_block_decomp_size"):
-            getattr(L, f).restype = C.c_uint32
-            getattr(L, f).argtypes = [C.c_void_p, C.c_uint32]
-        L.zxc_seekable_decompress_range.restype = C.c_int64
-        L.zxc_seekable_decompress_range.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_size_t]
-        L.zxc_seekable_decompress_range_mt.restype = C.c_int64
-        L.zxc_seekable_decompress_range_mt.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64,
-                                                       C.c_size_t, C.c_int]
-        L.zxc_seekable_set_dict.restype = C.c_int
-        L.zxc_seekable_set_dict.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p]
-        L.zxc_mi355x_device_count.restype = C.c_int
-        L.zxc_mi355x_set_device.argtypes = [C.c_int]
-        L.zxc_mi355x_plan_seekable.restype = C.c_int64
-        L.zxc_mi355x_plan_seekable.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]
-        L.zxc_mi355x_decode_blocks_device.restype = C.c_int
-        L.zxc_mi355x_decode_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                      C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
-        _LIB = L
+        _LIB = _bind(C.CDLL(p))
     return _LIB
+
+
+def _call(name, *args):
+    """lib().<name>(*args) by the table: where the prototype says void*, an integer device pointer or stream goes as
+    c_void_p (0 stays NULL); a ctypes struct or scalar goes by reference; the rest goes as it is. Raises ZxcError(rc, name) on
+    rc < 0."""
+    rc = getattr(lib(), name)(*[C.c_void_p(a or None) if t is _P else C.byref(a) if isinstance(a, (C.Structure, C._SimpleCData))
+                                else a for t, a in zip(_PROTOTYPES[name][1], args)])
+    if rc < 0:
+        raise ZxcError(rc, name)
+    return rc
 
 
 def error_name(code):
@@ -118,23 +241,33 @@ def get_decompressed_size(comp: bytes) -> int:
     return int(lib().zxc_get_decompressed_size(comp, len(comp)))
 
 
+def _set_dict(o, dict_, dict_huf):
+    """Point an opts struct at a dictionary (content + optional 128-byte shared table); returns the buffers to keep alive."""
+    if not dict_:
+        return None
+    keep = (C.create_string_buffer(dict_, len(dict_)), C.create_string_buffer(dict_huf, 128) if dict_huf else None)
+    o.dict = C.cast(keep[0], C.c_void_p)
+    o.dict_size = len(dict_)
+    o.dict_huf = C.cast(keep[1], C.c_void_p) if dict_huf else None
+    return keep
+
+
+def _host_result(rc, out, what, raise_on_error):
+    if rc < 0:
+        if raise_on_error:
+            raise ZxcError(rc, what)
+        return rc, b""
+    return out.raw[:rc] if raise_on_error else (rc, out.raw[:rc])
+
+
 def compress(data: bytes, level=3, block_size=65536, seekable=True, checksum=False, raise_on_error=True, dict_=None,
              dict_huf=None):
     """zxc_compress(): host buffer in, v8 archive out (blocks encoded on the GPU)."""
     o = _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
-    if dict_:
-        _keep = (C.create_string_buffer(dict_, len(dict_)), C.create_string_buffer(dict_huf, 128) if dict_huf else None)
-        o.dict = C.cast(_keep[0], C.c_void_p)
-        o.dict_size = len(dict_)
-        o.dict_huf = C.cast(_keep[1], C.c_void_p) if dict_huf else None
+    _keep = _set_dict(o, dict_, dict_huf)
     cap = int(lib().zxc_compress_bound(len(data)))
     out = C.create_string_buffer(max(cap, 64))
-    rc = lib().zxc_compress(data, len(data), out, cap, C.byref(o))
-    if rc < 0:
-        if raise_on_error:
-            raise ZxcError(rc, "zxc_compress")
-        return rc, b""
-    return out.raw[:rc] if raise_on_error else (rc, out.raw[:rc])
+    return _host_result(lib().zxc_compress(data, len(data), out, cap, C.byref(o)), out, "zxc_compress", raise_on_error)
 
 
 def decompress(comp: bytes, capacity=None, checksum=False, raise_on_error=True, dict_=None, dict_huf=None):
@@ -142,17 +275,9 @@ def decompress(comp: bytes, capacity=None, checksum=False, raise_on_error=True, 
     cap = get_decompressed_size(comp) if capacity is None else int(capacity)
     out = C.create_string_buffer(max(cap, 1))
     o = _DecompressOpts(checksum_enabled=int(checksum))
-    if dict_:
-        _keep = (C.create_string_buffer(dict_, len(dict_)), C.create_string_buffer(dict_huf, 128) if dict_huf else None)
-        o.dict = C.cast(_keep[0], C.c_void_p)
-        o.dict_size = len(dict_)
-        o.dict_huf = C.cast(_keep[1], C.c_void_p) if dict_huf else None
+    _keep = _set_dict(o, dict_, dict_huf)
     rc = lib().zxc_decompress(comp, len(comp), out if cap else None, cap, C.byref(o))
-    if rc < 0:
-        if raise_on_error:
-            raise ZxcError(rc, "zxc_decompress")
-        return rc, b""
-    return out.raw[:rc] if raise_on_error else (rc, out.raw[:rc])
+    return _host_result(rc, out, "zxc_decompress", raise_on_error)
 
 
 class Seekable:
@@ -211,42 +336,40 @@ class Seekable:
             rc = lib().zxc_seekable_decompress_range(self._h, out, length, offset, length)
         else:
             rc = lib().zxc_seekable_decompress_range_mt(self._h, out, length, offset, length, n_threads)
-        if rc < 0:
-            if raise_on_error:
-                raise ZxcError(rc, "zxc_seekable_decompress_range")
-            return rc, b""
-        return out.raw[:rc] if raise_on_error else (rc, out.raw[:rc])
+        return _host_result(rc, out, "zxc_seekable_decompress_range", raise_on_error)
 
     def plan(self, first=0, count=None, comp_rebase=0):
         """Job table (numpy structured array) for blocks [first, first+count)."""
         count = self.num_blocks - first if count is None else count
         jobs = np.zeros(count, dtype=JOB_DTYPE)
-        rc = lib().zxc_mi355x_plan_seekable(self._h, first, count, comp_rebase, jobs.ctypes.data)
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_plan_seekable")
+        _call("zxc_mi355x_plan_seekable", self._h, first, count, comp_rebase, jobs.ctypes.data)
         return jobs
 
 
 def decode_blocks_device(d_comp, d_jobs, n_jobs, d_out, d_status, block_size, verify_trailer=False, stream=0):
     """zxc_mi355x_decode_blocks_device(): raw device pointers (ints), asynchronous on `stream`."""
-    rc = lib().zxc_mi355x_decode_blocks_device(C.c_void_p(d_comp), C.c_void_p(d_jobs), n_jobs, C.c_void_p(d_out),
-                                               C.c_void_p(d_status), block_size, int(verify_trailer),
-                                               C.c_void_p(stream))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decode_blocks_device")
+    _call("zxc_mi355x_decode_blocks_device", d_comp, d_jobs, n_jobs, d_out, d_status, block_size, int(verify_trailer), stream)
 
 
-def _compress_device_opts(level, block_size, seekable, checksum):
+def _copts(level, block_size, seekable, checksum):
     return _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
+
+
+def _dopts(checksum):
+    return _DecompressOpts(checksum_enabled=int(checksum))
+
+
+def _dev_dict(dict_):
+    """dict_: None, or (d_content, size, d_huf or 0, d_id), raw device pointers as ints. -> a zxc_dev_dict_t or None"""
+    if dict_ is None:
+        return None
+    d_content, size, d_huf, d_id = dict_
+    return _DevDict(d_content or None, d_huf or None, d_id or None, size)
 
 
 def compress_device_work_size(src_size, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_device_work_size(): bytes of device scratch compress_device needs (0 for invalid options)."""
-    L = lib()
-    L.zxc_mi355x_compress_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts)]
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(L.zxc_mi355x_compress_device_work_size(src_size, C.byref(o)))
+    return int(_call("zxc_mi355x_compress_device_work_size", src_size, _copts(level, block_size, seekable, checksum)))
 
 
 def compress_device(d_src, src_size, d_dst, dst_capacity, d_work, work_size, d_result, level=3, block_size=0,
@@ -254,203 +377,96 @@ def compress_device(d_src, src_size, d_dst, dst_capacity, d_work, work_size, d_r
     """zxc_mi355x_compress_device(): raw device pointers (ints, e.g. tensor.data_ptr()), asynchronous on `stream`
     (e.g. torch.cuda.current_stream().cuda_stream). The archive size or a negative zxc_error_t lands in the int64 at
     d_result; a synchronous failure raises ZxcError."""
-    L = lib()
-    L.zxc_mi355x_compress_device.restype = C.c_int
-    L.zxc_mi355x_compress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts),
-                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = L.zxc_mi355x_compress_device(C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity,
-                                      C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None),
-                                      C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_device")
-
-
-def _bind_decompress_device(L):
-    L.zxc_mi355x_decompress_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_decompress_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
-    L.zxc_mi355x_decompress_device.restype = C.c_int
-    L.zxc_mi355x_decompress_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
-                                               C.POINTER(_DecompressOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_frame_info_device.restype = C.c_int
-    L.zxc_mi355x_frame_info_device.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
-                                               C.POINTER(C.c_int), C.c_void_p]
-    return L
+    _call("zxc_mi355x_compress_device", d_src, src_size, d_dst, dst_capacity, _copts(level, block_size, seekable, checksum),
+          d_work, work_size, d_result, stream)
 
 
 def decompress_device_work_size(src_size, dst_capacity, block_size):
     """zxc_mi355x_decompress_device_work_size(): bytes of device scratch decompress_device needs (0 for refused arguments)."""
-    return int(_bind_decompress_device(lib()).zxc_mi355x_decompress_device_work_size(src_size, dst_capacity, block_size))
+    return int(_call("zxc_mi355x_decompress_device_work_size", src_size, dst_capacity, block_size))
 
 
 def decompress_device(d_src, src_size, d_dst, dst_capacity, block_size, d_work, work_size, d_result, checksum=False, stream=0):
     """zxc_mi355x_decompress_device(): raw device pointers (ints, e.g. tensor.data_ptr()), asynchronous on `stream`. The
     decoded size or the negative zxc_error_t zxc_decompress would return lands in the int64 at d_result; a synchronous
     failure raises ZxcError."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
-    rc = _bind_decompress_device(lib()).zxc_mi355x_decompress_device(
-        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, block_size, C.byref(o),
-        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_device")
+    _call("zxc_mi355x_decompress_device", d_src, src_size, d_dst, dst_capacity, block_size, _dopts(checksum), d_work, work_size,
+          d_result, stream)
 
 
 def frame_info_device(d_src, src_size, stream=0):
     """zxc_mi355x_frame_info_device(): -> (block_size, decompressed_size, has_checksum) of an archive in device memory.
     Synchronises `stream`."""
     bs, n, ck = C.c_uint32(0), C.c_uint64(0), C.c_int(0)
-    rc = _bind_decompress_device(lib()).zxc_mi355x_frame_info_device(C.c_void_p(d_src or None), src_size, C.byref(bs), C.byref(n),
-                                                                     C.byref(ck), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_frame_info_device")
+    _call("zxc_mi355x_frame_info_device", d_src, src_size, bs, n, ck, stream)
     return int(bs.value), int(n.value), bool(ck.value)
-
-
-def _bind_ranges_device(L):
-    L.zxc_mi355x_seekable_index_size.restype = C.c_uint64
-    L.zxc_mi355x_seekable_index_size.argtypes = [C.c_uint32]
-    L.zxc_mi355x_seekable_open_device.restype = C.c_int
-    L.zxc_mi355x_seekable_open_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_decompress_ranges_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_decompress_ranges_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
-    L.zxc_mi355x_decompress_ranges_device.restype = C.c_int
-    L.zxc_mi355x_decompress_ranges_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
-                                                      C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                      C.c_void_p]
-    return L
 
 
 def seekable_index_size(max_blocks):
     """zxc_mi355x_seekable_index_size(): bytes of the device index of an archive of at most max_blocks blocks."""
-    return int(_bind_ranges_device(lib()).zxc_mi355x_seekable_index_size(max_blocks))
+    return int(_call("zxc_mi355x_seekable_index_size", max_blocks))
 
 
 def seekable_open_device(d_src, src_size, block_size, max_blocks, d_index, index_size, stream=0):
     """zxc_mi355x_seekable_open_device(): raw device pointers (ints), asynchronous on `stream`. Whether the archive's seek table
     was accepted lands in the index's first int32; a synchronous failure raises ZxcError."""
-    rc = _bind_ranges_device(lib()).zxc_mi355x_seekable_open_device(C.c_void_p(d_src or None), src_size, block_size, max_blocks,
-                                                                    C.c_void_p(d_index or None), index_size, C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_seekable_open_device")
+    _call("zxc_mi355x_seekable_open_device", d_src, src_size, block_size, max_blocks, d_index, index_size, stream)
 
 
 def decompress_ranges_device_work_size(n_ranges, max_len, block_size):
     """zxc_mi355x_decompress_ranges_device_work_size(): bytes of device scratch the call needs (0 for refused arguments)."""
-    return int(_bind_ranges_device(lib()).zxc_mi355x_decompress_ranges_device_work_size(n_ranges, max_len, block_size))
+    return int(_call("zxc_mi355x_decompress_ranges_device_work_size", n_ranges, max_len, block_size))
 
 
 def decompress_ranges_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, d_work, work_size,
                              d_results, stream=0):
     """zxc_mi355x_decompress_ranges_device(): raw device pointers (ints); d_ranges is n_ranges x RANGE_DTYPE in device memory,
     d_results n_ranges x int64. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
-    rc = _bind_ranges_device(lib()).zxc_mi355x_decompress_ranges_device(
-        C.c_void_p(d_src or None), src_size, C.c_void_p(d_index or None), C.c_void_p(d_ranges or None), n_ranges, max_len,
-        C.c_void_p(d_dst or None), dst_capacity, block_size, C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
-        C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_ranges_device")
+    _call("zxc_mi355x_decompress_ranges_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity,
+          block_size, d_work, work_size, d_results, stream)
 
 
 # ---- the device calls with a dictionary in device memory (include/zxc_mi355x.h: zxc_dev_dict_t)
-class _DevDict(C.Structure):  # zxc_dev_dict_t
-    _fields_ = [("d_content", C.c_void_p), ("d_huf", C.c_void_p), ("d_id", C.c_void_p), ("size", C.c_uint32)]
-
-
-def _dev_dict(dict_):
-    """dict_: None, or (d_content, size, d_huf or 0, d_id), raw device pointers as ints. -> a zxc_dev_dict_t pointer or None"""
-    if dict_ is None:
-        return None
-    d_content, size, d_huf, d_id = dict_
-    return C.byref(_DevDict(d_content or None, d_huf or None, d_id or None, size))
-
-
-def _bind_dict_device(L):
-    L.zxc_mi355x_dict_prepare_device.restype = C.c_int
-    L.zxc_mi355x_dict_prepare_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_compress_dict_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_dict_device_work_size.argtypes = [C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
-    L.zxc_mi355x_compress_dict_device.restype = C.c_int
-    L.zxc_mi355x_compress_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts),
-                                                  C.POINTER(_DevDict), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_decompress_dict_device.restype = C.c_int
-    L.zxc_mi355x_decompress_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
-                                                    C.POINTER(_DecompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64,
-                                                    C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_decompress_ranges_dict_device.restype = C.c_int
-    L.zxc_mi355x_decompress_ranges_dict_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
-                                                           C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_DevDict), C.c_void_p,
-                                                           C.c_uint64, C.c_void_p, C.c_void_p]
-    return L
-
-
 def dict_prepare_device(d_content, size, d_huf, d_id, stream=0):
     """zxc_mi355x_dict_prepare_device(): the uint32 at d_id receives zxc_dict_id of the content (and the 128-byte table at d_huf,
     or 0 for none), computed on the device, asynchronously on `stream`. A synchronous failure raises ZxcError."""
-    rc = _bind_dict_device(lib()).zxc_mi355x_dict_prepare_device(C.c_void_p(d_content or None), size, C.c_void_p(d_huf or None),
-                                                                 C.c_void_p(d_id or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_dict_prepare_device")
+    _call("zxc_mi355x_dict_prepare_device", d_content, size, d_huf, d_id, stream)
 
 
 def compress_dict_device_work_size(src_size, dict_size, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_dict_device_work_size(): bytes of device scratch compress_dict_device needs with a dictionary of
     dict_size bytes (0 for invalid options; dict_size 0 gives compress_device_work_size)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(_bind_dict_device(lib()).zxc_mi355x_compress_dict_device_work_size(src_size, C.byref(o), dict_size))
+    return int(_call("zxc_mi355x_compress_dict_device_work_size", src_size, _copts(level, block_size, seekable, checksum), dict_size))
 
 
 def compress_dict_device(d_src, src_size, d_dst, dst_capacity, dict_, d_work, work_size, d_result, level=3, block_size=0,
                          seekable=False, checksum=False, stream=0):
     """zxc_mi355x_compress_dict_device(): compress_device with a dictionary in device memory, dict_ = (d_content, size, d_huf or 0,
     d_id) with d_id prepared by dict_prepare_device, or None for no dictionary."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = _bind_dict_device(lib()).zxc_mi355x_compress_dict_device(
-        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, C.byref(o), _dev_dict(dict_),
-        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_dict_device")
+    _call("zxc_mi355x_compress_dict_device", d_src, src_size, d_dst, dst_capacity, _copts(level, block_size, seekable, checksum),
+          _dev_dict(dict_), d_work, work_size, d_result, stream)
 
 
 def decompress_dict_device(d_src, src_size, d_dst, dst_capacity, block_size, dict_, d_work, work_size, d_result, checksum=False,
                            stream=0):
     """zxc_mi355x_decompress_dict_device(): decompress_device with a dictionary in device memory (dict_ as in
     compress_dict_device); the work size is decompress_device_work_size."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
-    rc = _bind_dict_device(lib()).zxc_mi355x_decompress_dict_device(
-        C.c_void_p(d_src or None), src_size, C.c_void_p(d_dst or None), dst_capacity, block_size, C.byref(o), _dev_dict(dict_),
-        C.c_void_p(d_work or None), work_size, C.c_void_p(d_result or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_dict_device")
+    _call("zxc_mi355x_decompress_dict_device", d_src, src_size, d_dst, dst_capacity, block_size, _dopts(checksum), _dev_dict(dict_),
+          d_work, work_size, d_result, stream)
 
 
 def decompress_ranges_dict_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, dict_,
                                   d_work, work_size, d_results, stream=0):
     """zxc_mi355x_decompress_ranges_dict_device(): decompress_ranges_device with a dictionary in device memory (dict_ as in
     compress_dict_device); index and work size are the sibling's."""
-    rc = _bind_dict_device(lib()).zxc_mi355x_decompress_ranges_dict_device(
-        C.c_void_p(d_src or None), src_size, C.c_void_p(d_index or None), C.c_void_p(d_ranges or None), n_ranges, max_len,
-        C.c_void_p(d_dst or None), dst_capacity, block_size, _dev_dict(dict_), C.c_void_p(d_work or None), work_size,
-        C.c_void_p(d_results or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_ranges_dict_device")
+    _call("zxc_mi355x_decompress_ranges_dict_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity,
+          block_size, _dev_dict(dict_), d_work, work_size, d_results, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)
-def _bind_decompress_batch_device(L):
-    L.zxc_mi355x_decompress_batch_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_decompress_batch_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
-    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_DecompressOpts)]
-    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_decompress_batch_device.restype = C.c_int
-    L.zxc_mi355x_decompress_batch_device.argtypes = head + tail
-    L.zxc_mi355x_decompress_batch_dict_device.restype = C.c_int
-    L.zxc_mi355x_decompress_batch_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
-    return L
-
-
 def decompress_batch_device_work_size(n_items, max_capacity, block_size):
     """zxc_mi355x_decompress_batch_device_work_size(): bytes of device scratch the call needs (0 for refused arguments)."""
-    return int(_bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_device_work_size(n_items, max_capacity, block_size))
+    return int(_call("zxc_mi355x_decompress_batch_device_work_size", n_items, max_capacity, block_size))
 
 
 def decompress_batch_device(d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity, block_size, d_work, work_size,
@@ -458,51 +474,29 @@ def decompress_batch_device(d_src, src_capacity, d_items, n_items, max_capacity,
     """zxc_mi355x_decompress_batch_device(): raw device pointers (ints); d_items is n_items x ITEM_DTYPE in device memory, d_results
     n_items x int64, each what zxc_decompress would return for that item. Asynchronous on `stream`; a synchronous failure raises
     ZxcError."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
-    rc = _bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_capacity, C.c_void_p(d_dst or None),
-        dst_capacity, block_size, C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
-        C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_batch_device")
+    _call("zxc_mi355x_decompress_batch_device", d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity, block_size,
+          _dopts(checksum), d_work, work_size, d_results, stream)
 
 
 def decompress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity, block_size, dict_, d_work,
                                  work_size, d_results, checksum=False, stream=0):
     """zxc_mi355x_decompress_batch_dict_device(): decompress_batch_device with one dictionary in device memory for the whole batch
     (dict_ as in compress_dict_device); the work size is the sibling's."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
-    rc = _bind_decompress_batch_device(lib()).zxc_mi355x_decompress_batch_dict_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_capacity, C.c_void_p(d_dst or None),
-        dst_capacity, block_size, C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None),
-        C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_batch_dict_device")
+    _call("zxc_mi355x_decompress_batch_dict_device", d_src, src_capacity, d_items, n_items, max_capacity, d_dst, dst_capacity,
+          block_size, _dopts(checksum), _dev_dict(dict_), d_work, work_size, d_results, stream)
 
 
 # ---- many buffers per call: the write side (zxc_dev_item_t: src_* the buffer to compress, dst_* where its archive goes)
-def _bind_compress_batch_device(L):
-    L.zxc_mi355x_compress_batch_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_batch_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_batch_dict_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_batch_dict_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
-    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_CompressOpts)]
-    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_compress_batch_device.restype = C.c_int
-    L.zxc_mi355x_compress_batch_device.argtypes = head + tail
-    L.zxc_mi355x_compress_batch_dict_device.restype = C.c_int
-    L.zxc_mi355x_compress_batch_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
-    return L
+def _batch_work_size(name, n_items, max_size, o, dict_size):
+    if dict_size:
+        return int(_call(f"zxc_mi355x_{name}_dict_device_work_size", n_items, max_size, o, dict_size))
+    return int(_call(f"zxc_mi355x_{name}_device_work_size", n_items, max_size, o))
 
 
 def compress_batch_device_work_size(n_items, max_size, level=3, block_size=0, seekable=False, checksum=False, dict_size=0):
     """zxc_mi355x_compress_batch_device_work_size(), or with dict_size the _dict call's: bytes of device scratch the call needs
     (0 for refused arguments)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    L = _bind_compress_batch_device(lib())
-    if dict_size:
-        return int(L.zxc_mi355x_compress_batch_dict_device_work_size(n_items, max_size, C.byref(o), dict_size))
-    return int(L.zxc_mi355x_compress_batch_device_work_size(n_items, max_size, C.byref(o)))
+    return _batch_work_size("compress_batch", n_items, max_size, _copts(level, block_size, seekable, checksum), dict_size)
 
 
 def compress_batch_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, d_work, work_size, d_results, level=3,
@@ -510,49 +504,23 @@ def compress_batch_device(d_src, src_capacity, d_items, n_items, max_size, d_dst
     """zxc_mi355x_compress_batch_device(): raw device pointers (ints); d_items is n_items x ITEM_DTYPE in device memory (src_* the
     buffer to compress, dst_* where its archive goes), d_results n_items x int64, each the item's archive size or a negative
     zxc_error_t. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = _bind_compress_batch_device(lib()).zxc_mi355x_compress_batch_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
-        C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_batch_device")
+    _call("zxc_mi355x_compress_batch_device", d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity,
+          _copts(level, block_size, seekable, checksum), d_work, work_size, d_results, stream)
 
 
 def compress_batch_dict_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, dict_, d_work, work_size, d_results,
                                level=3, block_size=0, seekable=False, checksum=False, stream=0):
     """zxc_mi355x_compress_batch_dict_device(): compress_batch_device with one dictionary in device memory for the whole batch
     (dict_ as in compress_dict_device); the work size is compress_batch_device_work_size(..., dict_size=size)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = _bind_compress_batch_device(lib()).zxc_mi355x_compress_batch_dict_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
-        C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_results or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_batch_dict_device")
+    _call("zxc_mi355x_compress_batch_dict_device", d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity,
+          _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, d_results, stream)
 
 
 # ---- many buffers per call, the archives packed back to back (d_packed: the item table of decompress_batch_device)
-def _bind_compress_pack_device(L):
-    L.zxc_mi355x_compress_pack_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_pack_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_pack_dict_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_pack_dict_device_work_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
-    head = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_CompressOpts)]
-    tail = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_compress_pack_device.restype = C.c_int
-    L.zxc_mi355x_compress_pack_device.argtypes = head + tail
-    L.zxc_mi355x_compress_pack_dict_device.restype = C.c_int
-    L.zxc_mi355x_compress_pack_dict_device.argtypes = head + [C.POINTER(_DevDict)] + tail
-    return L
-
-
 def compress_pack_device_work_size(n_items, max_size, level=3, block_size=0, seekable=False, checksum=False, dict_size=0):
     """zxc_mi355x_compress_pack_device_work_size(), or with dict_size the _dict call's: bytes of device scratch the call needs
     (0 for refused arguments)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    L = _bind_compress_pack_device(lib())
-    if dict_size:
-        return int(L.zxc_mi355x_compress_pack_dict_device_work_size(n_items, max_size, C.byref(o), dict_size))
-    return int(L.zxc_mi355x_compress_pack_device_work_size(n_items, max_size, C.byref(o)))
+    return _batch_work_size("compress_pack", n_items, max_size, _copts(level, block_size, seekable, checksum), dict_size)
 
 
 def compress_pack_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align, d_work, work_size, d_packed,
@@ -561,81 +529,36 @@ def compress_pack_device(d_src, src_capacity, d_items, n_items, max_size, d_dst,
     Raw device pointers (ints); of d_items (n_items x ITEM_DTYPE) only src_off / src_size are read; d_packed (n_items x ITEM_DTYPE,
     may be d_items) receives the item table of decompress_batch_device, d_results n_items x int64, d_total one uint64: the end of
     the last archive, whatever dst_capacity was. Asynchronous on `stream`; a synchronous failure raises ZxcError."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = _bind_compress_pack_device(lib()).zxc_mi355x_compress_pack_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
-        align, C.byref(o), C.c_void_p(d_work or None), work_size, C.c_void_p(d_packed or None), C.c_void_p(d_results or None),
-        C.c_void_p(d_total or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_pack_device")
+    _call("zxc_mi355x_compress_pack_device", d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align,
+          _copts(level, block_size, seekable, checksum), d_work, work_size, d_packed, d_results, d_total, stream)
 
 
 def compress_pack_dict_device(d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align, dict_, d_work, work_size,
                               d_packed, d_results, d_total, level=3, block_size=0, seekable=False, checksum=False, stream=0):
     """zxc_mi355x_compress_pack_dict_device(): compress_pack_device with one dictionary in device memory for the whole batch
     (dict_ as in compress_dict_device); the work size is compress_pack_device_work_size(..., dict_size=size)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    rc = _bind_compress_pack_device(lib()).zxc_mi355x_compress_pack_dict_device(
-        C.c_void_p(d_src or None), src_capacity, C.c_void_p(d_items or None), n_items, max_size, C.c_void_p(d_dst or None), dst_capacity,
-        align, C.byref(o), _dev_dict(dict_), C.c_void_p(d_work or None), work_size, C.c_void_p(d_packed or None),
-        C.c_void_p(d_results or None), C.c_void_p(d_total or None), C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_pack_dict_device")
+    _call("zxc_mi355x_compress_pack_dict_device", d_src, src_capacity, d_items, n_items, max_size, d_dst, dst_capacity, align,
+          _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, d_packed, d_results, d_total, stream)
 
 
-# ---- one archive from many pieces: a session (zxc_dev_cappend_t is a host struct of 16 words, caller-owned)
-class _DevCappend(C.Structure):  # zxc_dev_cappend_t
-    _fields_ = [("opaque", C.c_uint64 * 16)]
-
-
-def _bind_compress_append_device(L):
-    L.zxc_mi355x_compress_append_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_append_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_begin_device.restype = C.c_int
-    L.zxc_mi355x_compress_begin_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
-                                                   C.POINTER(_CompressOpts), C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_compress_append_device.restype = C.c_int
-    L.zxc_mi355x_compress_append_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_compress_end_device.restype = C.c_int
-    L.zxc_mi355x_compress_end_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_void_p]
-    L.zxc_mi355x_compress_append_dict_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_append_dict_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
-    L.zxc_mi355x_compress_begin_dict_device.restype = C.c_int
-    L.zxc_mi355x_compress_begin_dict_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
-                                                        C.POINTER(_CompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_compress_appendv_device_scratch_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_appendv_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts)]
-    L.zxc_mi355x_compress_appendv_device.restype = C.c_int
-    L.zxc_mi355x_compress_appendv_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
-                                                     C.c_void_p]
-    L.zxc_mi355x_compress_appendv_dict_device_scratch_size.restype = C.c_uint64
-    L.zxc_mi355x_compress_appendv_dict_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(_CompressOpts), C.c_uint32]
-    L.zxc_mi355x_compress_appendv_dict_device.restype = C.c_int
-    L.zxc_mi355x_compress_appendv_dict_device.argtypes = [C.POINTER(_DevCappend), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
-                                                          C.c_void_p]
-    return L
-
-
+# ---- one archive from many pieces: a session
 def compress_append_device_work_size(max_total, max_piece, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_append_device_work_size(): bytes of device scratch a session needs (0 for refused arguments)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_append_device_work_size(max_total, max_piece, C.byref(o)))
+    return int(_call("zxc_mi355x_compress_append_device_work_size", max_total, max_piece, _copts(level, block_size, seekable, checksum)))
 
 
 def compress_appendv_device_scratch_size(n_iov, max_piece, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_appendv_device_scratch_size(): bytes of device scratch one appendv of n_iov entries needs in a session
     of that max_piece (0 for refused arguments)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_device_scratch_size(n_iov, max_piece, C.byref(o)))
+    return int(_call("zxc_mi355x_compress_appendv_device_scratch_size", n_iov, max_piece, _copts(level, block_size, seekable, checksum)))
 
 
 def compress_appendv_dict_device_scratch_size(n_iov, max_piece, dict_size, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_appendv_dict_device_scratch_size(): bytes of device scratch one appendv_dict of n_iov entries needs in a
     session of that max_piece with a dictionary of dict_size bytes (0 for refused arguments; dict_size 0 gives
     compress_appendv_device_scratch_size)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_dict_device_scratch_size(n_iov, max_piece, C.byref(o),
-                                                                                                        dict_size))
+    return int(_call("zxc_mi355x_compress_appendv_dict_device_scratch_size", n_iov, max_piece,
+                     _copts(level, block_size, seekable, checksum), dict_size))
 
 
 class CompressAppendSession:
@@ -648,56 +571,37 @@ class CompressAppendSession:
         self._cs = cs
 
     def append(self, d_src, n, stream=0):
-        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_append_device(C.byref(self._cs), C.c_void_p(d_src or None), n,
-                                                                                   C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_compress_append_device")
+        _call("zxc_mi355x_compress_append_device", self._cs, d_src, n, stream)
 
     def appendv(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
         """zxc_mi355x_compress_appendv_device(): appends the concatenation of the n_iov x IOV_DTYPE entries at d_iov (device
         memory), `total` bytes in all; the scratch size is compress_appendv_device_scratch_size(n_iov, max_piece, ...)."""
-        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_device(
-            C.byref(self._cs), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
-            C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_compress_appendv_device")
+        _call("zxc_mi355x_compress_appendv_device", self._cs, d_iov, n_iov, total, d_scratch, scratch_size, stream)
 
     def appendv_dict(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
         """zxc_mi355x_compress_appendv_dict_device(): appendv for a session begun with a dictionary (one begun without is served as
         appendv serves it); the scratch size is compress_appendv_dict_device_scratch_size(n_iov, max_piece, dict_size, ...)."""
-        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_appendv_dict_device(
-            C.byref(self._cs), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
-            C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_compress_appendv_dict_device")
+        _call("zxc_mi355x_compress_appendv_dict_device", self._cs, d_iov, n_iov, total, d_scratch, scratch_size, stream)
 
     def end(self, d_result, stream=0):
-        rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_end_device(C.byref(self._cs), C.c_void_p(d_result or None),
-                                                                                C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_compress_end_device")
+        _call("zxc_mi355x_compress_end_device", self._cs, d_result, stream)
 
 
 def compress_begin_device(d_dst, dst_capacity, max_total, max_piece, d_work, work_size, level=3, block_size=0, seekable=False,
                           checksum=False, stream=0):
     """zxc_mi355x_compress_begin_device(): -> a CompressAppendSession that writes one archive to d_dst from the pieces it is
     given; the work size is compress_append_device_work_size(max_total, max_piece, ...)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
     cs = _DevCappend()
-    rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_begin_device(
-        C.byref(cs), C.c_void_p(d_dst or None), dst_capacity, max_total, max_piece, C.byref(o), C.c_void_p(d_work or None), work_size,
-        C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_begin_device")
+    _call("zxc_mi355x_compress_begin_device", cs, d_dst, dst_capacity, max_total, max_piece,
+          _copts(level, block_size, seekable, checksum), d_work, work_size, stream)
     return CompressAppendSession(cs)
 
 
 def compress_append_dict_device_work_size(max_total, max_piece, dict_size, level=3, block_size=0, seekable=False, checksum=False):
     """zxc_mi355x_compress_append_dict_device_work_size(): bytes of device scratch a session with a dictionary of dict_size bytes
     needs (0 for refused arguments; dict_size 0 gives compress_append_device_work_size)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
-    return int(_bind_compress_append_device(lib()).zxc_mi355x_compress_append_dict_device_work_size(max_total, max_piece, C.byref(o),
-                                                                                                    dict_size))
+    return int(_call("zxc_mi355x_compress_append_dict_device_work_size", max_total, max_piece,
+                     _copts(level, block_size, seekable, checksum), dict_size))
 
 
 def compress_begin_dict_device(d_dst, dst_capacity, max_total, max_piece, dict_, d_work, work_size, level=3, block_size=0,
@@ -705,58 +609,22 @@ def compress_begin_dict_device(d_dst, dst_capacity, max_total, max_piece, dict_,
     """zxc_mi355x_compress_begin_dict_device(): compress_begin_device with a dictionary in device memory (dict_ as in
     compress_dict_device, or None for no dictionary) -> a CompressAppendSession; the work size is
     compress_append_dict_device_work_size(max_total, max_piece, dict_size, ...)."""
-    o = _compress_device_opts(level, block_size, seekable, checksum)
     cs = _DevCappend()
-    rc = _bind_compress_append_device(lib()).zxc_mi355x_compress_begin_dict_device(
-        C.byref(cs), C.c_void_p(d_dst or None), dst_capacity, max_total, max_piece, C.byref(o), _dev_dict(dict_),
-        C.c_void_p(d_work or None), work_size, C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_compress_begin_dict_device")
+    _call("zxc_mi355x_compress_begin_dict_device", cs, d_dst, dst_capacity, max_total, max_piece,
+          _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, stream)
     return CompressAppendSession(cs)
 
 
-# ---- one archive into many pieces: a session (zxc_dev_dtake_t is a host struct of 16 words, caller-owned)
-class _DevDtake(C.Structure):  # zxc_dev_dtake_t
-    _fields_ = [("opaque", C.c_uint64 * 16)]
-
-
-def _bind_decompress_take_device(L):
-    L.zxc_mi355x_decompress_take_device_work_size.restype = C.c_uint64
-    L.zxc_mi355x_decompress_take_device_work_size.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
-    L.zxc_mi355x_decompress_begin_device.restype = C.c_int
-    L.zxc_mi355x_decompress_begin_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
-                                                     C.POINTER(_DecompressOpts), C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_decompress_begin_dict_device.restype = C.c_int
-    L.zxc_mi355x_decompress_begin_dict_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
-                                                          C.POINTER(_DecompressOpts), C.POINTER(_DevDict), C.c_void_p, C.c_uint64,
-                                                          C.c_void_p]
-    L.zxc_mi355x_decompress_take_device.restype = C.c_int
-    L.zxc_mi355x_decompress_take_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint64, C.c_void_p]
-    L.zxc_mi355x_decompress_end_device.restype = C.c_int
-    L.zxc_mi355x_decompress_end_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_void_p]
-    return L
-
-
-def _bind_decompress_takev_device(L):
-    _bind_decompress_take_device(L)
-    L.zxc_mi355x_decompress_takev_device_scratch_size.restype = C.c_uint64
-    L.zxc_mi355x_decompress_takev_device_scratch_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
-    L.zxc_mi355x_decompress_takev_device.restype = C.c_int
-    L.zxc_mi355x_decompress_takev_device.argtypes = [C.POINTER(_DevDtake), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64,
-                                                     C.c_void_p]
-    return L
-
-
+# ---- one archive into many pieces: a session
 def decompress_takev_device_scratch_size(n_iov, max_piece, block_size):
     """zxc_mi355x_decompress_takev_device_scratch_size(): bytes of device scratch one takev of n_iov entries needs in a session
     of that max_piece and block_size (0 for refused arguments)."""
-    return int(_bind_decompress_takev_device(lib()).zxc_mi355x_decompress_takev_device_scratch_size(n_iov, max_piece, block_size))
+    return int(_call("zxc_mi355x_decompress_takev_device_scratch_size", n_iov, max_piece, block_size))
 
 
 def decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_size):
     """zxc_mi355x_decompress_take_device_work_size(): bytes of device scratch a session needs (0 for refused arguments)."""
-    return int(_bind_decompress_take_device(lib()).zxc_mi355x_decompress_take_device_work_size(src_size, dst_capacity, max_piece,
-                                                                                                block_size))
+    return int(_call("zxc_mi355x_decompress_take_device_work_size", src_size, dst_capacity, max_piece, block_size))
 
 
 class DecompressTakeSession:
@@ -769,37 +637,23 @@ class DecompressTakeSession:
         self._ds = ds
 
     def take(self, d_dst, n, stream=0):
-        rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_take_device(C.byref(self._ds), C.c_void_p(d_dst or None), n,
-                                                                                   C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_decompress_take_device")
+        _call("zxc_mi355x_decompress_take_device", self._ds, d_dst, n, stream)
 
     def takev(self, d_iov, n_iov, total, d_scratch, scratch_size, stream=0):
         """zxc_mi355x_decompress_takev_device(): delivers the next `total` bytes into the n_iov x IOV_DTYPE entries at d_iov (device
         memory), in table order; the scratch size is decompress_takev_device_scratch_size(n_iov, max_piece, block_size)."""
-        rc = _bind_decompress_takev_device(lib()).zxc_mi355x_decompress_takev_device(
-            C.byref(self._ds), C.c_void_p(d_iov or None), n_iov, total, C.c_void_p(d_scratch or None), scratch_size,
-            C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_decompress_takev_device")
+        _call("zxc_mi355x_decompress_takev_device", self._ds, d_iov, n_iov, total, d_scratch, scratch_size, stream)
 
     def end(self, d_result, stream=0):
-        rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_end_device(C.byref(self._ds), C.c_void_p(d_result or None),
-                                                                                  C.c_void_p(stream or None))
-        if rc < 0:
-            raise ZxcError(rc, "zxc_mi355x_decompress_end_device")
+        _call("zxc_mi355x_decompress_end_device", self._ds, d_result, stream)
 
 
 def decompress_begin_device(d_src, src_size, dst_capacity, max_piece, block_size, d_work, work_size, checksum=False, stream=0):
     """zxc_mi355x_decompress_begin_device(): -> a DecompressTakeSession that delivers the archive at d_src in the pieces it is
     asked for; the work size is decompress_take_device_work_size(src_size, dst_capacity, max_piece, block_size)."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
     ds = _DevDtake()
-    rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_begin_device(
-        C.byref(ds), C.c_void_p(d_src or None), src_size, dst_capacity, max_piece, block_size, C.byref(o), C.c_void_p(d_work or None),
-        work_size, C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_begin_device")
+    _call("zxc_mi355x_decompress_begin_device", ds, d_src, src_size, dst_capacity, max_piece, block_size, _dopts(checksum), d_work,
+          work_size, stream)
     return DecompressTakeSession(ds)
 
 
@@ -807,13 +661,9 @@ def decompress_begin_dict_device(d_src, src_size, dst_capacity, max_piece, block
                                  stream=0):
     """zxc_mi355x_decompress_begin_dict_device(): decompress_begin_device with a dictionary in device memory (dict_ as in
     compress_dict_device); the work size is the sibling's."""
-    o = _DecompressOpts(checksum_enabled=int(checksum))
     ds = _DevDtake()
-    rc = _bind_decompress_take_device(lib()).zxc_mi355x_decompress_begin_dict_device(
-        C.byref(ds), C.c_void_p(d_src or None), src_size, dst_capacity, max_piece, block_size, C.byref(o), _dev_dict(dict_),
-        C.c_void_p(d_work or None), work_size, C.c_void_p(stream or None))
-    if rc < 0:
-        raise ZxcError(rc, "zxc_mi355x_decompress_begin_dict_device")
+    _call("zxc_mi355x_decompress_begin_dict_device", ds, d_src, src_size, dst_capacity, max_piece, block_size, _dopts(checksum),
+          _dev_dict(dict_), d_work, work_size, stream)
     return DecompressTakeSession(ds)
 
 
@@ -845,34 +695,11 @@ class _File:
         _libc().fclose(self.fp)
 
 
-def _bind_stream(L):
-    L.zxc_stream_compress.restype = C.c_int64
-    L.zxc_stream_compress.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_CompressOpts)]
-    L.zxc_stream_decompress.restype = C.c_int64
-    L.zxc_stream_decompress.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_DecompressOpts)]
-    L.zxc_stream_get_decompressed_size.restype = C.c_int64
-    L.zxc_stream_get_decompressed_size.argtypes = [C.c_void_p]
-    L.zxc_seekable_open_file.restype = C.c_void_p
-    L.zxc_seekable_open_file.argtypes = [C.c_void_p]
-    return L
-
-
-def _set_dict(o, dict_, dict_huf):
-    """Point an opts struct at a dictionary (content + optional 128-byte shared table); returns the buffers to keep alive."""
-    if not dict_:
-        return None
-    keep = (C.create_string_buffer(dict_, len(dict_)), C.create_string_buffer(dict_huf, 128) if dict_huf else None)
-    o.dict = C.cast(keep[0], C.c_void_p)
-    o.dict_size = len(dict_)
-    o.dict_huf = C.cast(keep[1], C.c_void_p) if dict_huf else None
-    return keep
-
-
 def stream_compress(src_path, dst_path, level=3, block_size=65536, seekable=True, checksum=False, library=None, dict_=None,
                     dict_huf=None):
     """zxc_stream_compress(): file in, archive out. Returns bytes written or a negative zxc_error_t."""
-    L = _bind_stream(library or lib())
-    o = _CompressOpts(level=level, block_size=block_size, seekable=int(seekable), checksum_enabled=int(checksum))
+    L = _bind_stream(library) if library else lib()
+    o = _copts(level, block_size, seekable, checksum)
     _keep = _set_dict(o, dict_, dict_huf)
     with _File(src_path, "rb") as fi, _File(dst_path, "wb") as fo:
         return int(L.zxc_stream_compress(fi, fo, C.byref(o)))
@@ -880,8 +707,8 @@ def stream_compress(src_path, dst_path, level=3, block_size=65536, seekable=True
 
 def stream_decompress(src_path, dst_path, checksum=False, library=None, dict_=None, dict_huf=None):
     """zxc_stream_decompress(): archive in, file out (dst_path None = integrity check only)."""
-    L = _bind_stream(library or lib())
-    o = _DecompressOpts(checksum_enabled=int(checksum))
+    L = _bind_stream(library) if library else lib()
+    o = _dopts(checksum)
     _keep = _set_dict(o, dict_, dict_huf)
     with _File(src_path, "rb") as fi:
         if dst_path is None:
@@ -891,46 +718,17 @@ def stream_decompress(src_path, dst_path, checksum=False, library=None, dict_=No
 
 
 def stream_get_decompressed_size(path, library=None):
-    L = _bind_stream(library or lib())
+    L = _bind_stream(library) if library else lib()
     with _File(path, "rb") as fi:
         return int(L.zxc_stream_get_decompressed_size(fi))
 
 
 # ---- push streaming (include/zxc_pstream.h). The same prototypes bind the product and (in tests) the reference library.
-class _InBuf(C.Structure):  # zxc_inbuf_t
-    _fields_ = [("src", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
-
-
-class _OutBuf(C.Structure):  # zxc_outbuf_t
-    _fields_ = [("dst", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
-
-
-def _bind_pstream(L):
-    L.zxc_cstream_create.restype = C.c_void_p
-    L.zxc_cstream_create.argtypes = [C.POINTER(_CompressOpts)]
-    L.zxc_cstream_free.argtypes = [C.c_void_p]
-    L.zxc_cstream_compress.restype = C.c_int64
-    L.zxc_cstream_compress.argtypes = [C.c_void_p, C.POINTER(_OutBuf), C.POINTER(_InBuf)]
-    L.zxc_cstream_end.restype = C.c_int64
-    L.zxc_cstream_end.argtypes = [C.c_void_p, C.POINTER(_OutBuf)]
-    L.zxc_dstream_create.restype = C.c_void_p
-    L.zxc_dstream_create.argtypes = [C.POINTER(_DecompressOpts)]
-    L.zxc_dstream_free.argtypes = [C.c_void_p]
-    L.zxc_dstream_decompress.restype = C.c_int64
-    L.zxc_dstream_decompress.argtypes = [C.c_void_p, C.POINTER(_OutBuf), C.POINTER(_InBuf)]
-    L.zxc_dstream_finished.restype = C.c_int
-    L.zxc_dstream_finished.argtypes = [C.c_void_p]
-    for f in ("zxc_cstream_in_size", "zxc_cstream_out_size", "zxc_dstream_in_size", "zxc_dstream_out_size"):
-        getattr(L, f).restype = C.c_size_t
-        getattr(L, f).argtypes = [C.c_void_p]
-    return L
-
-
 def pstream_compress(data: bytes, in_chunk, out_chunk, level=3, block_size=0, checksum=False, library=None):
     """Feed `data` to a zxc_cstream in chunks of in_chunk bytes, drain through an out buffer of out_chunk bytes, finish with
     zxc_cstream_end (the loop of the reference's header example, include/zxc_pstream.h:26-49).
     -> (0, archive) or (negative zxc_error_t, bytes produced so far)."""
-    L = _bind_pstream(library or lib())
+    L = _bind_pstream(library) if library else lib()
     o = _CompressOpts(level=level, block_size=block_size, checksum_enabled=int(checksum))
     cs = L.zxc_cstream_create(C.byref(o))
     if not cs:
@@ -973,8 +771,8 @@ def pstream_decompress(comp: bytes, in_chunk, out_chunk, checksum=False, library
     """Feed `comp` to a zxc_dstream in chunks of in_chunk bytes, drain through an out buffer of out_chunk bytes, until the decoder
     neither consumes nor produces (reference tests/test_pstream_api.c:107-172).
     -> (rc of the last call, decoded bytes, finished flag, input bytes consumed)."""
-    L = _bind_pstream(library or lib())
-    o = _DecompressOpts(checksum_enabled=int(checksum))
+    L = _bind_pstream(library) if library else lib()
+    o = _dopts(checksum)
     ds = L.zxc_dstream_create(C.byref(o))
     if not ds:
         return None, b"", 0, 0

@@ -318,6 +318,7 @@ ZXC_EXPORT int zxc_mi355x_decompress_ranges_dict_device(const void* d_src, uint6
                                                         void* d_dst, uint64_t dst_capacity, uint32_t block_size,
                                                         const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size,
                                                         int64_t* d_results, void* stream);
+/* (The same two calls over ranges that carry the absolute device address of their own destination: zxc_mi355x_rangesv.h.) */
 
 /* ---- many archives per call, device to device (zxc_amd/csrc/zxc_batch_device.hip, rules in zxc_amd/csrc/zxc_batch.h) ----
  * zxc_mi355x_decompress_device for many small, independent archives that already live in device memory (cache pages, shards,

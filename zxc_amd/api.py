@@ -16,6 +16,8 @@ RANGE_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("dst_off", "<u8")])
 # zxc_dev_item_t (include/zxc_mi355x.h)
 ITEM_DTYPE = np.dtype([("src_off", "<u8"), ("src_size", "<u8"), ("dst_off", "<u8"), ("dst_capacity", "<u8")])
 IOV_DTYPE = np.dtype([("base", "<u8"), ("len", "<u8")])  # zxc_dev_iov_t
+# zxc_dev_rangev_t (include/zxc_mi355x_rangesv.h)
+RANGEV_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("base", "<u8")])
 
 
 class ZxcError(RuntimeError):
@@ -171,17 +173,28 @@ _PROTOTYPES = {
     "zxc_dstream_in_size": (_SZ, [_P]),
     "zxc_dstream_out_size": (_SZ, [_P]),
 }
+# include/zxc_mi355x_rangesv.h, a table of its own: tests/test_decompress_rangesv_device_cpu.py holds it against that header
+_RANGESV = [_P, _U64, _P, _P, _U32, _U64, _U32]  # d_src .. block_size of decompress_rangesv_device
+_PROTOTYPES_RANGESV = {
+    "zxc_mi355x_decompress_rangesv_device_work_size": (_U64, [_U32, _U64, _U32]),
+    "zxc_mi355x_decompress_rangesv_device": (_I, _RANGESV + _TAIL),
+    "zxc_mi355x_decompress_rangesv_dict_device": (_I, _RANGESV + [_DD] + _TAIL),
+}
 _STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
 _PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
 
 
-def _bind(L, names=_PROTOTYPES):
-    """Set restype and argtypes of those of `names` that L exports (the reference and the mock-device library have no device
-    calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
-    for name in names:
+def _prototype(name):
+    return _PROTOTYPES[name] if name in _PROTOTYPES else _PROTOTYPES_RANGESV[name]
+
+
+def _bind(L, names=None):
+    """Set restype and argtypes of those of `names` (both tables unless given) that L exports (the reference and the mock-device
+    library have no device calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
+    for name in (list(_PROTOTYPES) + list(_PROTOTYPES_RANGESV) if names is None else names):
         f = getattr(L, name, None)
         if f is not None:
-            f.restype, f.argtypes = _PROTOTYPES[name]
+            f.restype, f.argtypes = _prototype(name)
     return L
 
 
@@ -224,7 +237,7 @@ def _call(name, *args):
     c_void_p (0 stays NULL); a ctypes struct or scalar goes by reference; the rest goes as it is. Raises ZxcError(rc, name) on
     rc < 0."""
     rc = getattr(lib(), name)(*[C.c_void_p(a or None) if t is _P else C.byref(a) if isinstance(a, (C.Structure, C._SimpleCData))
-                                else a for t, a in zip(_PROTOTYPES[name][1], args)])
+                                else a for t, a in zip(_prototype(name)[1], args)])
     if rc < 0:
         raise ZxcError(rc, name)
     return rc
@@ -461,6 +474,29 @@ def decompress_ranges_dict_device(d_src, src_size, d_index, d_ranges, n_ranges, 
     compress_dict_device); index and work size are the sibling's."""
     _call("zxc_mi355x_decompress_ranges_dict_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity,
           block_size, _dev_dict(dict_), d_work, work_size, d_results, stream)
+
+
+# ---- random access into a pointer table (include/zxc_mi355x_rangesv.h: zxc_dev_rangev_t)
+def decompress_rangesv_device_work_size(n_ranges, max_len, block_size):
+    """zxc_mi355x_decompress_rangesv_device_work_size(): bytes of device scratch the call needs (0 for refused arguments); the
+    value decompress_ranges_device_work_size gives for the same arguments."""
+    return int(_call("zxc_mi355x_decompress_rangesv_device_work_size", n_ranges, max_len, block_size))
+
+
+def decompress_rangesv_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size, d_work, work_size, d_results, stream=0):
+    """zxc_mi355x_decompress_rangesv_device(): raw device pointers (ints); d_ranges is n_ranges x RANGEV_DTYPE in device memory,
+    each entry with the device address of its own destination, d_results n_ranges x int64; the index is seekable_open_device's.
+    Asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_decompress_rangesv_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size, d_work, work_size,
+          d_results, stream)
+
+
+def decompress_rangesv_dict_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size, dict_, d_work, work_size,
+                                   d_results, stream=0):
+    """zxc_mi355x_decompress_rangesv_dict_device(): decompress_rangesv_device with a dictionary in device memory (dict_ as in
+    compress_dict_device); index and work size are the sibling's."""
+    _call("zxc_mi355x_decompress_rangesv_dict_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size,
+          _dev_dict(dict_), d_work, work_size, d_results, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)

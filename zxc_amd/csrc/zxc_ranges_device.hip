@@ -22,8 +22,14 @@
 //
 // zxc_mi355x_decompress_ranges_dict_device is the ranges call with a dictionary in device memory: plan and verdict compare the
 // index's dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launch gets the dictionary.
+//
+// zxc_mi355x_decompress_rangesv_device (and _dict) is the ranges call over a table whose entries carry the absolute device address
+// of their destination (zxc_rangesv.h): the same four stages with a plan and a verdict kernel of its own. The decode launch's
+// d_out and the copy's destination base are the work area's 256-byte aligned base, and every place outside the work area is
+// counted from it modulo 2^64, so the decode kernels and zxc_ranges_copy_kernel run as they are.
 #include "zxc_device_util.h"  // the tile passes, the host-side plumbing
 #include "zxc_ranges.h"
+#include "zxc_rangesv.h"
 
 #define RNG_BAD (1ull << 63)  // in a tile's word: one of its entries is implausible (a tile's sum is <= 2^32)
 
@@ -158,6 +164,31 @@ zxc_ranges_verdict_kernel(const void* __restrict__ index, const zxc_dev_range_t*
                                  dict_id ? *dict_id : 0u);
 }
 
+// ---------------------------------------------------------------- rangesv
+extern "C" __global__ void __launch_bounds__(256)
+zxc_rangesv_plan_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
+                        uint64_t src_size, uint64_t max_len, uint32_t block_size, uint64_t out_base, uint64_t stage_rel,
+                        zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies, const uint32_t* __restrict__ dict_id) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_jobs) return;
+    const uint32_t r = i / J, j = i - r * J;
+    zxc_dev_job_t job;
+    zr_copy_t cp;
+    zrv_job(index, ranges[r], j, i, src_size, max_len, block_size, out_base, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, &job, &cp);
+    jobs[i] = job;
+    copies[i] = cp;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+zxc_rangesv_verdict_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
+                           const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint32_t block_size,
+                           int64_t* __restrict__ results, const uint32_t* __restrict__ dict_id) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_ranges) return;
+    results[r] = zrv_verdict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, block_size, dict_id != nullptr,
+                             dict_id ? *dict_id : 0u);
+}
+
 // ---------------------------------------------------------------- host side
 extern "C" {
 
@@ -238,6 +269,57 @@ int zxc_mi355x_decompress_ranges_dict_device(const void* d_src, uint64_t src_siz
                                              const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, int64_t* d_results, void* stream) {
     return ranges_call(d_src, src_size, d_index, d_ranges, n_ranges, max_len, d_dst, dst_capacity, block_size, dict, d_work, work_size, d_results,
                        stream);
+}
+
+uint64_t zxc_mi355x_decompress_rangesv_device_work_size(uint32_t n_ranges, uint64_t max_len, uint32_t block_size) {
+    return zxc_mi355x_decompress_ranges_device_work_size(n_ranges, max_len, block_size);
+}
+
+// Both rangesv calls. dict == NULL: the call that takes no dictionary. The copy's destinations are counted from the work area's
+// base, as the jobs' places are: zxc_ranges_copy_kernel adds cp.dst_at to the pointer it is given in 64 bits, and the base being a
+// multiple of 16 keeps dst_at & 15 the address's alignment.
+static int rangesv_call(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_rangev_t* d_ranges, uint32_t n_ranges,
+                        uint64_t max_len, uint32_t block_size, const zxc_dev_dict_t* dict, void* d_work, uint64_t work_size, int64_t* d_results,
+                        void* stream) {
+    if (!d_src || !d_index || !d_work || !d_results || (!d_ranges && n_ranges > 0)) return ZXC_ERROR_NULL_INPUT;
+    zr_shape_t s;
+    const int shape_rc = zr_shape(n_ranges, max_len, block_size, &s);
+    if (shape_rc == ZXC_ERROR_BAD_BLOCK_SIZE) return shape_rc;
+    const int drc = dict_arg(&dict);
+    if (drc != ZXC_OK) return drc;
+    if (shape_rc != 0 || work_size < s.bytes) return ZXC_ERROR_MEMORY;
+    if (n_ranges == 0) return ZXC_OK;
+    if (!have_device()) return ZXC_ERROR_GPU_UNAVAILABLE;
+
+    const hipStream_t st = (hipStream_t)stream;
+    const zd_dict_t dc = zd_dict_of(dict);
+    uint8_t* base = zd_work_base(d_work);
+    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
+    int32_t* status = (int32_t*)(base + s.o_status);
+    zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);
+
+    hipLaunchKernelGGL(zxc_rangesv_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
+                       max_len, block_size, (uint64_t)(uintptr_t)base, s.o_stage, jobs, copies, dc.id);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, base, status, block_size, 0, dc.content, dc.size, dc.huf, 0u, stream);
+    if (rc != ZXC_OK) return rc;
+    hipLaunchKernelGGL(zxc_ranges_copy_kernel, zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), dim3(256), 0, st, (const uint8_t*)(base + s.o_stage),
+                       s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks, base);
+    hipLaunchKernelGGL(zxc_rangesv_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
+                       (const int32_t*)status, src_size, max_len, block_size, d_results, dc.id);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
+
+int zxc_mi355x_decompress_rangesv_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_rangev_t* d_ranges,
+                                         uint32_t n_ranges, uint64_t max_len, uint32_t block_size, void* d_work, uint64_t work_size,
+                                         int64_t* d_results, void* stream) {
+    return rangesv_call(d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size, NULL, d_work, work_size, d_results, stream);
+}
+
+int zxc_mi355x_decompress_rangesv_dict_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_rangev_t* d_ranges,
+                                              uint32_t n_ranges, uint64_t max_len, uint32_t block_size, const zxc_dev_dict_t* dict, void* d_work,
+                                              uint64_t work_size, int64_t* d_results, void* stream) {
+    return rangesv_call(d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size, dict, d_work, work_size, d_results, stream);
 }
 
 }  // extern "C"

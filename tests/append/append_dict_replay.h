@@ -168,6 +168,42 @@ static int rpd_plan_check(uint32_t carry, uint64_t n, uint32_t bs) {
 static uint32_t rpd_rnd_state;
 static uint32_t rpd_rnd(void) { rpd_rnd_state = rpd_rnd_state * 1664525u + 1013904223u; return rpd_rnd_state >> 8; }
 
+/* the blocks of a complete, regular archive whose header carries a dictionary id (one block per block_size bytes of `total`), cut
+ * out one behind the other, with what the header says and whether a seek table follows. -> 0, or minus the line that failed */
+typedef struct rpd_arc {
+    uint8_t* blocks;
+    uint64_t* blk_at;
+    uint32_t *blk_size, nb, bs, ck, id;
+    int seekable;
+} rpd_arc_t;
+static int rpd_cut(const uint8_t* comp, uint64_t comp_size, uint64_t total, rpd_arc_t* a) {
+    uint32_t lg = 0;
+    memset(a, 0, sizeof *a);
+    if (comp_size < ZC_FILE_HDR + ZC_BLK_HDR + ZC_FOOTER || zc_file_header(comp, &lg, &a->ck, &a->id) != ZXC_OK || !(comp[6] & 0x40u)) return -__LINE__;
+    a->bs = 1u << lg;
+    const uint64_t nb64 = total / a->bs + (total % a->bs != 0);
+    a->blocks = malloc(comp_size);
+    a->blk_at = malloc((nb64 + 1u) * 8u);
+    a->blk_size = malloc((nb64 + 1u) * 4u);
+    uint64_t at = ZC_FILE_HDR, used = 0;
+    int line = 0;
+    for (;;) {
+        if (at + ZC_BLK_HDR > comp_size) { line = -__LINE__; break; }
+        const uint64_t w = zc_rd64(comp + at);
+        if (!zc_blk_hdr_ok(w)) { line = -__LINE__; break; }
+        if (zc_blk_type(w) == ZC_BLK_EOF) break;
+        const uint32_t sz = ZC_BLK_HDR + zc_blk_csz(w) + 4u * a->ck;
+        if (a->nb >= nb64 || at + sz > comp_size) { line = -__LINE__; break; }
+        a->blk_at[a->nb] = used; a->blk_size[a->nb] = sz;
+        memcpy(a->blocks + used, comp + at, sz);
+        used += sz; at += sz; a->nb++;
+    }
+    if (!line && (a->nb != nb64 || zc_rd64(comp + comp_size - ZC_FOOTER) != total)) line = -__LINE__; /* one block per block_size bytes */
+    a->seekable = !line && comp_size - at > ZC_BLK_HDR + ZC_FOOTER;
+    return line;
+}
+static void rpd_arc_free(rpd_arc_t* a) { free(a->blocks); free(a->blk_at); free(a->blk_size); }
+
 /* one session over these cuts with room behind the archive: the archive byte for byte, the pattern intact everywhere outside it;
  * with `exact` also with a capacity of exactly the archive, and of one byte less: -> 0, or the line that failed */
 static int rpd_check_cuts(const uint8_t* comp, uint64_t comp_size, const uint8_t* data, uint64_t total, const uint8_t* blocks,
@@ -200,36 +236,16 @@ static int rpd_check_cuts(const uint8_t* comp, uint64_t comp_size, const uint8_t
  * (zero-length appends among them) with pieces shorter than the appends. -> the number of cut sets, or minus the line that failed. */
 static int64_t rpd_check_archive(const uint8_t* comp, uint64_t comp_size, const uint8_t* data, uint64_t total, const uint8_t* dict,
                                  uint32_t dict_size, uint32_t seed, int dense) {
-    uint32_t lg = 0, ck = 0, id = 0;
-    if (comp_size < ZC_FILE_HDR + ZC_BLK_HDR + ZC_FOOTER || zc_file_header(comp, &lg, &ck, &id) != ZXC_OK || !(comp[6] & 0x40u)) return -__LINE__;
-    const uint32_t bs = 1u << lg;
-    const uint64_t nb64 = total / bs + (total % bs != 0);
-    uint8_t* blocks = malloc(comp_size);
-    uint64_t* blk_at = malloc((nb64 + 1u) * 8u);
-    uint32_t* blk_size = malloc((nb64 + 1u) * 4u);
+    rpd_arc_t a;
+    int64_t result = rpd_cut(comp, comp_size, total, &a);
+    const uint32_t bs = a.bs;
     uint64_t* lens = malloc((total / 7u + 64u) * 8u);
-    uint64_t at = ZC_FILE_HDR, used = 0;
-    uint32_t nb = 0;
-    int64_t result = 0;
-    for (;;) {
-        if (at + ZC_BLK_HDR > comp_size) { result = -__LINE__; break; }
-        const uint64_t w = zc_rd64(comp + at);
-        if (!zc_blk_hdr_ok(w)) { result = -__LINE__; break; }
-        if (zc_blk_type(w) == ZC_BLK_EOF) break;
-        const uint32_t sz = ZC_BLK_HDR + zc_blk_csz(w) + 4u * ck;
-        if (nb >= nb64 || at + sz > comp_size) { result = -__LINE__; break; }
-        blk_at[nb] = used; blk_size[nb] = sz;
-        memcpy(blocks + used, comp + at, sz);
-        used += sz; at += sz; nb++;
-    }
-    if (!result && (nb != nb64 || zc_rd64(comp + comp_size - ZC_FOOTER) != total)) result = -__LINE__; /* one block per block_size bytes */
-    const int seekable = comp_size - at > ZC_BLK_HDR + ZC_FOOTER;
     rpd_rnd_state = seed;
     const uint64_t first = total < bs ? total : bs;
     for (uint64_t c = 0; c <= first && result >= 0; c += (dense || c < 70u || c + 70u >= first) ? 1u : first > 8192u ? first / 41u : 97u) {
         lens[0] = c; lens[1] = total - c;
-        const int line = rpd_check_cuts(comp, comp_size, data, total, blocks, blk_at, blk_size, nb, bs, (int)ck, seekable, lens, 2u,
-                                        total > bs ? total : bs, dict, dict_size, id, 0u, c % 256u == 0);
+        const int line = rpd_check_cuts(comp, comp_size, data, total, a.blocks, a.blk_at, a.blk_size, a.nb, bs, (int)a.ck, a.seekable, lens,
+                                        2u, total > bs ? total : bs, dict, dict_size, a.id, 0u, c % 256u == 0);
         result = line ? -line : result + 1;
     }
     for (int k = 0; k < 12 && result >= 0; k++) {
@@ -245,11 +261,11 @@ static int64_t rpd_check_archive(const uint8_t* comp, uint64_t comp_size, const 
         }
         lens[n_lens++] = 0;
         const uint64_t mp[3] = {bs, 2ull * bs, 3ull * bs + 100u};
-        const int line = rpd_check_cuts(comp, comp_size, data, total, blocks, blk_at, blk_size, nb, bs, (int)ck, seekable, lens, n_lens,
-                                        mp[k % 3], dict, dict_size, id, k % 2 ? 2u : 0u, 1);
+        const int line = rpd_check_cuts(comp, comp_size, data, total, a.blocks, a.blk_at, a.blk_size, a.nb, bs, (int)a.ck, a.seekable, lens,
+                                        n_lens, mp[k % 3], dict, dict_size, a.id, k % 2 ? 2u : 0u, 1);
         result = line ? -line : result + 1;
     }
-    free(lens); free(blk_size); free(blk_at); free(blocks);
+    free(lens); rpd_arc_free(&a);
     return result;
 }
 

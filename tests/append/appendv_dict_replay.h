@@ -230,49 +230,14 @@ static int rpvd_calls(int pattern, uint64_t total, uint32_t bs, uint64_t* lens, 
     return 1;
 }
 
-/* the blocks of a complete, regular archive whose header carries a dictionary id, as rpd_check_archive cuts them */
-typedef struct rpvd_arc {
-    uint8_t* blocks;
-    uint64_t* blk_at;
-    uint32_t *blk_size, nb, bs, ck, id;
-    int seekable;
-} rpvd_arc_t;
-static int rpvd_cut(const uint8_t* comp, uint64_t comp_size, uint64_t total, rpvd_arc_t* a) {
-    uint32_t lg = 0;
-    memset(a, 0, sizeof *a);
-    if (comp_size < ZC_FILE_HDR + ZC_BLK_HDR + ZC_FOOTER || zc_file_header(comp, &lg, &a->ck, &a->id) != ZXC_OK || !(comp[6] & 0x40u)) return -__LINE__;
-    a->bs = 1u << lg;
-    const uint64_t nb64 = total / a->bs + (total % a->bs != 0);
-    a->blocks = malloc(comp_size);
-    a->blk_at = malloc((nb64 + 1u) * 8u);
-    a->blk_size = malloc((nb64 + 1u) * 4u);
-    uint64_t at = ZC_FILE_HDR, used = 0;
-    int line = 0;
-    for (;;) {
-        if (at + ZC_BLK_HDR > comp_size) { line = -__LINE__; break; }
-        const uint64_t w = zc_rd64(comp + at);
-        if (!zc_blk_hdr_ok(w)) { line = -__LINE__; break; }
-        if (zc_blk_type(w) == ZC_BLK_EOF) break;
-        const uint32_t sz = ZC_BLK_HDR + zc_blk_csz(w) + 4u * a->ck;
-        if (a->nb >= nb64 || at + sz > comp_size) { line = -__LINE__; break; }
-        a->blk_at[a->nb] = used; a->blk_size[a->nb] = sz;
-        memcpy(a->blocks + used, comp + at, sz);
-        used += sz; at += sz; a->nb++;
-    }
-    if (!line && (a->nb != nb64 || zc_rd64(comp + comp_size - ZC_FOOTER) != total)) line = -__LINE__; /* one block per block_size bytes */
-    a->seekable = !line && comp_size - at > ZC_BLK_HDR + ZC_FOOTER;
-    return line;
-}
-static void rpvd_arc_free(rpvd_arc_t* a) { free(a->blocks); free(a->blk_at); free(a->blk_size); }
-
-/* comp: such an archive; data: its total decoded bytes. One session per cut set (rpvd_calls), with room behind the archive; every
+/* comp: an archive as rpd_cut takes it; data: its total decoded bytes. One session per cut set (rpvd_calls), with room behind the archive; every
  * other one also with a capacity of exactly the archive and of one byte less: the archive byte for byte, the pattern intact
  * everywhere outside it. chunk: jobs per launch (0: the shape's). -> the number of sessions, or minus the line that failed.
  * *all adds up what the sessions saw. */
 static int64_t rpvd_check_archive(const uint8_t* comp, uint64_t comp_size, const uint8_t* data, uint64_t total, const uint8_t* dict,
                                   uint32_t dict_size, uint32_t seed, uint32_t chunk, rpvd_stats_t* all) {
-    rpvd_arc_t a;
-    int64_t result = rpvd_cut(comp, comp_size, total, &a);
+    rpd_arc_t a;
+    int64_t result = rpd_cut(comp, comp_size, total, &a);
     uint64_t* lens = malloc((total + 4096u) * 8u);
     uint32_t* counts = malloc((total + 4096u) * 4u);
     rpvd_rnd_state = seed;
@@ -303,7 +268,7 @@ static int64_t rpvd_check_archive(const uint8_t* comp, uint64_t comp_size, const
             result = line ? -line : result + 1;
         }
     }
-    free(counts); free(lens); rpvd_arc_free(&a);
+    free(counts); free(lens); rpd_arc_free(&a);
     return result;
 }
 

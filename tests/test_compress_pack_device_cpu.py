@@ -14,9 +14,9 @@ import pytest
 
 import cshim
 from conftest import GOLDEN
-from test_compress_batch_device_cpu import (BAD_BLOCK_SIZES, BLOCK_SIZES, CANARY, ERR, FAKE_DICT, FAKE_DST, FAKE_HUF, FAKE_ID, FAKE_ITEMS,
-                                            FAKE_RES, FAKE_SRC, FAKE_WORK, IMAGE_FIXED, JOB, JOB_BYTES, M64, REC_BYTES, WORK_FIXED, Arc, Item,
-                                            Rec, Shape, _dd, _host_dict_opts, _opts, _ref, _ref_arcs, _stride)
+from cpu_batch import (BAD_BLOCK_SIZES, BLOCK_SIZES, CANARY, ERR, FAKE_DICT, FAKE_DST, FAKE_HUF, FAKE_ID, FAKE_ITEMS, FAKE_RES, FAKE_SRC,
+                       FAKE_WORK, IMAGE_FIXED, JOB, JOB_BYTES, M64, REC_BYTES, WORK_FIXED, Arc, Item, Rec, Shape, _dd, _host_dict_opts, _opts,
+                       _ref, _ref_arcs, _stride)
 
 FAKE_PACKED, FAKE_TOTAL = 0xA0000, 0xB0000
 TILE_BYTES, PACK_FIXED = 8, 256  # the stated bound: the sibling's + 8 ceil(n / 1024) + 256

@@ -5,60 +5,16 @@ strict-capacity plan = the lean executor with strict checks inside the full kern
 executor), in a guarded job table: the bytes must equal the plain Python expansion, the status the reference's verdict, no
 byte outside the slot may change, and the path markers the case names must have been reached (ZXC_PATH, counted by the
 emulator), with the exact count where the case says so. The seeded random family runs packed, 400 blocks."""
-import ctypes as C
-import os
-import sys
-
-import numpy as np
 import pytest
 
 import decode_limit_cases as D
 import decode_plan_cases as P
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "wave_emu"))
-
-IDS = D.path_ids()
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import emu_py
-    e = emu_py.Emu()
-    e.lib.emu_path_read.argtypes = [C.c_void_p, C.c_uint32]
-    e.lib.emu_path_read.restype = C.c_uint32
-    e.lib.emu_set_pscratch_bytes.argtypes = [C.c_size_t]
-    e.lib.emu_set_rscratch_bytes.argtypes = [C.c_size_t]
-    assert e.lib.emu_path_read(None, 0) == len(IDS), "enum zxc_path_id and the emulator library disagree"
-    return e
-
-
-def counts(emu):
-    a = np.zeros(len(IDS), dtype=np.uint64)
-    emu.lib.emu_path_read(a.ctypes.data, len(IDS))
-    return {n: int(a[i]) for n, i in IDS.items()}
-
-
-def run(emu, case, lcases, route, **kw):
-    """One guarded launch; -> the path counters of it."""
-    size = P.guarded_layout(case)
-    if route == "strict":
-        kw["cap_override"] = case.block_size
-    emu.lib.emu_path_reset()
-    st, out = emu.decode_jobs(case.comp, case.jobs, size, case.block_size, verify_trailer=case.checksum, dict_=case.dict_,
-                              init=P.canary(size).tobytes(), **kw)
-    o = np.frombuffer(out, dtype=np.uint8)
-    assert emu.last_pads == 0, (case.label, "a store landed outside the output buffer", emu.last_pads)
-    try:
-        P.check_guarded(case, o, st)
-    except AssertionError as e:
-        raise AssertionError(f"{case.label}: {D.explain(case, lcases, o, st)}\n{e}") from None
-    return counts(emu)
+from decode_harness import IDS, emu, run  # noqa: F401  (the emulator fixture, its path ids and the guarded launch)
 
 
 @pytest.mark.parametrize("route", D.ROUTES)
 @pytest.mark.parametrize("fam", list(D.FAMILIES))
-def test_family(emu, oracle, ref, fam, route):
+def test_family(emu, oracle, ref, fam, route):  # noqa: F811
     cases = [c for c in D.family(fam) if route in c.routes]
     if fam == "dict":
         assert route == "dict" or not cases
@@ -73,7 +29,7 @@ def test_family(emu, oracle, ref, fam, route):
 
 
 @pytest.mark.parametrize("fam", [f for f in D.FAMILIES if f != "dict"])
-def test_family_packed_and_checksummed(emu, oracle, ref, fam):
+def test_family_packed_and_checksummed(emu, oracle, ref, fam):  # noqa: F811
     """One guarded job table per (family, block size), blocks at all four byte alignments of the compressed buffer, each
     with a verified checksum trailer: the checksum kernel beside the decode, then checksums inside the decode kernels."""
     for group in D.groups(D.family(fam), "lean"):
@@ -92,7 +48,7 @@ def test_every_path_id_has_a_case():
 
 
 @pytest.mark.parametrize("route", ["lean", "dict", "strict"])
-def test_random_family(emu, oracle, ref, route):
+def test_random_family(emu, oracle, ref, route):  # noqa: F811
     """400 seeded blocks around the boundary values, GLO 16- / 8-bit and GHI, 4 KiB to 128 KiB, all valid by construction:
     packed, one job table per block size. (The strict route runs the lean executor again: every eighth block.)"""
     cases = D.fam_random(400)
@@ -131,7 +87,7 @@ def _one(oracle, ref, route, **kw):
     return D.pack(oracle, ref, [b.case("routing", "routing", **kw)], route)
 
 
-def test_routing_table(emu, oracle, ref):
+def test_routing_table(emu, oracle, ref):  # noqa: F811
     lean_only = dict(X_FULL=0, X_FULL_GHI=0)
     full_only = dict(X_LEAN=0, X_LEAN_GHI=0, X_SETUP_RAW=0, X_SETUP_RLE=0, X_SETUP_PRE=0)
 

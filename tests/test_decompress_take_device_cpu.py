@@ -16,15 +16,13 @@ import pytest
 
 import cshim
 from conftest import GOLDEN
+from cpu_take import BAD_BLOCK_SIZES, BAD_PLAN, FAKE_DST, FAKE_RES, FAKE_SRC, FAKE_WORK, Blocks, _goldens, _host_walk
 from cshim import ref as _ref
 from devtest import ERR
 from zxc_amd.api import _DecompressOpts, _DevDict, _DevDtake as Ds  # zxc_dev_dtake_t
 
-FAKE_SRC, FAKE_DST, FAKE_WORK, FAKE_RES = 0x10000, 0x30000, 0x40000, 0x50000
-BAD_BLOCK_SIZES = (0, 1000, 2048, 4095, 5000, 3 << 12, 1 << 22)
 BLOCK_SIZES = (4096, 65536, 1 << 19, 1 << 21)
 BLOCK_BYTES, TILE_BYTES, JOB_BYTES, PAD, CARRIES, WORK_FIXED = 56, 16, 48, 64, 2, 4096  # the stated bound
-BAD_PLAN = -1000
 
 
 def _host_dict_opts():
@@ -248,30 +246,6 @@ def test_every_plan_keeps_its_promises(shim):
 
 
 # ---------------------------------------------------------------- host replay
-def _hash8(hdr7: bytes) -> int:
-    M = (1 << 64) - 1
-    h = int.from_bytes(hdr7 + b"\0", "little") ^ 0x9E3779B97F4A7C15
-    h ^= (h << 13) & M
-    h ^= h >> 7
-    h ^= (h << 17) & M
-    return ((h >> 32) ^ h) & 0xFF
-
-
-def _host_walk(comp: bytes, file_ck: int, limit: int):
-    """frame_source of zxc_host.c, restated: -> [(comp_off, comp_size)] of the blocks a header walk finds, at most `limit`"""
-    ip, jobs = 16, []
-    while len(jobs) < limit and ip < len(comp):
-        rem = len(comp) - ip
-        if rem < 8 or comp[ip + 7] != _hash8(comp[ip: ip + 7]) or comp[ip] == 255:
-            break
-        phys = 8 + int.from_bytes(comp[ip + 3: ip + 7], "little") + 4 * file_ck
-        jobs.append((ip, min(phys, rem)))
-        if phys >= rem:
-            break
-        ip += phys
-    return jobs
-
-
 def _cuts(total, bs, rng):
     """name -> (take lengths, max_piece): the patterns of the append test, and many takes inside one block"""
     whole = max(total, bs)
@@ -291,24 +265,6 @@ def _cuts(total, bs, rng):
             left -= n
         out["random %d" % k] = (lens, rng.choice((bs, 2 * bs, 3 * bs + 100, whole)))
     return out
-
-
-class Blocks:
-    """what the stand-in decoder answers for an archive: per block of the header walk the oracle decoder's bytes and status"""
-
-    def __init__(self, shim, oracle, comp, bs, cap, verify):
-        flags = int(shim.t_head(comp, len(comp), max(cap, 1), bs, int(verify)))
-        self.file_ck, self.verify = flags & 1, (flags >> 1) & 1
-        data, at, st = [], [], []
-        for off, n in _host_walk(comp, self.file_ck, -(-cap // bs) + 1):
-            rc, out = oracle.decode_block(comp[off: off + n], bs, checksum=bool(self.verify))
-            at.append(sum(len(d) for d in data))
-            st.append(rc)
-            data.append(out[:max(rc, 0)] if rc > 0 else b"")
-        self.n = len(st)
-        self.bytes = np.frombuffer(b"".join(data) + b"\0", dtype=np.uint8)
-        self.at = np.array(at + [0], dtype=np.uint64)
-        self.st = np.array(st + [0], dtype=np.int32)
 
 
 def _session(shim, comp, bs, cap, verify, lens, max_piece, align, blocks, use_table=1, have_dict=0, dict_id=0):
@@ -338,11 +294,6 @@ def _check_archive(shim, oracle, comp, bs, size, seed, what, decoder=None):
                     assert got[:rc] == data[:rc], (what, name, cap, verify, align)
                 n_sessions += 1
     return n_sessions
-
-
-def _goldens(sub):
-    p = os.path.join(GOLDEN, sub)
-    return [f"{sub}/{f}" for f in sorted(os.listdir(p)) if f.endswith(".zxc")]
 
 
 def test_sessions_take_the_valid_goldens_apart(shim, oracle, product):

@@ -13,8 +13,8 @@ import random
 import numpy as np
 import pytest
 
+import cpu_take as T
 import cshim
-import test_decompress_take_device_cpu as T
 from conftest import GOLDEN
 from devtest import ERR
 from zxc_amd.api import IOV_DTYPE, _DevDtake as Ds

@@ -7,7 +7,8 @@ text-like, and incompressible (stored blocks). Nothing here provokes a fault: ev
 import pytest
 
 import devtest
-from devtest import CANARY, ERR, UNSET, bound as _bound, pattern as _pattern, payload as _payload, piece as _piece, split as _split
+from dev_append import plain_baseline as _baseline, plain_session as Session
+from devtest import CANARY, ERR, UNSET, bound as _bound, pattern as _pattern, payload as _payload, split as _split
 
 pytestmark = pytest.mark.gpu
 
@@ -15,69 +16,6 @@ BS = 4096
 SIZES = (0, 1, 4095, 4096, 4097, 3 * 4096 + 5)
 
 gpu = devtest.gpu_fixture("compress_begin_device")
-
-_BASE = {}
-
-
-def _baseline(gpu, data, cap, level, bs, seekable, checksum):
-    """compress_device for the whole source -> (result word or the synchronous error, archive bytes or None); once per case"""
-    import torch
-    key = (data, cap, level, bs, seekable, checksum)
-    if key not in _BASE:
-        src = torch.frombuffer(bytearray(data + bytes(64)), dtype=torch.uint8).to("cuda")
-        ws = gpu.compress_device_work_size(len(data), level, bs, seekable, checksum)
-        work = torch.empty(ws, dtype=torch.uint8, device="cuda")
-        dst = torch.from_numpy(_pattern(cap + CANARY)).to("cuda")
-        res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        try:
-            gpu.compress_device(src.data_ptr(), len(data), dst.data_ptr(), cap, work.data_ptr(), ws, res.data_ptr(), level, bs, seekable,
-                                checksum, torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            rc = int(res.item())
-        except gpu.ZxcError as e:
-            rc = e.code
-        _BASE[key] = (rc, bytes(dst[:rc].cpu().numpy()) if rc > 0 else None)
-    return _BASE[key]
-
-
-class Session:
-    """one session with its destination (pattern, canary, optionally at an odd address), work area and result word"""
-
-    def __init__(self, gpu, cap, max_total, max_piece, level=3, bs=BS, seekable=0, checksum=0, odd_dst=0, stream=None):
-        import torch
-        self.gpu, self.cap, self.odd = gpu, cap, odd_dst
-        self.stream = torch.cuda.current_stream() if stream is None else stream
-        self.keep = []
-        ws = gpu.compress_append_device_work_size(max_total, max_piece, level, bs, seekable, checksum)
-        assert ws > 0
-        with torch.cuda.stream(self.stream):
-            self.work = torch.empty(ws + 1, dtype=torch.uint8, device="cuda")
-            self.dst = torch.from_numpy(_pattern(odd_dst + cap + CANARY)).to("cuda")
-            self.res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        self.s = gpu.compress_begin_device(self.dst.data_ptr() + odd_dst, cap, max_total, max_piece, self.work.data_ptr() + 1, ws, level, bs,
-                                           seekable, checksum, self.stream.cuda_stream)
-
-    def append(self, data, k=0):
-        import torch
-        with torch.cuda.stream(self.stream):
-            t, p = _piece(data, k)
-        self.keep.append(t)
-        self.s.append(p, len(data), self.stream.cuda_stream)
-
-    def end(self):
-        self.s.end(self.res.data_ptr(), self.stream.cuda_stream)
-
-    def result(self):
-        """-> (result word, archive bytes or None); the pattern in front of the destination and the canary behind the capacity hold"""
-        self.stream.synchronize()
-        rc, dst = int(self.res.item()), self.dst.cpu().numpy()
-        whole = _pattern(len(dst))
-        assert (dst[: self.odd] == whole[: self.odd]).all(), "bytes in front of d_dst changed"
-        assert (dst[self.odd + self.cap:] == whole[self.odd + self.cap:]).all(), "bytes at or past dst_capacity changed"
-        if rc > 0:
-            assert rc <= self.cap
-            assert (dst[self.odd + rc:] == whole[self.odd + rc:]).all(), "bytes behind the archive changed"
-        return rc, bytes(dst[self.odd: self.odd + rc]) if rc > 0 else None
 
 
 def _check(gpu, data, lens, level=3, bs=BS, seekable=0, checksum=0, cap=None, max_piece=None, odd_dst=0, what=""):

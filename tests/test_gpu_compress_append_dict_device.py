@@ -5,13 +5,12 @@ with the same options, dictionary and capacity; for round trips the unmodified r
 destination starts as a pattern and has a canary area behind dst_capacity; every piece is a tensor of its own at an odd offset
 inside a buffer that ends with the piece (nothing readable is promised behind n); d_work has an odd address. Payloads are
 text-like, and incompressible (stored blocks). Nothing here provokes a fault: every refused input is refused by status."""
-import os
-
 import numpy as np
 import pytest
 
+import dev_append
 import devtest
-from conftest import GOLDEN, load_dict
+from dev_append import dict_baseline as _baseline, dict_of as _dict, dict_session as Session, text as _text
 from devtest import (CANARY, ERR, UNSET, bound as _bound, pattern as _pattern, payload as _payload, piece as _piece,
                      ref_decompress as _ref_decompress, split as _split)
 
@@ -23,89 +22,7 @@ DICT_SIZES = (1, 100, 4096 + 3, 65535)
 
 gpu = devtest.gpu_fixture("compress_begin_dict_device")
 
-
-def _text():
-    return devtest.text(6 << 20)  # (the text the payloads are cut from)
-
-
-_DICTS = {}
-
-
-def _dict(gpu, size, with_huf=False, seed=0):
-    """a dictionary of `size` bytes of the text the payloads are cut from (so that it is used), with or without a shared table"""
-    key = (size, with_huf, seed)
-    if key not in _DICTS:
-        at = (5 << 20) + 70001 * seed
-        _, huf = load_dict(os.path.join(GOLDEN, "conformance", "valid", "dict_text.zxd"))
-        _DICTS[key] = devtest.DevDict(gpu, _text()[at: at + size], huf if with_huf else None, odd=True)  # at an odd address
-    return _DICTS[key]
-
-
-_BASE = {}
-
-
-def _baseline(gpu, data, dd, cap, level, bs, seekable, checksum):
-    """compress_dict_device for the whole source -> (result word or the synchronous error, archive bytes or None); once per case"""
-    import torch
-    key = (hash(data), len(data), id(dd), cap, level, bs, seekable, checksum)
-    if key not in _BASE:
-        src = torch.frombuffer(bytearray(data + bytes(64)), dtype=torch.uint8).to("cuda")
-        ws = gpu.compress_dict_device_work_size(len(data), dd.tup[1] if dd else 0, level, bs, seekable, checksum)
-        work = torch.empty(ws, dtype=torch.uint8, device="cuda")
-        dst = torch.from_numpy(_pattern(cap + CANARY)).to("cuda")
-        res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        try:
-            gpu.compress_dict_device(src.data_ptr(), len(data), dst.data_ptr(), cap, dd.tup if dd else None, work.data_ptr(), ws, res.data_ptr(),
-                                     level, bs, seekable, checksum, torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            rc = int(res.item())
-        except gpu.ZxcError as e:
-            rc = e.code
-        _BASE[key] = (rc, bytes(dst[:rc].cpu().numpy()) if rc > 0 else None)
-    return _BASE[key]
-
-
-class Session:
-    """one session with its destination (pattern, canary, optionally at an odd address), work area at an odd address and result word"""
-
-    def __init__(self, gpu, dd, cap, max_total, max_piece, level=3, bs=BS, seekable=0, checksum=0, odd_dst=0, stream=None, work=None,
-                 dict_="dd"):
-        import torch
-        self.gpu, self.cap, self.odd = gpu, cap, odd_dst
-        self.stream = torch.cuda.current_stream() if stream is None else stream
-        self.keep = []
-        tup = (dd.tup if dd else None) if isinstance(dict_, str) else dict_
-        ws = gpu.compress_append_dict_device_work_size(max_total, max_piece, tup[1] if tup else 0, level, bs, seekable, checksum)
-        assert ws > 0
-        with torch.cuda.stream(self.stream):
-            self.work = torch.empty(ws + 1, dtype=torch.uint8, device="cuda") if work is None else work
-            assert self.work.numel() >= ws + 1
-            self.dst = torch.from_numpy(_pattern(odd_dst + cap + CANARY)).to("cuda")
-            self.res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        self.s = gpu.compress_begin_dict_device(self.dst.data_ptr() + odd_dst, cap, max_total, max_piece, tup, self.work.data_ptr() + 1, ws,
-                                                level, bs, seekable, checksum, self.stream.cuda_stream)
-
-    def append(self, data, k=0):
-        import torch
-        with torch.cuda.stream(self.stream):
-            t, p = _piece(data, k)
-        self.keep.append(t)
-        self.s.append(p, len(data), self.stream.cuda_stream)
-
-    def end(self):
-        self.s.end(self.res.data_ptr(), self.stream.cuda_stream)
-
-    def result(self):
-        """-> (result word, archive bytes or None); the pattern in front of the destination and the canary behind the capacity hold"""
-        self.stream.synchronize()
-        rc, dst = int(self.res.item()), self.dst.cpu().numpy()
-        whole = _pattern(len(dst))
-        assert (dst[: self.odd] == whole[: self.odd]).all(), "bytes in front of d_dst changed"
-        assert (dst[self.odd + self.cap:] == whole[self.odd + self.cap:]).all(), "bytes at or past dst_capacity changed"
-        if rc > 0:
-            assert rc <= self.cap
-            assert (dst[self.odd + rc:] == whole[self.odd + rc:]).all(), "bytes behind the archive changed"
-        return rc, bytes(dst[self.odd: self.odd + rc]) if rc > 0 else None
+_BASE = dev_append.BASE[dev_append.DICT]  # (cleared behind the one very large case)
 
 
 def _check(gpu, data, lens, dd, level=3, bs=BS, seekable=0, checksum=0, cap=None, max_piece=None, odd_dst=0, what=""):

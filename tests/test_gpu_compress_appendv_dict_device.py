@@ -1,93 +1,36 @@
 """zxc_mi355x_compress_appendv_dict_device on the GPU: one call appends a table of buffers to an append session begun with a
 dictionary. The reference value is always existing code: the archive and the result word zxc_mi355x_compress_dict_device writes for
 the concatenation with the same options, dictionary and capacity; for round trips the unmodified reference decoder and a dictionary
-take session with takev. Set-up as in test_gpu_compress_append_dict_device.py and test_gpu_compress_appendv_device.py, whose helpers
-are used: every entry is a tensor of its own at an odd offset inside a buffer that ends with the entry (nothing readable is promised
-behind an entry), the destination is a pattern with a canary behind dst_capacity, the table lies in device memory, d_work and the
+take session with takev. Set-up as in test_gpu_compress_append_dict_device.py and test_gpu_compress_appendv_device.py, with the
+helpers of tests/dev_append.py: every entry is a tensor of its own at an odd offset inside a buffer that ends with the entry (nothing
+readable is promised behind an entry), the destination is a pattern with a canary behind dst_capacity, the table lies in device memory, d_work and the
 scratch sit at odd addresses, the scratch with a canary behind scratch_size. Nothing here provokes a fault: every refused input is
 refused by status, and a table that breaks a rule names only buffers that exist."""
 import numpy as np
 import pytest
 
+import dev_append
 import devtest
-import test_gpu_compress_append_device as A
-import test_gpu_compress_append_dict_device as D
-import test_gpu_compress_appendv_device as V
-import test_gpu_decompress_takev_device as T
-from devtest import ERR
+from dev_append import (Table, bad_table_cases as _bad_table_cases, cut as _cut, dict_baseline as _baseline, dict_of as _dict,
+                        dict_scratch as Scratch, dict_session as VSession, orders as _orders, plain_baseline as _plain_baseline,
+                        plain_session as PlainVSession, run_calls as _run, text as _text)
+from dev_take import TakevSession
+from devtest import CANARY, ERR, bound as _bound, pattern as _pattern, payload as _payload, ref_decompress as _ref_decompress, split as _split
 
 pytestmark = pytest.mark.gpu
 
 BS = 4096
-LENS = V.LENS
 DICT_SIZES = (1, 100, 4099, 65535)
-SCRATCH_CANARY = 256
 
 gpu = devtest.gpu_fixture(session_method=("CompressAppendSession", "appendv_dict"))
 
-
-class Scratch:
-    """scratch_size bytes at an odd address, a pattern, with a canary behind them"""
-
-    def __init__(self, gpu, n_iov, max_piece, dict_size, level, bs, seekable, checksum, stream):
-        import torch
-        self.size = gpu.compress_appendv_dict_device_scratch_size(n_iov, max_piece, dict_size, level, bs, seekable, checksum)
-        assert self.size > 0
-        if dict_size:
-            assert self.size <= 8 * (n_iov + 1) + 16 * -(-n_iov // 1024) + 4096  # no images
-        with torch.cuda.stream(stream):
-            self.t = torch.from_numpy(D._pattern(1 + self.size + SCRATCH_CANARY)).to("cuda")
-        self.ptr = self.t.data_ptr() + 1
-
-    def check(self):
-        tail = self.t[1 + self.size:].cpu().numpy()
-        assert (tail == D._pattern(1 + self.size + SCRATCH_CANARY)[1 + self.size:]).all(), "bytes at or past scratch_size changed"
-
-
-class VSession(D.Session):
-    """the dictionary session with appendv_dict: a call is a list of entries (bytes)"""
-
-    def __init__(self, gpu, dd, cap, max_total, max_piece, level=3, bs=BS, seekable=0, checksum=0, odd_dst=0, stream=None, work=None, dict_="dd"):
-        super().__init__(gpu, dd, cap, max_total, max_piece, level, bs, seekable, checksum, odd_dst, stream, work, dict_)
-        tup = (dd.tup if dd else None) if isinstance(dict_, str) else dict_
-        self.opt = (max_piece, tup[1] if tup else 0, level, bs, seekable, checksum)
-        self.scratches, self.calls = [], 0
-
-    def appendv(self, parts, total=None, fix=None, scratch=None):
-        tb = V.Table(self.gpu, parts, self.stream, 3 * self.calls, fix)
-        sc = scratch or Scratch(self.gpu, tb.n, *self.opt, self.stream)
-        self.keep.append(tb)
-        if sc not in self.scratches:
-            self.scratches.append(sc)
-        self.calls += 1
-        self.s.appendv_dict(tb.dev.data_ptr(), tb.n, tb.total if total is None else total, sc.ptr, sc.size, self.stream.cuda_stream)
-        return sc
-
-    def result(self):
-        out = super().result()
-        for sc in self.scratches:
-            sc.check()
-        return out
-
-
-def _run(s, data, calls):
-    """calls: a list of entry-length lists (an appendv_dict each) and ints (a plain append each), over data in order"""
-    at = 0
-    for k, c in enumerate(calls):
-        n = c if isinstance(c, int) else sum(c)
-        if isinstance(c, int):
-            s.append(data[at: at + n], k)
-        else:
-            s.appendv(V._cut(data[at: at + n], c))
-        at += n
-    assert at == len(data)
-    s.end()
-    return s.result()
+_BASE = dev_append.BASE[dev_append.DICT]  # (cleared behind the one very large case)
 
 
 def _check(gpu, data, calls, dd, level=3, bs=BS, seekable=0, checksum=0, cap=None, max_piece=None, odd_dst=0, what=""):
-    cap = D._bound(gpu, len(data)) if cap is None else cap
-    want_rc, want = D._baseline(gpu, data, dd, cap, level, bs, seekable, checksum)
+    """calls: a list of entry-length lists (an appendv_dict each) and ints (a plain append each), over data in order"""
+    cap = _bound(gpu, len(data)) if cap is None else cap
+    want_rc, want = _baseline(gpu, data, dd, cap, level, bs, seekable, checksum)
     max_piece = max(bs, len(data)) if max_piece is None else max_piece
     rc, got = _run(VSession(gpu, dd, cap, len(data), max_piece, level, bs, seekable, checksum, odd_dst), data, calls)
     print(what, len(data), "dict", dd.tup[1], "session", rc, "compress_dict_device", want_rc)
@@ -99,24 +42,24 @@ def _check(gpu, data, calls, dd, level=3, bs=BS, seekable=0, checksum=0, cap=Non
 
 
 @pytest.mark.parametrize("dict_size", DICT_SIZES)
-@pytest.mark.parametrize("order", list(V._orders()))
+@pytest.mark.parametrize("order", list(_orders()))
 def test_entry_lengths_in_several_orders(gpu, order, dict_size):
-    lens = V._orders()[order]
+    lens = _orders()[order]
     k = DICT_SIZES.index(dict_size)
     for seed in (2, 3):  # text, stored
-        _check(gpu, D._payload(sum(lens), seed), [lens], D._dict(gpu, dict_size, bool((k + seed) % 2)), 3, BS, 1, 1, what=order)
+        _check(gpu, _payload(sum(lens), seed), [lens], _dict(gpu, dict_size, bool((k + seed) % 2)), 3, BS, 1, 1, what=order)
     cut = list(lens)
     cut[cut.index(max(cut))] -= 7  # the same bytes behind a carry of 7, in chunks of two blocks
-    _check(gpu, D._payload(sum(lens), 2), [7, cut], D._dict(gpu, dict_size), 3, BS, 1, 1, max_piece=2 * BS, what=order + ", behind a carry, chunks")
+    _check(gpu, _payload(sum(lens), 2), [7, cut], _dict(gpu, dict_size), 3, BS, 1, 1, max_piece=2 * BS, what=order + ", behind a carry, chunks")
 
 
 @pytest.mark.parametrize("level", [1, 3, 7])
 @pytest.mark.parametrize("seekable,checksum", [(0, 0), (0, 1), (1, 0), (1, 1)])
 def test_options(gpu, level, seekable, checksum):
-    lens = V._orders()["shuffled 0"]
-    dd = D._dict(gpu, 4099, level == 7)
-    _check(gpu, D._payload(sum(lens), 4), [lens], dd, level, BS, seekable, checksum, what="level %d" % level)
-    _check(gpu, D._payload(sum(lens), 5), [lens[::-1]], dd, level, BS, seekable, checksum, max_piece=2 * BS, what="level %d, chunks" % level)
+    lens = _orders()["shuffled 0"]
+    dd = _dict(gpu, 4099, level == 7)
+    _check(gpu, _payload(sum(lens), 4), [lens], dd, level, BS, seekable, checksum, what="level %d" % level)
+    _check(gpu, _payload(sum(lens), 5), [lens[::-1]], dd, level, BS, seekable, checksum, max_piece=2 * BS, what="level %d, chunks" % level)
 
 
 def test_blocks_of_64_kib(gpu):
@@ -124,9 +67,9 @@ def test_blocks_of_64_kib(gpu):
     lens = [0, 1, bs + 31, 33, bs + 32, 0, 2 * bs + 33, 7]
     lens.append(5 * bs - 11 - sum(lens))  # five blocks in all, the last one short
     assert lens[-1] > 0
-    dd = D._dict(gpu, 65535)
-    _check(gpu, D._payload(sum(lens), 6), [lens], dd, 3, bs, 1, 1, what="64 KiB")
-    _check(gpu, D._payload(sum(lens), 7), [bs // 2 + 1, lens[:-1] + [lens[-1] - bs // 2 - 1]], dd, 3, bs, 1, 1, max_piece=2 * bs, what="64 KiB, chunks")
+    dd = _dict(gpu, 65535)
+    _check(gpu, _payload(sum(lens), 6), [lens], dd, 3, bs, 1, 1, what="64 KiB")
+    _check(gpu, _payload(sum(lens), 7), [bs // 2 + 1, lens[:-1] + [lens[-1] - bs // 2 - 1]], dd, 3, bs, 1, 1, max_piece=2 * bs, what="64 KiB, chunks")
 
 
 def test_tiny_entries(gpu):
@@ -135,14 +78,14 @@ def test_tiny_entries(gpu):
     n = 5 + sum(tiny)
     assert 2 * BS < n < 3 * BS
     for seed, size in ((8, 100), (9, 65535)):
-        _check(gpu, D._payload(n, seed), [5, tiny], D._dict(gpu, size), 3, BS, 1, 1, what="1- and 3-byte entries")
-    _check(gpu, D._payload(n, 8), [5, tiny], D._dict(gpu, 4099), 3, BS, 1, 1, max_piece=BS, what="1- and 3-byte entries, chunks of one block")
+        _check(gpu, _payload(n, seed), [5, tiny], _dict(gpu, size), 3, BS, 1, 1, what="1- and 3-byte entries")
+    _check(gpu, _payload(n, 8), [5, tiny], _dict(gpu, 4099), 3, BS, 1, 1, max_piece=BS, what="1- and 3-byte entries, chunks of one block")
 
 
 def test_append_and_appendv_dict_mixed_however_the_bytes_are_split(gpu):
     n = 11 * BS - 100  # eleven blocks in all; max_piece of two blocks: every longer call is a loop of chunks
-    data = D._payload(n, 10)
-    dd = D._dict(gpu, 4099, True)
+    data = _payload(n, 10)
+    dd = _dict(gpu, 4099, True)
     splits = {"a": [BS // 2, [100, 2 * BS, 0, 7, BS + 31], 3 * BS // 2 + 1, [5, 0, 9], None],       # a call wholly inside one block
               "b": [3 * BS + 5, [1] * 300 + [BS + 32, 2 * BS + 9], 17, [BS - 400], None],              # a call that ends inside a block
               "c": [[1], [5 * BS + 1], 4 * BS - 3, [2], None],
@@ -162,8 +105,8 @@ def test_a_call_of_more_than_max_piece(gpu):
     lens = [BS + 31, 0, 3, 2 * BS + 32, 17, 3 * BS - 1]
     lens.append(5 * mp + 3 - sum(lens))
     assert lens[-1] > 0
-    _check(gpu, D._payload(n, 12), [100, lens], D._dict(gpu, 4099), 3, BS, 1, 1, max_piece=mp, what="the chunk loop behind a carry")
-    _check(gpu, D._payload(5 * mp + 3, 13), [lens], D._dict(gpu, 1), 3, BS, 1, 1, max_piece=mp, what="the chunk loop")
+    _check(gpu, _payload(n, 12), [100, lens], _dict(gpu, 4099), 3, BS, 1, 1, max_piece=mp, what="the chunk loop behind a carry")
+    _check(gpu, _payload(5 * mp + 3, 13), [lens], _dict(gpu, 1), 3, BS, 1, 1, max_piece=mp, what="the chunk loop")
 
 
 def test_a_chunk_of_two_launches(gpu):
@@ -172,7 +115,7 @@ def test_a_chunk_of_two_launches(gpu):
     one table of a few thousand entries of mixed lengths."""
     max_piece = 4097 * BS + 7
     n = 5 + max_piece
-    base = np.frombuffer(D._text()[: 4 << 20], dtype=np.uint8)
+    base = np.frombuffer(_text()[: 4 << 20], dtype=np.uint8)
     arr = np.tile(base, n // len(base) + 1)[:n].copy()
     rng = np.random.default_rng(43)
     at = rng.integers(0, n, n // 200)
@@ -183,11 +126,11 @@ def test_a_chunk_of_two_launches(gpu):
                                      np.where(kinds == 2, rng.integers(0, 2 * BS, 3000), rng.integers(0, 5 * BS, 3000))))]
     assert sum(lens) < max_piece
     lens.append(max_piece - sum(lens))
-    dd = D._dict(gpu, 65535)
+    dd = _dict(gpu, 65535)
     ss = gpu.compress_appendv_dict_device_scratch_size(len(lens), max_piece, 65535, 3, BS, True, True)
     assert 0 < ss <= 8 * (len(lens) + 1) + 16 * -(-len(lens) // 1024) + 4096
     _check(gpu, data, [5, lens], dd, 3, BS, 1, 1, max_piece=max_piece, what="4097 blocks in one chunk")
-    D._BASE.clear()
+    _BASE.clear()
 
 
 def test_a_table_written_on_the_stream_and_one_scratch_for_two_calls(gpu):
@@ -195,10 +138,10 @@ def test_a_table_written_on_the_stream_and_one_scratch_for_two_calls(gpu):
     in between; two calls reuse one scratch back to back"""
     import torch
     n = 7 * BS + 50
-    data = D._payload(n, 12)
-    dd = D._dict(gpu, 4099)
-    cap = D._bound(gpu, n)
-    want = D._baseline(gpu, data, dd, cap, 3, BS, 1, 1)
+    data = _payload(n, 12)
+    dd = _dict(gpu, 4099)
+    cap = _bound(gpu, n)
+    want = _baseline(gpu, data, dd, cap, 3, BS, 1, 1)
     lens = [[BS + 9, 0, 40, 2 * BS], [5, n - 3 * BS - 54]]
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
@@ -209,7 +152,7 @@ def test_a_table_written_on_the_stream_and_one_scratch_for_two_calls(gpu):
     with torch.cuda.stream(side):
         table = torch.zeros(4 * 16, dtype=torch.uint8, device="cuda")  # one table, rewritten in stream order
         for ln in lens:
-            tb = V.Table(gpu, V._cut(data[at: at + sum(ln)], ln), side, at)
+            tb = Table(gpu, _cut(data[at: at + sum(ln)], ln), side, at)
             s.keep.append(tb)
             table[: 16 * tb.n].copy_(tb.dev, non_blocking=True)
             s.s.appendv_dict(table.data_ptr(), tb.n, tb.total, sc.ptr, sc.size, side.cuda_stream)
@@ -219,9 +162,9 @@ def test_a_table_written_on_the_stream_and_one_scratch_for_two_calls(gpu):
 
 
 def test_the_capacity_binds_exactly(gpu):
-    lens = V._orders()["shuffled 1"]
+    lens = _orders()["shuffled 1"]
     for seed in (14, 15):
-        data, dd = D._payload(sum(lens), seed), D._dict(gpu, 100 if seed % 2 else 4099)
+        data, dd = _payload(sum(lens), seed), _dict(gpu, 100 if seed % 2 else 4099)
         size, _ = _check(gpu, data, [lens], dd, 3, BS, 1, 1, what="bound")
         assert size > 0
         for cap, want in ((size, size), (size + 1, size), (size - 1, ERR["DST_TOO_SMALL"]), (size // 2, ERR["DST_TOO_SMALL"])):
@@ -229,21 +172,21 @@ def test_the_capacity_binds_exactly(gpu):
             assert rc == want
 
 
-@pytest.mark.parametrize("case", list(V._bad_table_cases()))
+@pytest.mark.parametrize("case", list(_bad_table_cases()))
 def test_table_errors_become_the_sessions_status_and_stay(gpu, case):
-    delta, fix, want = V._bad_table_cases()[case]
+    delta, fix, want = _bad_table_cases()[case]
     lens = [BS + 7, 3 * BS, 50, 0, 2 * BS + 1]
     n = sum(lens)
-    data = D._payload(n + 3 * BS, 16)
-    parts = V._cut(data[:n], lens)
+    data = _payload(n + 3 * BS, 16)
+    parts = _cut(data[:n], lens)
     # an entry longer than total: the promise is smaller than the second entry (and than the sum)
     promised = lens[1] - 1 if delta is None else n + delta
     for before, size in ((0, 100), (100, 65535)):
-        s = VSession(gpu, D._dict(gpu, size), D._bound(gpu, 3 * n), 3 * n, 2 * BS, 3, BS, 1, 1, odd_dst=1)
+        s = VSession(gpu, _dict(gpu, size), _bound(gpu, 3 * n), 3 * n, 2 * BS, 3, BS, 1, 1, odd_dst=1)
         if before:
             s.append(data[:before])
         s.appendv(parts, total=promised, fix=fix)
-        s.appendv(V._cut(data[n: n + 2 * BS + 5], [BS, 5, BS]))  # a later valid appendv_dict: the error stays
+        s.appendv(_cut(data[n: n + 2 * BS + 5], [BS, 5, BS]))  # a later valid appendv_dict: the error stays
         s.append(data[:77])
         s.end()
         rc, _ = s.result()  # the pattern outside [0, dst_capacity) and behind the scratch holds
@@ -260,36 +203,36 @@ def test_a_table_error_behind_a_chunked_call_keeps_what_was_gathered(gpu):
     tiny = [int(x) for x in rng.integers(1, 8, n)]
     tiny = tiny[: int(np.searchsorted(np.cumsum(tiny), n))]
     tiny.append(n - sum(tiny))
-    data = D._payload(n + more, 22)
-    dd = D._dict(gpu, 4099)
-    cap = D._bound(gpu, n + more)
-    want_rc, want = D._baseline(gpu, data[:n], dd, cap, 3, BS, 1, 1)
+    data = _payload(n + more, 22)
+    dd = _dict(gpu, 4099)
+    cap = _bound(gpu, n + more)
+    want_rc, want = _baseline(gpu, data[:n], dd, cap, 3, BS, 1, 1)
     assert want_rc > 0
     s = VSession(gpu, dd, cap, n + more, 2 * BS, 3, BS, 1, 1)
-    sc = s.appendv(V._cut(data[:n], tiny))
-    s.appendv(V._cut(data[n: n + more - 1], [BS, 7, BS - 8]), total=more, scratch=sc)
+    sc = s.appendv(_cut(data[:n], tiny))
+    s.appendv(_cut(data[n: n + more - 1], [BS, 7, BS - 8]), total=more, scratch=sc)
     s.end()
     rc, _ = s.result()
     assert rc == ERR["SRC_TOO_SMALL"], rc
-    dst, whole = s.dst.cpu().numpy(), D._pattern(cap + D.CANARY)
+    dst, whole = s.dst.cpu().numpy(), _pattern(cap + CANARY)
     sizes = np.frombuffer(want[-12 - 4 * 4: -12], dtype="<u4")  # the seek table of the one-shot archive: four blocks
     end = 16 + int(sizes[:3].sum())
     assert bytes(dst[16: end]) == want[16: end], "the blocks gathered before the error"
     assert (dst[:16] == whole[:16]).all() and (dst[end:] == whole[end:]).all(), "bytes outside the gathered blocks changed"
     s2 = VSession(gpu, dd, cap, n + more, 2 * BS, 3, BS, 1, 1, work=s.work)  # ... on the first session's work area
-    s2.appendv(V._cut(data[:n], tiny), scratch=sc)
+    s2.appendv(_cut(data[:n], tiny), scratch=sc)
     s2.end()
     assert s2.result() == (want_rc, want)
 
 
 def test_refusals_leave_the_session_usable(gpu):
     n = 3 * BS + 10
-    data = D._payload(n, 18)
-    dd = D._dict(gpu, 100)
-    cap = D._bound(gpu, n)
+    data = _payload(n, 18)
+    dd = _dict(gpu, 100)
+    cap = _bound(gpu, n)
     s = VSession(gpu, dd, cap, n, 2 * BS, 3, BS, 1, 1)
     s.append(data[: BS - 1])
-    tb = V.Table(gpu, V._cut(data[BS - 1:], [BS, n - 2 * BS + 1]), s.stream)
+    tb = Table(gpu, _cut(data[BS - 1:], [BS, n - 2 * BS + 1]), s.stream)
     sc = Scratch(gpu, tb.n, 2 * BS, 100, 3, BS, 1, 1, s.stream)
     sp = s.stream.cuda_stream
     for args, code in (((tb.dev.data_ptr(), tb.n, tb.total + 1, sc.ptr, sc.size), "OVERFLOW"),      # past max_total
@@ -303,26 +246,26 @@ def test_refusals_leave_the_session_usable(gpu):
     s.s.appendv_dict(tb.dev.data_ptr(), tb.n, tb.total, sc.ptr, sc.size, sp)  # exactly the size
     s.scratches.append(sc)
     s.end()
-    assert s.result() == D._baseline(gpu, data, dd, cap, 3, BS, 1, 1)
+    assert s.result() == _baseline(gpu, data, dd, cap, 3, BS, 1, 1)
 
 
 def test_without_a_dictionary_the_siblings_bytes(gpu):
     """a session begun without a dictionary through the new call: the archive of compress_device, which is the sibling's, and the
     sibling's scratch need"""
     n = 6 * BS + 77
-    data = A._payload(n, 30)
+    data = _payload(n, 30)
     calls = [BS - 3, [100, 2 * BS + 10, 0, 1], [n - 3 * BS - 108]]
-    cap = A._bound(gpu, n)
-    want = A._baseline(gpu, data, cap, 3, BS, 1, 1)
+    cap = _bound(gpu, n)
+    want = _plain_baseline(gpu, data, cap, 3, BS, 1, 1)
     assert want[0] > 0 and not want[1][6] & 0x40
     assert gpu.compress_appendv_dict_device_scratch_size(4, 2 * BS, 0, 3, BS, True, True) == gpu.compress_appendv_device_scratch_size(4, 2 * BS, 3, BS, True, True)
-    dd = D._dict(gpu, 100)
+    dd = _dict(gpu, 100)
     for tup in (None, (dd.tup[0], 0, dd.tup[2], dd.tup[3])):
         assert _run(VSession(gpu, None, cap, n, 2 * BS, 3, BS, 1, 1, dict_=tup), data, calls) == want, tup
-    sib = V.VSession(gpu, cap, n, 2 * BS, 3, BS, 1, 1)  # ... and the sibling itself
+    sib = PlainVSession(gpu, cap, n, 2 * BS, 3, BS, 1, 1)  # ... and the sibling itself
     sib.append(data[: BS - 3])
-    sib.appendv(V._cut(data[BS - 3: 3 * BS + 108], calls[1]))
-    sib.appendv(V._cut(data[3 * BS + 108:], calls[2]))
+    sib.appendv(_cut(data[BS - 3: 3 * BS + 108], calls[1]))
+    sib.appendv(_cut(data[3 * BS + 108:], calls[2]))
     sib.end()
     assert sib.result() == want
 
@@ -330,17 +273,17 @@ def test_without_a_dictionary_the_siblings_bytes(gpu):
 def test_two_sessions_interleaved_on_two_streams(gpu):
     import torch
     n = 9 * BS + 5
-    datas = [D._payload(n, 22), D._payload(n, 24)]
-    dds = [D._dict(gpu, 4099), D._dict(gpu, 65535, True)]
+    datas = [_payload(n, 22), _payload(n, 24)]
+    dds = [_dict(gpu, 4099), _dict(gpu, 65535, True)]
     lens = [[[BS + 3], [4 * BS - 9, 9], [7, 0, n - 5 * BS - 10]], [[7], [1] * 40 + [2 * BS - 40], [n - 2 * BS - 7]]]
-    cap = D._bound(gpu, n)
-    want = [D._baseline(gpu, d, dd, cap, 3, BS, 1, 1) for d, dd in zip(datas, dds)]
+    cap = _bound(gpu, n)
+    want = [_baseline(gpu, d, dd, cap, 3, BS, 1, 1) for d, dd in zip(datas, dds)]
     torch.cuda.synchronize()
     sess = [VSession(gpu, dd, cap, n, 4 * BS, 3, BS, 1, 1, stream=torch.cuda.Stream()) for dd in dds]
-    parts = [D._split(d, [sum(c) for c in ln]) for d, ln in zip(datas, lens)]
+    parts = [_split(d, [sum(c) for c in ln]) for d, ln in zip(datas, lens)]
     for k in range(3):
         for s, p, ln in zip(sess, parts, lens):
-            s.appendv(V._cut(p[k], ln[k]))
+            s.appendv(_cut(p[k], ln[k]))
     for s in sess:
         s.end()
     for s, w in zip(sess, want):
@@ -349,17 +292,17 @@ def test_two_sessions_interleaved_on_two_streams(gpu):
 
 
 def test_round_trips(gpu, ref):
-    lens = V._orders()["reversed"]
+    lens = _orders()["reversed"]
     n = sum(lens)
     for seed, checksum, with_huf in ((20, 1, True), (21, 0, False)):
-        data, dd = D._payload(n, seed), D._dict(gpu, 4099, with_huf)
+        data, dd = _payload(n, seed), _dict(gpu, 4099, with_huf)
         rc, arc = _check(gpu, data, [lens], dd, 3, BS, 1, checksum, max_piece=3 * BS, what="round trip")
         assert rc > 0
-        size, back = D._ref_decompress(ref, arc, n, dd.content, dd.huf, bool(checksum))
+        size, back = _ref_decompress(ref, arc, n, dd.content, dd.huf, bool(checksum))
         assert size == n and back == data
-        assert D._ref_decompress(ref, arc, n)[0] == ERR["DICT_REQUIRED"]
+        assert _ref_decompress(ref, arc, n)[0] == ERR["DICT_REQUIRED"]
         # read back through a dictionary take session, into a table of other entries than it was written from
-        t = T.VSession(gpu, arc, n, BS, max_piece=2 * BS, checksum=bool(checksum), dd=dd)
+        t = TakevSession(gpu, arc, n, BS, max_piece=2 * BS, checksum=bool(checksum), dd=dd)
         t.takev([BS + 5, 0, 1, 7 * BS], aligned=False)
         t.takev([n - 8 * BS - 6], aligned=True)
         t.end()

@@ -17,9 +17,8 @@ import pytest
 
 import devtest
 from conftest import GOLDEN, load_dict
+from dev_batch import SIZES_4K, Area, host as _host, payload as _payload, run as _run_batch  # (the batch call's)
 from devtest import CANARY, ERR, UNSET, pattern as _pattern, to_dev as _to_dev
-from test_gpu_compress_batch_device import SIZES_4K, Area, _host, _payload  # (the batch call's areas, payloads and host archives)
-from test_gpu_compress_batch_device import _run as _run_batch
 
 pytestmark = pytest.mark.gpu
 

@@ -10,56 +10,15 @@ run behind a dummy one); the strict capacity of zxc_decompress_block_safe (the f
 executor with strict checks: see "Decode executor routing" in DESIGN.md), one call per block.
 Every launch is on the caller's default stream: the module takes no launch-order slot of its own. No case is built to fault:
 every error case has a defined negative status and stays inside its slot."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import decode_limit_cases as D
-import decode_plan_cases as P
+from decode_harness import dev, launch  # noqa: F401  (the device fixture and the guarded launch)
 
 pytestmark = pytest.mark.gpu
 
 FAMS = [f for f in D.FAMILIES if f != "dict"]
-
-
-@pytest.fixture(scope="module")
-def dev(product):
-    import torch
-    assert product.lib().zxc_mi355x_device_count() >= 1, "no HIP device"
-    product.lib().zxc_mi355x_set_device(0)
-    torch.cuda.set_device(0)
-    L = product.lib()
-    L.zxc_mi355x_decode_blocks_dict_device.restype = C.c_int
-    L.zxc_mi355x_decode_blocks_dict_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                       C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    return product
-
-
-def launch(dev, case, lcases, what):
-    """One guarded launch of a packed job table on the default stream, then the checks."""
-    import torch
-    size = P.guarded_layout(case, seed=case.n)
-    d_comp = torch.frombuffer(bytearray(case.comp) + bytearray(64), dtype=torch.uint8).to("cuda")
-    d_jobs = torch.frombuffer(bytearray(case.jobs.tobytes()), dtype=torch.uint8).to("cuda")
-    d_out = torch.from_numpy(P.canary(size)).to("cuda")
-    d_st = torch.full((case.n,), -999, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    if case.dict_ is not None:
-        d_dict = torch.frombuffer(bytearray(case.dict_), dtype=torch.uint8).to("cuda")
-        torch.cuda.synchronize()
-        rc = dev.lib().zxc_mi355x_decode_blocks_dict_device(d_comp.data_ptr(), d_jobs.data_ptr(), case.n, d_out.data_ptr(), d_st.data_ptr(),
-                                                            case.block_size, int(case.checksum), d_dict.data_ptr(), len(case.dict_), None, None)
-        assert rc == 0, (what, rc)
-    else:
-        dev.decode_blocks_device(d_comp.data_ptr(), d_jobs.data_ptr(), case.n, d_out.data_ptr(), d_st.data_ptr(), case.block_size,
-                                 case.checksum, 0)
-    torch.cuda.synchronize()
-    out, st = d_out.cpu().numpy(), d_st.cpu().numpy()
-    try:
-        P.check_guarded(case, out, st, what)
-    except AssertionError as e:
-        raise AssertionError(f"{what}: {D.explain(case, lcases, out, st)}\n{e}") from None
 
 
 def tables(oracle, ref, fam, route, checksum=False):
@@ -70,7 +29,7 @@ def tables(oracle, ref, fam, route, checksum=False):
 
 
 @pytest.mark.parametrize("fam", FAMS + ["random"])
-def test_two_pass_launch(dev, oracle, ref, fam, monkeypatch):
+def test_two_pass_launch(dev, oracle, ref, fam, monkeypatch):  # noqa: F811
     monkeypatch.delenv("ZXC_MI355X_CK_INLINE", raising=False)
     for case, lc in tables(oracle, ref, fam, "lean"):
         launch(dev, case, lc, case.label)
@@ -78,7 +37,7 @@ def test_two_pass_launch(dev, oracle, ref, fam, monkeypatch):
 
 @pytest.mark.parametrize("inline", [False, True], ids=["ck_apart", "ck_inline"])
 @pytest.mark.parametrize("fam", FAMS + ["random"])
-def test_checksummed_launch(dev, oracle, ref, fam, inline, monkeypatch):
+def test_checksummed_launch(dev, oracle, ref, fam, inline, monkeypatch):  # noqa: F811
     """The blocks carry trailers and the launch verifies them: beside the decode (zxc_block_checksum_kernel + merge), or
     inside the decode kernels. The environment is restored by monkeypatch."""
     if inline:
@@ -90,13 +49,13 @@ def test_checksummed_launch(dev, oracle, ref, fam, inline, monkeypatch):
 
 
 @pytest.mark.parametrize("fam", list(D.FAMILIES) + ["random"])
-def test_dictionary_launch(dev, oracle, ref, fam):
+def test_dictionary_launch(dev, oracle, ref, fam):  # noqa: F811
     for case, lc in tables(oracle, ref, fam, "dict"):
         launch(dev, case, lc, case.label)
 
 
 @pytest.mark.parametrize("fam", FAMS)
-def test_strict_capacity_calls(dev, oracle, ref, fam):
+def test_strict_capacity_calls(dev, oracle, ref, fam):  # noqa: F811
     """zxc_decompress_block_safe, one call per block with dst_capacity = the block size: the strict-capacity plan (the full
     kernel alone, exact checks). Verdicts: the oracle's strict decoders, as in D.verdict(route='strict')."""
     import oracle_py
@@ -127,7 +86,7 @@ def _to_dev(data):
 
 
 @pytest.mark.parametrize("fam", FAMS)
-def test_whole_frames(dev, oracle, fam):
+def test_whole_frames(dev, oracle, fam):  # noqa: F811
     """A handful of cases per family as one-block seekable frames through zxc_decompress, zxc_mi355x_decompress_device and
     zxc_mi355x_decompress_ranges_device (the whole block, and a slice out of its middle)."""
     import craft

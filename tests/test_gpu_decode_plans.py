@@ -23,13 +23,11 @@ child process: in this one it would change the plan of every later test.
                        behind the order pass, no list
   S6 no free slot      (child process) 16 streams take every slot, a 17th decodes S1's and S4's inputs: one plain kernel
 """
-import ctypes as C
 import os
 import subprocess
 import sys
 import time
 
-import numpy as np
 import pytest
 
 if __name__ == "__main__":  # (S6's child process: the same paths conftest.py sets up)
@@ -37,70 +35,12 @@ if __name__ == "__main__":  # (S6's child process: the same paths conftest.py se
     sys.path[:0] = [_ROOT, os.path.join(_ROOT, "oracle"), os.path.join(_ROOT, "tests")]
 
 import decode_plan_cases as P
+from decode_harness import Runner, _hip, new_stream
 
 pytestmark = pytest.mark.gpu
 
 BIG = (66 << 20) - 13  # 16 896 blocks of 4 KiB (> ZXC_RLE_LEAN_MAX_JOBS = 16 384, > 8 192 scratch slots), unaligned tail
 MID = (8 << 20) - 13   # 128 blocks of 64 KiB
-
-
-def _hip():
-    """The HIP runtime the process already uses (torch loads it before the product library)."""
-    import torch  # noqa: F401
-    path = None
-    with open("/proc/self/maps") as f:
-        for line in f:
-            if "libamdhip64.so" in line:
-                path = line.split()[-1]
-                break
-    H = C.CDLL(path or "libamdhip64.so")
-    H.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    H.hipStreamCreateWithFlags.restype = C.c_int
-    return H
-
-
-def new_stream(H):
-    s = C.c_void_p()
-    assert H.hipStreamCreateWithFlags(C.byref(s), 1) == 0 and s.value  # hipStreamNonBlocking
-    return s.value
-
-
-class Runner:
-    """Uploads a case, lays its output out guarded, launches it on a stream and checks the result."""
-
-    def __init__(self, zxc):
-        import torch
-        self.torch = torch
-        self.dev = torch.device("cuda", 0)
-        self.L = zxc.lib()
-        self.L.zxc_mi355x_decode_blocks_dict_device.restype = C.c_int
-        self.L.zxc_mi355x_decode_blocks_dict_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                                C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        self.zxc = zxc
-
-    def run(self, case, stream, what=""):
-        torch = self.torch
-        size = P.guarded_layout(case, seed=case.n)
-        d_comp = torch.frombuffer(bytearray(case.comp) + bytearray(64), dtype=torch.uint8).to(self.dev)
-        d_jobs = torch.frombuffer(bytearray(case.jobs.tobytes()), dtype=torch.uint8).to(self.dev)
-        d_out = torch.from_numpy(P.canary(size)).to(self.dev)
-        d_st = torch.full((case.n,), -999, dtype=torch.int32, device=self.dev)
-        keep = []
-        torch.cuda.synchronize()
-        if case.dict_ is not None:
-            d_dict = torch.frombuffer(bytearray(case.dict_), dtype=torch.uint8).to(self.dev)
-            d_huf = torch.frombuffer(bytearray(case.dict_huf), dtype=torch.uint8).to(self.dev) if case.dict_huf else None
-            keep += [d_dict, d_huf]
-            torch.cuda.synchronize()
-            rc = self.L.zxc_mi355x_decode_blocks_dict_device(d_comp.data_ptr(), d_jobs.data_ptr(), case.n, d_out.data_ptr(), d_st.data_ptr(),
-                                                             case.block_size, int(case.checksum), d_dict.data_ptr(), len(case.dict_),
-                                                             d_huf.data_ptr() if d_huf is not None else None, stream)
-            assert rc == 0, (case.label, rc)
-        else:
-            self.zxc.decode_blocks_device(d_comp.data_ptr(), d_jobs.data_ptr(), case.n, d_out.data_ptr(), d_st.data_ptr(), case.block_size,
-                                          case.checksum, stream)
-        torch.cuda.synchronize()  # (the launch's hint has landed before the next launch on this stream reads it)
-        P.check_guarded(case, d_out.cpu().numpy(), d_st.cpu().numpy(), what)
 
 
 @pytest.fixture(scope="module")

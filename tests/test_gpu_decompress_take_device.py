@@ -8,89 +8,14 @@ blocks). Nothing here provokes a fault: every refused input is refused by status
 import pytest
 
 import devtest
-from devtest import ERR, PAD, UNSET, DevDict, pattern as _pattern, payload as _payload, to_dev as _to_dev
+from dev_take import BS, TakeSession as Session, archive as _archive, blocks_at as _blocks_at, oneshot as _oneshot
+from devtest import ERR, PAD, UNSET, DevDict, payload as _payload, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
-FRONT = 256   # pattern bytes in front of a piece (keeps an aligned piece 16-byte aligned)
-CANARY = 256  # ... and behind it
-BS = 4096
 SIZES = (0, 1, 4095, 4096, 4097, 3 * 4096 + 5)
 
 gpu = devtest.gpu_fixture("decompress_begin_device")
-
-_ONE = {}
-
-
-def _oneshot(gpu, arc, cap, bs, checksum, dd=None):
-    """decompress_device / decompress_dict_device -> (result word, the bytes it wrote when it succeeded); once per case"""
-    import torch
-    key = (arc, cap, bs, checksum, id(dd))
-    if key not in _ONE:
-        d_arc = _to_dev(arc, PAD)
-        ws = gpu.decompress_device_work_size(len(arc), cap, bs)
-        work = torch.empty(max(ws, 1), dtype=torch.uint8, device="cuda")
-        dst = torch.from_numpy(_pattern(cap + CANARY)).to("cuda")
-        res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        st = torch.cuda.current_stream().cuda_stream
-        if dd is None:
-            gpu.decompress_device(d_arc.data_ptr(), len(arc), dst.data_ptr(), cap, bs, work.data_ptr(), ws, res.data_ptr(), checksum, st)
-        else:
-            gpu.decompress_dict_device(d_arc.data_ptr(), len(arc), dst.data_ptr(), cap, bs, dd.tup, work.data_ptr(), ws, res.data_ptr(),
-                                       checksum, st)
-        torch.cuda.synchronize()
-        rc = int(res.item())
-        assert rc != UNSET
-        _ONE[key] = (rc, bytes(dst[:rc].cpu().numpy()) if rc >= 0 else None)
-    return _ONE[key]
-
-
-class Session:
-    """one session with its archive, work area (at an odd address) and result word; every take gets a tensor of its own"""
-
-    def __init__(self, gpu, arc, cap, bs=BS, max_piece=None, checksum=False, aligned=True, dd=None, stream=None, with_dict_begin=False):
-        import torch
-        self.gpu, self.cap, self.aligned, self.pieces = gpu, cap, aligned, []
-        self.stream = torch.cuda.current_stream() if stream is None else stream
-        max_piece = max(bs, cap) if max_piece is None else max_piece
-        ws = gpu.decompress_take_device_work_size(len(arc), cap, max_piece, bs)
-        assert ws > 0
-        with torch.cuda.stream(self.stream):
-            self.arc = _to_dev(arc, PAD)
-            self.work = torch.empty(ws + 1, dtype=torch.uint8, device="cuda")
-            self.res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        if dd is not None or with_dict_begin:
-            self.s = gpu.decompress_begin_dict_device(self.arc.data_ptr(), len(arc), cap, max_piece, bs, dd.tup if dd else None,
-                                                      self.work.data_ptr() + 1, ws, checksum, self.stream.cuda_stream)
-        else:
-            self.s = gpu.decompress_begin_device(self.arc.data_ptr(), len(arc), cap, max_piece, bs, self.work.data_ptr() + 1, ws, checksum,
-                                                 self.stream.cuda_stream)
-
-    def take(self, n, k=0):
-        import torch
-        off = FRONT + (0 if self.aligned else 1 + 2 * (k % 7))
-        with torch.cuda.stream(self.stream):
-            t = torch.from_numpy(_pattern(off + n + CANARY)).to("cuda")
-        self.s.take(t.data_ptr() + off, n, self.stream.cuda_stream)  # (a refused take raises in front of the append below)
-        self.pieces.append((t, off, n))
-
-    def end(self):
-        self.s.end(self.res.data_ptr(), self.stream.cuda_stream)
-
-    def result(self):
-        """-> (result word, the pieces' bytes concatenated); the pattern in front of every piece and the canary behind it hold"""
-        self.stream.synchronize()
-        rc, out = int(self.res.item()), []
-        for k, (t, off, n) in enumerate(self.pieces):
-            got, whole = t.cpu().numpy(), _pattern(off + n + CANARY)
-            assert (got[:off] == whole[:off]).all(), "bytes in front of piece %d changed" % k
-            assert (got[off + n:] == whole[off + n:]).all(), "bytes behind piece %d changed" % k
-            out.append(bytes(got[off: off + n]))
-        return rc, b"".join(out)
-
-    def untouched(self):
-        return all((t.cpu().numpy() == _pattern(off + n + CANARY)).all() for t, off, n in self.pieces)
-
 
 def _check(gpu, arc, cap, lens, bs=BS, checksum=False, aligned=True, max_piece=None, dd=None, what=""):
     assert sum(lens) == cap
@@ -131,10 +56,6 @@ def _on_16(lens):
         out.append(end - at)
         at = end
     return out + [total - at]
-
-
-def _archive(gpu, data, level=3, bs=BS, seekable=True, checksum=True):
-    return gpu.compress(data, level, bs, seekable, checksum)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -240,15 +161,6 @@ def test_capacities(gpu):
         assert rc == ERR["DST_TOO_SMALL"]
     rc, _, _ = _check(gpu, _archive(gpu, b""), 0, [0], what="the probe of the empty archive")
     assert rc == 0
-
-
-def _blocks_at(arc, checksum=True):
-    at, out = 16, []
-    while arc[at] != 255:
-        n = 8 + int.from_bytes(arc[at + 3: at + 7], "little") + (4 if checksum else 0)
-        out.append((at, n))
-        at += n
-    return out
 
 
 def test_damaged_archives_give_the_result_of_decompress_device(gpu):

@@ -9,105 +9,15 @@ import numpy as np
 import pytest
 
 import devtest
-import test_gpu_decompress_take_device as K
-from devtest import ERR, PAD, UNSET, pattern as _pattern, payload as _payload, to_dev as _to_dev
-from test_gpu_decompress_take_device import BS, _archive, _oneshot  # (the take session's archives and one-shot reference)
+from dev_take import BS, TakevSession as VSession, archive as _archive, blocks_at as _blocks_at, oneshot as _oneshot
+from devtest import ERR, PAD, UNSET, DevDict, payload as _payload, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
-GAP = 64  # canary bytes between two entries
 ERRV = ERR
 EDGE_LENS = [0, 1, 15, 16, 17, 31, 32, 33, 4095, 4096, 4097, 4096 + 31, 4096 + 32, 4096 + 33, 2 * 4096 + 32, 3 * 4096 + 5]
 
 gpu = devtest.gpu_fixture(session_method=("DecompressTakeSession", "takev"))
-
-
-class VSession:
-    """one session with its archive, work area (at an odd address) and result word; every call gets a tensor of its own, whose
-    entries are slices with canaries around each"""
-
-    def __init__(self, gpu, arc, cap, bs=BS, max_piece=None, checksum=False, dd=None):
-        import torch
-        from zxc_amd.api import IOV_DTYPE
-        self.gpu, self.cap, self.bs, self.calls, self.IOV = gpu, cap, bs, [], IOV_DTYPE
-        self.max_piece = max(bs, cap) if max_piece is None else max_piece
-        self.st = torch.cuda.current_stream().cuda_stream
-        ws = gpu.decompress_take_device_work_size(len(arc), cap, self.max_piece, bs)
-        assert ws > 0
-        self.arc = _to_dev(arc, PAD)
-        self.work = torch.empty(ws + 1, dtype=torch.uint8, device="cuda")
-        self.res = torch.full((1,), UNSET, dtype=torch.int64, device="cuda")
-        if dd is not None:
-            self.s = gpu.decompress_begin_dict_device(self.arc.data_ptr(), len(arc), cap, self.max_piece, bs, dd.tup, self.work.data_ptr() + 1,
-                                                      ws, checksum, self.st)
-        else:
-            self.s = gpu.decompress_begin_device(self.arc.data_ptr(), len(arc), cap, self.max_piece, bs, self.work.data_ptr() + 1, ws,
-                                                 checksum, self.st)
-
-    def scratch(self, n_iov):
-        import torch
-        ss = self.gpu.decompress_takev_device_scratch_size(n_iov, self.max_piece, self.bs)
-        assert ss > 0
-        return torch.empty(ss + 3, dtype=torch.uint8, device="cuda"), ss
-
-    def layout(self, lens, aligned):
-        """-> (tensor of pattern bytes, [(offset, len)]): the entries with GAP or more canary bytes around each"""
-        import torch
-        at, places = GAP, []
-        for k, n in enumerate(lens):
-            at = (at + 15) // 16 * 16 + (0 if aligned else 1 + 2 * (k % 7))
-            places.append((at, n))
-            at += n + GAP
-        return torch.from_numpy(_pattern(at + GAP)).to("cuda"), places
-
-    def takev(self, lens, aligned=True, total=None, mutate=None, scratch=None, via_stream_copy=False):
-        """one takev over entries of these lengths; mutate(table) may damage the table (never in a way that is dereferenced)"""
-        import torch
-        t, places = self.layout(lens, aligned)
-        table = np.zeros(max(len(lens), 1), dtype=self.IOV)
-        for i, (off, n) in enumerate(places):
-            table[i] = (t.data_ptr() + off if n else 0, n)  # an empty entry's base is not looked at
-        if mutate:
-            mutate(table)
-        raw = torch.from_numpy(table.view(np.uint8).copy())
-        pinned = None
-        if via_stream_copy:  # the table is written on the stream by a copy enqueued just before the call
-            d_iov = torch.zeros(len(raw), dtype=torch.uint8, device="cuda")
-            pinned = raw.pin_memory()
-            d_iov.copy_(pinned, non_blocking=True)
-        else:
-            d_iov = raw.to("cuda")
-        sc, ss = scratch if scratch is not None else self.scratch(len(lens))
-        self.s.takev(d_iov.data_ptr(), len(lens), sum(lens) if total is None else total, sc.data_ptr() + 3, ss, self.st)
-        self.calls.append((t, places, (d_iov, pinned), sc))
-        return len(self.calls) - 1
-
-    def take(self, n, aligned=True):
-        t, places = self.layout([n], aligned)
-        self.s.take(t.data_ptr() + places[0][0], n, self.st)
-        self.calls.append((t, places, None, None))
-        return len(self.calls) - 1
-
-    def end(self):
-        self.s.end(self.res.data_ptr(), self.st)
-
-    def result(self):
-        """-> (result word, per call the entries' bytes concatenated); every byte outside the entries holds"""
-        import torch
-        torch.cuda.synchronize()
-        rc, out = int(self.res.item()), []
-        for k, (t, places, _, _) in enumerate(self.calls):
-            got = t.cpu().numpy()
-            keep = np.ones(len(got), dtype=bool)
-            for off, n in places:
-                keep[off: off + n] = False
-            assert (got[keep] == _pattern(len(got))[keep]).all(), "bytes outside the entries of call %d changed" % k
-            out.append(b"".join(bytes(got[off: off + n]) for off, n in places))
-        return rc, out
-
-    def untouched(self, k):
-        t = self.calls[k][0]
-        return bool((t.cpu().numpy() == _pattern(len(t))).all())
 
 
 def _check(gpu, arc, cap, calls, bs=BS, checksum=False, aligned=True, max_piece=None, dd=None, what=""):
@@ -204,7 +114,7 @@ def test_a_session_begun_with_a_dictionary(gpu):
     from zxc_amd import corpus
     n = 9 * BS + 50
     data = _payload(n, 42)
-    dd = K.DevDict(gpu, corpus.synth_text(30000, seed=8))
+    dd = DevDict(gpu, corpus.synth_text(30000, seed=8))
     src = _to_dev(data, PAD)
     ws = gpu.compress_dict_device_work_size(n, len(dd.content), 3, BS, True, True)
     work = torch.empty(ws, dtype=torch.uint8, device="cuda")
@@ -306,7 +216,7 @@ def test_a_failing_block_gives_the_result_of_decompress_device(gpu):
     n = 8 * BS + 77
     data = _payload(n, 50)
     arc = _archive(gpu, data)
-    at, size = K._blocks_at(arc)[4]
+    at, size = _blocks_at(arc)[4]
     bad = bytearray(arc)
     bad[at + size - 2] ^= 0x10  # the checksum trailer of block 4
     bad = bytes(bad)

@@ -10,7 +10,7 @@ import pytest
 import decode_limit_cases as D
 import decode_plan_cases as P
 import lean_predicate_cases as L
-from test_gpu_decode_limits import dev, launch  # noqa: F401  (the device fixture and the guarded launch of the limits test)
+from decode_harness import dev, launch  # noqa: F401  (the device fixture and the guarded launch of the limits test)
 
 pytestmark = pytest.mark.gpu
 

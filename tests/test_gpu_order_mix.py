@@ -11,7 +11,7 @@ import pytest
 
 import decode_plan_cases as P
 from conftest import ROOT
-from test_gpu_decode_plans import Runner, _hip, new_stream
+from decode_harness import Runner, _hip, new_stream
 
 pytestmark = pytest.mark.gpu
 

@@ -6,7 +6,7 @@ import pytest
 
 import decode_limit_cases as D
 import lean_predicate_cases as L
-from test_decode_limits_cpu import emu, run  # noqa: F401  (the emulator fixture and the guarded launch of the limits test)
+from decode_harness import emu, run  # noqa: F401  (the emulator fixture and the guarded launch of the limits test)
 
 
 @pytest.mark.parametrize("fam", L.FAMS)

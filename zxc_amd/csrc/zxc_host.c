@@ -478,6 +478,12 @@ static double pipe_now_ms(void) {
 typedef struct { double src0, up0, up1, launched, ready, sunk; uint32_t n; size_t comp, out; } pipe_dbg_t;
 static pipe_dbg_t* g_pipe_dbg = NULL; /* ZXC_MI355X_DEBUG_TIMES=1: one caller at a time, a timeline of the pieces on stderr */
 
+/* the test switch ZXC_MI355X_FRAME_BATCH_MIB = 1 .. 1024: every piece of every pipelined call this size, no ramp (0: not set) */
+static size_t frame_batch_bytes(void) {
+    const char* ev = getenv("ZXC_MI355X_FRAME_BATCH_MIB");
+    return ev && atoi(ev) >= 1 && atoi(ev) <= 1024 ? (size_t)atoi(ev) << 20 : 0;
+}
+
 static uint32_t pipe_piece_blocks(const pipe_t* e, uint64_t i) { /* the ramp: 4, 8, 16, ... MiB of output up to the piece size */
     uint32_t want = e->first_blocks;
     for (uint64_t r = 0; r < i && want < e->max_blocks; r++) want <<= 1;
@@ -605,8 +611,8 @@ static int pipe_run_ex(pipe_source_fn source, void* source_ctx, pipe_sink_fn sin
     e->verify = verify;
     e->dr = dr;
     e->device = dev;
-    int fixed = 0; /* (the test switch: every piece this size, no ramp) */
-    { const char* ev = getenv("ZXC_MI355X_FRAME_BATCH_MIB"); if (ev && atoi(ev) >= 1 && atoi(ev) <= 1024) { piece_bytes = (size_t)atoi(ev) << 20; fixed = 1; } }
+    const int fixed = frame_batch_bytes() != 0;
+    if (fixed) piece_bytes = frame_batch_bytes();
     if (piece_bytes == 0) piece_bytes = PIPE_PIECE_BYTES;
     e->max_blocks = (uint32_t)(piece_bytes / block_size);
     if (e->max_blocks < 16u) e->max_blocks = 16u;
@@ -877,8 +883,7 @@ int64_t zxc_decompress(const void* src_v, const size_t src_size, void* dst_v, co
         w.c.done = 0;
         w.c.saw_eof = 0;
         w.c.tail_err = 0;
-        uint32_t nb = (uint32_t)(PIPE_PIECE_BYTES / block_size); /* (at most what a piece can hold: the walk stops where the piece did) */
-        { const char* ev = getenv("ZXC_MI355X_FRAME_BATCH_MIB"); if (ev && atoi(ev) >= 1 && atoi(ev) <= 1024) nb = (uint32_t)(((size_t)atoi(ev) << 20) / block_size); }
+        uint32_t nb = (uint32_t)((frame_batch_bytes() ? frame_batch_bytes() : PIPE_PIECE_BYTES) / block_size); /* (at most what a piece can hold: the walk stops where the piece did) */
         if (nb < 16u) nb = 16u;
         /* the piece had exactly this many blocks or fewer: walk block by block up to where it ended */
         w.stop_ip = (size_t)k.irr[2];
@@ -952,22 +957,31 @@ int64_t zxc_decompress_inplace(void* buffer, const size_t buffer_capacity, const
  * thread, upload and launch of batch i + 1 in series beside the download of batch i, 3 ms of hipMalloc / hipFree per call:
  * 1 GiB in 41-44 ms against 28 ms of encode launches. Archives are byte for byte the one-shot ones whatever the piece size
  * (tests/test_gpu_encode.py); ZXC_MI355X_DEBUG_TIMES=1 prints the pieces' timeline. */
+/* The blocks of [a[0..alen) | b[0..blen)]: b is the caller's input; a, when alen != 0, is ONE block in front of it (the push
+ * stream's accumulator, or its last partial block) and becomes a piece of its own. */
 typedef struct {
-    const uint8_t* src;
-    size_t src_size, block_size;
+    const uint8_t *a, *b;
+    size_t alen, blen, block_size;
     uint32_t next, nb;
 } comp_src_t;
 static int comp_source(void* ctx, uint32_t max_blocks, pipe_piece_t* p) {
     comp_src_t* c = (comp_src_t*)ctx;
-    if (c->next >= c->nb) return 0;
-    const uint32_t f = c->next, n = c->nb - f < max_blocks ? c->nb - f : max_blocks;
-    const size_t o = (size_t)f * c->block_size;
-    p->h_comp = c->src + o; /* (here: the SOURCE bytes of the piece's blocks) */
-    p->comp_bytes = c->src_size - o < (size_t)n * c->block_size ? c->src_size - o : (size_t)n * c->block_size;
-    p->n = n;
-    p->out_bytes = (size_t)n * (c->block_size + 64);
+    const uint32_t f = c->next;
+    if (f >= c->nb) return 0;
+    if (c->alen && f == 0) {
+        p->h_comp = c->a; /* (here: the SOURCE bytes of the piece's blocks) */
+        p->comp_bytes = c->alen;
+        p->n = 1;
+    } else {
+        const uint32_t fb = f - (c->alen ? 1u : 0u), n = c->nb - f < max_blocks ? c->nb - f : max_blocks;
+        const size_t o = (size_t)fb * c->block_size;
+        p->h_comp = c->b + o;
+        p->comp_bytes = c->blen - o < (size_t)n * c->block_size ? c->blen - o : (size_t)n * c->block_size;
+        p->n = n;
+    }
+    p->out_bytes = (size_t)p->n * (c->block_size + 64);
     p->cookie[0] = f;
-    c->next = f + n;
+    c->next = f + p->n;
     return 1;
 }
 typedef struct { int level, checksum; } comp_enq_t;
@@ -1026,10 +1040,12 @@ static int comp_sink(void* ctx, const pipe_piece_t* p, const int32_t* st, const 
     return 0;
 }
 #define COMP_PIECE_BYTES ((size_t)64 << 20)
-/* -> ZXC_OK and *op_io advanced over the nb encoded blocks, sizes[] and *hash_io filled; or a negative zxc_error_t */
-static int compress_pieces(const uint8_t* src, size_t src_size, size_t block_size, int level, int checksum_enabled, size_t tail_need,
-                           uint8_t* dst, size_t dst_capacity, size_t* op_io, uint32_t* sizes, uint32_t nb, size_t piece_bytes, uint32_t* hash_io) {
-    comp_src_t cs = {src, src_size, block_size, 0, nb};
+/* The pipelined encode of zxc_compress, zxc_compress_block and the push stream: the nb blocks of a | b (comp_src_t) land back to
+ * back at dst + *op_io, leaving tail_need bytes of the capacity free behind them.
+ * -> ZXC_OK and *op_io advanced over the blocks, sizes[nb] and *hash_io filled; or a negative zxc_error_t */
+static int compress_pieces(const uint8_t* a, size_t alen, const uint8_t* b, size_t blen, uint32_t nb, size_t block_size, int level, int checksum_enabled,
+                           size_t tail_need, uint8_t* dst, size_t dst_capacity, size_t* op_io, uint32_t* sizes, uint32_t* hash_io) {
+    comp_src_t cs = {a, b, alen, blen, block_size, 0, nb};
     comp_enq_t ce = {level, checksum_enabled};
     comp_sink_t ck;
     memset(&ck, 0, sizeof ck);
@@ -1041,13 +1057,13 @@ static int compress_pieces(const uint8_t* src, size_t src_size, size_t block_siz
     ck.sizes = sizes;
     ck.global_hash = *hash_io;
     ck.checksum = checksum_enabled;
-    uint32_t piece_blocks = (uint32_t)(piece_bytes / block_size);
-    if (piece_blocks < 16u) piece_blocks = 16u;
+    const size_t piece_bytes = frame_batch_bytes() ? frame_batch_bytes() : COMP_PIECE_BYTES;
+    const uint32_t piece_blocks = (uint32_t)(piece_bytes / block_size > 16 ? piece_bytes / block_size : 16);
     ck.offs = (uint64_t*)malloc((size_t)piece_blocks * sizeof(uint64_t));
     if (!ck.offs) return ZXC_ERROR_MEMORY;
     /* (a short ramp — 16, 32, 64 MiB — so that the first encodes start while the link is still busy with the uploads behind them;
      *  six slots: a piece's encode takes ~3.5 ms whatever its size, five of them in flight keep the chip full across their tails) */
-    const int rc = pipe_run_ex(comp_source, &cs, comp_sink, &ck, comp_enqueue, &ce, (uint32_t)block_size, 0, NULL, src_size, (uint64_t)nb * block_size,
+    const int rc = pipe_run_ex(comp_source, &cs, comp_sink, &ck, comp_enqueue, &ce, (uint32_t)block_size, 0, NULL, alen + blen, (uint64_t)nb * block_size,
                                (size_t)piece_blocks * block_size, (size_t)16 << 20, 0, PIPE_SLOTS);
     free(ck.offs);
     if (rc != 0) return rc < 0 ? rc : ZXC_ERROR_CORRUPT_DATA;
@@ -1056,111 +1072,171 @@ static int compress_pieces(const uint8_t* src, size_t src_size, size_t block_siz
     return ZXC_OK;
 }
 
+/* ---- what the compress entry points share: the options, the serial encode, the archive's tail */
+/* zxc_compress_opts_t as every compress entry point reads it: level 3 unless given and at most 7, 512 KiB blocks unless given, a
+ * dictionary only where opts->dict is set and dict_size > 0. The defaults are the caller's (the library's, or a context's sticky
+ * values). Nothing is validated here: every entry point keeps its own checks in its own order. */
+_Static_assert(ZXC_BLOCK_SIZE_MIN == (1u << 12) && ZXC_BLOCK_SIZE_MAX == (1u << 21), "zc_block_size_ok() is the public block-size rule");
+typedef struct {
+    int level, raw_level; /* raw_level: as given, not clamped (zxc_init_static_cctx refuses what is out of range) */
+    size_t block_size;
+    int checksum, seekable;
+    const uint8_t *dict, *dict_huf;
+    size_t dict_size;
+} copts_t;
+static copts_t read_copts(const zxc_compress_opts_t* opts, int def_level, size_t def_block_size, int def_checksum) {
+    copts_t o;
+    o.raw_level = (opts && opts->level > 0) ? opts->level : def_level;
+    o.level = o.raw_level > ZXC_LEVEL_ULTRA ? ZXC_LEVEL_ULTRA : o.raw_level;
+    o.block_size = (opts && opts->block_size > 0) ? opts->block_size : def_block_size;
+    o.checksum = opts ? opts->checksum_enabled : def_checksum;
+    o.seekable = opts ? opts->seekable : 0;
+    const int has_dict = opts && opts->dict && opts->dict_size > 0;
+    o.dict = has_dict ? (const uint8_t*)opts->dict : NULL;
+    o.dict_huf = has_dict ? (const uint8_t*)opts->dict_huf : NULL;
+    o.dict_size = has_dict ? opts->dict_size : 0;
+    return o;
+}
+
+/* The serial encode (the calls with a dictionary, and every batch of zxc_stream_compress): upload, encode into per-block slots,
+ * sizes back, prefix sum on the host, offsets up, compaction (zxc_gather_blocks_kernel), bytes back — plain copies and the default
+ * stream, device buffers of the call's own. One set of buffers serves every run of up to max_src bytes. */
+typedef struct {
+    size_t block_size, dict_size;
+    uint32_t max_blocks;
+    void *d_src, *d_slots, *d_sizes, *d_offs, *d_out, *d_dict, *d_work;
+    uint64_t* offs; /* host: the blocks' offsets in the compacted output */
+} senc_t;
+static void senc_free(senc_t* s) {
+    zxc_mi355x_free(s->d_src); zxc_mi355x_free(s->d_slots); zxc_mi355x_free(s->d_sizes); zxc_mi355x_free(s->d_offs);
+    zxc_mi355x_free(s->d_out); zxc_mi355x_free(s->d_dict); zxc_mi355x_free(s->d_work);
+    free(s->offs);
+    memset(s, 0, sizeof *s);
+}
+/* (max_src > 0) uploads the dictionary, once. On failure nothing is left allocated. */
+static int senc_alloc(senc_t* s, size_t max_src, size_t block_size, const uint8_t* dict, size_t dict_size) {
+    memset(s, 0, sizeof *s);
+    s->block_size = block_size;
+    s->dict_size = dict_size;
+    s->max_blocks = (uint32_t)((max_src + block_size - 1) / block_size);
+    const size_t nb = s->max_blocks;
+    s->d_src = zxc_mi355x_malloc(max_src + 64);
+    s->d_slots = zxc_mi355x_malloc(nb * zxc_mi355x_encode_slot_stride((uint32_t)block_size));
+    s->d_sizes = zxc_mi355x_malloc(nb * 4);
+    int ok = s->d_src && s->d_slots && s->d_sizes;
+    if (nb > 1) { /* (one block is read from its slot: no compaction) */
+        s->offs = (uint64_t*)malloc(nb * 8);
+        s->d_offs = zxc_mi355x_malloc(nb * 8);
+        s->d_out = zxc_mi355x_malloc(nb * (block_size + 64) + 64);
+        ok = ok && s->offs && s->d_offs && s->d_out;
+    }
+    if (dict_size) {
+        s->d_dict = zxc_mi355x_malloc(dict_size + 64);
+        s->d_work = zxc_mi355x_malloc((size_t)zxc_mi355x_encode_dict_work_size(max_src, (uint32_t)block_size, (uint32_t)dict_size));
+        ok = ok && s->d_dict && s->d_work;
+    }
+    const int rc = !ok ? ZXC_ERROR_MEMORY : dict_size ? zxc_mi355x_memcpy_h2d(s->d_dict, dict, dict_size) : ZXC_OK;
+    if (rc != ZXC_OK) senc_free(s);
+    return rc;
+}
+/* src[0..n) (0 < n <= max_src) -> its blocks back to back in dst[0..*total), sizes[] filled, the trailers folded into *hash_io.
+ * ZXC_ERROR_DST_TOO_SMALL when they need more than `room`. */
+static int senc_run(senc_t* s, const uint8_t* src, size_t n, int level, int checksum, uint8_t* dst, size_t room, uint32_t* sizes,
+                    size_t* total, uint32_t* hash_io) {
+    const uint32_t bs = (uint32_t)s->block_size, nb = (uint32_t)((n + bs - 1) / bs);
+    int rc = zxc_mi355x_memcpy_h2d(s->d_src, src, n);
+    if (rc == ZXC_OK)
+        rc = s->dict_size ? zxc_mi355x_encode_blocks_dict_device(s->d_src, n, bs, level, checksum, s->d_dict, (uint32_t)s->dict_size, s->d_work,
+                                                                 s->d_slots, (uint32_t*)s->d_sizes, NULL)
+                          : zxc_mi355x_encode_blocks_device(s->d_src, n, bs, level, checksum, s->d_slots, (uint32_t*)s->d_sizes, NULL);
+    if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
+    if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(sizes, s->d_sizes, (size_t)nb * 4);
+    if (rc != ZXC_OK) return rc;
+    uint64_t tot = 0;
+    for (uint32_t i = 0; i < nb; i++) { /* (a size the device wrote is never trusted as a copy length, nor as the place of a trailer: comp_sink) */
+        if (sizes[i] > bs + 64u || sizes[i] < 8u + (checksum ? 4u : 0u)) return ZXC_ERROR_CORRUPT_DATA;
+        if (nb > 1) s->offs[i] = tot;
+        tot += sizes[i];
+    }
+    if (tot > (uint64_t)room) return ZXC_ERROR_DST_TOO_SMALL;
+    if (nb == 1) rc = zxc_mi355x_memcpy_d2h(dst, s->d_slots, (size_t)tot);
+    else {
+        rc = zxc_mi355x_memcpy_h2d(s->d_offs, s->offs, (size_t)nb * 8);
+        if (rc == ZXC_OK) rc = zxc_mi355x_gather_blocks_device(s->d_slots, bs, (const uint32_t*)s->d_sizes, (const uint64_t*)s->d_offs, s->d_out, nb, NULL);
+        if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
+        if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(dst, s->d_out, (size_t)tot);
+    }
+    if (rc != ZXC_OK) return rc;
+    if (checksum) { /* fold the block trailers in stream order (zxc_dispatch.c:754-759) */
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < nb; i++) { at += sizes[i]; *hash_io = zc_hash_fold(*hash_io, zc_rd32(dst + at - 4)); }
+    }
+    *total = (size_t)tot;
+    return ZXC_OK;
+}
+
+/* What follows an archive's blocks: the EOF block, the seek table when asked for (none for an empty archive), the footer
+ * (src/lib/zxc_dispatch.c:784-815) */
+static size_t tail_size(uint32_t nb, int seekable) { return ZC_BLK_HDR + (seekable && nb ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE; }
+/* -> tail_size(nb, seekable) bytes written at dst, or ZXC_ERROR_DST_TOO_SMALL (or what zxc_write_seek_table refuses) */
+static int64_t put_tail(uint8_t* dst, size_t capacity, const uint32_t* sizes, uint32_t nb, int seekable, uint64_t src_total, uint32_t hash) {
+    const size_t need = tail_size(nb, seekable);
+    if (capacity < need) return ZXC_ERROR_DST_TOO_SMALL;
+    zc_st_le(dst, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
+    if (seekable && nb) {
+        const int64_t st = zxc_write_seek_table(dst + ZC_BLK_HDR, capacity - ZC_BLK_HDR, sizes, nb);
+        if (st < 0) return st;
+    }
+    zc_put_footer(dst + need - ZXC_FILE_FOOTER_SIZE, src_total, hash);
+    return (int64_t)need;
+}
+
 int64_t zxc_compress(const void* src, const size_t src_size, void* dst_v, const size_t dst_capacity,
                      const zxc_compress_opts_t* opts) {
     uint8_t* dst = (uint8_t*)dst_v;
     if (!dst || dst_capacity == 0 || (src_size > 0 && !src)) return ZXC_ERROR_NULL_INPUT;
-    const int checksum_enabled = opts ? opts->checksum_enabled : 0;
-    const int seekable = opts ? opts->seekable : 0;
-    int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
-    if (level > ZXC_LEVEL_ULTRA) level = ZXC_LEVEL_ULTRA;
-    const size_t block_size = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    const size_t dict_size = (opts && opts->dict) ? opts->dict_size : 0;
-    if (dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
+    const copts_t o = read_copts(opts, ZXC_LEVEL_DEFAULT, ZXC_BLOCK_SIZE_DEFAULT, 0);
+    const size_t block_size = o.block_size;
+    if (o.dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
     if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    const uint8_t* dict = dict_size ? (const uint8_t*)opts->dict : NULL;
-    const uint8_t* dict_huf = dict_size ? (const uint8_t*)opts->dict_huf : NULL;
     if (dst_capacity < ZXC_FILE_HEADER_SIZE) return ZXC_ERROR_DST_TOO_SMALL;
 
     /* file header (src/lib/zxc_common.c:534-558): with a dictionary, the id that binds its content (and shared table) */
-    zc_put_file_header(dst, zc_block_size_lg(block_size), checksum_enabled, dict_size != 0, dict_id_of(dict, dict_size, dict_huf));
+    zc_put_file_header(dst, zc_block_size_lg(block_size), o.checksum, o.dict_size != 0, dict_id_of(o.dict, o.dict_size, o.dict_huf));
     size_t op = ZXC_FILE_HEADER_SIZE;
 
     const uint64_t nb64 = ((uint64_t)src_size + block_size - 1) / block_size;
     if (nb64 > 0x7FFFFFFFull) return ZXC_ERROR_BAD_BLOCK_SIZE;
     const uint32_t nb = (uint32_t)nb64;
+    const size_t tail_need = tail_size(nb, o.seekable);
     uint32_t* sizes = NULL;
     uint32_t global_hash = 0;
-    size_t batch_bytes = COMP_PIECE_BYTES;
-    { const char* e = getenv("ZXC_MI355X_FRAME_BATCH_MIB"); if (e && atoi(e) >= 1 && atoi(e) <= 1024) batch_bytes = (size_t)atoi(e) << 20; }
-    const uint32_t batch_blocks = (uint32_t)(batch_bytes / block_size > 16 ? batch_bytes / block_size : 16);
-    if (nb > 0 && !dict_size) { /* through the piece pipeline: pipelined when there is more than one piece, else in series on this thread —
-                                 * in the staging arenas either way (round 4: five hipMalloc + hipFree = ~3 ms per call up to 64 MiB) */
+    if (nb > 0) {
         if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
         sizes = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t));
         if (!sizes) return ZXC_ERROR_MEMORY;
-        const size_t tail_need = ZC_BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
-        const int rc = compress_pieces((const uint8_t*)src, src_size, block_size, level, checksum_enabled, tail_need, dst, dst_capacity,
-                                       &op, sizes, nb, (size_t)batch_blocks * block_size, &global_hash);
-        if (rc != ZXC_OK) { free(sizes); return rc; }
-    } else if (nb > 0) { /* with a dictionary: one shot */
-        if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
-        const uint32_t stride = zxc_mi355x_encode_slot_stride((uint32_t)block_size);
-        sizes = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t));
-        uint64_t* offs = (uint64_t*)malloc((size_t)nb * sizeof(uint64_t));
-        void* d_src = zxc_mi355x_malloc(src_size + 64);
-        void* d_slots = zxc_mi355x_malloc((size_t)nb * stride);
-        void* d_sizes = zxc_mi355x_malloc((size_t)nb * 4);
-        void* d_offs = zxc_mi355x_malloc((size_t)nb * 8);
-        void* d_out = NULL;
-        void* d_dict = dict_size ? zxc_mi355x_malloc(dict_size + 64) : NULL;
-        void* d_work = dict_size ? zxc_mi355x_malloc((size_t)zxc_mi355x_encode_dict_work_size(src_size, (uint32_t)block_size, (uint32_t)dict_size)) : NULL;
-        int64_t rc = ZXC_ERROR_MEMORY;
-        if (sizes && offs && d_src && d_slots && d_sizes && d_offs && (!dict_size || (d_dict && d_work))) {
-            rc = zxc_mi355x_memcpy_h2d(d_src, src, src_size);
-            if (rc == ZXC_OK && dict_size) rc = zxc_mi355x_memcpy_h2d(d_dict, dict, dict_size);
-            if (rc == ZXC_OK)
-                rc = dict_size ? zxc_mi355x_encode_blocks_dict_device(d_src, src_size, (uint32_t)block_size, level, checksum_enabled,
-                                                                      d_dict, (uint32_t)dict_size, d_work, d_slots, (uint32_t*)d_sizes, NULL)
-                               : zxc_mi355x_encode_blocks_device(d_src, src_size, (uint32_t)block_size, level, checksum_enabled,
-                                                                 d_slots, (uint32_t*)d_sizes, NULL);
-            if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
-            if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(sizes, d_sizes, (size_t)nb * 4);
-            uint64_t total = 0;
+        int rc;
+        if (!o.dict_size) { /* through the piece pipeline: pipelined when there is more than one piece, else in series on this thread —
+                             * in the staging arenas either way (round 4: five hipMalloc + hipFree = ~3 ms per call up to 64 MiB) */
+            rc = compress_pieces(NULL, 0, (const uint8_t*)src, src_size, nb, block_size, o.level, o.checksum, tail_need, dst, dst_capacity, &op, sizes,
+                                 &global_hash);
+        } else { /* with a dictionary: one shot */
+            senc_t s;
+            size_t total = 0;
+            rc = senc_alloc(&s, src_size, block_size, o.dict, o.dict_size);
             if (rc == ZXC_OK) {
-                for (uint32_t i = 0; i < nb; i++) { offs[i] = total; total += sizes[i]; }
-                const uint64_t need = op + total + ZC_BLK_HDR + (seekable ? zxc_seek_table_size(nb) : 0) + ZXC_FILE_FOOTER_SIZE;
-                if (need > dst_capacity) rc = ZXC_ERROR_DST_TOO_SMALL;
+                const size_t left = dst_capacity - op;
+                rc = senc_run(&s, (const uint8_t*)src, src_size, o.level, o.checksum, dst + op, left > tail_need ? left - tail_need : 0, sizes, &total,
+                              &global_hash);
+                senc_free(&s);
             }
-            if (rc == ZXC_OK) {
-                d_out = zxc_mi355x_malloc((size_t)total + 64);
-                if (!d_out) rc = ZXC_ERROR_MEMORY;
-            }
-            if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_h2d(d_offs, offs, (size_t)nb * 8);
-            if (rc == ZXC_OK)
-                rc = zxc_mi355x_gather_blocks_device(d_slots, (uint32_t)block_size, (const uint32_t*)d_sizes,
-                                                     (const uint64_t*)d_offs, d_out, nb, NULL);
-            if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
-            if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(dst + op, d_out, (size_t)total);
-            if (rc == ZXC_OK && checksum_enabled) /* fold the block trailers in stream order (zxc_dispatch.c:754-759) */
-                for (uint32_t i = 0; i < nb; i++)
-                    global_hash = zc_hash_fold(global_hash, zc_rd32(dst + op + offs[i] + sizes[i] - 4));
-            if (rc == ZXC_OK) op += (size_t)total;
+            op += total;
         }
-        zxc_mi355x_free(d_src);
-        zxc_mi355x_free(d_slots);
-        zxc_mi355x_free(d_sizes);
-        zxc_mi355x_free(d_offs);
-        zxc_mi355x_free(d_out);
-        zxc_mi355x_free(d_dict);
-        zxc_mi355x_free(d_work);
-        free(offs);
         if (rc != ZXC_OK) { free(sizes); return rc; }
     }
-    /* EOF block, optional seek table, footer (src/lib/zxc_dispatch.c:784-815) */
-    if (dst_capacity - op < ZC_BLK_HDR) { free(sizes); return ZXC_ERROR_DST_TOO_SMALL; }
-    zc_st_le(dst + op, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
-    op += ZC_BLK_HDR;
-    if (seekable && nb > 0) {
-        const int64_t st = zxc_write_seek_table(dst + op, dst_capacity - op, sizes, nb);
-        if (st < 0) { free(sizes); return st; }
-        op += (size_t)st;
-    }
+    const int64_t tail = put_tail(dst + op, dst_capacity - op, sizes, nb, o.seekable, src_size, o.checksum ? global_hash : 0); /* (the hash: zero when checksums are off) */
     free(sizes);
-    if (dst_capacity - op < ZXC_FILE_FOOTER_SIZE) return ZXC_ERROR_DST_TOO_SMALL;
-    zc_put_footer(dst + op, src_size, checksum_enabled ? global_hash : 0); /* zero when checksums are off */
-    op += ZXC_FILE_FOOTER_SIZE;
-    return (int64_t)op;
+    return tail < 0 ? tail : (int64_t)op + tail;
 }
 
 /* ---------------------------------------------------------------- seekable */
@@ -1559,14 +1635,13 @@ uint64_t zxc_estimate_cctx_size(const size_t src_size, const int level) {
 }
 
 zxc_cctx* zxc_create_cctx(const zxc_compress_opts_t* opts) {
-    const size_t bs = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    if (bs < ZXC_BLOCK_SIZE_MIN || bs > ZXC_BLOCK_SIZE_MAX || (bs & (bs - 1))) return NULL;
+    const copts_t o = read_copts(opts, ZXC_LEVEL_DEFAULT, ZXC_BLOCK_SIZE_DEFAULT, 0);
+    if (!zc_block_size_ok(o.block_size)) return NULL;
     zxc_cctx* c = (zxc_cctx*)calloc(1, sizeof(*c));
     if (!c) return NULL;
-    int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
-    c->level = level > ZXC_LEVEL_ULTRA ? ZXC_LEVEL_ULTRA : level;
-    c->block_size = bs;
-    c->checksum = opts ? opts->checksum_enabled : 0;
+    c->level = o.level;
+    c->block_size = o.block_size;
+    c->checksum = o.checksum;
     return c;
 }
 void zxc_free_cctx(zxc_cctx* cctx) { if (cctx && !cctx->in_workspace) free(cctx); }
@@ -1589,17 +1664,16 @@ size_t zxc_static_cctx_workspace_size(const size_t block_size, const int level) 
 
 zxc_cctx* zxc_init_static_cctx(void* workspace, const size_t workspace_size, const zxc_compress_opts_t* opts) {
     if (!workspace || !opts || ((uintptr_t)workspace & (_Alignof(zxc_cctx) - 1))) return NULL;
-    const int level = opts->level > 0 ? opts->level : ZXC_LEVEL_DEFAULT;
-    const size_t bs = opts->block_size > 0 ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    const size_t need = zxc_static_cctx_workspace_size(bs, level);
+    const copts_t o = read_copts(opts, ZXC_LEVEL_DEFAULT, ZXC_BLOCK_SIZE_DEFAULT, 0);
+    const size_t need = zxc_static_cctx_workspace_size(o.block_size, o.raw_level); /* (the level as given: one above the range has no size) */
     if (need == 0 || workspace_size < need) return NULL;
     zxc_cctx* c = (zxc_cctx*)workspace;
     memset(c, 0, sizeof(*c));
-    c->level = level;
-    c->block_size = bs;
-    c->checksum = opts->checksum_enabled;
+    c->level = o.level;
+    c->block_size = o.block_size;
+    c->checksum = o.checksum;
     c->in_workspace = 1;
-    c->dense = level >= ZXC_LEVEL_DENSITY;
+    c->dense = o.level >= ZXC_LEVEL_DENSITY;
     return c;
 }
 
@@ -1619,15 +1693,14 @@ zxc_dctx* zxc_init_static_dctx(void* workspace, const size_t workspace_size, con
 int64_t zxc_compress_cctx(zxc_cctx* cctx, const void* src, const size_t src_size, void* dst, const size_t dst_capacity,
                           const zxc_compress_opts_t* opts) {
     if (!cctx) return ZXC_ERROR_NULL_INPUT;
+    const copts_t r = read_copts(opts, cctx->level, cctx->block_size, cctx->checksum); /* (what the call leaves open: the context's) */
     zxc_compress_opts_t o;
     memset(&o, 0, sizeof o);
     if (opts) o = *opts;
-    if (o.level <= 0) o.level = cctx->level;
-    if (o.block_size == 0) o.block_size = cctx->block_size;
-    if (!opts) o.checksum_enabled = cctx->checksum;
-    if (o.level > ZXC_LEVEL_ULTRA) o.level = ZXC_LEVEL_ULTRA;
-    if (o.block_size < ZXC_BLOCK_SIZE_MIN || o.block_size > ZXC_BLOCK_SIZE_MAX || (o.block_size & (o.block_size - 1)))
-        return ZXC_ERROR_BAD_BLOCK_SIZE;
+    o.level = r.level;
+    o.block_size = r.block_size;
+    o.checksum_enabled = r.checksum;
+    if (!zc_block_size_ok(o.block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
     /* a static context: the block size is locked, the dense tier only if carved for it (src/lib/zxc_dispatch.c:1348-1355) */
     if (cctx->in_workspace && o.block_size != cctx->block_size) return ZXC_ERROR_BAD_BLOCK_SIZE;
     if (cctx->in_workspace && o.level >= ZXC_LEVEL_DENSITY && !cctx->dense) return ZXC_ERROR_BAD_LEVEL;
@@ -1654,18 +1727,14 @@ int64_t zxc_compress_block(zxc_cctx* cctx, const void* src, const size_t src_siz
                            const zxc_compress_opts_t* opts) {
     if (!cctx || !src || !dst || src_size == 0 || dst_capacity == 0) return ZXC_ERROR_NULL_INPUT;
     if (src_size > ZXC_BLOCK_SIZE_MAX) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    const int checksum_enabled = opts ? opts->checksum_enabled : cctx->checksum;
-    int level = (opts && opts->level > 0) ? opts->level : cctx->level;
-    if (level > ZXC_LEVEL_ULTRA) level = ZXC_LEVEL_ULTRA;
-    const uint8_t* b_dict = (opts && opts->dict && opts->dict_size > 0) ? (const uint8_t*)opts->dict : NULL;
-    const size_t b_dict_size = b_dict ? opts->dict_size : 0;
-    if (b_dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
-    const size_t want_bs = (opts && opts->block_size > 0) ? opts->block_size : cctx->block_size;
+    const copts_t o = read_copts(opts, cctx->level, cctx->block_size, cctx->checksum);
+    const int checksum_enabled = o.checksum, level = o.level;
+    if (o.dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
     const size_t min_bs = block_size_ceil(src_size);
-    const size_t bs = want_bs > min_bs ? want_bs : min_bs; /* one block: block_size >= src_size */
+    const size_t bs = o.block_size > min_bs ? o.block_size : min_bs; /* one block: block_size >= src_size */
     if (bs > ZXC_BLOCK_SIZE_MAX || (bs & (bs - 1))) return ZXC_ERROR_BAD_BLOCK_SIZE;
     if (cctx->in_workspace) { /* src/lib/zxc_dispatch.c:1653-1661 */
-        const size_t eff = b_dict_size ? block_size_ceil(b_dict_size + bs) : bs;
+        const size_t eff = o.dict_size ? block_size_ceil(o.dict_size + bs) : bs;
         if (eff != cctx->block_size) return ZXC_ERROR_BAD_BLOCK_SIZE;
         if (level >= ZXC_LEVEL_DENSITY && !cctx->dense) return ZXC_ERROR_BAD_LEVEL;
     }
@@ -1676,39 +1745,20 @@ int64_t zxc_compress_block(zxc_cctx* cctx, const void* src, const size_t src_siz
     if (!cctx->in_workspace) cctx->block_size = bs;
     cctx->checksum = checksum_enabled;
     if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
-    if (!b_dict_size) { /* one piece of one block in the staging arena (no allocation on the device per call) */
-        size_t op = 0;
-        uint32_t one_size = 0, unused_hash = 0;
-        const int prc = compress_pieces((const uint8_t*)src, src_size, bs, level, checksum_enabled, 0, (uint8_t*)dst, dst_capacity, &op, &one_size, 1u,
-                                        COMP_PIECE_BYTES, &unused_hash);
-        return prc == ZXC_OK ? (int64_t)op : prc;
+    size_t csize = 0;
+    uint32_t one_size = 0, unused_hash = 0;
+    int rc;
+    if (!o.dict_size) { /* one piece of one block in the staging arena (no allocation on the device per call) */
+        rc = compress_pieces(NULL, 0, (const uint8_t*)src, src_size, 1u, bs, level, checksum_enabled, 0, (uint8_t*)dst, dst_capacity, &csize, &one_size,
+                             &unused_hash);
+    } else {
+        senc_t s;
+        rc = senc_alloc(&s, src_size, bs, o.dict, o.dict_size);
+        if (rc == ZXC_OK) {
+            rc = senc_run(&s, (const uint8_t*)src, src_size, level, checksum_enabled, (uint8_t*)dst, dst_capacity, &one_size, &csize, &unused_hash);
+            senc_free(&s);
+        }
     }
-    const uint32_t stride = zxc_mi355x_encode_slot_stride((uint32_t)bs);
-    void* d_src = zxc_mi355x_malloc(src_size + 64);
-    void* d_slot = zxc_mi355x_malloc(stride);
-    void* d_size = zxc_mi355x_malloc(4);
-    void* d_dict = b_dict_size ? zxc_mi355x_malloc(b_dict_size + 64) : NULL;
-    void* d_work = b_dict_size ? zxc_mi355x_malloc((size_t)zxc_mi355x_encode_dict_work_size(src_size, (uint32_t)bs, (uint32_t)b_dict_size)) : NULL;
-    int64_t rc = ZXC_ERROR_MEMORY;
-    uint32_t csize = 0;
-    if (d_src && d_slot && d_size && (!b_dict_size || (d_dict && d_work))) {
-        rc = zxc_mi355x_memcpy_h2d(d_src, src, src_size);
-        if (rc == ZXC_OK && b_dict_size) rc = zxc_mi355x_memcpy_h2d(d_dict, b_dict, b_dict_size);
-        if (rc == ZXC_OK)
-            rc = b_dict_size ? zxc_mi355x_encode_blocks_dict_device(d_src, src_size, (uint32_t)bs, level, checksum_enabled, d_dict,
-                                                                    (uint32_t)b_dict_size, d_work, d_slot, (uint32_t*)d_size, NULL)
-                             : zxc_mi355x_encode_blocks_device(d_src, src_size, (uint32_t)bs, level, checksum_enabled, d_slot,
-                                                               (uint32_t*)d_size, NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(&csize, d_size, 4);
-        if (rc == ZXC_OK && csize > dst_capacity) rc = ZXC_ERROR_DST_TOO_SMALL;
-        if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(dst, d_slot, csize);
-    }
-    zxc_mi355x_free(d_src);
-    zxc_mi355x_free(d_slot);
-    zxc_mi355x_free(d_size);
-    zxc_mi355x_free(d_dict);
-    zxc_mi355x_free(d_work);
     return rc == ZXC_OK ? (int64_t)csize : rc;
 }
 

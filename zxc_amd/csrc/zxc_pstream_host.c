@@ -68,13 +68,13 @@ static int cs_fail(zxc_cstream* cs, int code) {
 zxc_cstream* zxc_cstream_create(const zxc_compress_opts_t* opts) {
     /* dictionaries are refused, not dropped: the push format has no dict_id (src/lib/zxc_pstream.c:275-280) */
     if (opts && (opts->dict || opts->dict_size || opts->dict_huf)) return NULL;
-    const size_t bs = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
+    const copts_t o = read_copts(opts, ZXC_LEVEL_DEFAULT, ZXC_BLOCK_SIZE_DEFAULT, 0);
+    const size_t bs = o.block_size;
     if (!zc_block_size_ok(bs)) return NULL;
     zxc_cstream* cs = (zxc_cstream*)calloc(1, sizeof(*cs));
     if (!cs) return NULL;
-    int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
-    cs->level = level > ZXC_LEVEL_ULTRA ? ZXC_LEVEL_ULTRA : level;
-    cs->checksum = opts ? (opts->checksum_enabled != 0) : 0;
+    cs->level = o.level;
+    cs->checksum = o.checksum != 0;
     cs->block_size = bs;
     cs->max_blocks = ps_window_blocks(bs);
     cs->in_block = (uint8_t*)malloc(bs);
@@ -98,34 +98,8 @@ size_t zxc_cstream_out_size(const zxc_cstream* cs) {
 }
 
 /* The blocks of [a[0..alen) | b[0..blen)] (a: the accumulator — one block, or the stream's last partial one; b: whole blocks in the
- * caller's input) through the encode pipeline of zxc_compress (comp_enqueue / comp_sink above): the accumulator's block is a piece
- * of its own, the blocks of b follow in pieces. Their frames land back to back in out (when it has room for their bound) or in
- * pending. */
-typedef struct {
-    const uint8_t *a, *b;
-    size_t alen, blen, block_size;
-    uint32_t next, nb;
-} cs_src_t;
-static int cs_source(void* ctx, uint32_t max_blocks, pipe_piece_t* p) {
-    cs_src_t* c = (cs_src_t*)ctx;
-    const uint32_t f = c->next;
-    if (f >= c->nb) return 0;
-    if (c->alen && f == 0) {
-        p->h_comp = c->a;
-        p->comp_bytes = c->alen;
-        p->n = 1;
-    } else {
-        const uint32_t fb = f - (c->alen ? 1u : 0u), n = c->nb - f < max_blocks ? c->nb - f : max_blocks;
-        const size_t o = (size_t)fb * c->block_size;
-        p->h_comp = c->b + o;
-        p->comp_bytes = c->blen - o < (size_t)n * c->block_size ? c->blen - o : (size_t)n * c->block_size;
-        p->n = n;
-    }
-    p->out_bytes = (size_t)p->n * (c->block_size + 64);
-    p->cookie[0] = f;
-    c->next = f + p->n;
-    return 1;
-}
+ * caller's input) through the encode pipeline of zxc_compress (compress_pieces above): the accumulator's block is a piece of its
+ * own, the blocks of b follow in pieces. Their frames land back to back in out (when it has room for their bound) or in pending. */
 static int cs_encode(zxc_cstream* cs, const uint8_t* a, size_t alen, const uint8_t* b, size_t blen, zxc_outbuf_t* out) {
     const size_t bs = cs->block_size;
     const uint32_t nb = (alen ? 1u : 0u) + (uint32_t)((blen + bs - 1) / bs);
@@ -138,33 +112,18 @@ static int cs_encode(zxc_cstream* cs, const uint8_t* a, size_t alen, const uint8
         if (ps_host_reserve(&cs->pending, &cs->pending_cap, bound, 0) != ZXC_OK) return ZXC_ERROR_MEMORY;
         land = cs->pending;
     }
-    size_t piece_bytes = COMP_PIECE_BYTES;
-    { const char* e = getenv("ZXC_MI355X_FRAME_BATCH_MIB"); if (e && atoi(e) >= 1 && atoi(e) <= 1024) piece_bytes = (size_t)atoi(e) << 20; }
-    const uint32_t piece_blocks = (uint32_t)(piece_bytes / bs > 16 ? piece_bytes / bs : 16);
-    cs_src_t src = {a, b, alen, blen, bs, 0, nb};
-    comp_enq_t ce = {cs->level, cs->checksum};
-    comp_sink_t ck;
-    memset(&ck, 0, sizeof ck);
-    ck.dst = land;
-    ck.dst_capacity = bound;
-    ck.block_size = bs;
-    ck.global_hash = cs->global_hash;
-    ck.checksum = cs->checksum;
-    ck.sizes = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t));
-    ck.offs = (uint64_t*)malloc((size_t)piece_blocks * sizeof(uint64_t));
-    int rc = (ck.sizes && ck.offs) ? 0 : ZXC_ERROR_MEMORY;
-    if (rc == 0)
-        rc = pipe_run_ex(cs_source, &src, comp_sink, &ck, comp_enqueue, &ce, (uint32_t)bs, 0, NULL, alen + blen, (uint64_t)nb * bs,
-                         (size_t)piece_blocks * bs, (size_t)16 << 20, 0, PIPE_SLOTS);
-    free(ck.sizes);
-    free(ck.offs);
-    if (rc != 0) return rc < 0 ? rc : ZXC_ERROR_CORRUPT_DATA;
-    cs->global_hash = ck.global_hash; /* (the block trailers, folded in stream order: src/lib/zxc_pstream.c:198-203) */
+    uint32_t* sizes = (uint32_t*)malloc((size_t)nb * sizeof(uint32_t)); /* (the sink's record; a push stream writes no seek table) */
+    if (!sizes) return ZXC_ERROR_MEMORY;
+    size_t op = 0;
+    /* (the block trailers go into the stream's hash, folded in stream order: src/lib/zxc_pstream.c:198-203) */
+    const int rc = compress_pieces(a, alen, b, blen, nb, bs, cs->level, cs->checksum, 0, land, bound, &op, sizes, &cs->global_hash);
+    free(sizes);
+    if (rc != ZXC_OK) return rc;
     if (land == cs->pending) {
-        cs->pending_len = ck.op;
+        cs->pending_len = op;
         cs->pending_pos = 0;
     } else {
-        out->pos += ck.op;
+        out->pos += op;
         cs->pending_len = cs->pending_pos = 0;
     }
     cs->total_in += alen + blen;

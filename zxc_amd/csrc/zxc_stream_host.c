@@ -305,46 +305,32 @@ int64_t zxc_stream_decompress(FILE* f_in, FILE* f_out, const zxc_decompress_opts
 
 int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* opts) {
     if (!f_in) return ZXC_ERROR_NULL_INPUT; /* (f_out NULL: the reference's dry-run mode — everything but the writes, src/lib/zxc_driver.c:1038) */
-    const int checksum_enabled = opts ? opts->checksum_enabled : 0;
-    const int seekable = opts ? opts->seekable : 0;
-    int level = (opts && opts->level > 0) ? opts->level : ZXC_LEVEL_DEFAULT;
-    if (level > ZXC_LEVEL_ULTRA) level = ZXC_LEVEL_ULTRA;
-    const size_t block_size = (opts && opts->block_size > 0) ? opts->block_size : ZXC_BLOCK_SIZE_DEFAULT;
-    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE;
-    const size_t dict_size = (opts && opts->dict) ? opts->dict_size : 0;
-    if (dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
-    const uint8_t* dict = dict_size ? (const uint8_t*)opts->dict : NULL;
-    const uint8_t* dict_huf = dict_size ? (const uint8_t*)opts->dict_huf : NULL;
+    const copts_t o = read_copts(opts, ZXC_LEVEL_DEFAULT, ZXC_BLOCK_SIZE_DEFAULT, 0);
+    const size_t block_size = o.block_size;
+    const int seekable = o.seekable;
+    if (!zc_block_size_ok(block_size)) return ZXC_ERROR_BAD_BLOCK_SIZE; /* (in front of the dictionary here, like the reference) */
+    if (o.dict_size > ZXC_DICT_SIZE_MAX) return ZXC_ERROR_DICT_TOO_LARGE;
     if (zxc_mi355x_device_count() <= 0) return ZXC_ERROR_GPU_UNAVAILABLE;
 
     uint8_t fh[ZXC_FILE_HEADER_SIZE];
-    zc_put_file_header(fh, zc_block_size_lg(block_size), checksum_enabled, dict_size != 0, dict_id_of(dict, dict_size, dict_huf)); /* like zxc_compress */
+    zc_put_file_header(fh, zc_block_size_lg(block_size), o.checksum, o.dict_size != 0, dict_id_of(o.dict, o.dict_size, o.dict_huf)); /* like zxc_compress */
     if (f_out && fwrite(fh, 1, sizeof fh, f_out) != sizeof fh) return ZXC_ERROR_IO;
     int64_t out_total = ZXC_FILE_HEADER_SIZE;
 
     size_t batch = STREAM_BATCH_BYTES / 4; /* source bytes per launch */
     if (batch < block_size) batch = block_size;
     batch -= batch % block_size;
-    const uint32_t bpb = (uint32_t)(batch / block_size);
-    const uint32_t stride = zxc_mi355x_encode_slot_stride((uint32_t)block_size);
+    const size_t bpb = batch / block_size, out_cap = bpb * (block_size + 64) + 64;
     uint8_t* h_in = (uint8_t*)malloc(batch);
-    uint8_t* h_out = (uint8_t*)malloc((size_t)bpb * (block_size + 64) + 64);
-    uint32_t* h_sizes = (uint32_t*)malloc((size_t)bpb * 4);
-    uint64_t* h_offs = (uint64_t*)malloc((size_t)bpb * 8);
-    void* d_src = zxc_mi355x_malloc(batch + 64);
-    void* d_slots = zxc_mi355x_malloc((size_t)bpb * stride);
-    void* d_sizes = zxc_mi355x_malloc((size_t)bpb * 4);
-    void* d_offs = zxc_mi355x_malloc((size_t)bpb * 8);
-    void* d_out = zxc_mi355x_malloc((size_t)bpb * (block_size + 64) + 64);
-    void* d_dict = dict_size ? zxc_mi355x_malloc(dict_size + 64) : NULL;
-    void* d_work = dict_size ? zxc_mi355x_malloc((size_t)zxc_mi355x_encode_dict_work_size(batch, (uint32_t)block_size, (uint32_t)dict_size)) : NULL;
+    uint8_t* h_out = (uint8_t*)malloc(out_cap);
+    uint32_t* h_sizes = (uint32_t*)malloc(bpb * 4);
     uint32_t* all_sizes = NULL; /* seek table entries */
     size_t all_n = 0, all_cap = 0;
     uint64_t src_total = 0;
     uint32_t global_hash = 0;
-    int64_t ret = (h_in && h_out && h_sizes && h_offs && d_src && d_slots && d_sizes && d_offs && d_out && (!dict_size || (d_dict && d_work)))
-                      ? 0 : ZXC_ERROR_MEMORY;
-    if (ret == 0 && dict_size) ret = zxc_mi355x_memcpy_h2d(d_dict, dict, dict_size);
+    senc_t enc; /* (its buffers and the uploaded dictionary serve every batch) */
+    int64_t ret = senc_alloc(&enc, batch, block_size, o.dict, o.dict_size);
+    if (ret == 0 && !(h_in && h_out && h_sizes)) ret = ZXC_ERROR_MEMORY;
     while (ret == 0) {
         const size_t got = fread(h_in, 1, batch, f_in);
         if (got == 0) {
@@ -352,28 +338,9 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
             break;
         }
         const uint32_t nb = (uint32_t)((got + block_size - 1) / block_size);
-        int rc = zxc_mi355x_memcpy_h2d(d_src, h_in, got);
-        if (rc == ZXC_OK)
-            rc = dict_size ? zxc_mi355x_encode_blocks_dict_device(d_src, got, (uint32_t)block_size, level, checksum_enabled, d_dict,
-                                                                  (uint32_t)dict_size, d_work, d_slots, (uint32_t*)d_sizes, NULL)
-                           : zxc_mi355x_encode_blocks_device(d_src, got, (uint32_t)block_size, level, checksum_enabled, d_slots,
-                                                             (uint32_t*)d_sizes, NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(h_sizes, d_sizes, (size_t)nb * 4);
-        uint64_t tot = 0;
-        if (rc == ZXC_OK) {
-            for (uint32_t i = 0; i < nb; i++) { h_offs[i] = tot; tot += h_sizes[i]; }
-            rc = zxc_mi355x_memcpy_h2d(d_offs, h_offs, (size_t)nb * 8);
-        }
-        if (rc == ZXC_OK)
-            rc = zxc_mi355x_gather_blocks_device(d_slots, (uint32_t)block_size, (const uint32_t*)d_sizes, (const uint64_t*)d_offs,
-                                                 d_out, nb, NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_synchronize(NULL);
-        if (rc == ZXC_OK) rc = zxc_mi355x_memcpy_d2h(h_out, d_out, (size_t)tot);
+        size_t tot = 0;
+        const int rc = senc_run(&enc, h_in, got, o.level, o.checksum, h_out, out_cap, h_sizes, &tot, &global_hash);
         if (rc != ZXC_OK) { ret = rc; break; }
-        if (checksum_enabled)
-            for (uint32_t i = 0; i < nb; i++)
-                global_hash = zc_hash_fold(global_hash, zc_rd32(h_out + h_offs[i] + h_sizes[i] - 4));
         if (seekable) {
             if (all_n + nb > all_cap) {
                 all_cap = all_cap ? all_cap * 2 : 4096;
@@ -394,36 +361,18 @@ int64_t zxc_stream_compress(FILE* f_in, FILE* f_out, const zxc_compress_opts_t* 
             break;
         }
     }
-    if (ret == 0) { /* EOF block, optional seek table, footer */
-        uint8_t eofb[ZC_BLK_HDR];
-        zc_st_le(eofb, zc_blk_hdr(ZC_BLK_EOF, 0), ZC_BLK_HDR);
-        if (f_out && fwrite(eofb, 1, sizeof eofb, f_out) != sizeof eofb) ret = ZXC_ERROR_IO;
-        else out_total += ZC_BLK_HDR;
-        if (ret == 0 && seekable && all_n > 0) {
-            if (all_n > 0x3FFFFFFFu) ret = ZXC_ERROR_OVERFLOW;
-            else {
-                const size_t tsz = zxc_seek_table_size((uint32_t)all_n);
-                uint8_t* tbl = (uint8_t*)malloc(tsz);
-                if (!tbl) ret = ZXC_ERROR_MEMORY;
-                else {
-                    const int64_t w = zxc_write_seek_table(tbl, tsz, all_sizes, (uint32_t)all_n);
-                    if (w < 0) ret = w;
-                    else if (f_out && fwrite(tbl, 1, (size_t)w, f_out) != (size_t)w) ret = ZXC_ERROR_IO;
-                    else out_total += w;
-                    free(tbl);
-                }
-            }
-        }
-        if (ret == 0) {
-            uint8_t foot[ZXC_FILE_FOOTER_SIZE];
-            zc_put_footer(foot, src_total, checksum_enabled ? global_hash : 0);
-            if (f_out && (fwrite(foot, 1, sizeof foot, f_out) != sizeof foot || fflush(f_out) != 0)) ret = ZXC_ERROR_IO;
-            else out_total += ZXC_FILE_FOOTER_SIZE;
-        }
+    if (ret == 0 && all_n > 0x3FFFFFFFu) ret = ZXC_ERROR_OVERFLOW; /* (more entries than a seek table holds) */
+    if (ret == 0) { /* EOF block, optional seek table, footer: one write */
+        const size_t tsz = tail_size((uint32_t)all_n, seekable);
+        uint8_t* tail = (uint8_t*)malloc(tsz);
+        const int64_t w = tail ? put_tail(tail, tsz, all_sizes, (uint32_t)all_n, seekable, src_total, o.checksum ? global_hash : 0) : ZXC_ERROR_MEMORY;
+        if (w < 0) ret = w;
+        else if (f_out && (fwrite(tail, 1, tsz, f_out) != tsz || fflush(f_out) != 0)) ret = ZXC_ERROR_IO;
+        else out_total += w;
+        free(tail);
     }
-    free(h_in); free(h_out); free(h_sizes); free(h_offs); free(all_sizes);
-    zxc_mi355x_free(d_src); zxc_mi355x_free(d_slots); zxc_mi355x_free(d_sizes); zxc_mi355x_free(d_offs); zxc_mi355x_free(d_out);
-    zxc_mi355x_free(d_dict); zxc_mi355x_free(d_work);
+    free(h_in); free(h_out); free(h_sizes); free(all_sizes);
+    senc_free(&enc);
     return ret < 0 ? ret : out_total;
 }
 

@@ -180,18 +180,31 @@ _PROTOTYPES_RANGESV = {
     "zxc_mi355x_decompress_rangesv_device": (_I, _RANGESV + _TAIL),
     "zxc_mi355x_decompress_rangesv_dict_device": (_I, _RANGESV + [_DD] + _TAIL),
 }
+# include/zxc_mi355x_shuffle.h, a table of its own: tests/test_shuffle_device_cpu.py holds it against that header
+_SHUFFLE = [_P, _P, _U64, _U32, _U32, _P]  # d_src, d_dst, n, elem_size, unit, stream
+_PROTOTYPES_SHUFFLE = {
+    "zxc_mi355x_shuffle_device": (_I, _SHUFFLE),
+    "zxc_mi355x_unshuffle_device": (_I, _SHUFFLE),
+    "zxc_mi355x_compress_shuffle_device_work_size": (_U64, [_U64, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_shuffle_device": (_I, [_P, _U64, _U32, _P, _U64, _U64, _CO, _DD] + _TAIL),
+    "zxc_mi355x_decompress_shuffle_device_work_size": (_U64, [_U64, _U64, _U64, _U32]),
+    "zxc_mi355x_decompress_shuffle_device": (_I, [_P, _U64, _P, _U64, _U32, _U64, _U32, _DO, _DD] + _TAIL),
+}
 _STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
 _PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
 
 
 def _prototype(name):
-    return _PROTOTYPES[name] if name in _PROTOTYPES else _PROTOTYPES_RANGESV[name]
+    for table in (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def _bind(L, names=None):
-    """Set restype and argtypes of those of `names` (both tables unless given) that L exports (the reference and the mock-device
+    """Set restype and argtypes of those of `names` (all three tables unless given) that L exports (the reference and the mock-device
     library have no device calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
-    for name in (list(_PROTOTYPES) + list(_PROTOTYPES_RANGESV) if names is None else names):
+    for name in (list(_PROTOTYPES) + list(_PROTOTYPES_RANGESV) + list(_PROTOTYPES_SHUFFLE) if names is None else names):
         f = getattr(L, name, None)
         if f is not None:
             f.restype, f.argtypes = _prototype(name)
@@ -497,6 +510,51 @@ def decompress_rangesv_dict_device(d_src, src_size, d_index, d_ranges, n_ranges,
     compress_dict_device); index and work size are the sibling's."""
     _call("zxc_mi355x_decompress_rangesv_dict_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, block_size,
           _dev_dict(dict_), d_work, work_size, d_results, stream)
+
+
+# ---- the byte-shuffle pre-filter for typed tensors (include/zxc_mi355x_shuffle.h)
+def shuffle_device(d_src, d_dst, n, elem_size, unit, stream=0):
+    """zxc_mi355x_shuffle_device(): d_dst[0, n) = the bytes of d_src[0, n) regrouped into byte planes per unit (elem_size 2, 4 or 8;
+    unit a power of two in [4 KiB, 2 MiB], the block size for the archive calls). Raw device pointers (ints) of any alignment,
+    asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_shuffle_device", d_src, d_dst, n, elem_size, unit, stream)
+
+
+def unshuffle_device(d_src, d_dst, n, elem_size, unit, stream=0):
+    """zxc_mi355x_unshuffle_device(): the inverse of shuffle_device for the same n, elem_size and unit."""
+    _call("zxc_mi355x_unshuffle_device", d_src, d_dst, n, elem_size, unit, stream)
+
+
+def compress_shuffle_device_work_size(src_size, max_piece=0, dict_size=0, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_shuffle_device_work_size(): bytes of device scratch compress_shuffle_device needs (0 for refused
+    arguments): the append session's for a chunk of max_piece bytes (0: the default) plus one chunk."""
+    return int(_call("zxc_mi355x_compress_shuffle_device_work_size", src_size, max_piece, _copts(level, block_size, seekable, checksum),
+                     dict_size))
+
+
+def compress_shuffle_device(d_src, src_size, elem_size, d_dst, dst_capacity, d_work, work_size, d_result, max_piece=0, dict_=None,
+                            level=3, block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_shuffle_device(): the archive compress_device (with dict_, as in compress_dict_device: that call) writes
+    for the byte-shuffled source, shuffled chunk by chunk into a stage of the work area. The archive does not record the filter:
+    the caller keeps elem_size. Raw device pointers (ints), asynchronous on `stream`; the archive size or a negative zxc_error_t
+    lands in the int64 at d_result; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_compress_shuffle_device", d_src, src_size, elem_size, d_dst, dst_capacity, max_piece,
+          _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, d_result, stream)
+
+
+def decompress_shuffle_device_work_size(src_size, dst_size, max_piece, block_size):
+    """zxc_mi355x_decompress_shuffle_device_work_size(): bytes of device scratch decompress_shuffle_device needs (0 for refused
+    arguments): the take session's for a chunk of max_piece bytes (0: the default) plus one chunk."""
+    return int(_call("zxc_mi355x_decompress_shuffle_device_work_size", src_size, dst_size, max_piece, block_size))
+
+
+def decompress_shuffle_device(d_src, src_size, d_dst, dst_size, elem_size, block_size, d_work, work_size, d_result, max_piece=0, dict_=None,
+                              checksum=False, stream=0):
+    """zxc_mi355x_decompress_shuffle_device(): decodes the archive chunk by chunk into a stage of the work area and un-shuffles it
+    into d_dst (any alignment). dst_size is the decoded size exactly; dst_size or a negative zxc_error_t lands in the int64 at
+    d_result. Raw device pointers (ints), asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_decompress_shuffle_device", d_src, src_size, d_dst, dst_size, elem_size, max_piece, block_size, _dopts(checksum),
+          _dev_dict(dict_), d_work, work_size, d_result, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)

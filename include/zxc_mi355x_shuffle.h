@@ -12,7 +12,8 @@
  * shuffled bytes. The caller keeps elem_size (and the block size, which is in the file header) and un-shuffles. A block-aligned
  * range fetched with zxc_mi355x_decompress_ranges_device / _rangesv_device is un-shuffled on its own by
  * zxc_mi355x_unshuffle_device with unit = block_size (the range that reaches the end of the archive included: its last unit is
- * the archive's ragged last block).
+ * the archive's ragged last block). Ranges of the plain bytes at any offset, each into a destination of its own, are
+ * zxc_mi355x_decompress_rangesv_shuffle_device's (zxc_mi355x_rangesv_shuffle.h): one call, no second pass.
  *
  * The transform works per unit, a power of two in [4 KiB, 2 MiB]; the archive calls use unit = the block size, so every block holds
  * its own planes. Unit u covers bytes [u unit, min((u + 1) unit, n)); with m its length, E = elem_size, q = m / E and r = m % E:

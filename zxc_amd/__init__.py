@@ -18,5 +18,6 @@ from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_siz
                   decompress_begin_dict_device, decompress_takev_device_scratch_size, DecompressTakeSession, lib, lib_path, JOB_DTYPE, RANGE_DTYPE, ITEM_DTYPE, IOV_DTYPE,
                   error_name, RANGEV_DTYPE, decompress_rangesv_device_work_size, decompress_rangesv_device,
                   decompress_rangesv_dict_device, shuffle_device, unshuffle_device, compress_shuffle_device_work_size,
-                  compress_shuffle_device, decompress_shuffle_device_work_size, decompress_shuffle_device)
+                  compress_shuffle_device, decompress_shuffle_device_work_size, decompress_shuffle_device,
+                  decompress_rangesv_shuffle_device_work_size, decompress_rangesv_shuffle_device)
 from . import api  # noqa: F401  (stream_* helpers live there)

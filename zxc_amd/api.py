@@ -190,21 +190,27 @@ _PROTOTYPES_SHUFFLE = {
     "zxc_mi355x_decompress_shuffle_device_work_size": (_U64, [_U64, _U64, _U64, _U32]),
     "zxc_mi355x_decompress_shuffle_device": (_I, [_P, _U64, _P, _U64, _U32, _U64, _U32, _DO, _DD] + _TAIL),
 }
+# include/zxc_mi355x_rangesv_shuffle.h, a table of its own: tests/test_decompress_rangesv_shuffle_device_cpu.py holds it against that header
+_PROTOTYPES_RANGESV_SHUFFLE = {
+    "zxc_mi355x_decompress_rangesv_shuffle_device_work_size": (_U64, [_U32, _U64, _U32]),
+    "zxc_mi355x_decompress_rangesv_shuffle_device": (_I, [_P, _U64, _P, _P, _U32, _U64, _U32, _U32, _DD] + _TAIL),
+}
+_TABLES = (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE, _PROTOTYPES_RANGESV_SHUFFLE)
 _STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
 _PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
 
 
 def _prototype(name):
-    for table in (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE):
+    for table in _TABLES:
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def _bind(L, names=None):
-    """Set restype and argtypes of those of `names` (all three tables unless given) that L exports (the reference and the mock-device
+    """Set restype and argtypes of those of `names` (all four tables unless given) that L exports (the reference and the mock-device
     library have no device calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
-    for name in (list(_PROTOTYPES) + list(_PROTOTYPES_RANGESV) + list(_PROTOTYPES_SHUFFLE) if names is None else names):
+    for name in ([n for table in _TABLES for n in table] if names is None else names):
         f = getattr(L, name, None)
         if f is not None:
             f.restype, f.argtypes = _prototype(name)
@@ -555,6 +561,23 @@ def decompress_shuffle_device(d_src, src_size, d_dst, dst_size, elem_size, block
     d_result. Raw device pointers (ints), asynchronous on `stream`; a synchronous failure raises ZxcError."""
     _call("zxc_mi355x_decompress_shuffle_device", d_src, src_size, d_dst, dst_size, elem_size, max_piece, block_size, _dopts(checksum),
           _dev_dict(dict_), d_work, work_size, d_result, stream)
+
+
+# ---- ranges of the plain bytes of a byte-shuffled archive into a pointer table (include/zxc_mi355x_rangesv_shuffle.h)
+def decompress_rangesv_shuffle_device_work_size(n_ranges, max_len, block_size):
+    """zxc_mi355x_decompress_rangesv_shuffle_device_work_size(): bytes of device scratch the call needs (0 for refused arguments):
+    rangesv's layout with a gather record per job."""
+    return int(_call("zxc_mi355x_decompress_rangesv_shuffle_device_work_size", n_ranges, max_len, block_size))
+
+
+def decompress_rangesv_shuffle_device(d_src, src_size, d_index, d_ranges, n_ranges, max_len, elem_size, block_size, d_work, work_size,
+                                      d_results, dict_=None, stream=0):
+    """zxc_mi355x_decompress_rangesv_shuffle_device(): decompress_rangesv_device for an archive of byte-shuffled blocks (elem_size 2,
+    4 or 8; unit = block_size): the ranges of d_ranges (n_ranges x RANGEV_DTYPE in device memory) count bytes of the plain tensor,
+    at any offset, and every destination receives plain bytes. dict_ as in compress_dict_device, or None. Raw device pointers
+    (ints), asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_decompress_rangesv_shuffle_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, elem_size, block_size,
+          _dev_dict(dict_), d_work, work_size, d_results, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)

@@ -1,6 +1,6 @@
 // zxc_kernels.h — every kernel that is launched from another translation unit, declared once. HIP only. Included by
 // zxc_hip_shim.hip, which launches them, AND by the files that define them (zxc_decode_kernel.hip with zxc_pivco_dir.inc,
-// zxc_encode_kernel.hip): the names are extern "C", so a definition whose argument list departs from the declaration here is a
+// zxc_encode_kernel.hip, zxc_rangesv_shuffle_device.hip, which launches its own): the names are extern "C", so a definition whose argument list departs from the declaration here is a
 // conflicting redeclaration and does not compile, where two hand-kept copies would link and launch with a shifted argument
 // block. __launch_bounds__ stay on the definitions; the workgroup sizes the shim launches with are the ones below.
 #ifndef ZXC_KERNELS_H
@@ -11,6 +11,7 @@
 #include "zxc_appendv.h"    // zav_ctl_t, zap_ctl_t
 #include "zxc_container.h"  // zc_ctl_t
 #include "zxc_dev.h"
+#include "zxc_rangesv_shuffle.h"  // zrs_gather_t, zxc_dev_rangev_t
 
 // threads of the three builds of the section decoder (zxc_pivco_dir.inc): launch bounds, loop strides and the shim's launches
 #define PDIR_SMALL_THREADS 128
@@ -116,6 +117,22 @@ extern "C" __global__ void zxc_appendv_reduce_kernel(const zxc_dev_iov_t* iov, u
 extern "C" __global__ void zxc_appendv_scan_kernel(uint64_t* tile_sum, const uint32_t* tile_flags, uint32_t n_tiles, uint64_t total,
                                                    uint64_t* starts, uint32_t n_iov, zav_ctl_t* vctl, zap_ctl_t* ctl);
 extern "C" __global__ void zxc_appendv_starts_kernel(const zxc_dev_iov_t* iov, uint32_t n_iov, const uint64_t* tile_off, uint64_t* starts);
+
+// ---------------------------------------------------------------- zxc_rangesv_shuffle_device.hip
+// zxc_mi355x_decompress_rangesv_shuffle_device: plan, the gather out of a slot's planes per element size, verdict.
+extern "C" __global__ void zxc_rangesv_shuffle_plan_kernel(const void* index, const zxc_dev_rangev_t* ranges, uint32_t J, uint32_t n_jobs,
+                                                           uint64_t src_size, uint64_t max_len, uint32_t block_size, uint64_t out_base,
+                                                           uint64_t stage_rel, zxc_dev_job_t* jobs, zrs_gather_t* gathers, const uint32_t* dict_id);
+#define ZXC_RANGESV_SHUFFLE_GATHER_DECL(name)                                                                                      \
+    extern "C" __global__ void name(const uint8_t* stage, uint32_t slot_stride, const zrs_gather_t* gathers, const int32_t* status, \
+                                    uint32_t n_jobs, uint32_t chunks, uint8_t* out)
+ZXC_RANGESV_SHUFFLE_GATHER_DECL(zxc_rangesv_shuffle_gather2_kernel);
+ZXC_RANGESV_SHUFFLE_GATHER_DECL(zxc_rangesv_shuffle_gather4_kernel);
+ZXC_RANGESV_SHUFFLE_GATHER_DECL(zxc_rangesv_shuffle_gather8_kernel);
+#undef ZXC_RANGESV_SHUFFLE_GATHER_DECL
+extern "C" __global__ void zxc_rangesv_shuffle_verdict_kernel(const void* index, const zxc_dev_rangev_t* ranges, uint32_t n_ranges, uint32_t J,
+                                                              const int32_t* status, uint64_t src_size, uint64_t max_len, uint32_t block_size,
+                                                              int64_t* results, const uint32_t* dict_id);
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
 extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 #endif

@@ -31,47 +31,22 @@ static void run(uint32_t bs, uint64_t total, int checksum) {
 
     enum { MAXR = 96 };
     uint64_t off[MAXR], len[MAXR];
-    uint32_t n = 0;
     const uint64_t fixed[][2] = {{0, total}, {0, 1}, {total - 1, 1}, {0, 0}, {total, 0}, {total + 5, 0}, {total, 1}, {total - 1, 2},
                                  {bs - 3, 6}, {bs, bs}, {bs - 1, bs + 2}, {0, bs}, {0, bs + 31}, {0, bs + 32}, {0, bs + 33}, {16, bs + 48},
                                  {bs + 16, 2ull * bs + 100}, {5, 3ull * bs}, {2ull * bs, bs + 40}, {bs - 16, 2ull * bs + 64}, {0, 3ull * bs + 32}};
-    for (unsigned i = 0; i < sizeof fixed / sizeof fixed[0]; i++) { off[n] = fixed[i][0]; len[n] = fixed[i][1]; n++; }
-    while (n < MAXR - 3) {
-        off[n] = rnd() % total;
-        len[n] = 1u + rnd() % (3ull * bs + 40u);
-        if (len[n] > total - off[n] && (rnd() & 7u)) len[n] = total - off[n];
-        n++;
-    }
-    uint64_t max_len = 1;
-    for (uint32_t r = 0; r < n; r++) if (off[r] + len[r] <= total && len[r] > max_len) max_len = len[r];
-    if (max_len > 3ull * bs + 40u && total > 8ull * bs) max_len = 3ull * bs + 40u; /* (the whole archive is then refused: len > max_len) */
-    const uint32_t r_long = n, r_null = n + 1u, r_wrap = n + 2u;
-    off[n] = 0; len[n] = max_len + 1u; n++;
-    off[n] = 0; len[n] = total < 100u ? total : 100u; n++;
-    off[n] = 0; len[n] = total < 50u ? total : 50u; n++;
+    uint64_t max_len;
+    const uint32_t n = rvr_san_table(fixed, sizeof fixed / sizeof fixed[0], MAXR, total, bs, rnd, off, len, &max_len);
 
     for (uint32_t shift = 0; shift < 3u; shift++) {
         zxc_dev_rangev_t tab[MAXR];
         uint8_t* raw[MAXR];
         uint32_t k[MAXR];
         int64_t results[MAXR];
-        for (uint32_t r = 0; r < n; r++) {
-            k[r] = (uint32_t)((off[r] + ((r & 1u) ? 1u + ((r >> 1) + 5u * shift) % 15u : 0u)) & 15u);
-            /* a refused or empty range gets no buffer at all: its base is never dereferenced */
-            const int valid = len[r] > 0 && len[r] <= max_len && off[r] <= total && len[r] <= total - off[r] && r != r_null && r != r_wrap;
-            raw[r] = valid ? malloc(len[r] + k[r]) : NULL;
-            tab[r].offset = off[r]; tab[r].len = len[r];
-            tab[r].base = valid ? (uint64_t)(uintptr_t)(raw[r] + k[r]) : 0x1000u + k[r];
-            if (r == r_null) tab[r].base = 0;
-            if (r == r_wrap) tab[r].base = ~(uint64_t)0 - (shift ? len[r] / 2u : len[r] - 1u); /* the end at 2^64, and past it */
-        }
+        for (uint32_t r = 0; r < n; r++) k[r] = (uint32_t)((off[r] + ((r & 1u) ? 1u + ((r >> 1) + 5u * shift) % 15u : 0u)) & 15u);
+        rvr_san_pass(off, len, k, n, max_len, total, shift != 0, tab, raw);
         CHECK(rvr_call(a.size, index, tab, n, max_len, bs, 0, 0u, &blk, results) == ZXC_OK);
         for (uint32_t r = 0; r < n; r++) {
-            int64_t want = (int64_t)len[r];
-            if (len[r] == 0) want = 0;
-            else if (len[r] > max_len || r == r_wrap) want = ZXC_ERROR_DST_TOO_SMALL;
-            else if (r == r_null) want = ZXC_ERROR_NULL_INPUT;
-            else if (off[r] > total || len[r] > total - off[r]) want = ZXC_ERROR_SRC_TOO_SMALL;
+            const int64_t want = rvr_san_want(off, len, n, r, max_len, total);
             CHECK(results[r] == want);
             CHECK((raw[r] != NULL) == (want > 0));
             if (raw[r]) CHECK(memcmp(raw[r] + k[r], data + off[r], len[r]) == 0);
@@ -79,7 +54,6 @@ static void run(uint32_t bs, uint64_t total, int checksum) {
             n_checked++;
         }
     }
-    CHECK(r_long < n);
     free(index); free(blk_status); free(blk_at); rp_archive_free(&a); free(data);
 }
 

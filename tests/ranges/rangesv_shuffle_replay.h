@@ -1,20 +1,17 @@
 /* Test-only: zxc_mi355x_decompress_rangesv_shuffle_device replayed on the host, stage by stage as the entry point of
- * zxc_rangesv_shuffle_device.hip enqueues them, over the rule functions the kernels call (zxc_amd/csrc/zxc_rangesv_shuffle.h):
- *   plan     zrs_job for every job (r, j) into the work area's job and gather tables
- *   decode   a stand-in for the decode launch: block b's SHUFFLED bytes (what the archive holds) go to its slot, 32 more bytes are
- *            scribbled behind them (what the decoders may store), a failing block leaves junk in the front half of its slot, an
- *            empty job (comp_size 0) is answered with an error and touches nothing
+ * zxc_rangesv_shuffle_device.hip enqueues them, over the rule functions the kernels call (zxc_amd/csrc/zxc_rangesv_shuffle.h on top
+ * of zxc_ranges.h). The stages are the frame of rangesv_replay.h (rvr_stages: plan, the stand-in decode, verdict) with this front
+ * end: no block decoded in place, so block b's SHUFFLED bytes (what the archive holds) always go to its slot; exact statuses; and
  *   gather   the gather kernels' arithmetic for every (job, chunk, lane): per whole group E 16-byte loads from the planes,
  *            zsh_regs_unshuffle and E 16-byte stores; the single bytes one at a time
- *   verdict  zrs_verdict for every range
- * The work area is the caller's, of exactly zrs_shape's size, and the destinations are the caller's host addresses above or below
+ * The work area is the caller's, of exactly the shape's size, and the destinations are the caller's host addresses above or below
  * it, so that a sanitizer sees every byte written outside either. d_out is the work area's 256-byte aligned base and every address
  * is that base plus a 64-bit offset modulo 2^64, computed in integers as the kernels' pointer arithmetic comes out. Every store
  * into a destination goes through RSR_HIT(address, bytes), which the includer may define to count the writes. */
 #ifndef RANGESV_SHUFFLE_REPLAY_H
 #define RANGESV_SHUFFLE_REPLAY_H
 #include "../../zxc_amd/csrc/zxc_rangesv_shuffle.h"
-#include "rangesv_replay.h" /* rvr_blocks_t, rvr_at, RVR_BAD_PLAN */
+#include "rangesv_replay.h" /* rvr_blocks_t, rvr_at, RVR_BAD_PLAN, rvr_stages */
 
 #ifndef RSR_HIT
 #define RSR_HIT(addr, n) ((void)0)
@@ -26,9 +23,9 @@ static inline void rsr_put(uint64_t out_base, uint64_t off, const void* v, uint3
 }
 
 /* the gather of job i, as the wavefronts of zxc_rangesv_shuffle_gather{2,4,8}_kernel make it with out = d_out */
-static inline void rsr_gather_job(const uint8_t* stage, uint32_t slot_stride, const zrs_gather_t* gathers, const int32_t* status, uint32_t i,
+static inline void rsr_gather_job(const uint8_t* stage, uint32_t slot_stride, const void* gathers, const int32_t* status, uint32_t i,
                                   uint32_t chunks, uint32_t E, uint64_t out_base) {
-    const zrs_gather_t ga = gathers[i];
+    const zrs_gather_t ga = ((const zrs_gather_t*)gathers)[i];
     for (uint32_t c = 0; c < chunks; c++) {
         zrs_item_t item;
         if (ga.n == 0 || !zrs_item(ga.from, ga.n, ga.m, E, c, &item)) continue;
@@ -52,43 +49,21 @@ static inline void rsr_gather_job(const uint8_t* stage, uint32_t slot_stride, co
     }
 }
 
-/* The whole call. work: zrs_shape's bytes, of any alignment. -> ZXC_OK, a synchronous error of the entry point's argument checks
+static inline void rsr_job(const void* index, zxc_dev_rangev_t r, uint32_t j, uint64_t i, uint64_t src_size, uint64_t max_len, uint32_t bs,
+                           uint64_t out_base, uint64_t stage_rel, int have_dict, uint32_t have_id, zxc_dev_job_t* job, void* recs) {
+    zrs_job(index, r, j, i, src_size, max_len, bs, out_base, stage_rel, have_dict, have_id, job, (zrs_gather_t*)recs + i);
+}
+/* The whole call. work: the shape's bytes, of any alignment. -> ZXC_OK, a synchronous error of the entry point's argument checks
  * (the NULL checks excepted), or RVR_BAD_PLAN. */
 static inline int rsr_call(uint64_t src_size, const void* index, const zxc_dev_rangev_t* ranges, uint32_t n_ranges, uint64_t max_len,
                            uint32_t E, uint32_t bs, int have_dict, uint32_t have_id, const rvr_blocks_t* blk, uint8_t* work,
                            uint64_t work_size, int64_t* results) {
-    zrs_shape_t s;
+    zr_shape_t s;
     if (!zsh_elem_ok(E)) return ZXC_ERROR_GPU_UNSUPPORTED;
     const int shape_rc = zrs_shape(n_ranges, max_len, bs, &s);
     if (shape_rc != 0) return shape_rc;
     if (work_size < s.bytes) return ZXC_ERROR_MEMORY;
     if (n_ranges == 0) return ZXC_OK;
-    const uint64_t out_base = zc_round_up((uint64_t)(uintptr_t)work, 256u);
-    uint8_t* base = work + (out_base - (uint64_t)(uintptr_t)work);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
-    int32_t* status = (int32_t*)(base + s.o_status);
-    zrs_gather_t* gathers = (zrs_gather_t*)(base + s.o_gather);
-    const uint64_t* offs = zr_coffsets(index);
-
-    for (uint32_t i = 0; i < s.n_jobs; i++)
-        zrs_job(index, ranges[i / s.J], i % s.J, i, src_size, max_len, bs, out_base, s.o_stage, have_dict, have_id, &jobs[i], &gathers[i]);
-
-    for (uint32_t i = 0; i < s.n_jobs; i++) {
-        status[i] = ZXC_ERROR_SRC_TOO_SMALL;
-        if (jobs[i].out_len != bs || jobs[i].out_off != s.o_stage + (uint64_t)i * s.slot_stride) return RVR_BAD_PLAN; /* always the slot */
-        if (jobs[i].comp_size == 0) continue;
-        const uint64_t b = ranges[i / s.J].offset / bs + i % s.J;
-        if (b >= blk->n || offs[b] != jobs[i].comp_off || offs[b + 1u] - offs[b] != jobs[i].comp_size) return RVR_BAD_PLAN;
-        uint8_t* out = rvr_at(out_base, jobs[i].out_off);
-        status[i] = blk->status[b];
-        if (status[i] < 0) { memset(out, 0x5A, bs / 2u); continue; }
-        const uint32_t n = (uint32_t)status[i] < bs ? (uint32_t)status[i] : bs;
-        memcpy(out, blk->bytes + blk->at[b], n);
-        memset(out + n, 0xA5, 32);
-    }
-    for (uint32_t i = 0; i < s.n_jobs; i++) rsr_gather_job(base + s.o_stage, s.slot_stride, gathers, status, i, s.chunks, E, out_base);
-    for (uint32_t r = 0; r < n_ranges; r++)
-        results[r] = zrs_verdict(index, ranges[r], s.J, status + (uint64_t)r * s.J, src_size, max_len, bs, have_dict, have_id);
-    return ZXC_OK;
+    return rvr_stages(0, rsr_job, zrs_verdict, rsr_gather_job, E, src_size, index, ranges, n_ranges, max_len, bs, have_dict, have_id, blk, &s, work, results);
 }
 #endif

@@ -144,7 +144,8 @@ def case(name, E, d_src, total, bs, a, stream):
         walls = sorted(m)
         line = {"variant": vname, "data": name, "elem_size": E, "bytes": total, "ranges": n, "min_len": int(lens.min()), "max_len": max_len,
                 "level": a.level, "block_size": bs, "wanted_bytes": wanted, "archive_bytes": n_arc, "work_bytes": ws,
-                "extra_hbm_bytes": extra, "host_calls": calls, "runs": a.runs, "wall_ms": round(wall, 3), "wall_ms_min": round(walls[0], 3),
+                "extra_hbm_bytes": extra, "host_calls": calls, "runs": a.runs, "wall_ms": round(wall, 3), "wall_ms_p10": round(devbench.pct(walls, 0.1), 3),
+                "wall_ms_p90": round(devbench.pct(walls, 0.9), 3), "wall_ms_min": round(walls[0], 3),
                 "wall_ms_max": round(walls[-1], 3), "spread": round((walls[-1] - walls[0]) / wall, 4),
                 "wanted_gbps": round(wanted / wall / 1e6, 2)}
         if vname.startswith("a "):

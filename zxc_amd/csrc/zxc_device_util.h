@@ -2,7 +2,8 @@
 // zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_cpack_device.hip, zxc_append_device.hip, zxc_take_device.hip,
 // zxc_dict_device.hip, zxc_shuffle_device.hip, zxc_rangesv_shuffle_device.hip): the three tile passes every container stage is made of, the 64-bit workgroup scan, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
 // of an entry point: the launch check, the work area's base, the dictionary argument, the one reader of zxc_compress_opts_t, and
-// the launches the decode-side calls share: the verification tables, the copy grid, the container and the verdict stages.
+// the launches the decode-side calls share: the verification tables, the copy grid, the container and the verdict stages, and the
+// ranges family's plan and verdict kernel bodies and its four stages (zd_ranges_plan, zd_ranges_verdict, zd_ranges_stages).
 // HIP only; the container rules themselves are the plain C of zxc_container.h / zxc_ranges.h / zxc_batch.h / zxc_cbatch.h.
 //
 // A tile is ZC_TILE_BLOCKS consecutive blocks, handled by one workgroup of ZD_TILE_THREADS threads, ZD_PER_THREAD consecutive
@@ -163,6 +164,31 @@ __device__ __forceinline__ void zd_gather_blocks(const uint8_t* __restrict__ slo
     }
 }
 
+// ---------------------------------------------------------------- the ranges family: plan and verdict
+// The bodies of the plan and verdict kernels of ranges, rangesv (zxc_ranges_device.hip) and the shuffled ranges
+// (zxc_rangesv_shuffle_device.hip). The rules stand once in zxc_ranges.h; a front end hands in its thin function over them.
+// plan: one thread per job, 256 per workgroup; job_of(range, j, job_index, &job, &record) is zr_job_dict, zrv_job or zrs_job.
+template <class Range, class Rec, class JobOf>
+__device__ __forceinline__ void zd_ranges_plan(const Range* __restrict__ ranges, uint32_t J, uint32_t n_jobs, zxc_dev_job_t* __restrict__ jobs,
+                                               Rec* __restrict__ recs, JobOf job_of) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_jobs) return;
+    const uint32_t r = i / J, j = i - r * J;
+    zxc_dev_job_t job;
+    Rec rec;
+    job_of(ranges[r], j, i, &job, &rec);
+    jobs[i] = job;
+    recs[i] = rec;
+}
+// verdict: one thread per range, 256 per workgroup; verdict_of(range, its J statuses) is zr_verdict_dict, zrv_verdict or zrs_verdict.
+template <class Range, class VerdictOf>
+__device__ __forceinline__ void zd_ranges_verdict(const Range* __restrict__ ranges, uint32_t n_ranges, uint32_t J, const int32_t* __restrict__ status,
+                                                  int64_t* __restrict__ results, VerdictOf verdict_of) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_ranges) return;
+    results[r] = verdict_of(ranges[r], status + (uint64_t)r * J);
+}
+
 // ---------------------------------------------------------------- a kernel two files launch
 // zxc_frame_device.hip defines it; zxc_append_device.hip launches it per piece. Declared once, here, which both include: a
 // definition that departs from this is a conflicting redeclaration and does not compile (as zxc_kernels.h).
@@ -220,6 +246,24 @@ static inline uint8_t* zd_out_base(void* d_dst, uint8_t* stage, uint64_t* dst_re
 }
 // The grid of a copy launch over `units` (copy, 8 KiB) pairs: a wavefront each, four to a workgroup; past 2^20 workgroups the kernels stride.
 static inline dim3 zd_copy_grid(uint64_t units) { return dim3((uint32_t)((units + 3u) / 4u < (1u << 20) ? (units + 3u) / 4u : (1u << 20))); }
+// A call of the ranges family (ranges, rangesv, the shuffled ranges) in stream order, behind its entry point's own checks: plan,
+// one decode launch over all jobs with d_out = out, the copy-out of the staged slots, verdict. base: the work area's; the jobs, the
+// statuses, the front end's records and the slots are carved from the shape. The launches a front end owns are handed in:
+// plan(grid, jobs, recs), copy_out(grid, stage, recs, status), verdict(grid, status).
+template <class Plan, class CopyOut, class Verdict>
+static inline int zd_ranges_stages(const void* d_src, const zr_shape_t& s, uint8_t* base, void* out, uint32_t n_ranges, uint32_t block_size,
+                                   const zd_dict_t& dict, void* stream, Plan plan, CopyOut copy_out, Verdict verdict) {
+    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
+    int32_t* status = (int32_t*)(base + s.o_status);
+    void* recs = base + s.o_copy;
+    plan(dim3((s.n_jobs + 255u) / 256u), jobs, recs);
+    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
+    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, dict.content, dict.size, dict.huf, 0u, stream);
+    if (rc != ZXC_OK) return rc;
+    copy_out(zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), (const uint8_t*)(base + s.o_stage), (const void*)recs, (const int32_t*)status);
+    verdict(dim3((n_ranges + 255u) / 256u), (const int32_t*)status);
+    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+}
 // The container's parts of a work area, from a zc_shape_t or from a zt_shape_t, which keeps zc_shape's offsets up to o_status.
 struct zd_cwork_t {
     zc_ctl_t* ctl;

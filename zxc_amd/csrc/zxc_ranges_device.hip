@@ -24,12 +24,16 @@
 // index's dictionary id with the word zxc_mi355x_dict_prepare_device wrote, and the decode launch gets the dictionary.
 //
 // zxc_mi355x_decompress_rangesv_device (and _dict) is the ranges call over a table whose entries carry the absolute device address
-// of their destination (zxc_rangesv.h): the same four stages with a plan and a verdict kernel of its own. The decode launch's
-// d_out and the copy's destination base are the work area's 256-byte aligned base, and every place outside the work area is
-// counted from it modulo 2^64, so the decode kernels and zxc_ranges_copy_kernel run as they are.
-#include "zxc_device_util.h"  // the tile passes, the host-side plumbing
-#include "zxc_ranges.h"
-#include "zxc_rangesv.h"
+// of their destination (zxc_rangesv.h). The decode launch's d_out and the copy's destination base are the work area's 256-byte
+// aligned base, and every place outside the work area is counted from it modulo 2^64, so the decode kernels and
+// zxc_ranges_copy_kernel run as they are.
+//
+// One rule set, three front ends: ranges and rangesv here, the shuffled ranges in zxc_rangesv_shuffle_device.hip. The rules of
+// zxc_ranges.h are written over a normalised request (zr_req_t) that each front end builds of its table entry; the plan and verdict
+// kernels are instantiations of zd_ranges_plan / zd_ranges_verdict, and zd_ranges_stages (zxc_device_util.h) enqueues the four
+// stages for every entry point, behind that entry point's own synchronous checks.
+#include "zxc_device_util.h"  // the tile passes, the ranges family's kernel bodies and stages, the host-side plumbing
+#include "zxc_rangesv.h"      // on top of zxc_ranges.h
 
 #define RNG_BAD (1ull << 63)  // in a tile's word: one of its entries is implausible (a tile's sum is <= 2^32)
 
@@ -110,15 +114,9 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_ranges_plan_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
                        uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size, uint64_t dst_rel, uint64_t stage_rel,
                        zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies, const uint32_t* __restrict__ dict_id) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_jobs) return;
-    const uint32_t r = i / J, j = i - r * J;
-    zxc_dev_job_t job;
-    zr_copy_t cp;
-    zr_job_dict(index, ranges[r], j, i, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u,
-                &job, &cp);
-    jobs[i] = job;
-    copies[i] = cp;
+    zd_ranges_plan(ranges, J, n_jobs, jobs, copies, [=](zxc_dev_range_t r, uint32_t j, uint32_t i, zxc_dev_job_t* job, zr_copy_t* cp) {
+        zr_job_dict(index, r, j, i, src_size, max_len, dst_capacity, block_size, dst_rel, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, job, cp);
+    });
 }
 
 // One wavefront per item = (job, chunk): chunk k of a job is the part of its copy whose destination addresses lie in
@@ -158,10 +156,9 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_ranges_verdict_kernel(const void* __restrict__ index, const zxc_dev_range_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
                           const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint64_t dst_capacity, uint32_t block_size,
                           int64_t* __restrict__ results, const uint32_t* __restrict__ dict_id) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_ranges) return;
-    results[r] = zr_verdict_dict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, dst_capacity, block_size, dict_id != nullptr,
-                                 dict_id ? *dict_id : 0u);
+    zd_ranges_verdict(ranges, n_ranges, J, status, results, [=](zxc_dev_range_t r, const int32_t* st) {
+        return zr_verdict_dict(index, r, J, st, src_size, max_len, dst_capacity, block_size, dict_id != nullptr, dict_id ? *dict_id : 0u);
+    });
 }
 
 // ---------------------------------------------------------------- rangesv
@@ -169,24 +166,18 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_rangesv_plan_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
                         uint64_t src_size, uint64_t max_len, uint32_t block_size, uint64_t out_base, uint64_t stage_rel,
                         zxc_dev_job_t* __restrict__ jobs, zr_copy_t* __restrict__ copies, const uint32_t* __restrict__ dict_id) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_jobs) return;
-    const uint32_t r = i / J, j = i - r * J;
-    zxc_dev_job_t job;
-    zr_copy_t cp;
-    zrv_job(index, ranges[r], j, i, src_size, max_len, block_size, out_base, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, &job, &cp);
-    jobs[i] = job;
-    copies[i] = cp;
+    zd_ranges_plan(ranges, J, n_jobs, jobs, copies, [=](zxc_dev_rangev_t r, uint32_t j, uint32_t i, zxc_dev_job_t* job, zr_copy_t* cp) {
+        zrv_job(index, r, j, i, src_size, max_len, block_size, out_base, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, job, cp);
+    });
 }
 
 extern "C" __global__ void __launch_bounds__(256)
 zxc_rangesv_verdict_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
                            const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint32_t block_size,
                            int64_t* __restrict__ results, const uint32_t* __restrict__ dict_id) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_ranges) return;
-    results[r] = zrv_verdict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, block_size, dict_id != nullptr,
-                             dict_id ? *dict_id : 0u);
+    zd_ranges_verdict(ranges, n_ranges, J, status, results, [=](zxc_dev_rangev_t r, const int32_t* st) {
+        return zrv_verdict(index, r, J, st, src_size, max_len, block_size, dict_id != nullptr, dict_id ? *dict_id : 0u);
+    });
 }
 
 // ---------------------------------------------------------------- host side
@@ -220,6 +211,14 @@ uint64_t zxc_mi355x_decompress_ranges_device_work_size(uint32_t n_ranges, uint64
     return zr_shape(n_ranges, max_len, block_size, &s) != 0 ? 0u : s.bytes;
 }
 
+// The copy-out launch of ranges and rangesv, as zd_ranges_stages takes it: the staged slots -> dst + dst_at.
+static auto copy_out(const zr_shape_t& s, uint8_t* dst, hipStream_t st) {
+    return [&s, dst, st](dim3 grid, const uint8_t* stage, const void* copies, const int32_t* status) {
+        hipLaunchKernelGGL(zxc_ranges_copy_kernel, grid, dim3(256), 0, st, stage, s.slot_stride, (const zr_copy_t*)copies, status, s.n_jobs,
+                           s.copy_chunks, dst);
+    };
+}
+
 // Both calls. dict == NULL: the call that takes no dictionary.
 static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges, uint32_t n_ranges,
                        uint64_t max_len, void* d_dst, uint64_t dst_capacity, uint32_t block_size, const zxc_dev_dict_t* dict, void* d_work,
@@ -238,23 +237,19 @@ static int ranges_call(const void* d_src, uint64_t src_size, const void* d_index
     const hipStream_t st = (hipStream_t)stream;
     const zd_dict_t dc = zd_dict_of(dict);
     uint8_t* base = zd_work_base(d_work);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
-    int32_t* status = (int32_t*)(base + s.o_status);
-    zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);
-    uint8_t* stage = base + s.o_stage;
     uint64_t dst_rel, stage_rel;
-    uint8_t* out = zd_out_base(d_dst, stage, &dst_rel, &stage_rel);
-
-    hipLaunchKernelGGL(zxc_ranges_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
-                       max_len, dst_capacity, block_size, dst_rel, stage_rel, jobs, copies, dc.id);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, out, status, block_size, 0, dc.content, dc.size, dc.huf, 0u, stream);
-    if (rc != ZXC_OK) return rc;
-    hipLaunchKernelGGL(zxc_ranges_copy_kernel, zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), dim3(256), 0, st, (const uint8_t*)stage,
-                       s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks, (uint8_t*)d_dst);
-    hipLaunchKernelGGL(zxc_ranges_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
-                       (const int32_t*)status, src_size, max_len, dst_capacity, block_size, d_results, dc.id);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    uint8_t* out = zd_out_base(d_dst, base + s.o_stage, &dst_rel, &stage_rel);
+    return zd_ranges_stages(
+        d_src, s, base, out, n_ranges, block_size, dc, stream,
+        [&](dim3 grid, zxc_dev_job_t* jobs, void* copies) {
+            hipLaunchKernelGGL(zxc_ranges_plan_kernel, grid, dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size, max_len, dst_capacity,
+                               block_size, dst_rel, stage_rel, jobs, (zr_copy_t*)copies, dc.id);
+        },
+        copy_out(s, (uint8_t*)d_dst, st),
+        [&](dim3 grid, const int32_t* status) {
+            hipLaunchKernelGGL(zxc_ranges_verdict_kernel, grid, dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J, status, src_size, max_len,
+                               dst_capacity, block_size, d_results, dc.id);
+        });
 }
 
 int zxc_mi355x_decompress_ranges_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_range_t* d_ranges,
@@ -294,20 +289,17 @@ static int rangesv_call(const void* d_src, uint64_t src_size, const void* d_inde
     const hipStream_t st = (hipStream_t)stream;
     const zd_dict_t dc = zd_dict_of(dict);
     uint8_t* base = zd_work_base(d_work);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
-    int32_t* status = (int32_t*)(base + s.o_status);
-    zr_copy_t* copies = (zr_copy_t*)(base + s.o_copy);
-
-    hipLaunchKernelGGL(zxc_rangesv_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size,
-                       max_len, block_size, (uint64_t)(uintptr_t)base, s.o_stage, jobs, copies, dc.id);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, base, status, block_size, 0, dc.content, dc.size, dc.huf, 0u, stream);
-    if (rc != ZXC_OK) return rc;
-    hipLaunchKernelGGL(zxc_ranges_copy_kernel, zd_copy_grid((uint64_t)s.n_jobs * s.copy_chunks), dim3(256), 0, st, (const uint8_t*)(base + s.o_stage),
-                       s.slot_stride, (const zr_copy_t*)copies, (const int32_t*)status, s.n_jobs, s.copy_chunks, base);
-    hipLaunchKernelGGL(zxc_rangesv_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
-                       (const int32_t*)status, src_size, max_len, block_size, d_results, dc.id);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return zd_ranges_stages(
+        d_src, s, base, base, n_ranges, block_size, dc, stream,
+        [&](dim3 grid, zxc_dev_job_t* jobs, void* copies) {
+            hipLaunchKernelGGL(zxc_rangesv_plan_kernel, grid, dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size, max_len, block_size,
+                               (uint64_t)(uintptr_t)base, s.o_stage, jobs, (zr_copy_t*)copies, dc.id);
+        },
+        copy_out(s, base, st),
+        [&](dim3 grid, const int32_t* status) {
+            hipLaunchKernelGGL(zxc_rangesv_verdict_kernel, grid, dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J, status, src_size, max_len,
+                               block_size, d_results, dc.id);
+        });
 }
 
 int zxc_mi355x_decompress_rangesv_device(const void* d_src, uint64_t src_size, const void* d_index, const zxc_dev_rangev_t* d_ranges,

@@ -1,11 +1,12 @@
 /* zxc_rangesv_shuffle.h — the rules of zxc_mi355x_decompress_rangesv_shuffle_device on top of zxc_rangesv.h and zxc_shuffle.h:
  * ranges of the PLAIN bytes of an archive that holds byte-shuffled blocks (unit = the block size), each into a destination of its
  * own. The transform keeps sizes and every unit is one block, so plain bytes [offset, offset + len) lie in the blocks the same
- * shuffled bytes lie in: the index, the early verdict, the jobs per range and the slots are rangesv's as they are. What is new is
- * what the planes change: no block can be decoded in place (job (r, j) has no direct rule), a block's planes are laid out by its
- * length, so the block verdict holds the status against the length the index gives the block, and the copy-out becomes a gather
- * across the E planes of a slot. Plain inline C that hipcc and a host C compiler both take, so that the kernels of
- * zxc_rangesv_shuffle_device.hip and the CPU tests (tests/ranges/rangesv_shuffle_replay.h) run the same lines.
+ * shuffled bytes lie in: the request (zrv_req), the index, the early verdict, the jobs per range and the slots are rangesv's as
+ * they are. What the planes change are two arguments of the family's rules (zxc_ranges.h) and the record: no block can be decoded
+ * in place (zrs_job: zr_req_job with may_direct 0), a block's planes are laid out by its length, so the block verdict holds the status against
+ * the length the index gives the block (zrs_verdict, zrs_block_verdict: exact 1), and the copy-out becomes a gather across the
+ * E planes of a slot, which is what this file has. Plain inline C that hipcc and a host C compiler both take, so that the kernels
+ * of zxc_rangesv_shuffle_device.hip and the CPU tests (tests/ranges/rangesv_shuffle_replay.h) run the same lines.
  *
  * The gather plan. A job wants plain bytes [from, from + n) of a block of m bytes, counted from the block's first byte. With
  * q = m / E and Gq = q / 16, whole group g < Gq of the block is plain bytes [16 E g, 16 E (g + 1)) and 16 bytes at
@@ -31,52 +32,21 @@ typedef struct zrs_gather {
     uint32_t from, n, m, rsv;
 } zrs_gather_t;
 
-/* the length the index gives block b < nb: min(block_size, total - b block_size) */
-ZC_FN uint32_t zrs_block_len(const zr_index_t* ix, uint64_t b, uint32_t block_size) {
-    const uint64_t left = ix->total - b * block_size;
-    return left < block_size ? (uint32_t)left : block_size;
-}
-/* Job j of range r (job_index = r J + j): zrv_job's lines without the direct rule. Every covered block is staged in its slot; the
+/* Job j of range r (job_index = r J + j): rangesv's job without the direct rule. Every covered block is staged in its slot; the
  * record names what of its plain bytes goes where (dst_at counted from out_base modulo 2^64) and the block's length. */
 ZC_FN void zrs_job(const void* index, zxc_dev_rangev_t r, uint32_t j, uint64_t job_index, uint64_t src_size, uint64_t max_len,
                    uint32_t block_size, uint64_t out_base, uint64_t stage_rel, int have_dict, uint32_t have_id, zxc_dev_job_t* job,
                    zrs_gather_t* ga) {
-    const zr_index_t* ix = (const zr_index_t*)index;
-    const uint64_t* offs = zr_coffsets(index);
-    int64_t res;
-    uint32_t from, to;
-    job->comp_off = 0; job->out_off = stage_rel + job_index * ((uint64_t)block_size + ZR_SLOT_PAD); job->comp_size = 0; job->out_len = block_size;
-    ga->dst_at = 0; ga->from = 0; ga->n = 0; ga->m = 0; ga->rsv = 0;
-    if (zrv_range_final(ix, r, src_size, max_len, block_size, have_dict, have_id, &res)) return;
-    const uint64_t b = r.offset / block_size + j;
-    zr_wanted(zrv_range(r), b, block_size, &from, &to);
-    if (to == from) return;
-    job->comp_off = offs[b];
-    job->comp_size = (uint32_t)(offs[b + 1u] - offs[b]);
-    ga->dst_at = r.base + (b * block_size + from - r.offset) - out_base;
-    ga->from = from; ga->n = to - from; ga->m = zrs_block_len(ix, b, block_size);
+    zr_part_t p;
+    zr_req_job(index, zrv_req(r, max_len, out_base), j, job_index, src_size, block_size, stage_rel, 0, have_dict, have_id, job, &p);
+    ga->dst_at = p.dst_at; ga->from = p.from; ga->n = p.n; ga->rsv = 0;
+    ga->m = p.n ? zr_block_len((const zr_index_t*)index, p.b, block_size) : 0;
 }
-/* A covered block's own error, or CORRUPT_DATA when it did not decode to the length its planes were laid out by; 0 = fine.
- * (Contains zr_block_verdict's "decoded short of what the range needs": need_to <= m.) */
-ZC_FN int32_t zrs_block_verdict(int32_t status, uint32_t m) {
-    if (status < 0) return status;
-    return (uint32_t)status != m ? ZXC_ERROR_CORRUPT_DATA : 0;
-}
-/* The range's result from its J statuses: the early verdict, then the first failing covered block in block order, else len. */
+/* the block rule and the verdict with exact statuses: the block must have decoded to the length its planes were laid out by */
+ZC_FN int32_t zrs_block_verdict(int32_t status, uint32_t m) { return zr_block_rule(status, m, 1); }
 ZC_FN int64_t zrs_verdict(const void* index, zxc_dev_rangev_t r, uint32_t J, const int32_t* status, uint64_t src_size, uint64_t max_len,
                           uint32_t block_size, int have_dict, uint32_t have_id) {
-    const zr_index_t* ix = (const zr_index_t*)index;
-    int64_t res;
-    if (zrv_range_final(ix, r, src_size, max_len, block_size, have_dict, have_id, &res)) return res;
-    const uint64_t b0 = r.offset / block_size;
-    for (uint32_t j = 0; j < J; j++) {
-        uint32_t from, to;
-        zr_wanted(zrv_range(r), b0 + j, block_size, &from, &to);
-        if (to == from) break;
-        const int32_t v = zrs_block_verdict(status[j], zrs_block_len(ix, b0 + j, block_size));
-        if (v != 0) return v;
-    }
-    return (int64_t)r.len;
+    return zr_req_verdict(index, zrv_req(r, max_len, 0u), J, status, src_size, block_size, 1, have_dict, have_id);
 }
 
 /* ---- the gather plan (E: 2, 4 or 8; from + n <= m <= 2 MiB) */
@@ -111,24 +81,9 @@ ZC_FN int zrs_item(uint32_t from, uint32_t n, uint32_t m, uint32_t E, uint32_t c
 /* single byte k < head_n + tail_n of an item: its place in the block's plain bytes */
 ZC_FN uint32_t zrs_single(const zrs_item_t* it, uint32_t k) { return k < it->head_n ? it->head_at + k : it->tail_at + (k - it->head_n); }
 
-/* ---- the call's shape: rangesv's jobs and slots (zr_shape), a gather record per job in the copy record's place */
-typedef struct zrs_shape {
-    uint32_t J, n_jobs, slot_stride, chunks; /* jobs per range; n_ranges J; bytes per slot; gather chunks per job */
-    uint64_t o_jobs, o_status, o_gather, o_stage, bytes; /* work-area offsets from its 256-byte aligned base */
-} zrs_shape_t;
-/* -> 0, ZXC_ERROR_BAD_BLOCK_SIZE, or ZXC_ERROR_MEMORY, as zr_shape */
+/* ---- the call's shape: rangesv's jobs and slots, a gather record per job in the copy record's place, ZRS_CHUNK chunks per job */
+typedef zr_shape_t zrs_shape_t;
 ZC_FN int zrs_shape(uint32_t n_ranges, uint64_t max_len, uint32_t block_size, zrs_shape_t* s) {
-    zr_shape_t z;
-    const int rc = zr_shape(n_ranges, max_len, block_size, &z);
-    if (rc != 0) return rc;
-    s->J = z.J; s->n_jobs = z.n_jobs; s->slot_stride = z.slot_stride;
-    s->chunks = (block_size + ZRS_CHUNK - 1u) / ZRS_CHUNK;
-    uint64_t o = 0;
-    s->o_jobs = o;   o = zc_round_up(o + (uint64_t)s->n_jobs * sizeof(zxc_dev_job_t), 256u);
-    s->o_status = o; o = zc_round_up(o + 4ull * s->n_jobs, 256u);
-    s->o_gather = o; o = zc_round_up(o + (uint64_t)s->n_jobs * sizeof(zrs_gather_t), 256u);
-    s->o_stage = o;  o += (uint64_t)s->n_jobs * s->slot_stride;
-    s->bytes = o + 256u; /* (the caller's d_work may have any alignment) */
-    return 0;
+    return zr_shape_of(n_ranges, max_len, block_size, sizeof(zrs_gather_t), (block_size + ZRS_CHUNK - 1u) / ZRS_CHUNK, s);
 }
 #endif

@@ -1,8 +1,10 @@
 // zxc_rangesv_shuffle_device.hip — zxc_mi355x_decompress_rangesv_shuffle_device (include/zxc_mi355x_rangesv_shuffle.h): ranges of
-// the plain bytes of a seekable archive of byte-shuffled blocks, each into a destination of its own, device to device. The rules
-// are the inline C of zxc_rangesv_shuffle.h on top of zxc_rangesv.h and zxc_shuffle.h, which the CPU tests run as well.
+// the plain bytes of a seekable archive of byte-shuffled blocks, each into a destination of its own, device to device. The third
+// front end of the ranges family (ranges and rangesv are zxc_ranges_device.hip's): rangesv's request over the one rule set of
+// zxc_ranges.h with no block decoded in place and a block's status held against its length, and the gather plan of
+// zxc_rangesv_shuffle.h on top of zxc_shuffle.h, all of it inline C that the CPU tests run as well.
 //
-// In stream order, as rangesv_call of zxc_ranges_device.hip:
+// In stream order, enqueued by zd_ranges_stages (zxc_device_util.h) as for the two siblings:
 //   plan     one thread per job: validates its range, writes the job (always a staged slot) and the gather record
 //   decode   the existing decode launch, once, over all jobs (with the dictionary when there is one)
 //   gather   one wavefront per (job, 8 KiB of the block's plain bytes): the slot's planes -> the range's destination
@@ -20,14 +22,9 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_rangesv_shuffle_plan_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t J, uint32_t n_jobs,
                                 uint64_t src_size, uint64_t max_len, uint32_t block_size, uint64_t out_base, uint64_t stage_rel,
                                 zxc_dev_job_t* __restrict__ jobs, zrs_gather_t* __restrict__ gathers, const uint32_t* __restrict__ dict_id) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_jobs) return;
-    const uint32_t r = i / J, j = i - r * J;
-    zxc_dev_job_t job;
-    zrs_gather_t ga;
-    zrs_job(index, ranges[r], j, i, src_size, max_len, block_size, out_base, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, &job, &ga);
-    jobs[i] = job;
-    gathers[i] = ga;
+    zd_ranges_plan(ranges, J, n_jobs, jobs, gathers, [=](zxc_dev_rangev_t r, uint32_t j, uint32_t i, zxc_dev_job_t* job, zrs_gather_t* ga) {
+        zrs_job(index, r, j, i, src_size, max_len, block_size, out_base, stage_rel, dict_id != nullptr, dict_id ? *dict_id : 0u, job, ga);
+    });
 }
 
 namespace {
@@ -91,16 +88,15 @@ extern "C" __global__ void __launch_bounds__(256)
 zxc_rangesv_shuffle_verdict_kernel(const void* __restrict__ index, const zxc_dev_rangev_t* __restrict__ ranges, uint32_t n_ranges, uint32_t J,
                                    const int32_t* __restrict__ status, uint64_t src_size, uint64_t max_len, uint32_t block_size,
                                    int64_t* __restrict__ results, const uint32_t* __restrict__ dict_id) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_ranges) return;
-    results[r] = zrs_verdict(index, ranges[r], J, status + (uint64_t)r * J, src_size, max_len, block_size, dict_id != nullptr,
-                             dict_id ? *dict_id : 0u);
+    zd_ranges_verdict(ranges, n_ranges, J, status, results, [=](zxc_dev_rangev_t r, const int32_t* st) {
+        return zrs_verdict(index, r, J, st, src_size, max_len, block_size, dict_id != nullptr, dict_id ? *dict_id : 0u);
+    });
 }
 
 extern "C" {
 
 uint64_t zxc_mi355x_decompress_rangesv_shuffle_device_work_size(uint32_t n_ranges, uint64_t max_len, uint32_t block_size) {
-    zrs_shape_t s;
+    zr_shape_t s;
     return zrs_shape(n_ranges, max_len, block_size, &s) != 0 ? 0u : s.bytes;
 }
 
@@ -110,7 +106,7 @@ int zxc_mi355x_decompress_rangesv_shuffle_device(const void* d_src, uint64_t src
                                                  void* stream) {
     if (!d_src || !d_index || !d_work || !d_results || (!d_ranges && n_ranges > 0)) return ZXC_ERROR_NULL_INPUT;
     if (!zsh_elem_ok(elem_size)) return ZXC_ERROR_GPU_UNSUPPORTED;
-    zrs_shape_t s;
+    zr_shape_t s;
     const int shape_rc = zrs_shape(n_ranges, max_len, block_size, &s);
     if (shape_rc == ZXC_ERROR_BAD_BLOCK_SIZE) return shape_rc;
     const int drc = dict_arg(&dict);
@@ -122,29 +118,23 @@ int zxc_mi355x_decompress_rangesv_shuffle_device(const void* d_src, uint64_t src
     const hipStream_t st = (hipStream_t)stream;
     const zd_dict_t dc = zd_dict_of(dict);
     uint8_t* base = zd_work_base(d_work);
-    zxc_dev_job_t* jobs = (zxc_dev_job_t*)(base + s.o_jobs);
-    int32_t* status = (int32_t*)(base + s.o_status);
-    zrs_gather_t* gathers = (zrs_gather_t*)(base + s.o_gather);
-    const uint8_t* stage = base + s.o_stage;
-
-    hipLaunchKernelGGL(zxc_rangesv_shuffle_plan_kernel, dim3((s.n_jobs + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs,
-                       src_size, max_len, block_size, (uint64_t)(uintptr_t)base, s.o_stage, jobs, gathers, dc.id);
-    if (!launched()) return ZXC_ERROR_GPU_UNAVAILABLE;
-    const int rc = zxc_hip_decode_blocks(d_src, jobs, s.n_jobs, base, status, block_size, 0, dc.content, dc.size, dc.huf, 0u, stream);
-    if (rc != ZXC_OK) return rc;
-    const dim3 grid = zd_copy_grid((uint64_t)s.n_jobs * s.chunks), block(256);
-    if (elem_size == 2u)
-        hipLaunchKernelGGL(zxc_rangesv_shuffle_gather2_kernel, grid, block, 0, st, stage, s.slot_stride, (const zrs_gather_t*)gathers,
-                           (const int32_t*)status, s.n_jobs, s.chunks, base);
-    else if (elem_size == 4u)
-        hipLaunchKernelGGL(zxc_rangesv_shuffle_gather4_kernel, grid, block, 0, st, stage, s.slot_stride, (const zrs_gather_t*)gathers,
-                           (const int32_t*)status, s.n_jobs, s.chunks, base);
-    else
-        hipLaunchKernelGGL(zxc_rangesv_shuffle_gather8_kernel, grid, block, 0, st, stage, s.slot_stride, (const zrs_gather_t*)gathers,
-                           (const int32_t*)status, s.n_jobs, s.chunks, base);
-    hipLaunchKernelGGL(zxc_rangesv_shuffle_verdict_kernel, dim3((n_ranges + 255u) / 256u), dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J,
-                       (const int32_t*)status, src_size, max_len, block_size, d_results, dc.id);
-    return launched() ? ZXC_OK : ZXC_ERROR_GPU_UNAVAILABLE;
+    return zd_ranges_stages(
+        d_src, s, base, base, n_ranges, block_size, dc, stream,
+        [&](dim3 grid, zxc_dev_job_t* jobs, void* gathers) {
+            hipLaunchKernelGGL(zxc_rangesv_shuffle_plan_kernel, grid, dim3(256), 0, st, d_index, d_ranges, s.J, s.n_jobs, src_size, max_len,
+                               block_size, (uint64_t)(uintptr_t)base, s.o_stage, jobs, (zrs_gather_t*)gathers, dc.id);
+        },
+        [&](dim3 grid, const uint8_t* stage, const void* gathers, const int32_t* status) {
+            const auto kernel = elem_size == 2u   ? zxc_rangesv_shuffle_gather2_kernel
+                                : elem_size == 4u ? zxc_rangesv_shuffle_gather4_kernel
+                                                  : zxc_rangesv_shuffle_gather8_kernel;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, stage, s.slot_stride, (const zrs_gather_t*)gathers, status, s.n_jobs, s.copy_chunks,
+                               base);
+        },
+        [&](dim3 grid, const int32_t* status) {
+            hipLaunchKernelGGL(zxc_rangesv_shuffle_verdict_kernel, grid, dim3(256), 0, st, d_index, d_ranges, n_ranges, s.J, status, src_size,
+                               max_len, block_size, d_results, dc.id);
+        });
 }
 
 }  // extern "C"

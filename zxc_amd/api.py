@@ -195,7 +195,14 @@ _PROTOTYPES_RANGESV_SHUFFLE = {
     "zxc_mi355x_decompress_rangesv_shuffle_device_work_size": (_U64, [_U32, _U64, _U32]),
     "zxc_mi355x_decompress_rangesv_shuffle_device": (_I, [_P, _U64, _P, _P, _U32, _U64, _U32, _U32, _DD] + _TAIL),
 }
-_TABLES = (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE, _PROTOTYPES_RANGESV_SHUFFLE)
+# include/zxc_mi355x_shufflev.h, a table of its own: tests/test_compress_shufflev_device_cpu.py holds it against that header
+_PROTOTYPES_SHUFFLEV = {
+    "zxc_mi355x_shufflev_device_scratch_size": (_U64, [_U32]),
+    "zxc_mi355x_shufflev_device": (_I, [_P, _U32, _U64, _P, _U32, _U32, _P, _U64, _P, _P]),
+    "zxc_mi355x_compress_shufflev_device_work_size": (_U64, [_U32, _U64, _U64, _CO, _U32]),
+    "zxc_mi355x_compress_shufflev_device": (_I, [_P, _U32, _U64, _U32, _P, _U64, _U64, _CO, _DD] + _TAIL),
+}
+_TABLES = (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE, _PROTOTYPES_RANGESV_SHUFFLE, _PROTOTYPES_SHUFFLEV)
 _STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
 _PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
 
@@ -208,7 +215,7 @@ def _prototype(name):
 
 
 def _bind(L, names=None):
-    """Set restype and argtypes of those of `names` (all four tables unless given) that L exports (the reference and the mock-device
+    """Set restype and argtypes of those of `names` (all five tables unless given) that L exports (the reference and the mock-device
     library have no device calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
     for name in ([n for table in _TABLES for n in table] if names is None else names):
         f = getattr(L, name, None)
@@ -578,6 +585,37 @@ def decompress_rangesv_shuffle_device(d_src, src_size, d_index, d_ranges, n_rang
     (ints), asynchronous on `stream`; a synchronous failure raises ZxcError."""
     _call("zxc_mi355x_decompress_rangesv_shuffle_device", d_src, src_size, d_index, d_ranges, n_ranges, max_len, elem_size, block_size,
           _dev_dict(dict_), d_work, work_size, d_results, stream)
+
+
+# ---- the byte-shuffle of a table of typed tensors (include/zxc_mi355x_shufflev.h): the write side of the shuffled ranges
+def shufflev_device_scratch_size(n_iov):
+    """zxc_mi355x_shufflev_device_scratch_size(): bytes of device scratch shufflev_device needs for a table of n_iov entries."""
+    return int(_call("zxc_mi355x_shufflev_device_scratch_size", n_iov))
+
+
+def shufflev_device(d_iov, n_iov, total, d_dst, elem_size, unit, d_scratch, scratch_size, d_status, stream=0):
+    """zxc_mi355x_shufflev_device(): d_dst[0, total) = shuffle_device's bytes for the concatenation of the n_iov x IOV_DTYPE entries
+    at d_iov (device memory), `total` bytes in all, with no concatenated copy. 0 or the table's error lands in the int64 at
+    d_status. Raw device pointers (ints) of any alignment, asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_shufflev_device", d_iov, n_iov, total, d_dst, elem_size, unit, d_scratch, scratch_size, d_status, stream)
+
+
+def compress_shufflev_device_work_size(n_iov, total, max_piece=0, dict_size=0, level=3, block_size=0, seekable=False, checksum=False):
+    """zxc_mi355x_compress_shufflev_device_work_size(): bytes of device scratch compress_shufflev_device needs (0 for refused
+    arguments): compress_shuffle_device's rounded up to 256, the table's scratch and 256 bytes."""
+    return int(_call("zxc_mi355x_compress_shufflev_device_work_size", n_iov, total, max_piece,
+                     _copts(level, block_size, seekable, checksum), dict_size))
+
+
+def compress_shufflev_device(d_iov, n_iov, total, elem_size, d_dst, dst_capacity, d_work, work_size, d_result, max_piece=0, dict_=None,
+                             level=3, block_size=0, seekable=False, checksum=False, stream=0):
+    """zxc_mi355x_compress_shufflev_device(): the archive compress_shuffle_device writes for the concatenation of the n_iov x
+    IOV_DTYPE entries at d_iov (device memory), `total` bytes in all, gathered and shuffled chunk by chunk into the stage: no
+    concatenated copy. Tensor r is read back with decompress_rangesv_shuffle_device at offset = the lengths in front of it. The
+    archive size, a negative zxc_error_t or the table's error lands in the int64 at d_result. Raw device pointers (ints),
+    asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_compress_shufflev_device", d_iov, n_iov, total, elem_size, d_dst, dst_capacity, max_piece,
+          _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, d_result, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)

@@ -1,6 +1,6 @@
 // zxc_device_util.h — what the device-to-device calls share (zxc_frame_device.hip, zxc_unframe_device.hip, zxc_ranges_device.hip,
 // zxc_batch_device.hip, zxc_cbatch_device.hip, zxc_cpack_device.hip, zxc_append_device.hip, zxc_take_device.hip,
-// zxc_dict_device.hip, zxc_shuffle_device.hip, zxc_rangesv_shuffle_device.hip): the three tile passes every container stage is made of, the 64-bit workgroup scan, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
+// zxc_dict_device.hip, zxc_shuffle_device.hip, zxc_rangesv_shuffle_device.hip, zxc_shufflev_device.hip): the three tile passes every container stage is made of, the 64-bit workgroup scan, the copy out of a staged slot, the gather of a run of blocks, and the host-side plumbing
 // of an entry point: the launch check, the work area's base, the dictionary argument, the one reader of zxc_compress_opts_t, and
 // the launches the decode-side calls share: the verification tables, the copy grid, the container and the verdict stages, and the
 // ranges family's plan and verdict kernel bodies and its four stages (zd_ranges_plan, zd_ranges_verdict, zd_ranges_stages).

@@ -11,7 +11,7 @@
 #include "zxc_appendv.h"    // zav_ctl_t, zap_ctl_t
 #include "zxc_container.h"  // zc_ctl_t
 #include "zxc_dev.h"
-#include "zxc_rangesv_shuffle.h"  // zrs_gather_t, zxc_dev_rangev_t
+#include "zxc_rangesv_shuffle.h"  // zrs_gather_t, zxc_dev_rangev_t; zsh_plan_t (zxc_shuffle.h)
 
 // threads of the three builds of the section decoder (zxc_pivco_dir.inc): launch bounds, loop strides and the shim's launches
 #define PDIR_SMALL_THREADS 128
@@ -133,6 +133,18 @@ ZXC_RANGESV_SHUFFLE_GATHER_DECL(zxc_rangesv_shuffle_gather8_kernel);
 extern "C" __global__ void zxc_rangesv_shuffle_verdict_kernel(const void* index, const zxc_dev_rangev_t* ranges, uint32_t n_ranges, uint32_t J,
                                                               const int32_t* status, uint64_t src_size, uint64_t max_len, uint32_t block_size,
                                                               int64_t* results, const uint32_t* dict_id);
+
+// ---------------------------------------------------------------- zxc_shufflev_device.hip
+// zxc_mi355x_shufflev_device / _compress_shufflev_device: the gather-shuffle of a chunk of a table's concatenation per element
+// size, and the kernel that writes the call's status or result word.
+#define ZXC_SHUFFLEV_DECL(name)                                                                                                     \
+    extern "C" __global__ void name(const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov, const zav_ctl_t* vctl, uint64_t v, \
+                                    uint8_t* dst, zsh_plan_t pl, uint64_t n)
+ZXC_SHUFFLEV_DECL(zxc_shufflev2_kernel);
+ZXC_SHUFFLEV_DECL(zxc_shufflev4_kernel);
+ZXC_SHUFFLEV_DECL(zxc_shufflev8_kernel);
+#undef ZXC_SHUFFLEV_DECL
+extern "C" __global__ void zxc_shufflev_result_kernel(const zav_ctl_t* vctl, const int64_t* word, int64_t* d_result);
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
 extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 #endif

@@ -20,5 +20,6 @@ from .api import (ZxcError, Seekable, compress, decompress, get_decompressed_siz
                   decompress_rangesv_dict_device, shuffle_device, unshuffle_device, compress_shuffle_device_work_size,
                   compress_shuffle_device, decompress_shuffle_device_work_size, decompress_shuffle_device,
                   decompress_rangesv_shuffle_device_work_size, decompress_rangesv_shuffle_device, shufflev_device,
-                  shufflev_device_scratch_size, compress_shufflev_device, compress_shufflev_device_work_size)
+                  shufflev_device_scratch_size, compress_shufflev_device, compress_shufflev_device_work_size, unshufflev_device,
+                  unshufflev_device_scratch_size, decompress_shufflev_device, decompress_shufflev_device_work_size)
 from . import api  # noqa: F401  (stream_* helpers live there)

@@ -202,22 +202,30 @@ _PROTOTYPES_SHUFFLEV = {
     "zxc_mi355x_compress_shufflev_device_work_size": (_U64, [_U32, _U64, _U64, _CO, _U32]),
     "zxc_mi355x_compress_shufflev_device": (_I, [_P, _U32, _U64, _U32, _P, _U64, _U64, _CO, _DD] + _TAIL),
 }
+# include/zxc_mi355x_unshufflev.h, a table of its own: tests/test_decompress_shufflev_device_cpu.py holds it against that header
+_PROTOTYPES_UNSHUFFLEV = {
+    "zxc_mi355x_unshufflev_device_scratch_size": (_U64, [_U32]),
+    "zxc_mi355x_unshufflev_device": (_I, [_P, _P, _U32, _U64, _U32, _U32, _P, _U64, _P, _P]),
+    "zxc_mi355x_decompress_shufflev_device_work_size": (_U64, [_U32, _U64, _U64, _U64, _U32]),
+    "zxc_mi355x_decompress_shufflev_device": (_I, [_P, _U64, _P, _U32, _U64, _U32, _U64, _U32, _DO, _DD] + _TAIL),
+}
 _TABLES = (_PROTOTYPES, _PROTOTYPES_RANGESV, _PROTOTYPES_SHUFFLE, _PROTOTYPES_RANGESV_SHUFFLE, _PROTOTYPES_SHUFFLEV)
+_TABLES_MORE = (_PROTOTYPES_UNSHUFFLEV,)  # the tables behind the first five; _prototype and _bind walk both tuples
 _STREAM = ("zxc_stream_compress", "zxc_stream_decompress", "zxc_stream_get_decompressed_size", "zxc_seekable_open_file")
 _PSTREAM = tuple(n for n in _PROTOTYPES if n.startswith(("zxc_cstream_", "zxc_dstream_")))
 
 
 def _prototype(name):
-    for table in _TABLES:
+    for table in _TABLES + _TABLES_MORE:
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def _bind(L, names=None):
-    """Set restype and argtypes of those of `names` (all five tables unless given) that L exports (the reference and the mock-device
+    """Set restype and argtypes of those of `names` (all tables unless given) that L exports (the reference and the mock-device
     library have no device calls, an experiment build may lack some): a missing symbol fails when it is called, not here. -> L"""
-    for name in ([n for table in _TABLES for n in table] if names is None else names):
+    for name in ([n for table in _TABLES + _TABLES_MORE for n in table] if names is None else names):
         f = getattr(L, name, None)
         if f is not None:
             f.restype, f.argtypes = _prototype(name)
@@ -616,6 +624,37 @@ def compress_shufflev_device(d_iov, n_iov, total, elem_size, d_dst, dst_capacity
     asynchronous on `stream`; a synchronous failure raises ZxcError."""
     _call("zxc_mi355x_compress_shufflev_device", d_iov, n_iov, total, elem_size, d_dst, dst_capacity, max_piece,
           _copts(level, block_size, seekable, checksum), _dev_dict(dict_), d_work, work_size, d_result, stream)
+
+
+# ---- the inverse byte-shuffle into a table of typed tensors (include/zxc_mi355x_unshufflev.h): the load side of shufflev
+def unshufflev_device_scratch_size(n_iov):
+    """zxc_mi355x_unshufflev_device_scratch_size(): bytes of device scratch unshufflev_device needs for a table of n_iov entries
+    (shufflev_device_scratch_size's)."""
+    return int(_call("zxc_mi355x_unshufflev_device_scratch_size", n_iov))
+
+
+def unshufflev_device(d_src, d_iov, n_iov, total, elem_size, unit, d_scratch, scratch_size, d_status, stream=0):
+    """zxc_mi355x_unshufflev_device(): the n_iov x IOV_DTYPE entries at d_iov (device memory), `total` bytes in all, receive
+    unshuffle_device's bytes for d_src[0, total), cut by the table, with no contiguous copy. 0 or the table's error lands in the
+    int64 at d_status. Raw device pointers (ints) of any alignment, asynchronous on `stream`; a synchronous failure raises
+    ZxcError."""
+    _call("zxc_mi355x_unshufflev_device", d_src, d_iov, n_iov, total, elem_size, unit, d_scratch, scratch_size, d_status, stream)
+
+
+def decompress_shufflev_device_work_size(n_iov, src_size, total, max_piece, block_size):
+    """zxc_mi355x_decompress_shufflev_device_work_size(): bytes of device scratch decompress_shufflev_device needs (0 for refused
+    arguments): decompress_shuffle_device's rounded up to 256 and the table's scratch."""
+    return int(_call("zxc_mi355x_decompress_shufflev_device_work_size", n_iov, src_size, total, max_piece, block_size))
+
+
+def decompress_shufflev_device(d_src, src_size, d_iov, n_iov, total, elem_size, block_size, d_work, work_size, d_result, max_piece=0,
+                               dict_=None, checksum=False, stream=0):
+    """zxc_mi355x_decompress_shufflev_device(): decodes the archive chunk by chunk into a stage of the work area and un-shuffles it
+    into the n_iov x IOV_DTYPE entries at d_iov (device memory), `total` bytes in all: what decompress_shuffle_device writes for
+    dst_size = total, cut by the table. total, a negative zxc_error_t or the table's error lands in the int64 at d_result. Raw
+    device pointers (ints), asynchronous on `stream`; a synchronous failure raises ZxcError."""
+    _call("zxc_mi355x_decompress_shufflev_device", d_src, src_size, d_iov, n_iov, total, elem_size, max_piece, block_size, _dopts(checksum),
+          _dev_dict(dict_), d_work, work_size, d_result, stream)
 
 
 # ---- many archives per call (include/zxc_mi355x.h: zxc_dev_item_t)

@@ -145,6 +145,18 @@ ZXC_SHUFFLEV_DECL(zxc_shufflev4_kernel);
 ZXC_SHUFFLEV_DECL(zxc_shufflev8_kernel);
 #undef ZXC_SHUFFLEV_DECL
 extern "C" __global__ void zxc_shufflev_result_kernel(const zav_ctl_t* vctl, const int64_t* word, int64_t* d_result);
+
+// ---------------------------------------------------------------- zxc_unshufflev_device.hip
+// zxc_mi355x_unshufflev_device / _decompress_shufflev_device: the un-shuffle of a contiguous chunk scattered into a chunk of a
+// table's concatenation per element size, and the kernel that writes the call's status or result word.
+#define ZXC_UNSHUFFLEV_DECL(name)                                                                                                  \
+    extern "C" __global__ void name(const uint8_t* src, const zxc_dev_iov_t* iov, const uint64_t* starts, uint32_t n_iov,          \
+                                    const zav_ctl_t* vctl, uint64_t v, zsh_plan_t pl, uint64_t n)
+ZXC_UNSHUFFLEV_DECL(zxc_unshufflev2_kernel);
+ZXC_UNSHUFFLEV_DECL(zxc_unshufflev4_kernel);
+ZXC_UNSHUFFLEV_DECL(zxc_unshufflev8_kernel);
+#undef ZXC_UNSHUFFLEV_DECL
+extern "C" __global__ void zxc_unshufflev_result_kernel(const zav_ctl_t* vctl, const int64_t* word, uint64_t total, int64_t* d_result);
 #ifdef EXP_ENC_CLOCKS  // (experiment build only, tools/encclk.py)
 extern "C" __global__ void zxc_enc_clk_read_kernel(unsigned long long* out);
 #endif
